@@ -10,6 +10,11 @@ z-buffer SE(3) reprojection -> MaskUnet -> DDNM condition -> T-step sampler over
 MaskUnet -> float64 unprojection, everything resident in HBM when the clock starts.  Scene pairs are
 independent, so ranks take disjoint scene indices and never communicate on the data path (weak scaling);
 `value` = pairs produced by all ranks / max-over-ranks wall time.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the diagnostic legs (conv roofline, memory
+rooflines, file leg, drift against the fixtures, parity modes, configs[4], CPU baseline) and writes the sidecar.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (same arguments, same inputs: two builds compare
+output for output).
 """
 import argparse
 import json
@@ -68,6 +73,30 @@ def write_sidecar(res):
         except OSError as e:          # a read-only checkout must not cost the contract line
             print(f"bench.py: could not write {p}: {e}", file=sys.stderr)
     return SIDECAR
+
+
+DUMP_LIMIT = 64 << 20      # bytes of --dump-outputs in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the arrays of the last timed step as DIR/<name>.npy (float32 / float64 as computed, masks as float32).  Above
+    DUMP_LIMIT in all, every array keeps the same fixed, seeded sample of scenes (leading axis) and `rows.npy` lists them.
+    Returns the names written."""
+    out = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu()
+        out[k] = (v if v.dtype in (torch.float32, torch.float64) else v.float()).numpy()
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        n = len(next(iter(out.values())))
+        keep = (n * (DUMP_LIMIT - 8 * n - 4096)) // total
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, keep), replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["rows"] = keep.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return sorted(out)
 
 
 def _r(x, n=4):
@@ -177,6 +206,11 @@ def parse():
     p.add_argument("--uncalibrated", action="store_true", help="round-1/2 synthetic weights (98 %% of in-painted pixels saturate)")
     p.add_argument("--no-parity-mode", action="store_true", help="skip the parity_mode legs (fp32 and f16x3 at the headline shape)")
     p.add_argument("--parity-transitions", type=int, default=100, help="timed ancestral transitions of the parity_mode legs (extrapolated to 1000)")
+    p.add_argument("--full", action="store_true", help="also run the diagnostic legs (conv roofline, memory rooflines, file leg, drift, "
+                   "parity modes, configs[4], CPU baseline; each still subject to its --no-* switch), gather the per-rank table and write "
+                   "the sidecar.  A plain run only sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                   "(rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     p.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)   # internal: one host_filled worker with N threads
     return p.parse_args()
 
@@ -630,7 +664,11 @@ def parity_mode_leg(a, G, synthetic, rank, dt, shape=None, lanes=1):
         if errs:
             raise errs[0]
 
-    run(0, False)
+    # untimed warm-up, one lane at a time (as the headline leg's lane setup): a lane's first batch allocates its workspaces, and
+    # doing that while another lane captures its graph can invalidate the capture ("operation failed ... during capture")
+    for k, pp in enumerate(pipes):
+        with torch.cuda.stream(pp["stream"]):
+            one(batches[k], pp)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     run(lanes, True)
@@ -784,13 +822,18 @@ def main():
         if a.sampler_only:
             rpj, hit = G.reproject_tensor(bt["depth"], bt["K"], bt["pose"], clip=(0, 10), depth_unit=10.0, out_scale=0.1)
             _, _, cond = G.apply_mask(torch.ones_like(rpj), rpj, hit, 0.5)
-            return diff_.sample(param_cond=pc, img_cond=cond, seeds=bt["seeds"])
+            img = diff_.sample(param_cond=pc, img_cond=cond, seeds=bt["seeds"])
+            if bt is batches[-1]:
+                last.update(sampled=img)
+            return img
         rpj, hit = G.reproject_tensor(bt["depth"], bt["K"], bt["pose"], clip=(0, 10), depth_unit=10.0, out_scale=0.1)
         _, hit_c, cond = G.apply_mask(mask_(rpj), rpj, hit, 0.99)
         img = diff_.sample(param_cond=pc, img_cond=cond, seeds=bt["seeds"])
         out, _, _ = G.apply_mask(mask_(img), img, None, 0.99, want_cond=False)
         xyz, valid = G.unproject_f64(out, bt["K"], bt["pose"])
-        last.update(img=img, known=hit_c, valid=valid)          # (references only: read after the clock stops)
+        if bt is batches[-1]:
+            # the last timed step, whichever lane ran it (references only: read after the clock stops)
+            last.update(img=img, known=hit_c, valid=valid, xyz=xyz, depth=out)
         return xyz
 
     last = {}
@@ -861,12 +904,20 @@ def main():
     dt_own = time.perf_counter() - t0              # this rank's own time (before the closing barrier)
     barrier()
     dt = time.perf_counter() - t0
-    free_b, total_b = torch.cuda.mem_get_info()
+    if a.full:
+        free_b, total_b = torch.cuda.mem_get_info()
+    if a.dump_outputs and rank == 0:
+        if a.sampler_only:
+            outs = {"sampled": last["sampled"]}
+        else:           # pixels outside the depth clip carry NaN coordinates: written as 0 (`valid` marks them), so dumps compare exactly
+            outs = {"xyz": last["xyz"].masked_fill(~last["valid"][..., None], 0.0), "valid": last["valid"], "depth": last["depth"]}
+        dump_outputs(a.dump_outputs, outs)
     per_rank = None
     if dist is not None:
         tt = torch.tensor([dt], device=red_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if dist is not None and a.full:
         # per-rank attribution of a slow barrier: every rank's setup / warm-up / own timed seconds and
         # the device memory in use on its GPU, gathered to rank 0
         mine = torch.tensor([setup_s, warmup_s, dt_own, float(total_b - free_b), float(affinity.get("cpus", 0)),
@@ -900,13 +951,14 @@ def main():
         "end_to_end_mfma_frac": value / world * tflop_pair / MFMA_PEAK_TFLOPS[a.dtype],
         "setup": {"setup_s": setup_s, "warmup_s": warmup_s, "timed_s_this_rank": dt_own,
                   "what": "setup = process group + weight synthesis / upload + input synthesis + lane workspaces and graph capture (untimed)"},
-        "device_memory": {"in_use_bytes": int(total_b - free_b), "total_bytes": int(total_b),
-                          "what": "hipMemGetInfo on this rank's device after the timed loop (all ranks sharing the device included)"},
         "cpu_affinity": affinity,
     }
+    if a.full:
+        res["device_memory"] = {"in_use_bytes": int(total_b - free_b), "total_bytes": int(total_b),
+                                "what": "hipMemGetInfo on this rank's device after the timed loop (all ranks sharing the device included)"}
     if per_rank is not None:
         res["per_rank"] = per_rank
-    if last:
+    if a.full and "img" in last:
         # the timed workload is not degenerate: how many in-painted pixels of the last timed batch ended on the [0,1] clamp,
         # and how many pixels survive the second depth correction into the clouds
         img, known = last["img"], last["known"].bool()
@@ -916,7 +968,7 @@ def main():
                            "inpainted_depth_m": {"mean": float(img[free].mean()) * 10, "std": float(img[free].std()) * 10},
                            "points_kept_fraction": float(last["valid"].float().mean())}
 
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         # dominant kernel class = the MFMA convolutions (w256 + c64 + ws + igemm).  Their launches are timed live with HIP
         # events on the sampler's own stream over `profile_transitions` transitions of the same workload (eager launches).
         nprof = min(a.profile_transitions, n_trans)
@@ -963,7 +1015,7 @@ def main():
         if not a.sampler_only:
             res["roofline_mem"] = mem_rooflines(G, bt, S, B, pr, stream_batch=1024 * (128 * 128) // (S * S) if B >= 16 else 4 * B)
         pdiff.close()
-    if not a.no_e2e_files and not a.sampler_only:
+    if a.full and not a.no_e2e_files and not a.sampler_only:
         # every rank runs its own shard of the generate_dataset loop; aggregate like the headline metric
         e2e = e2e_files(a, unet, mask, diff, rank, world, B, S, lanes=[(pp["diff"], pp["mask"]) for pp in pipes[1:]])
         dt_e = e2e["seconds"]
@@ -978,9 +1030,9 @@ def main():
         res["e2e_files"] = e2e
     # the single-GPU diagnostics (drift against the fixtures, the configs[4] leg, the CPU baseline) belong to the N = 1 line
     # only: at N > 1 the other ranks would sit in the closing barrier while rank 0 runs them
-    if rank == 0 and world == 1 and not a.no_drift and a.dim == 64:
+    if rank == 0 and world == 1 and a.full and not a.no_drift and a.dim == 64:
         res["drift_vs_reference"] = drift_vs_reference(sorted({a.dtype, "bf16", "mxfp8", "f16x3", "fp32"}), a.dim)
-    if rank == 0 and world == 1 and not a.no_parity_mode and not a.sampler_only and a.dtype == "bf16":
+    if rank == 0 and world == 1 and a.full and not a.no_parity_mode and not a.sampler_only and a.dtype == "bf16":
         # the modes that hold the north-star tolerance (1e-4 m point-XYZ against the reference: tests/test_gpu_f16x3.py,
         # test_long_chain_fp32_north_star), at the headline shape: what "correct" costs next to the bf16 headline
         # fp32 on one lane (as in rounds 3-4); f16x3 on the headline leg's `--streams` lanes, its one-lane figure kept beside it
@@ -1013,7 +1065,7 @@ def main():
                            "labelled_parity": "fp32 (tests/test_gpu_parity.py::test_long_chain_fp32_north_star) and f16x3 "
                                               "(tests/test_gpu_f16x3.py) on every calibrated chain"}
         res["parity_mode"] = pm
-    if rank == 0 and world == 1 and not a.no_configs4 and not a.sampler_only:
+    if rank == 0 and world == 1 and a.full and not a.no_configs4 and not a.sampler_only:
         res["configs4"] = configs4_leg(a, G, synthetic, rank)
         # the same shape, same call, same box in bf16: whether fp8 operands buy anything on their own config
         cmp_ = configs4_leg(a, G, synthetic, rank, dt="bf16")
@@ -1023,14 +1075,16 @@ def main():
         res["configs4"]["mxfp8_over_bf16_same_shape"] = res["configs4"]["value"] / cmp_["value"]
         # the measured ceiling of MX operands on this network (profiles/r05_mxcap_activations_in_memory_cap.txt)
         res["configs4"]["mx_cap_measured"] = "<=1.15x bf16 (profiles/r05_mxcap_activations_in_memory_cap.txt)"
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(S, a.dim)
 
     if rank == 0:
-        res["evidence"] = EVIDENCE
         # the driver parses the LAST stdout line: a short contract line (< 4 KB, asserted here and in the tests); every table,
         # per-rank row, drift chain and prose string lives in the sidecar
-        side = write_sidecar(res)
+        side = None
+        if a.full:                  # a plain run has no tables: no sidecar, `full` is null
+            res["evidence"] = EVIDENCE
+            side = write_sidecar(res)
         line = contract_line(res, side)
         print(json.dumps(res), file=sys.stderr, flush=True)
         print(line, flush=True)

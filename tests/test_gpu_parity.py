@@ -1527,7 +1527,7 @@ def test_bench_contract_line(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
                         "--size", "64", "--sampling-steps", "6", "--profile-transitions", "3", "--e2e-batches", "2", "--c4-batch", "2",
-                        "--c4-steps", "1", "--no-cpu-baseline", "--no-drift", "--parity-transitions", "4"], cwd=tmp_path, capture_output=True,
+                        "--c4-steps", "1", "--no-cpu-baseline", "--no-drift", "--parity-transitions", "4", "--full"], cwd=tmp_path, capture_output=True,
                        text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1561,6 +1561,44 @@ def test_bench_contract_line(tmp_path):
     assert len(j["roofline"]["per_kernel"]) > 0
     assert j["e2e_files"]["files_written"] == 9 * 8 * (2 + 2) and j["e2e_files"]["gt_log"]["lines"] >= 0
     assert j["configs4"]["dtype"] == "mxfp8" and j["configs4"]["config"]["image_size"] == 256 and j["configs4"]["roofline"]["peak"] == 5000.0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the steps and prints the contract line without any diagnostic leg or sidecar;
+    `--dump-outputs DIR` writes the last timed step's outputs (float32 / float64 .npy, <= 64 MB), and a second run with the same
+    arguments writes the same arrays bit for bit."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, S = 8, 64
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                            "--size", str(S), "--sampling-steps", "4", "--dump-outputs", str(d)], cwd=tmp_path, capture_output=True,
+                           text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        c = json.loads(lines[0])
+        assert c["steps"] == 3 and c["warmup"] == 1 and c["dtype"] == "bf16" and c["unit"] == "pairs/s" and c["higher_is_better"] is True
+        assert abs(c["value"] - 3 * B / (c["ms_per_step"] * 3 / 1e3)) < 1e-6 * c["value"]
+        for k in ("roofline", "e2e_files", "configs4", "parity_mode", "cpu_baseline", "roofline_mem"):
+            assert k not in c, k
+        assert c["full"] is None
+        files = sorted(os.listdir(d))
+        assert files == ["depth.npy", "valid.npy", "xyz.npy"], files
+        arr = {f[:-4]: np.load(d / f) for f in files}
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert arr["xyz"].dtype == np.float64 and arr["xyz"].shape == (B, S * S, 3)
+        assert arr["valid"].dtype == np.float32 and arr["valid"].shape == (B, S * S) and set(np.unique(arr["valid"])) <= {0.0, 1.0}
+        assert arr["depth"].dtype == np.float32 and arr["depth"].shape == (B, 1, S, S)
+        assert arr["valid"].any() and np.isfinite(arr["xyz"]).all() and not arr["xyz"][arr["valid"] == 0].any()
+        dumps.append(arr)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_bench_gpus_flag_spawns_its_own_ranks(tmp_path):
@@ -1622,7 +1660,7 @@ def test_bench_eight_ranks_rehearsal_on_one_device(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", "4", "--size", "64",
-           "--sampling-steps", "3", "--no-roofline", "--no-e2e-files", "--no-drift", "--no-configs4", "--no-cpu-baseline", "--no-parity-mode"]
+           "--sampling-steps", "3", "--no-roofline", "--no-e2e-files", "--no-drift", "--no-configs4", "--no-cpu-baseline", "--no-parity-mode", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PRG_NO_AFFINITY")}
     r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=1500, env=dict(env, PRG_BENCH_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -399,6 +399,34 @@ def test_bench_contract_line_is_short_for_a_full_result():
     assert len(bench.contract_line(full, bench.SIDECAR)) < 4096
 
 
+def test_bench_dump_outputs_formats_and_cap(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays as computed, masks as float32; above 64 MB in all, the same fixed, seeded
+    sample of scenes from every array (listed in rows.npy), identical from call to call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = {"xyz": torch.randn((2, 16, 3), generator=g, dtype=torch.float64), "valid": torch.rand((2, 16), generator=g) > 0.5,
+             "depth": torch.rand((2, 1, 4, 4), generator=g)}
+    assert bench.dump_outputs(str(tmp_path / "s"), small) == ["depth", "valid", "xyz"]
+    got = {k: np.load(tmp_path / "s" / f"{k}.npy") for k in small}
+    assert got["xyz"].dtype == np.float64 and np.array_equal(got["xyz"], small["xyz"].numpy())
+    assert got["valid"].dtype == np.float32 and np.array_equal(got["valid"], small["valid"].numpy().astype(np.float32))
+    assert got["depth"].dtype == np.float32 and np.array_equal(got["depth"], small["depth"].numpy())
+    n = 96                                                   # 96 scenes x 1 MB of float64 = 96 MB > 64 MB
+    big = {"xyz": torch.arange(n, dtype=torch.float64)[:, None, None].expand(n, 1 << 14, 8).contiguous(),
+           "valid": torch.ones((n, 1 << 14), dtype=torch.bool)}
+    rows = []
+    for run in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / run), big) == ["rows", "valid", "xyz"]
+        files = [tmp_path / run / f"{k}.npy" for k in ("rows", "valid", "xyz")]
+        assert sum(os.path.getsize(f) for f in files) <= 64 << 20
+        r, v, x = (np.load(f) for f in files)
+        assert r.dtype == np.float64 and len(r) == len(v) == len(x) > n // 2 and np.all(np.diff(r) > 0)
+        assert np.array_equal(x[:, 0, 0], r)                 # every array keeps the same scenes
+        rows.append(r)
+    assert np.array_equal(rows[0], rows[1])
+
+
 def test_rank_cpu_budget_divides_a_shared_mask_but_not_a_pinned_one():
     """a mask narrower than the host that pin_rank_cpus did NOT set (container cpuset, job-wide taskset,
     PRG_NO_AFFINITY) is shared by every rank and must be divided by the rank count; a mask pin_rank_cpus set is the rank's own."""

@@ -4,7 +4,7 @@
 # copy what is to be judged into profiles/r06_*.  Stages:
 #   tests            full `-m gpu` suite (log with -rA)          tests:<expr>   pytest -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command: bench.py --gpus 1 --steps 20 --warmup 5 (contract line + sidecar)
+#   bench            the driver's command with every diagnostic leg: bench.py --full --gpus 1 --steps 20 --warmup 5 (contract line + sidecar)
 #   benchq           the same with --steps 4 --warmup 2 (quick)
 #   prof:<dtype>     rocprofv3 --kernel-trace --stats of 20 DDIM transitions (bf16 / mxfp8) or 10 ancestral ones (fp32 / f16x3), one lane
 #   pmc              the three PMC passes (FETCH_SIZE, WRITE_SIZE, SQ_*) + conv_hbm_traffic.json
@@ -25,7 +25,7 @@ for ST in "$@"; do
     tests:*) python -m pytest tests -m gpu -q -rA -k "${ST#tests:}" > $O/${T}_tests_k.log 2>&1; echo "pytest rc=$?" >> $O/${T}_tests_k.log; grep -E "passed|failed|rc=|^FAILED|^ERROR" $O/${T}_tests_k.log | tail -12;;
     smoke) python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $O/${T}_smoke.log;;
     bench|benchq)
-      A="--gpus 1 --steps 20 --warmup 5"; [ $ST = benchq ] && A="--gpus 1 --steps 4 --warmup 2"
+      A="--full --gpus 1 --steps 20 --warmup 5"; [ $ST = benchq ] && A="--full --gpus 1 --steps 4 --warmup 2"
       T0=$(date +%s)
       python bench.py $A > $O/${T}_bench_line.json 2> $O/${T}_bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"
       cp bench_full.json $O/${T}_bench_full.json 2>/dev/null
