@@ -37,21 +37,15 @@ constexpr int kTilesPerBlock = 8;
 // Linear attention: tiles per block as a function of the image size ONLY (a batch-independent slab structure keeps a
 // scene's result identical for every batch size): 8 from 64 x 64 pixels up, fewer for the small levels, whose launches
 // otherwise fill a quarter of the CUs with blocks that walk four tiles in series (16 x 16: 64 blocks -> 256).
-// (compile-time overrides for A/B builds; measured round 3: 16 or 32 tiles per la_ctx block 73-75 against 72 us, 4 or 16 per
-// la_out block 105-108 against 99 us)
-#ifndef PRG_LA_CTX_TPB
-#define PRG_LA_CTX_TPB 8
-#endif
-#ifndef PRG_LA_OUT_TPB
-#define PRG_LA_OUT_TPB 8
-#endif
+// (measured round 3: 16 or 32 tiles per la_ctx block 73-75 against 72 us, 4 or 16 per la_out block 105-108 against 99 us)
+constexpr int kLaCtxTpb = 8, kLaOutTpb = 8;
 __host__ __device__ inline int la_tpb(int ntiles) {             // la_kmax / la_ctx (the slab structure of the partials)
   const int t = ntiles / 8;
-  return t < 1 ? 1 : (t > PRG_LA_CTX_TPB ? PRG_LA_CTX_TPB : t);
+  return t < 1 ? 1 : (t > kLaCtxTpb ? kLaCtxTpb : t);
 }
 __host__ __device__ inline int la_out_tpb(int ntiles) {         // la_out (pixels are independent there: any partition)
   const int t = ntiles / 8;
-  return t < 1 ? 1 : (t > PRG_LA_OUT_TPB ? PRG_LA_OUT_TPB : t);
+  return t < 1 ? 1 : (t > kLaOutTpb ? kLaOutTpb : t);
 }
 constexpr int kLdO = kHid + 8;       // LDS row stride of 128-wide rows (bf16 elements)
 constexpr float kLnEps = 1e-5f;
@@ -887,7 +881,7 @@ int launch_c(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const floa
     PRG_LAUNCH_CHECK();
   }
   // PRG_LA_PSUM: sum_n p on the matrix pipe: -1 (default) where measured faster, 0 never, 1 always
-  static const int psum_env = [] { const char* e = std::getenv("PRG_LA_PSUM"); return e ? std::atoi(e) : -1; }();
+  static const int psum_env = env_int("PRG_LA_PSUM", -1);
   const bool psum = psum_env > 0 || (psum_env < 0 && kPsumDefault<C>);
 #define PRG_LA_CTX_GO(PS, KS) la_ctx_fused_kernel<C, PS, KS><<<grid, 256, lds_kmax<C>(), s>>>(x, wqkv, pmax, ctxp, sump, N, nslab)
   if (kshift) { if (psum) PRG_LA_CTX_GO(true, true); else PRG_LA_CTX_GO(false, true); }

@@ -57,19 +57,10 @@ __device__ inline f32x16 mma3(const h8& ah, const h8& al, const h8& bh, const h8
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, c, 0, 0, 0);
 }
 // v - hi as one v_fma_mix_f32 (conv_split.hip's split8, where it took 8 % off the persistent 64-channel kernel) bought nothing in
-// these kernels (same-box A/B, round 5: la_ctx -1 %, la_out +1-2 %): off; -DPRG_ATTN_SPLIT_MIX=1 builds it
-#ifndef PRG_ATTN_SPLIT_MIX
-#define PRG_ATTN_SPLIT_MIX 0
-#endif
+// these kernels (same-box A/B, round 5: la_ctx -1 %, la_out +1-2 %): plain float subtraction here
 __device__ inline void split1(float v, _Float16& h, _Float16& l) {
   h = (_Float16)v;
-#if PRG_ATTN_SPLIT_MIX
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-  l = (_Float16)r;
-#else
   l = (_Float16)(v - (float)h);
-#endif
 }
 #define SPLIT_TO(v, H, L, idx)                \
   do {                                        \
@@ -504,7 +495,7 @@ int launch_c(const float* x, const uint16_t* wqkv_h, const uint16_t* wqkv_l, con
   uint16_t* ctxT_l = ctxT_h + (size_t)B * 4 * 1024;
   const dim3 grid(nslab, B);
   // PRG_SPLIT_LA_ONLINE=0: the two-sweep form of rounds 4 (column maxima first)
-  static const int online = [] { const char* e = std::getenv("PRG_SPLIT_LA_ONLINE"); return e ? std::atoi(e) : 1; }();
+  static const int online = env_int("PRG_SPLIT_LA_ONLINE", 1);
   if (online) la_ctx_split_kernel<C, true><<<grid, 256, lds_ctx<C>(), s>>>(x, wqkv_h, wqkv_l, ctxp, sump, maxp, N, nslab);
   else la_ctx_split_kernel<C, false><<<grid, 256, lds_ctx<C>(), s>>>(x, wqkv_h, wqkv_l, ctxp, sump, maxp, N, nslab);
   PRG_LAUNCH_CHECK();
@@ -670,8 +661,7 @@ int launch_fa(const float* qkv, float* out, int B, hipStream_t s) {
 }  // namespace
 
 bool linattn_split_supported(int C, int N) {
-  static const int c128 = [] { const char* e = std::getenv("PRG_SPLIT_ATTN_C128"); return e ? std::atoi(e) : 1; }();
-  return (C == 64 || (C == 128 && c128)) && N % kTP == 0 && N >= kTP;
+  return (C == 64 || C == 128) && N % kTP == 0 && N >= kTP;
 }
 
 size_t linattn_split_ws_floats(int B, int N) {
@@ -691,7 +681,7 @@ int launch_linear_attention_split(const float* x, const uint16_t* wqkv_h, const 
 
 // Bottleneck attention core on split-f16 MFMAs: qkv (B, N, 384) float32 -> out (B, N, 128) float32.  PRG_SPLIT_FULLATTN=0: never.
 bool full_attention_split_supported(int N) {
-  static const int on = [] { const char* e = std::getenv("PRG_SPLIT_FULLATTN"); return e ? std::atoi(e) : 1; }();
+  static const int on = env_int("PRG_SPLIT_FULLATTN", 1);
   return on && (N == 128 || N == 256 || N == 512 || N == 1024);
 }
 

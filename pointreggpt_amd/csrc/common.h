@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/prg.h"
@@ -157,7 +158,13 @@ __device__ inline double wave_sum_d(double v) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-constexpr int kMaxTicketImages = 4096;   // per-image arrival counters (conv kernels folding GroupNorm coefficients): B <= this
+// integer value of environment switch `name`, or `dflt` when unset.  Every PRG_* switch the library reads goes through here (call
+// sites cache it in a function-local static); each one pins an alternative schedule that a test compares against the default.
+inline int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+
 constexpr int kGnMaxSplit = 1024;  // max GroupNorm (sum, sumsq) partial slabs per image (256x256: 8x32 tiles x 4 wave rows)
 
 // GroupNorm parameters of one Block (+ the ResnetBlock conditioning): what folds the statistics into y = x * A + B

@@ -52,13 +52,13 @@ struct ConvLaunch {
   // coefficients (sd:690-696).  null = off.
   const float* pro_a;
   const float* pro_b;
-  // Optional in-kernel coefficient folding (kernels that support it report so through launch_conv's coef_done): the
-  // workgroup that completes an image's last tile turns the image's partial sums into gn_coef_a/b [B][Cout]
-  // (= what gn_coeff_kernel would compute in a launch of its own).  gn_tickets: [B] ints, zero between launches.
-  GnApply gn;
-  float* gn_coef_a;
-  float* gn_coef_b;
-  int* gn_tickets;
+  // Retired in-kernel coefficient folding of conv3x3_c64_kernel (conv_c64.hip keeps its device code): the workgroup that
+  // completed an image's last tile turned the image's partial sums into gn_coef_a/b [B][Cout].  Never set: the launcher passes
+  // gn_tickets = null.
+  GnApply gn{};
+  float* gn_coef_a = nullptr;
+  float* gn_coef_b = nullptr;
+  int* gn_tickets = nullptr;
   // Fixed-point statistics (common.h, GnFold): producers that support it add their wave totals into gn_acc [B][gn_groups][2]
   // (zeroed by the caller) INSTEAD of writing gn_partials slabs and report so through launch_conv's acc_done; consumers
   // with pro_fold.acc != null compute the prologue coefficients themselves (pro_a / pro_b then point to [B][C0] scratch
@@ -185,7 +185,7 @@ float e4m3_to_f32(uint8_t b);
 // when statistics were requested but this shape cannot fuse them.  `allow_prologue` must be checked by the
 // caller with conv_supports_prologue() before setting pro_a / pro_b.
 template <typename T>
-int launch_conv(const ConvLaunch<T>& L, hipStream_t s, int* gn_nsplit_out, int* coef_done = nullptr, int* acc_done = nullptr);
+int launch_conv(const ConvLaunch<T>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done = nullptr);
 
 // true when the 3x3 halo kernel will run this conv (so a fused input prologue is available)
 template <typename T>

@@ -805,7 +805,7 @@ int materialize_prologue(ConvLaunch<bf16_t>& L, hipStream_t s) {
 static int materialize_prologue(ConvLaunch<float>&, hipStream_t) { return PRG_OK; }
 
 static int mx_pure_env() {
-  static const int pure = [] { const char* e = std::getenv("PRG_MX_PURE"); return e ? std::atoi(e) : 0; }();
+  static const int pure = env_int("PRG_MX_PURE", 0);
   return pure;
 }
 int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                     // conv_w256.hip
@@ -813,9 +813,8 @@ static int try_mx(ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int*
   if (!L.w_mx || !L.w_mx_scale) return 0;
   // Round 5: the wide Upsample convs of an mxfp8 handle run the bf16 SUB-PIXEL form (four 2 x 2-tap convolutions, 4 / 9 of the MACs:
   // 64-67 us at the configs[4] shape) — the nine-tap MX launch took 77-81 us (same box, same positions:
-  // profiles/r05_configs4_conv_per_launch_bf16_vs_mxfp8.txt); PRG_MX_UP=1 / mx_pure keep them on MX operands
-  static const int mx_up = [] { const char* e = std::getenv("PRG_MX_UP"); return e ? std::atoi(e) : 0; }();
-  if (L.d.ups && !L.gn_partials && !mx_up && !L.mx_pure && !mx_pure_env()) {
+  // profiles/r05_configs4_conv_per_launch_bf16_vs_mxfp8.txt); mx_pure keeps them on MX operands
+  if (L.d.ups && !L.gn_partials && !L.mx_pure && !mx_pure_env()) {
     const int r = try_launch_conv3x3_up_w256(L, s);
     if (r == 1) g_last_exec_scale = 4.0 / 9.0;
     if (r != 0) return r;
@@ -848,14 +847,14 @@ static int try_mx(ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int*
 static int try_mx(ConvLaunch<float>&, hipStream_t, int*, int*) { return 0; }
 
 int try_launch_conv3x3_ws(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);   // conv_ws.hip
-int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* coef_done, int* acc_done);  // conv_c64.hip
+int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);  // conv_c64.hip
 int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);   // conv_w256.hip
 int try_launch_conv4x4s2_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                       // conv_w256.hip
 int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                     // conv_w256.hip
 static inline int try_down(const ConvLaunch<bf16_t>& L, hipStream_t s) { return try_launch_conv4x4s2_w256(L, s); }
 static inline int try_down(const ConvLaunch<float>&, hipStream_t) { return 0; }
-static inline int try_ws(ConvLaunch<bf16_t>& L, hipStream_t s, int* n, int* coef_done, int* acc_done) {
-  int r = try_launch_conv3x3_c64(L, s, n, coef_done, acc_done);   // weights-stationary kernel for the 64 -> 64 convs
+static inline int try_ws(ConvLaunch<bf16_t>& L, hipStream_t s, int* n, int* acc_done) {
+  int r = try_launch_conv3x3_c64(L, s, n, acc_done);   // weights-stationary kernel for the 64 -> 64 convs
   if (r == 0 && L.d.ups && !L.gn_partials) {
     r = try_launch_conv3x3_up_w256(L, s);                    // Upsample convs as four 2 x 2-tap sub-pixel convs
     if (r == 1) g_last_exec_scale = 4.0 / 9.0;               // (what the profile reports as EXECUTED work)
@@ -869,17 +868,16 @@ static inline int try_ws(ConvLaunch<bf16_t>& L, hipStream_t s, int* n, int* coef
     if (int rc = materialize_prologue(L, s)) return rc;
   return try_launch_conv3x3_ws(L, s, n, acc_done);
 }
-static inline int try_ws(ConvLaunch<float>&, hipStream_t, int*, int*, int*) { return 0; }
+static inline int try_ws(ConvLaunch<float>&, hipStream_t, int*, int*) { return 0; }
 static inline int try_split(const ConvLaunch<float>& L, hipStream_t s, int* n) { return try_launch_conv_split(L, s, n); }
 static inline int try_split(const ConvLaunch<bf16_t>&, hipStream_t, int*) { return 0; }
 
 // h16 (conv.h): would both convs of a ResnetBlock take kernels that implement the f16 format?  The same try_launch_* functions
 // the dispatch below calls, in the same order, in probe mode (they stop where they would launch).
 bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1in, const ConvLaunch<bf16_t>& L2in) {
-  // PRG_H16: 0 off; bit 0 pairs whose conv2 runs on the 64 -> 64 kernel, bit 1 on the 256-pixel kernel, bit 2 conv1 on the
-  // wave-specialised kernel (debugging aid; default 7 = everything)
-  static const int mask = [] { const char* e = std::getenv("PRG_H16"); return e ? std::atoi(e) : 7; }();
-  if (!mask) return false;
+  // PRG_H16=0: off (every ResnetBlock keeps its bf16 h1)
+  static const int on = env_int("PRG_H16", 1);
+  if (!on) return false;
   ConvLaunch<bf16_t> L1 = L1in, L2 = L2in;
   // mxfp8 handles: a conv whose MX copy would run (the 256-pixel MX kernel takes Cout % 128 == 0; PRG_MX_PURE / mx_pure take every
   // 3x3 conv) never carries the f16 format — the 64-channel pairs, which the bf16 kernels run in that mode too, do
@@ -888,28 +886,20 @@ bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1in, const ConvLaunch<bf16_t>& 
   L1.probe = L2.probe = 1;
   L1.out_f16 = 1;
   L2.in_f16 = 1;
-  int ns = 0, cd = 0, ad = 0;
-  int r = try_launch_conv3x3_c64(L1, nullptr, &ns, &cd, &ad);
-  if (r == 0) r = try_launch_conv3x3_w256(L1, nullptr, &ns, &ad);
-  if (r == 0 && (mask & 4)) r = try_launch_conv3x3_ws(L1, nullptr, &ns, &ad);
-  static const int verbose = [] { const char* e = std::getenv("PRG_H16_VERBOSE"); return e ? std::atoi(e) : 0; }();
-  const int r1 = r, ad1 = ad;
-  int r2 = 0;
-  if (r1 == 1 && ad1) {
-    r2 = (mask & 1) ? try_launch_conv3x3_c64(L2, nullptr, &ns, &cd, &ad) : 0;
-    if (r2 == 0 && (mask & 2)) r2 = try_launch_conv3x3_w256(L2, nullptr, &ns, &ad);
-  }
-  if (verbose)
-    std::fprintf(stderr, "h16 probe: %d+%d -> %d @ %dx%d B=%d: conv1 %d (acc %d), conv2 %d\n", L1.d.C0, L1.d.C1, L1.d.Cout, L1.d.Hout, L1.d.Wout,
-                 L1.d.B, r1, ad1, r2);
-  return r1 == 1 && ad1 && r2 == 1;
+  int ns = 0, ad = 0;
+  int r1 = try_launch_conv3x3_c64(L1, nullptr, &ns, &ad);
+  if (r1 == 0) r1 = try_launch_conv3x3_w256(L1, nullptr, &ns, &ad);
+  if (r1 == 0) r1 = try_launch_conv3x3_ws(L1, nullptr, &ns, &ad);
+  if (r1 != 1 || !ad) return false;
+  int r2 = try_launch_conv3x3_c64(L2, nullptr, &ns, &ad);
+  if (r2 == 0) r2 = try_launch_conv3x3_w256(L2, nullptr, &ns, &ad);
+  return r2 == 1;
 }
 
 template <typename T>
-int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int* coef_done, int* acc_done) {
+int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
   g_last_exec_scale = 1.0;
   g_last_mx = 0;
-  if (coef_done) *coef_done = 0;
   if (acc_done) *acc_done = 0;
   ConvLaunch<T> L = Lin;          // (materialize_prologue clears pro_fold once the coefficient tables are filled)
   const ConvDesc& d = L.d;
@@ -934,7 +924,7 @@ int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int
     if (r == 1) return PRG_OK;
   }
   {
-    int r = try_ws(L, s, gn_nsplit_out, coef_done, acc_done);   // persistent kernels of the bf16 throughput path
+    int r = try_ws(L, s, gn_nsplit_out, acc_done);   // persistent kernels of the bf16 throughput path
     if (r == 0 && !L.gn_partials) r = try_down(L, s);       // Downsample (4 x 4, stride 2) as a 2 x 2-tap conv of the same kernel
     if (r < 0) return r;
     if (r == 1) return PRG_OK;
@@ -960,9 +950,8 @@ int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int
   if constexpr (std::is_same<T, bf16_t>::value) {
     // 256 x 128 tiles (round 5): the 1x1 res_convs / projections of the coarse levels are bound by L2 -> LDS operand traffic
     // (M N K (1 / BM + 1 / BN) elements: 0.75x of the 128 x 128 tile's) and meet one barrier per 16 instead of 8 MFMAs per wave;
-    // taken when the launch still has PRG_IGEMM_BM256 (default 2) workgroups per CU.  PRG_IGEMM_BM256=0: never.
-    static const int bm256 = [] { const char* e = std::getenv("PRG_IGEMM_BM256"); return e ? std::atoi(e) : 2; }();
-    if (bm256 && d.CoutPad % 128 == 0 && M % 256 == 0 && (int64_t)(M / 256) * (d.CoutPad / 128) >= (int64_t)bm256 * 256)
+    // taken when the launch still has two workgroups per CU.
+    if (d.CoutPad % 128 == 0 && M % 256 == 0 && (int64_t)(M / 256) * (d.CoutPad / 128) >= (int64_t)2 * 256)
       return launch_igemm<T, 256, 128>(L, M, s, want_stats, gn_nsplit_out);
   }
   if (d.CoutPad % 128 == 0) return launch_igemm<T, 128, 128>(L, M, s, want_stats, gn_nsplit_out);
@@ -998,8 +987,8 @@ void s2d_equivalent_weights(const float* w, int Cout, int Cin, std::vector<float
         }
 }
 
-template int launch_conv<float>(const ConvLaunch<float>&, hipStream_t, int*, int*, int*);
-template int launch_conv<bf16_t>(const ConvLaunch<bf16_t>&, hipStream_t, int*, int*, int*);
+template int launch_conv<float>(const ConvLaunch<float>&, hipStream_t, int*, int*);
+template int launch_conv<bf16_t>(const ConvLaunch<bf16_t>&, hipStream_t, int*, int*);
 
 // ---------------------------------------------------------------------------------------------
 // weight packing (host)

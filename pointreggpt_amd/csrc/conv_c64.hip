@@ -37,14 +37,6 @@ typedef __attribute__((ext_vector_type(8))) _Float16 c64_f16x8;
 
 namespace {
 
-// Timing experiments only (results become garbage): -DPRG_C64_EXP=1 consumers skip fragment reads + MFMAs, 2 producers skip
-// the halo loads / writes, 4 no epilogue, 8 no priority raise, 32 producers skip only the prologue arithmetic, 256 SiLU
-// without transcendentals, 1024 the round-5 consumer loop (one read per MFMA) instead of the row-reuse loop; with 1024: 512 half the
-// fragment reads (pairs of MFMAs share a fragment), 2048 all the reads but MFMA pairs sharing their operands (both with opaque accumulators).
-#ifndef PRG_C64_EXP
-#define PRG_C64_EXP 0
-#endif
-
 constexpr int TH = 8, TW = 32, HP = TW + 2, HALO = (TH + 2) * HP;   // 340 halo rows
 constexpr int ROWB = 144;                                              // padded LDS row (64 bf16 = 128 B + 16)
 constexpr int NPT = 256;                                               // producer threads
@@ -52,7 +44,6 @@ constexpr int RPP = NPT / 8;                                           // halo r
 constexpr int KU = (HALO + RPP - 1) / RPP;                             // 11 units per producer thread
 constexpr size_t AH_BYTES = (size_t)KU * RPP * ROWB;                   // 352 rows: the units past the halo end land in spare rows
 constexpr size_t C64_LDS = 2 * AH_BYTES + 64 * sizeof(float);          // + the bias
-constexpr bool kRowReuse = (PRG_C64_EXP & 1024) == 0;                 // -DPRG_C64_EXP=1024: the round-5 consumer loop (one read per MFMA), for A/B builds
 
 __device__ inline float c64_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ inline float c64_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
@@ -62,7 +53,6 @@ __device__ inline uint32_t c64_pack(float a, float b) {
   return __builtin_bit_cast(uint32_t, v);
 }
 __device__ inline float c64_silu(float x) {
-  if (PRG_C64_EXP & 256) return x * fmaf(fmaf(x, -1.4426950408889634f, 1.0f), x, 0.5f);   // timing experiment: no transcendentals
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 template <int CTRL>
@@ -92,6 +82,10 @@ __device__ __forceinline__ void c64_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// The per-image ticket fold below (c64_fold_coefficients, the `ticket` lambda, flags bit 1 = 0: contiguous tile runs) is retired:
+// try_launch_conv3x3_c64 never passes tickets and always asks for interleaved runs.  Its device code stays as it was because deleting
+// it changes the producers' register allocation (conv3x3_c64_kernel<1 | 2> then spill to scratch) and measured 0.4 % slower end to end.
+//
 // What gn_coeff_kernel does in a launch of its own, for ONE image, by one wave (lane = channel of the 64): the image's
 // (sum, sumsq) slabs summed in float64 — lanes of a group take slabs (c % cpg), + cpg, ... then a fixed xor tree —, mean /
 // rstd, folded with the norm's gain / bias and the ResnetBlock conditioning into y = x * A + B.  The slabs were written by
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 
   // ---------------------------------------------------------------------------------------------------
   if (wave < 4) {
-    if (!(PRG_C64_EXP & 8)) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     const int wm = wave >> 1, wn = wave & 1;              // pixel half (tile rows 4 wm .. 4 wm + 3), channel half
     const int l31 = lane & 31, hi = lane >> 5;
     // weights of channel wn*32 + l31: 9 taps x 4 k-steps; lane half hi takes k = 16 c + 8 hi .. + 7
@@ -205,107 +199,35 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       const char* const xb = smem + (size_t)(s & 1) * AH_BYTES + x0off;
       // Round 5: the accumulators START at the bias (16 values per lane, re-read from LDS per tile: they are dead again before the
       // fragment sets fill up) instead of at zero — the epilogue's 64 bias additions per tile and wave are gone; the sum's rounding
-      // order changes (bias first), far below the bf16 / f16 output rounding.  PRG_C64_EXP & 256: the old form (A/B builds).
+      // order changes (bias first), far below the bf16 / f16 output rounding.
       c64_f32x16 acc[4];
-      if constexpr ((PRG_C64_EXP & 256) != 0) {
 #pragma unroll
-        for (int pt = 0; pt < 4; ++pt)
+      for (int q = 0; q < 4; ++q) {
+        const float4 b4 = *reinterpret_cast<const float4*>(biasp + 8 * q);
 #pragma unroll
-          for (int e = 0; e < 16; ++e) acc[pt][e] = 0.0f;
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 b4 = *reinterpret_cast<const float4*>(biasp + 8 * q);
-#pragma unroll
-          for (int pt = 0; pt < 4; ++pt) { acc[pt][4 * q] = b4.x; acc[pt][4 * q + 1] = b4.y; acc[pt][4 * q + 2] = b4.z; acc[pt][4 * q + 3] = b4.w; }
-        }
+        for (int pt = 0; pt < 4; ++pt) { acc[pt][4 * q] = b4.x; acc[pt][4 * q + 1] = b4.y; acc[pt][4 * q + 2] = b4.z; acc[pt][4 * q + 3] = b4.w; }
       }
-      if constexpr ((PRG_C64_EXP & (512 | 2048)) != 0) {
-        // the shared-operand timing experiments: make the accumulators opaque, or the compiler proves acc[1] == acc[0] and acc[3] == acc[2]
-        // (identical initial values, identical MFMA chains) and DROPS half the MFMAs — which is what the first version of these experiments
-        // measured (74 v_mfma instead of 144 in the ISA; profiles/r06_c64_half_reads_bound.txt)
+      // Round 6: ROW REUSE.  Tap (dy, dx) of pixel row pt reads halo row pt + dy: the twelve (pt, dy) pairs of one (dx, k-step) touch
+      // only SIX halo rows.  The four accumulators are independent chains, so they are skewed by one tap row: fragment (halo row r,
+      // dx, c) is read ONCE and feeds acc[r] at tap (0, dx), acc[r-1] at (1, dx) and acc[r-2] at (2, dx) back to back — 72 reads
+      // per tile instead of 144 (0.5 ds_read_b128 per MFMA), no extra registers, and every accumulator still sees its MFMAs in
+      // tap-major order: the outputs are bit-identical.  Measured -1.0 ... -1.5 % per launch (profiles/r06_ab_c64_row_reuse.txt): the
+      // fragment reads are a small term of this kernel (profiles/r06_c64_half_reads_bound.txt).  Ring of four fragments, three ahead.
+      constexpr int FD = 3, FR = 4, NF = 72;
+      c64_bf16x8 fr[FR];
+      auto foff = [](int n) { return ((n / 12) * HP + (n / 4) % 3) * ROWB + (n & 3) * 32; };   // n = (r * 3 + dx) * 4 + c
 #pragma unroll
-        for (int pt = 0; pt < 4; ++pt) asm volatile("" : "+v"(acc[pt]));
-      }
-      if constexpr (kRowReuse) {
-        // Round 6: ROW REUSE.  Tap (dy, dx) of pixel row pt reads halo row pt + dy: the twelve (pt, dy) pairs of one (dx, k-step) touch
-        // only SIX halo rows.  The four accumulators are independent chains, so they are skewed by one tap row: fragment (halo row r,
-        // dx, c) is read ONCE and feeds acc[r] at tap (0, dx), acc[r-1] at (1, dx) and acc[r-2] at (2, dx) back to back — 72 reads
-        // per tile instead of 144 (0.5 ds_read_b128 per MFMA), no extra registers, and every accumulator still sees its MFMAs in
-        // tap-major order: the outputs are bit-identical.  Measured -1.0 ... -1.5 % per launch (profiles/r06_ab_c64_row_reuse.txt): the
-        // fragment reads are a small term of this kernel (profiles/r06_c64_half_reads_bound.txt).  Ring of four fragments, three ahead.
-        constexpr int FD = 3, FR = 4, NF = (PRG_C64_EXP & 1) ? 0 : 72;
-        c64_bf16x8 fr[FR];
-        auto foff = [](int n) { return ((n / 12) * HP + (n / 4) % 3) * ROWB + (n & 3) * 32; };   // n = (r * 3 + dx) * 4 + c
+      for (int j = 0; j < FD && j < NF; ++j) fr[j] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(j));
 #pragma unroll
-        for (int j = 0; j < FD && j < NF; ++j) fr[j] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(j));
+      for (int n = 0; n < NF; ++n) {
+        const int r = n / 12, dx = (n / 4) % 3, c = n & 3;
+        if (n + FD < NF) fr[(n + FD) % FR] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(n + FD));
 #pragma unroll
-        for (int n = 0; n < NF; ++n) {
-          const int r = n / 12, dx = (n / 4) % 3, c = n & 3;
-          if (n + FD < NF) fr[(n + FD) % FR] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(n + FD));
-#pragma unroll
-          for (int dy = 0; dy < 3; ++dy) {
-            const int pt = r - dy;
-            if (pt >= 0 && pt < 4) acc[pt] = mma(wf[dy * 3 + dx][c], fr[n % FR], acc[pt]);
-          }
-          __builtin_amdgcn_sched_barrier(0);
+        for (int dy = 0; dy < 3; ++dy) {
+          const int pt = r - dy;
+          if (pt >= 0 && pt < 4) acc[pt] = mma(wf[dy * 3 + dx][c], fr[n % FR], acc[pt]);
         }
-      } else {
-        c64_bf16x8 fx[2][4];
-#pragma unroll
-        for (int pt = 0; pt < 4; ++pt) fx[0][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB);
-#pragma unroll
-        for (int tap = 0; tap < ((PRG_C64_EXP & 1) ? 0 : 9); ++tap) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int cur = (tap * 4 + c) & 1, nxt = cur ^ 1;
-            const int ntap = c == 3 ? tap + 1 : tap, nc = c == 3 ? 0 : c + 1;   // the call after this one
-            if (ntap < 9) {
-              const int toff = ((ntap / 3) * HP + (ntap % 3)) * ROWB + nc * 32;
-              if constexpr ((PRG_C64_EXP & 64) != 0) {         // variant: the next call's four reads first, then the four MFMAs
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt) fx[nxt][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB + toff);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt)
-                  acc[pt] = mma(wf[tap][c], fx[cur][pt], acc[pt]);
-                __builtin_amdgcn_sched_barrier(0);
-              } else if constexpr ((PRG_C64_EXP & 128) != 0) { // variant: leave the interleave to the compiler
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                  fx[nxt][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB + toff);
-                  acc[pt] = mma(wf[tap][c], fx[cur][pt], acc[pt]);
-                }
-              } else if constexpr ((PRG_C64_EXP & 2048) != 0) { // timing experiment: ALL the reads, but MFMA pairs share their operands (garbage results)
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                  fx[nxt][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB + toff);
-                  asm volatile("" ::"v"(fx[cur][pt]));      // (the fragment is waited for where its MFMA would consume it)
-                  acc[pt] = mma(wf[tap][c], fx[cur][pt & ~1], acc[pt]);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-              } else if constexpr ((PRG_C64_EXP & 512) != 0) { // timing experiment: HALF the fragment reads (0.5 per MFMA; garbage results)
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                  if ((pt & 1) == 0) fx[nxt][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB + toff);
-                  acc[pt] = mma(wf[tap][c], fx[cur][pt & ~1], acc[pt]);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-              } else {
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                  fx[nxt][pt] = *reinterpret_cast<const c64_bf16x8*>(xb + pt * HP * ROWB + toff);
-                  acc[pt] = mma(wf[tap][c], fx[cur][pt], acc[pt]);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-              }
-            } else {
-#pragma unroll
-              for (int pt = 0; pt < 4; ++pt)
-                acc[pt] = mma(wf[tap][c], fx[cur][pt], acc[pt]);
-            }
-          }
-        }
+        __builtin_amdgcn_sched_barrier(0);
       }
       // ---- epilogue: lane holds pixel (row 4 wm + pt, col l31), channels wn*32 + 8 q + 4 hi + {0..3}
       int tb, ty0, tx0;
@@ -313,55 +235,42 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       // the partial sums of the previous tile have left this CU before the barrier its ticket is taken behind
       if (fuse_stats && L.gn_tickets) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       c64_barrier();                                       // halo s+1 is written; nobody reads buffer s & 1 any more
-      if (PRG_C64_EXP & 4) {                               // keep the accumulators live (no dead-code elimination of the MFMAs)
-#pragma unroll
-        for (int pt = 0; pt < 4; ++pt) asm volatile("" ::"v"(acc[pt]));
-      }
       float V[8];                                          // [sum | sumsq][q]
-      if (!(PRG_C64_EXP & 4)) {
-        float bv[4][4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        V[q] = 0.0f;
+        V[4 + q] = 0.0f;
+      }
+      char* const obase = reinterpret_cast<char*>(L.out) +
+                          ((((size_t)tb * d.Hout + ty0 + wm * 4) * d.Wout + tx0 + l31) * 64 + wn * 32 + 8 * hi) * 2;
+      const size_t orow = (size_t)d.Wout * 128;          // output bytes per image row
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+        uint32_t pk[8];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if constexpr ((PRG_C64_EXP & 256) != 0) {
-            const float4 b4 = *reinterpret_cast<const float4*>(biasp + 8 * q);
-            bv[q][0] = b4.x; bv[q][1] = b4.y; bv[q][2] = b4.z; bv[q][3] = b4.w;
-          } else {
-            bv[q][0] = bv[q][1] = bv[q][2] = bv[q][3] = 0.0f;        // (the bias rode in as the accumulators' initial value)
+          float v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            v[r] = acc[pt][4 * q + r];   // (the bias rode in as the accumulators' initial value)
+            V[q] += v[r];
+            V[4 + q] = fmaf(v[r], v[r], V[4 + q]);
           }
-          V[q] = 0.0f;
-          V[4 + q] = 0.0f;
+          pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : c64_pack(v[0], v[1]);
+          pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : c64_pack(v[2], v[3]);
         }
-        char* const obase = reinterpret_cast<char*>(L.out) +
-                            ((((size_t)tb * d.Hout + ty0 + wm * 4) * d.Wout + tx0 + l31) * 64 + wn * 32 + 8 * hi) * 2;
-        const size_t orow = (size_t)d.Wout * 128;          // output bytes per image row
+        // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper half
+        // of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m, half 1 with
+        // those of chunk 2m+1: one 16-byte store each
 #pragma unroll
-        for (int pt = 0; pt < 4; ++pt) {
-          uint32_t pk[8];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              v[r] = (PRG_C64_EXP & 256) ? acc[pt][4 * q + r] + bv[q][r] : acc[pt][4 * q + r];
-              V[q] += v[r];
-              V[4 + q] = fmaf(v[r], v[r], V[4 + q]);
-            }
-            pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : c64_pack(v[0], v[1]);
-            pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : c64_pack(v[2], v[3]);
-          }
-          // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper half
-          // of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m, half 1 with
-          // those of chunk 2m+1: one 16-byte store each
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-            const c64_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-            *reinterpret_cast<c64_u32x4*>(obase + pt * orow + m * 32) = o;
-          }
+        for (int m = 0; m < 2; ++m) {
+          const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
+          const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
+          const c64_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+          *reinterpret_cast<c64_u32x4*>(obase + pt * orow + m * 32) = o;
         }
       }
-      if (fuse_stats && !(PRG_C64_EXP & 4)) {
+      if (fuse_stats) {
         // 8 full-wave sums with a halving butterfly (conv_ws.hip's, one level shorter): fixed order, deterministic
         const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
         float A4[4], B2[2];
@@ -485,9 +394,9 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 #pragma unroll
       for (int k = 0; k < KU; ++k) {
         c64_u32x4 v = h[k];
-        if constexpr (PRO == 3 && !(PRG_C64_EXP & 32)) {
+        if constexpr (PRO == 3) {
           v = h16_silu8(v, ah2, bh2);
-        } else if constexpr (PRO && !(PRG_C64_EXP & 32)) {
+        } else if constexpr (PRO) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float lo = c64_silu(fmaf(c64_lo(v[j]), a8[2 * j], b8[2 * j]));
@@ -576,21 +485,10 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 
 }  // namespace
 
-int try_launch_conv3x3_c64w(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* coef_done, int* acc_done);   // conv_c64w.hip
-
 // Returns 1 when it launched, 0 when the shape is not covered (caller falls back), negative on error.
-int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* coef_done, int* acc_done) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_CONV_C64");
-    return e ? std::atoi(e) : 1;
-  }();
+int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
+  static const int enabled = env_int("PRG_CONV_C64", 1);
   if (!enabled) return 0;
-  {
-    // round 6: the one-wave-per-SIMD form (conv_c64w.hip: 64 channels of weights per wave, 0.5 fragment reads per MFMA) takes the
-    // launches it covers — probe calls included, so that conv_h16_pair_ok sees the dispatch that will run
-    const int r = try_launch_conv3x3_c64w(L, s, gn_nsplit_out, coef_done, acc_done);
-    if (r != 0) return r;
-  }
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
   if (d.C0 != 64 || d.C1 != 0 || d.Cout != 64 || d.CoutPad != 64 || d.kchunks != 2) return 0;
@@ -628,19 +526,13 @@ int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_n
     attr_done[variant].mark();
   }
   if (gn_nsplit_out) *gn_nsplit_out = fuse ? tiles_x * tiles_y * 2 * split_n : 0;
-  // the image-completing workgroup folds the statistics into the coefficients itself (no gn_coeff launch)
-  const bool use_acc = fuse && L.gn_acc != nullptr;          // fixed-point accumulators instead of slabs (+ no in-kernel ticket fold)
-  const bool fold = fuse && !use_acc && L.gn_tickets && L.gn_coef_a && L.gn_coef_b && L.gn.gamma && L.gn.beta && d.B <= kMaxTicketImages;
+  const bool use_acc = fuse && L.gn_acc != nullptr;          // fixed-point accumulators instead of slabs
   ConvLaunch<bf16_t> Lk = L;
-  if (!fold) Lk.gn_tickets = nullptr;
+  Lk.gn_tickets = nullptr;                                   // (the in-kernel ticket fold is retired: never launched)
   if (!use_acc) Lk.gn_acc = nullptr;
-  if (coef_done) *coef_done = fold ? 1 : 0;
   if (acc_done) *acc_done = use_acc ? 1 : 0;
-  // interleaved tile runs are ~2 % faster (neighbouring tiles run at the same time on neighbouring CUs of the XCD); the
-  // coefficient fold wants contiguous runs (one ticket per workgroup and image).  PRG_C64_INTERLEAVE=0/1 overrides.
-  static const int interleave_env = [] { const char* e = std::getenv("PRG_C64_INTERLEAVE"); return e ? std::atoi(e) : -1; }();
-  const int interleave = interleave_env >= 0 ? interleave_env : (fold ? 0 : 1);
-  const int flags = (fuse ? 1 : 0) | (interleave ? 2 : 0);
+  // interleaved tile runs are ~2 % faster (neighbouring tiles run at the same time on neighbouring CUs of the XCD)
+  const int flags = (fuse ? 1 : 0) | 2;
   if (L.probe) return 1;
   if (variant == 4) conv3x3_c64_kernel<0, true><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
   else if (pro == 3) conv3x3_c64_kernel<3, false><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);

@@ -505,12 +505,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
       const int c = it / NT, tap = it - NT * c;
       const char* p = wtile + (size_t)(tap * L.split_kchunks + c) * wstep;
       char* dst = Bs + ((it & (NS - 1)) * BN + pw * WPW * 8) * 128;
-      if constexpr (!ablate::ws_no_wdma) {
 #pragma unroll
-        for (int r = 0; r < WPW; ++r)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                           (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
-      }
+      for (int r = 0; r < WPW; ++r)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
+                                         (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
     };
     gload_b(0);
     if (niter > 1) gload_b(1);
@@ -551,13 +549,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
       const bool first = c < d.C0;
       const float* base = first ? L.src0 : L.src1;
       const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
-      if constexpr (!ablate::ws_no_halo) {
 #pragma unroll
-        for (int k = 0; k < NHP; ++k) {
-          const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-          g0[k] = p[0];
-          g1[k] = p[1];
-        }
+      for (int k = 0; k < NHP; ++k) {
+        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
+        g0[k] = p[0];
+        g1[k] = p[1];
       }
     };
     float4 (&g0)[NHP] = gA0;
@@ -567,13 +563,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
       const bool first = c < d.C0;
       const float* base = first ? L.src0 : L.src1;
       const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
-      if constexpr (!ablate::ws_no_halo) {
 #pragma unroll
-        for (int k = 0; k < NHP; ++k) {
-          const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-          g0[k] = p[0];
-          g1[k] = p[1];
-        }
+      for (int k = 0; k < NHP; ++k) {
+        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
+        g0[k] = p[0];
+        g1[k] = p[1];
       }
     };
     float pa[8], pb[8];
@@ -589,7 +583,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
     auto write_pass_set = [&](int buf, auto K, const float4 (&h0)[NHP], const float4 (&h1)[NHP]) {
       constexpr int k = decltype(K)::value;
       const int hp = prow + k * 32;
-      if (!ablate::ws_no_halo && hp < HALO) {
+      if (hp < HALO) {
         float v[8] = {h0[k].x, h0[k].y, h0[k].z, h0[k].w, h1[k].x, h1[k].y, h1[k].z, h1[k].w};
         if (L.pro_a) {
 #pragma unroll
@@ -696,12 +690,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
     constexpr int toff = UP ? (T / 2) * RSTRIDE + (T % 2) * PITCH : (T / 3) * RSTRIDE + (T % 3) * PITCH;
     const char* A = Ah + cb * HBYTES + toff + st * 32 + pho;
     const char* Bb = Bs + slot * (BN * 128);
-    if constexpr (ablate::ws_no_reads) {
-      (void)A; (void)Bb;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { asm volatile("" : "+v"(fa[st][i])); asm volatile("" : "+v"(fw[st][i])); }   // (opaque values, no LDS read)
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       fa[st][2 * i] = ld_frag(reinterpret_cast<const uint4*>(A + a_lane[i]));
@@ -715,11 +703,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
   };
   auto mfmas = [&](auto ST) {
     constexpr int st = decltype(ST)::value;
-    if constexpr (ablate::ws_no_mfma) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { asm volatile("" ::"v"(fa[st][i])); asm volatile("" ::"v"(fw[st][i])); }   // (keep the fragment loads alive)
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -741,30 +724,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
     // is free for the producers, this chunk's halo is complete.  No wait: a consumer's outstanding fragment loads read only
     // images that stay valid for another tap.
     if (T > 0 || c > 0) asm volatile("s_barrier" ::: "memory");
-    if constexpr (ablate::kInterleave) {
-      // one fragment read in each of the first eight MFMA shadows instead of eight reads in a row behind the twelfth MFMA: the four
-      // consumers are barrier-aligned, so a burst is 32 ds_read_b128 at once on the CU's LDS port (4 cycles each) against one
-      // 32-cycle MFMA of cover
-      __builtin_amdgcn_sched_barrier(0);
-      reads(IC<1>(), TAP, c & 1, it & (NS - 1));
-      mfmas(IC<0>());
-      interleave_8_reads_12_mfmas();
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), c & 1, (it + 1) & (NS - 1));
-      else if (more) reads(IC<0>(), IC<0>(), (c + 1) & 1, (it + 1) & (NS - 1));
-      mfmas(IC<1>());
-      interleave_8_reads_12_mfmas();
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-      reads(IC<1>(), TAP, c & 1, it & (NS - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(IC<0>());
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), c & 1, (it + 1) & (NS - 1));
-      else if (more) reads(IC<0>(), IC<0>(), (c + 1) & 1, (it + 1) & (NS - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(IC<1>());
-    }
+    // one fragment read in each of the first eight MFMA shadows instead of eight reads in a row behind the twelfth MFMA: the four
+    // consumers are barrier-aligned, so a burst is 32 ds_read_b128 at once on the CU's LDS port (4 cycles each) against one
+    // 32-cycle MFMA of cover
+    __builtin_amdgcn_sched_barrier(0);
+    reads(IC<1>(), TAP, c & 1, it & (NS - 1));
+    mfmas(IC<0>());
+    interleave_8_reads_12_mfmas();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), c & 1, (it + 1) & (NS - 1));
+    else if (more) reads(IC<0>(), IC<0>(), (c + 1) & 1, (it + 1) & (NS - 1));
+    mfmas(IC<1>());
+    interleave_8_reads_12_mfmas();
+    __builtin_amdgcn_sched_barrier(0);
     if constexpr (T == NT - 1) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -774,7 +746,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
           for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.0f; }
     }
   };
-  if constexpr (ablate::kConsumerPrio > 0) __builtin_amdgcn_s_setprio(ablate::kConsumerPrio);
   asm volatile("s_barrier" ::: "memory");                // the producers' prologue: chunk 0's halo, weight tiles 0 and 1
   reads(IC<0>(), IC<0>(), 0, 0);
   for (int c = 0; c < nchunks; ++c) {
@@ -929,12 +900,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     auto gload_next = [&](int it) {
       const char* p = wtile + (size_t)(tap_n * L.split_kchunks + c_n) * wstep;
       char* dst = Bs + ((it & (NS - 1)) * BN + pw * WPW * 8) * 128;
-      if constexpr (!ablate::p64_no_wdma) {
 #pragma unroll
-        for (int r = 0; r < WPW; ++r)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                           (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
-      }
+      for (int r = 0; r < WPW; ++r)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
+                                         (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
       if (++tap_n == NT) { tap_n = 0; if (++c_n == nchunks) c_n = 0; }
     };
     gload_next(0);
@@ -988,13 +957,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
       const bool first = c < d.C0;
       const float* base = first ? L.src0 : L.src1;
       const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
-      if constexpr (!ablate::p64_no_halo) {
 #pragma unroll
-        for (int k = 0; k < NHP; ++k) {
-          const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-          g0[k] = p[0];
-          g1[k] = p[1];
-        }
+      for (int k = 0; k < NHP; ++k) {
+        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
+        g0[k] = p[0];
+        g1[k] = p[1];
       }
     };
     float pa[8], pb[8];
@@ -1009,7 +976,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     };
     auto write_pass = [&](int buf, auto K) {
       constexpr int k = decltype(K)::value;
-      if (!ablate::p64_no_halo && hyx[k] >= 0) {
+      if (hyx[k] >= 0) {
         float v[8] = {g0[k].x, g0[k].y, g0[k].z, g0[k].w, g1[k].x, g1[k].y, g1[k].z, g1[k].w};
         if (L.pro_a) {
 #pragma unroll
@@ -1093,12 +1060,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
   f16x8 fa[2][4], fw[2][4];                              // [k16 step][A: (hi, lo) x row tile | W: (hi, lo) x column tile]
   auto reads = [&](auto ST, auto TAP, int cb, int slot) {
     constexpr int st = decltype(ST)::value, T = decltype(TAP)::value;
-    if constexpr (ablate::p64_no_reads) {
-      (void)cb; (void)slot; (void)T;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { asm volatile("" : "+v"(fa[st][i])); asm volatile("" : "+v"(fw[st][i])); }   // (opaque values, no LDS read)
-      return;
-    }
     constexpr int toff = (T / 3) * RSTRIDE + (T % 3) * PITCH;
     const char* A = Ah + cb * HBYTES + toff + st * 32;
     const char* Bb = Bs + slot * (BN * 128);
@@ -1115,11 +1076,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
   };
   auto mfmas = [&](auto ST) {
     constexpr int st = decltype(ST)::value;
-    if constexpr (ablate::p64_no_mfma) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { asm volatile("" ::"v"(fa[st][i])); asm volatile("" ::"v"(fw[st][i])); }   // (keep the fragment loads alive)
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1141,27 +1097,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     // it - 1's slot is free for the producers, this chunk's halo is complete.  No wait: a consumer's outstanding fragment loads
     // read only images that stay valid for another tap.
     if (it > 0) asm volatile("s_barrier" ::: "memory");
-    if constexpr (ablate::kInterleave) {
-      __builtin_amdgcn_sched_barrier(0);
-      reads(IC<1>(), TAP, g & 1, it & (NS - 1));
-      mfmas(IC<0>());
-      interleave_8_reads_12_mfmas();
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), g & 1, (it + 1) & (NS - 1));
-      else if (more) reads(IC<0>(), IC<0>(), (g + 1) & 1, (it + 1) & (NS - 1));
-      mfmas(IC<1>());
-      interleave_8_reads_12_mfmas();
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-      reads(IC<1>(), TAP, g & 1, it & (NS - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(IC<0>());
-      __builtin_amdgcn_sched_barrier(0);
-      if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), g & 1, (it + 1) & (NS - 1));
-      else if (more) reads(IC<0>(), IC<0>(), (g + 1) & 1, (it + 1) & (NS - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(IC<1>());
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    reads(IC<1>(), TAP, g & 1, it & (NS - 1));
+    mfmas(IC<0>());
+    interleave_8_reads_12_mfmas();
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (T < NT - 1) reads(IC<0>(), IC<(T + 1) % NT>(), g & 1, (it + 1) & (NS - 1));
+    else if (more) reads(IC<0>(), IC<0>(), (g + 1) & 1, (it + 1) & (NS - 1));
+    mfmas(IC<1>());
+    interleave_8_reads_12_mfmas();
+    __builtin_amdgcn_sched_barrier(0);
     if constexpr (T == NT - 1) {                         // the 288-term partial of this channel chunk
       // (a tile's FIRST partial is assigned, not added to a zeroed total: 0 + x = x, and the epilogue no longer zeroes 64 registers)
       if (first) {
@@ -1181,7 +1126,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
       }
     }
   };
-  if constexpr (ablate::kConsumerPrio > 0) __builtin_amdgcn_s_setprio(ablate::kConsumerPrio);
   asm volatile("s_barrier" ::: "memory");                // barrier(0): the producers' prologue — tile 0's first halo, weight tiles 0 and 1
   reads(IC<0>(), IC<0>(), 0, 0);
   const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 64;          // 8, 16, 32 or 64 when the statistics are fused
@@ -1225,11 +1169,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
         for (int e = 0; e < 16; ++e) {
           // (sc is an exact power of two: the fused form rounds once, exactly where the product-then-sum form rounds — same bits)
           const float v = __builtin_fmaf(tot[i][j][e], sc, bv);
-          if constexpr (ablate::p64_no_store) {
-            if (v == 1.2345e-30f) r0[0] = v;     // (keeps the accumulators alive, stores nothing)
-          } else {
-            ((e >> 3) ? r1 : r0)[((e & 3) + 8 * ((e >> 2) & 1)) * BN] = v;
-          }
+          ((e >> 3) ? r1 : r0)[((e & 3) + 8 * ((e >> 2) & 1)) * BN] = v;
           s1 += v;
           q1 = fmaf(v, v, q1);
         }
@@ -1465,11 +1405,6 @@ static int launch_split_halo(const ConvLaunch<float>& L, hipStream_t s, int fuse
     PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<TH, TW, NS>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     attr_done.mark();
-    if (std::getenv("PRG_SPLIT_DEBUG")) {
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv3x3_split_kernel<TH, TW, NS>, 256, lds);
-      fprintf(stderr, "conv3x3_split_kernel<%d,%d,%d>: %zu bytes of LDS, %d workgroups per CU\n", TH, TW, NS, lds, nb);
-    }
   }
   conv3x3_split_kernel<TH, TW, NS><<<dim3(tiles_x * tiles_y * tiles_n * d.B), 256, lds, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
   PRG_LAUNCH_CHECK();
@@ -1565,14 +1500,6 @@ int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsp
   // the activated residual (ConvLaunch::res_a: the ResnetBlock tail in a 1x1 res_conv's epilogue) is the shared transposing
   // epilogue's feature: the gather kernel below has it, the 3x3 kernels do not
   if (L.res_a && !(d.KH == 1 && d.KW == 1)) return 0;
-  // precision budget (tools/gpu_r5_precision.sh): PRG_SPLIT_EXACT is a bit mask of convolution classes handed back to the exact-f32
-  // kernels — 1: 3x3 / s1 (Block.proj, the last down conv, the top level's "Upsample"), 2: 1x1 (res_conv, attention projections of
-  // the unfused blocks), 4: 4x4 / s2 (Downsample), 8: 3x3 on the upsampled image (Upsample).  0 (default) = every class split.
-  static const int exact_mask = [] { const char* e = std::getenv("PRG_SPLIT_EXACT"); return e ? std::atoi(e) : 0; }();
-  if (exact_mask && !L.probe) {
-    const int cls = d.KH == 1 ? 2 : d.KH == 4 ? 4 : d.ups ? 8 : 1;
-    if (exact_mask & cls) return 0;
-  }
   const int64_t M64 = (int64_t)d.B * d.Hout * d.Wout;
   if ((int64_t)d.B * d.Hin * d.Win >= ((int64_t)1 << 31) || M64 >= ((int64_t)1 << 31)) return 0;
   const int M = (int)M64;
@@ -1585,8 +1512,6 @@ int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsp
     auto fuse = [&](int TH, int TW, int BN) {
       return want_stats && cpg % 8 == 0 && cpg <= BN && (W / TW) * (H / TH) <= kGnMaxSplit;
     };
-    // Cout % 128 == 0: the wave-specialised kernel (128-pixel x 128-channel tiles, one workgroup per CU); PRG_SPLIT_WS=0: never
-    static const int ws_on = [] { const char* e = std::getenv("PRG_SPLIT_WS"); return e ? std::atoi(e) : 1; }();
     // The Upsample convs as four 2 x 2-tap sub-pixel convolutions (4 / 9 of their MFMAs: 0.3 ms = 2.5 % of an f16x3 evaluation): OFF by
     // default.  Per evaluation it is as accurate as the nine-tap form (test_split_upsample_conv_against_float64: rms 2.0e-7 against
     // torch-CPU's 2.9e-7), but every change of the rounding pattern RE-DRAWS the long chains' distance from the reference — over nine
@@ -1594,8 +1519,8 @@ int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsp
     // (profiles/r05_chain_metric_spread_f16x3.txt; the reference's own 1-vs-8-thread spread is 4.7e-5 m) — and round 5 tried it as the
     // default: G21b drew 5.9e-5 m at B = 1 and 1.001e-4 m at B = 8 (the batch that selects the persistent 64-channel kernel).  The
     // mode's claim is the LITERAL 1e-4 m on that chain at the tested batches, so the nine-tap form stays.  PRG_SPLIT_UP2X2=1: on.
-    static const int up_on = [] { const char* e = std::getenv("PRG_SPLIT_UP2X2"); return e ? std::atoi(e) : 0; }();
-    if (ws_on && up_on && d.ups && L.w_up_split && d.C1 == 0 && d.Cout % 128 == 0 && d.Win % 16 == 0 && d.Hin % 8 == 0 && d.Hout == 2 * d.Hin &&
+    static const int up_on = env_int("PRG_SPLIT_UP2X2", 0);
+    if (up_on && d.ups && L.w_up_split && d.C1 == 0 && d.Cout % 128 == 0 && d.Win % 16 == 0 && d.Hin % 8 == 0 && d.Hout == 2 * d.Hin &&
         d.Wout == 2 * d.Win && !L.residual && !L.pro_a && !want_stats) {
       rc = launch_split_ws_up(L, s);
       return rc ? rc : 1;
@@ -1606,22 +1531,21 @@ int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsp
       const int r = try_launch_conv3x3_split_w512(L, s, want_stats, gn_nsplit_out);
       if (r != 0) return r;
     }
-    if (ws_on && d.Cout % 128 == 0 && W % 16 == 0 && H % 8 == 0 && !L.residual) {
+    // Cout % 128 == 0: the wave-specialised kernel (128-pixel x 128-channel tiles, one workgroup per CU)
+    if (d.Cout % 128 == 0 && W % 16 == 0 && H % 8 == 0 && !L.residual) {
       const int tiles = (W / 16) * (H / 8) * 2;
       const int f = want_stats && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && tiles <= kGnMaxSplit;
       if (f || !want_stats) { rc = launch_split_ws(L, s, f, gn_nsplit_out); return rc ? rc : 1; }
     }
     // Cout = 64 and a launch that fills the chip (>= one 16 x 16 tile per CU): the persistent kernel; PRG_SPLIT_P64=0: never,
     // PRG_SPLIT_P64=<n>: from n tiles (tests force it at small shapes)
-    static const int p64_min = [] { const char* e = std::getenv("PRG_SPLIT_P64"); return e ? std::atoi(e) : 256; }();
+    static const int p64_min = env_int("PRG_SPLIT_P64", 256);
     if (p64_min > 0 && d.Cout == 64 && W % 16 == 0 && H % 16 == 0 && !L.residual && !L.res_a && d.B * (W / 16) * (H / 16) >= p64_min &&
         (d.C0 + d.C1) >= 64) {
       const int tiles = (W / 16) * (H / 16) * 4;
       const int f = want_stats && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && tiles <= kGnMaxSplit;
       if (f || !want_stats) { rc = launch_split_p64(L, s, f, gn_nsplit_out); return rc ? rc : 1; }
     }
-    static const int pref32 = [] { const char* e = std::getenv("PRG_SPLIT_TW32"); return e ? std::atoi(e) : 0; }();
-    if (pref32 && W % 32 == 0 && H % 4 == 0) { rc = launch_split_halo<4, 32>(L, s, fuse(4, 32, 64), gn_nsplit_out); return rc ? rc : 1; }
     if (W % 16 == 0 && H % 8 == 0) { rc = launch_split_halo<8, 16>(L, s, fuse(8, 16, 64), gn_nsplit_out); return rc ? rc : 1; }
     if (W % 32 == 0 && H % 4 == 0) { rc = launch_split_halo<4, 32>(L, s, fuse(4, 32, 64), gn_nsplit_out); return rc ? rc : 1; }
   }
@@ -1651,9 +1575,8 @@ void pack_conv_weight_split(const float* w, int Cout, int Cin, int KH, int KW, s
   // max|w| into [2^9, 2^10) (hi exact to 2^-2, lo's 2^-25 floor = 2^-35 of the maximum; |w| < 2^10 stays far from f16's 65504
   // with O(100) activations in the other operand being a float32-accumulated product), and the kernels multiply the float32
   // total by the inverse (exact) before the bias: split_scale.
-  static const int wscale_on = [] { const char* e = std::getenv("PRG_SPLIT_WSCALE"); return e ? std::atoi(e) : 1; }();
   std::vector<float> mul((size_t)Cout, 1.0f);
-  if (oscale && wscale_on) {
+  if (oscale) {
     const size_t per = (size_t)Cin * KH * KW;
     for (int n = 0; n < Cout; ++n) {
       float m = 0.0f;

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 // whole f16x3 pipeline +2.4 %; with half as many workgroups as the 128-pixel kernel a launch below that size leaves CUs idle:
 // 256 -> 256 @16x16 at B = 64 ran 83 us against 52).  PRG_SPLIT_W512=0: never; =2: every shape it covers (tests).
 int try_launch_conv3x3_split_w512(const ConvLaunch<float>& L, hipStream_t s, int want_stats, int* gn_nsplit_out) {
-  static const int on = [] { const char* e = std::getenv("PRG_SPLIT_W512"); return e ? std::atoi(e) : 1; }();
+  static const int on = env_int("PRG_SPLIT_W512", 1);
   if (!on) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Cout % 128 == 0 && d.Wout % 16 == 0 && d.Hout % 16 == 0 && !L.residual &&

@@ -3,7 +3,6 @@
 // pipeline that interleaves a consumer's fragment reads with its MFMAs.
 #pragma once
 #include "conv_epi.h"
-#include "conv_split_ablate.h"
 
 namespace prg {
 

@@ -46,12 +46,6 @@ typedef __attribute__((ext_vector_type(8))) _Float16 w2_f16x8;
 
 namespace {
 
-// Timing experiments only (results become garbage): 1 consumers skip reads + MFMAs, 2 producers skip the halo, 4 no
-// epilogue, 8 producers skip the weights, 16 no prologue arithmetic.
-#ifndef PRG_W256_EXP
-#define PRG_W256_EXP 0
-#endif
-
 constexpr int kCH = 64, BN = 128, ROWB = 144;
 
 template <int TW>
@@ -221,17 +215,15 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     w2_barrier<true>();                                      // halo 0 and weight tiles 0, 1 are in LDS; the bias too
     // Round 5: the accumulators START at the bias (here, and again at the end of every tile's epilogue, where the bias registers are
     // live anyway) instead of at zero: the epilogue's 128 bias additions per tile and wave are gone; the sum's rounding order changes
-    // (bias first), far below the bf16 / f16 output rounding.  PRG_W256_EXP & 128: the old form (A/B builds).
-    if constexpr (!(PRG_W256_EXP & 128)) {
+    // (bias first), far below the bf16 / f16 output rounding.
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
+      for (int q = 0; q < 4; ++q) {
+        const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
 #pragma unroll
-          for (int pt = 0; pt < 4; ++pt) { acc[ct][pt][4 * q] = b4.x; acc[ct][pt][4 * q + 1] = b4.y; acc[ct][pt][4 * q + 2] = b4.z; acc[ct][pt][4 * q + 3] = b4.w; }
-        }
-    }
+        for (int pt = 0; pt < 4; ++pt) { acc[ct][pt][4 * q] = b4.x; acc[ct][pt][4 * q + 1] = b4.y; acc[ct][pt][4 * q + 2] = b4.z; acc[ct][pt][4 * q + 3] = b4.w; }
+      }
     {
       constexpr int t0 = w2_toff<MODE, HP>(0);
       W2_LW(0, 0, 0, 0); W2_LX(0, 0, xa, t0, 0); W2_LX(0, 1, xa, t0, 0); W2_LX(0, 2, xa, t0, 0); W2_LX(0, 3, xa, t0, 0); W2_LW(0, 1, 0, 0);
@@ -249,7 +241,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
         const int toff = w2_toff<MODE, HP>(p);
         const int toffN = w2_toff<MODE, HP>(p == NPH - 1 ? 0 : p + 1);
 #pragma unroll
-        for (int call = 0; call < ((PRG_W256_EXP & 1) ? 0 : 4); ++call) {
+        for (int call = 0; call < 4; ++call) {
           const int cur = call & 1, nxt = cur ^ 1;           // 4 NPH calls per step (even): the set parity is the call parity
           // the next call's six fragments, one load between two MFMAs, earliest-needed first
           if (call < 3) {
@@ -282,93 +274,81 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
           // tile finished.  Lane holds pixel (group pt, lpx), channels ct*32 + 8q + 4hi + {0..3} of the wave's 64.
           int tb, ty0, tx0;
           tm.decode(it, tb, ty0, tx0, TH, TW);
-          if (PRG_W256_EXP & 4) {
+          const int oph = MODE == 2 ? tm.phase(it) : 0, osc = MODE == 2 ? 2 : 1;   // MODE 2: output pixel (2 y + dy, 2 x + dx)
+          const int ody = dual ? oph : oph >> 1, odx = dual ? wn : oph & 1, och = dual ? 0 : tm.tn * BN + wn * 64;
+          char* const obase = reinterpret_cast<char*>(L.out) +
+                              ((((size_t)tb * d.Hout + osc * (ty0 + prow) + ody) * d.Wout + osc * (tx0 + pcol) + odx) * d.Cout + och + 8 * hi) * 2;
+          const size_t optb = (size_t)GROWS * osc * d.Wout * d.Cout * 2;   // bytes between the wave's pixel groups
+          float V[16];                                     // [sum | sum of squares][ct][q]
+          const bool o16 = L.out_f16 != 0;                  // (wave-uniform; MODE 1 = Downsample never stores f16)
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
+          for (int ct = 0; ct < 2; ++ct) {
+            float bv[4][4];
 #pragma unroll
-              for (int pt = 0; pt < 4; ++pt) asm volatile("" ::"v"(acc[ct][pt]));
-          } else {
-            const int oph = MODE == 2 ? tm.phase(it) : 0, osc = MODE == 2 ? 2 : 1;   // MODE 2: output pixel (2 y + dy, 2 x + dx)
-            const int ody = dual ? oph : oph >> 1, odx = dual ? wn : oph & 1, och = dual ? 0 : tm.tn * BN + wn * 64;
-            char* const obase = reinterpret_cast<char*>(L.out) +
-                                ((((size_t)tb * d.Hout + osc * (ty0 + prow) + ody) * d.Wout + osc * (tx0 + pcol) + odx) * d.Cout + och + 8 * hi) * 2;
-            const size_t optb = (size_t)GROWS * osc * d.Wout * d.Cout * 2;   // bytes between the wave's pixel groups
-            float V[16];                                     // [sum | sum of squares][ct][q]
-            const bool o16 = L.out_f16 != 0;                  // (wave-uniform; MODE 1 = Downsample never stores f16)
+            for (int q = 0; q < 4; ++q) {
+              const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
+              bv[q][0] = b4.x; bv[q][1] = b4.y; bv[q][2] = b4.z; bv[q][3] = b4.w;
+              V[ct * 4 + q] = 0.0f;
+              V[8 + ct * 4 + q] = 0.0f;
+            }
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-              float bv[4][4];
+            for (int pt = 0; pt < 4; ++pt) {
+              uint32_t pk[8];
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
-                bv[q][0] = b4.x; bv[q][1] = b4.y; bv[q][2] = b4.z; bv[q][3] = b4.w;
-                V[ct * 4 + q] = 0.0f;
-                V[8 + ct * 4 + q] = 0.0f;
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  v[r] = acc[ct][pt][4 * q + r];
+                  acc[ct][pt][4 * q + r] = bv[q][r];          // the next tile's initial value
+                  V[ct * 4 + q] += v[r];
+                  V[8 + ct * 4 + q] = fmaf(v[r], v[r], V[8 + ct * 4 + q]);
+                }
+                if (!MODE && o16) {
+                  pk[2 * q] = h16_pack(v[0], v[1]);
+                  pk[2 * q + 1] = h16_pack(v[2], v[3]);
+                } else {
+                  pk[2 * q] = w2_pack(v[0], v[1]);
+                  pk[2 * q + 1] = w2_pack(v[2], v[3]);
+                }
               }
+              // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
+              // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
+              // half 1 with those of chunk 2m+1 — one 16-byte store each.
 #pragma unroll
-              for (int pt = 0; pt < 4; ++pt) {
-                uint32_t pk[8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  float v[4];
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) {
-                    if constexpr ((PRG_W256_EXP & 128) != 0) {
-                      v[r] = acc[ct][pt][4 * q + r] + bv[q][r];
-                      acc[ct][pt][4 * q + r] = 0.0f;
-                    } else {
-                      v[r] = acc[ct][pt][4 * q + r];
-                      acc[ct][pt][4 * q + r] = bv[q][r];          // the next tile's initial value
-                    }
-                    V[ct * 4 + q] += v[r];
-                    V[8 + ct * 4 + q] = fmaf(v[r], v[r], V[8 + ct * 4 + q]);
-                  }
-                  if (!MODE && o16) {
-                    pk[2 * q] = h16_pack(v[0], v[1]);
-                    pk[2 * q + 1] = h16_pack(v[2], v[3]);
-                  } else {
-                    pk[2 * q] = w2_pack(v[0], v[1]);
-                    pk[2 * q + 1] = w2_pack(v[2], v[3]);
-                  }
-                }
-                // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
-                // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
-                // half 1 with those of chunk 2m+1 — one 16-byte store each.
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                  const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-                  const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-                  const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-                  *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
-                }
+              for (int m = 0; m < 2; ++m) {
+                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
+                const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+                *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
               }
             }
-            if (fuse_stats) {
-              // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
-              const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-              float A8[8], B4[4], C2[2];
+          }
+          if (fuse_stats) {
+            // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
+            const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+            float A8[8], B4[4], C2[2];
 #pragma unroll
-              for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
+            for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
 #pragma unroll
-              for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
+            for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
 #pragma unroll
-              for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
-              float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
-              D += w2_swz<16>(D);
-              D += __shfl_xor(D, 32, 64);
-              // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
-              if (gn_per >= 2) D += w2_swz<8>(D);
-              if (gn_per >= 4) D += w2_swz<4>(D);
-              if (gn_per >= 8) D += w2_dpp<0x4E>(D);
-              const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
-              const int cc = i & 7;
-              if (lane < 16 && (cc & (gn_per - 1)) == 0) {
-                const int nsplit = tiles_x * tiles_y * 2;
-                const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
-                const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
-                if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
-                else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
-              }
+            for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
+            float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
+            D += w2_swz<16>(D);
+            D += __shfl_xor(D, 32, 64);
+            // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
+            if (gn_per >= 2) D += w2_swz<8>(D);
+            if (gn_per >= 4) D += w2_swz<4>(D);
+            if (gn_per >= 8) D += w2_dpp<0x4E>(D);
+            const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
+            const int cc = i & 7;
+            if (lane < 16 && (cc & (gn_per - 1)) == 0) {
+              const int nsplit = tiles_x * tiles_y * 2;
+              const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
+              const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
+              if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
+              else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
             }
           }
         }
@@ -541,16 +521,16 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     // hardware's range check returns zeros — no always-mapped stand-in pixel, and without a prologue no select before the
     // LDS write either (conv_c64.hip's producers, same idea).
     auto issue_unit = [&](int k) {                           // k is a compile-time constant at every call site
-      const bool ok = (hedge[k] & ld_tedge) == 0 && !(PRG_W256_EXP & 2);
+      const bool ok = (hedge[k] & ld_tedge) == 0;
       const unsigned voff = (__umul24(hpix[k], ld_cs2) + (unsigned)(slot * 16)) | (ok ? 0u : 0xffffffffu);   // (branch-free)
       hreg[k] = __builtin_amdgcn_raw_buffer_load_b128(ld_rsrc, (int)voff, 0, 0);
       if constexpr (PRO) hvalid_nxt |= (ok ? 1u : 0u) << k;
     };
     auto write_unit = [&](int k, int bufoff) {
       w2_u32x4 v = hreg[k];
-      if constexpr (PRO == 3 && !(PRG_W256_EXP & 16)) {
+      if constexpr (PRO == 3) {
         v = h16_silu8(v, ah2, bh2);
-      } else if constexpr (PRO && !(PRG_W256_EXP & 16)) {
+      } else if constexpr (PRO) {
         const float a8[8] = {cf[0].x, cf[0].y, cf[0].z, cf[0].w, cf[1].x, cf[1].y, cf[1].z, cf[1].w};
         const float b8[8] = {cf[2].x, cf[2].y, cf[2].z, cf[2].w, cf[3].x, cf[3].y, cf[3].z, cf[3].w};
 #pragma unroll
@@ -573,7 +553,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     auto w_issue = [&](int set, const char* p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        wset[set][j] = *reinterpret_cast<const w2_u32x4*>(p + ((PRG_W256_EXP & 8) ? 0 : (j & wj_mask) * 2048) + ((dual && j >= 2) ? wsub : (size_t)0));
+        wset[set][j] = *reinterpret_cast<const w2_u32x4*>(p + (j & wj_mask) * 2048 + ((dual && j >= 2) ? wsub : (size_t)0));
     };
     auto w_write = [&](int set, int ring) {
 #pragma unroll
@@ -759,92 +739,83 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
         const int toffN = p == 8 ? 0 : ((p + 1) / 3) * HP + (p + 1) % 3;
         const char* const bd = p == 8 ? xn : xa;
         const char* const bs = p == 8 ? sn : sa;
-        if (!(PRG_W256_EXP & 1)) {
-          ldw(nxt, 0, ringN); W2X_MM(cur, 0, 0); W2X_SB();
-          ldw(nxt, 1, ringN); W2X_MM(cur, 1, 0); W2X_SB();
-          ldx(0, bd, bs, toffN); W2X_MM(cur, 0, 1); W2X_MM(cur, 1, 1); W2X_SB();
-          ldx(1, bd, bs, toffN); W2X_MM(cur, 0, 2); W2X_MM(cur, 1, 2); W2X_SB();
-          ldx(2, bd, bs, toffN); W2X_MM(cur, 0, 3); W2X_MM(cur, 1, 3); W2X_SB();
-          ldx(3, bd, bs, toffN); W2X_SB();
-        }
+        ldw(nxt, 0, ringN); W2X_MM(cur, 0, 0); W2X_SB();
+        ldw(nxt, 1, ringN); W2X_MM(cur, 1, 0); W2X_SB();
+        ldx(0, bd, bs, toffN); W2X_MM(cur, 0, 1); W2X_MM(cur, 1, 1); W2X_SB();
+        ldx(1, bd, bs, toffN); W2X_MM(cur, 0, 2); W2X_MM(cur, 1, 2); W2X_SB();
+        ldx(2, bd, bs, toffN); W2X_MM(cur, 0, 3); W2X_MM(cur, 1, 3); W2X_SB();
+        ldx(3, bd, bs, toffN); W2X_SB();
         if (p == 8 && tile_end) {
           // tile finished.  Lane holds pixel (group pt, lpx), channels ct*32 + 8q + 4hi + {0..3} of the wave's 64.
           int tb, ty0, tx0;
           tm.decode(it, tb, ty0, tx0, TH, TW);
-          if (PRG_W256_EXP & 4) {
+          char* const obase = reinterpret_cast<char*>(L.out) +
+                              ((((size_t)tb * d.Hout + ty0 + prow) * d.Wout + tx0 + pcol) * d.Cout + tm.tn * BN + wn * 64 + 8 * hi) * 2;
+          const size_t optb = (size_t)GROWS * d.Wout * d.Cout * 2;   // bytes between the wave's pixel groups
+          float V[16];                                     // [sum | sum of squares][ct][q]
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
+          for (int ct = 0; ct < 2; ++ct) {
+            float bv[4][4];
 #pragma unroll
-              for (int pt = 0; pt < 4; ++pt) asm volatile("" ::"v"(acc[ct][pt]));
-          } else {
-            char* const obase = reinterpret_cast<char*>(L.out) +
-                                ((((size_t)tb * d.Hout + ty0 + prow) * d.Wout + tx0 + pcol) * d.Cout + tm.tn * BN + wn * 64 + 8 * hi) * 2;
-            const size_t optb = (size_t)GROWS * d.Wout * d.Cout * 2;   // bytes between the wave's pixel groups
-            float V[16];                                     // [sum | sum of squares][ct][q]
+            for (int q = 0; q < 4; ++q) {
+              const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
+              bv[q][0] = b4.x; bv[q][1] = b4.y; bv[q][2] = b4.z; bv[q][3] = b4.w;
+              V[ct * 4 + q] = 0.0f;
+              V[8 + ct * 4 + q] = 0.0f;
+            }
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-              float bv[4][4];
+            for (int pt = 0; pt < 4; ++pt) {
+              uint32_t pk[8];
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const float4 b4 = *reinterpret_cast<const float4*>(bias_lds + wn * 64 + ct * 32 + 8 * q + 4 * hi);
-                bv[q][0] = b4.x; bv[q][1] = b4.y; bv[q][2] = b4.z; bv[q][3] = b4.w;
-                V[ct * 4 + q] = 0.0f;
-                V[8 + ct * 4 + q] = 0.0f;
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  v[r] = acc[ct][pt][4 * q + r] + bv[q][r];
+                  V[ct * 4 + q] += v[r];
+                  V[8 + ct * 4 + q] = fmaf(v[r], v[r], V[8 + ct * 4 + q]);
+                  acc[ct][pt][4 * q + r] = 0.0f;
+                }
+                pk[2 * q] = w2_pack(v[0], v[1]);
+                pk[2 * q + 1] = w2_pack(v[2], v[3]);
               }
+              // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
+              // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
+              // half 1 with those of chunk 2m+1 — one 16-byte store each.
 #pragma unroll
-              for (int pt = 0; pt < 4; ++pt) {
-                uint32_t pk[8];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  float v[4];
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) {
-                    v[r] = acc[ct][pt][4 * q + r] + bv[q][r];
-                    V[ct * 4 + q] += v[r];
-                    V[8 + ct * 4 + q] = fmaf(v[r], v[r], V[8 + ct * 4 + q]);
-                    acc[ct][pt][4 * q + r] = 0.0f;
-                  }
-                  pk[2 * q] = w2_pack(v[0], v[1]);
-                  pk[2 * q + 1] = w2_pack(v[2], v[3]);
-                }
-                // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
-                // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
-                // half 1 with those of chunk 2m+1 — one 16-byte store each.
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                  const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-                  const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-                  const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-                  *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
-                }
+              for (int m = 0; m < 2; ++m) {
+                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
+                const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+                *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
               }
             }
-            if (fuse_stats) {
-              // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
-              const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-              float A8[8], B4[4], C2[2];
+          }
+          if (fuse_stats) {
+            // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
+            const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+            float A8[8], B4[4], C2[2];
 #pragma unroll
-              for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
+            for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
 #pragma unroll
-              for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
+            for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
 #pragma unroll
-              for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
-              float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
-              D += w2_swz<16>(D);
-              D += __shfl_xor(D, 32, 64);
-              // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
-              if (gn_per >= 2) D += w2_swz<8>(D);
-              if (gn_per >= 4) D += w2_swz<4>(D);
-              if (gn_per >= 8) D += w2_dpp<0x4E>(D);
-              const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
-              const int cc = i & 7;
-              if (lane < 16 && (cc & (gn_per - 1)) == 0) {
-                const int nsplit = tiles_x * tiles_y * 2;
-                const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
-                const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
-                if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
-                else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
-              }
+            for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
+            float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
+            D += w2_swz<16>(D);
+            D += __shfl_xor(D, 32, 64);
+            // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
+            if (gn_per >= 2) D += w2_swz<8>(D);
+            if (gn_per >= 4) D += w2_swz<4>(D);
+            if (gn_per >= 8) D += w2_dpp<0x4E>(D);
+            const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
+            const int cc = i & 7;
+            if (lane < 16 && (cc & (gn_per - 1)) == 0) {
+              const int nsplit = tiles_x * tiles_y * 2;
+              const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
+              const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
+              if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
+              else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
             }
           }
         }
@@ -969,19 +940,10 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
       }
     };
     auto issue_unit = [&](int k) {
-      const bool ok = (hedge[k] & ld_tedge) == 0 && !(PRG_W256_EXP & 2);   // 2: timing experiment, every unit loads the tile origin
+      const bool ok = (hedge[k] & ld_tedge) == 0;
       const unsigned pix = ok ? hpix[k] : ld_dummy;
       const unsigned voff = __umul24(pix, ld_cs2) + (unsigned)(slot * 16);
-      if constexpr (!PRO && (PRG_W256_EXP & 64)) {
-        // 64: CAP EXPERIMENT (tools/gpu_r5_mxcap.sh): what "MX activations in memory" could buy at most — the unit gathers 8 bytes
-        // (as if the producer had stored e4m3) plus one dword standing in for the block scales, and write_unit stores them as they
-        // are (masked to finite e4m3, scale 1): HALF the gather bytes, NO quantisation arithmetic.  Results are meaningless.
-        const uint2 h = *reinterpret_cast<const uint2*>(ld_base + (voff >> 1));
-        const unsigned sc = *reinterpret_cast<const unsigned*>(ld_base + ((voff >> 5) << 2));
-        hreg[k] = w2_u32x4{h.x, h.y, sc, 0u};
-      } else {
-        hreg[k] = *reinterpret_cast<const w2_u32x4*>(ld_base + voff);
-      }
+      hreg[k] = *reinterpret_cast<const w2_u32x4*>(ld_base + voff);
       hvalid_nxt |= (ok ? 1u : 0u) << k;
     };
     // one unit = 8 channels of one halo pixel: optional prologue (its result rounded to bf16, like the tensor it replaces),
@@ -992,7 +954,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     __builtin_amdgcn_s_setreg((1 | (23 << 6) | (0 << 11)), 1);          // hwreg(MODE, offset 23, 1 bit) = FP16_OVFL
     auto write_unit = [&](int k, int buf) {
       w2_u32x4 v = hreg[k];
-      if constexpr (PRO && !(PRG_W256_EXP & 16)) {
+      if constexpr (PRO) {
         const float a8[8] = {cf[0].x, cf[0].y, cf[0].z, cf[0].w, cf[1].x, cf[1].y, cf[1].z, cf[1].w};
         const float b8[8] = {cf[2].x, cf[2].y, cf[2].z, cf[2].w, cf[3].x, cf[3].y, cf[3].z, cf[3].w};
 #pragma unroll
@@ -1000,15 +962,6 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
           v[j] = w2_pack(w2_silu(fmaf(w2_lo(v[j]), a8[2 * j], b8[2 * j])), w2_silu(fmaf(w2_hi(v[j]), a8[2 * j + 1], b8[2 * j + 1])));
       }
       if (!((hvalid >> k) & 1u)) v = w2_u32x4{0u, 0u, 0u, 0u};
-      if constexpr (!PRO && (PRG_W256_EXP & 64)) {          // cap experiment (see issue_unit): finite e4m3 bytes, unit scale
-        *reinterpret_cast<uint2*>(Ah0 + buf * G::AH + k * RPP * MXROW) = make_uint2(v[0] & 0x77777777u, v[1] & 0x77777777u);
-        Hs0[buf * G::HS + k * RPP * 2] = (unsigned char)(127u + (v[2] & 0u));
-        return;
-      }
-      if (PRG_W256_EXP & 32) {                               // timing experiment: no quantisation arithmetic
-        *reinterpret_cast<uint2*>(Ah0 + buf * G::AH + k * RPP * MXROW) = make_uint2(v[0], v[1]);
-        return;
-      }
       uint32_t m = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1033,7 +986,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     };
     auto w_issue = [&](int set, int tap, int chunk) {
       const size_t tile = ((size_t)(tap * nchunks + chunk) * d.CoutPad + (size_t)tm.tn * BN);
-      const char* p = reinterpret_cast<const char*>(L.w_mx) + ((PRG_W256_EXP & 8) ? 0 : tile * 64) + w_voff;   // 8: timing experiment, one L1-resident tile
+      const char* p = reinterpret_cast<const char*>(L.w_mx) + tile * 64 + w_voff;
       wset[set][0] = *reinterpret_cast<const w2_u32x4*>(p);
       wset[set][1] = *reinterpret_cast<const w2_u32x4*>(p + 64 * 64);                     // rows 64 .. 127
       wsc[set] = *reinterpret_cast<const w2_u32x4*>(reinterpret_cast<const char*>(L.w_mx_scale) + tile * 2 + (ptid & 15) * 16);
@@ -1114,11 +1067,15 @@ static int w256_prepare_fold(ConvLaunch<bf16_t>& Lk, hipStream_t s) {
   return materialize_prologue(Lk, s);
 }
 
+// whether a launch of `total` tiles is large enough for these kernels (at least `dflt` tiles); PRG_W256_MIN_TILES=<n> > 0 replaces
+// the threshold (tests force small shapes onto them)
+static bool w256_fills(long total, int dflt) {
+  static const int min_tiles = env_int("PRG_W256_MIN_TILES", 0);
+  return total >= (min_tiles > 0 ? min_tiles : dflt);
+}
+
 int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_CONV_W256");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int enabled = env_int("PRG_CONV_W256", 1);
   if (!enabled) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
@@ -1138,9 +1095,8 @@ int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_
   const int num_cus = device_cu_count();
   if (num_cus <= 0) return 0;
   // fewer tiles than CUs: the 128-pixel tiles of conv_ws.hip fill the chip better
-  static const int min_fill = [] { const char* e = std::getenv("PRG_W256_MIN_TILES"); return e ? std::atoi(e) : 0; }();
   const int grid = num_cus & ~7;
-  if (grid < 8 || total < (min_fill > 0 ? min_fill : grid)) return 0;
+  if (grid < 8 || !w256_fills(total, grid)) return 0;
   const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
   const int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 &&
                    tiles_x * tiles_y * 2 <= kGnMaxSplit;
@@ -1185,10 +1141,7 @@ int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_
 
 // Upsample (nearest x2) + 3x3 conv as four 2 x 2-tap sub-pixel convolutions of the source image (MODE 2).  Returns 1 / 0 / negative.
 int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_UP2X2");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int enabled = env_int("PRG_UP2X2", 1);
   if (!enabled || !L.w_up) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.ups == 1 && d.C1 == 0)) return 0;
@@ -1208,8 +1161,7 @@ int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
   const int num_cus = device_cu_count();
   if (num_cus <= 0) return 0;
   const int grid = num_cus & ~7;
-  static const int min_fill = [] { const char* e = std::getenv("PRG_W256_MIN_TILES"); return e ? std::atoi(e) : 0; }();
-  if (grid < 8 || total < (min_fill > 0 ? min_fill : grid / 2)) return 0;
+  if (grid < 8 || !w256_fills(total, grid / 2)) return 0;
   const void* fn = tw == 32 ? reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 0, 2>)
                             : reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 0, 2>);
   const size_t lds = tw == 32 ? W2Geom<32>::LDS : W2Geom<16>::LDS;
@@ -1228,10 +1180,7 @@ int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
 
 // MX-fp8 operands (handles of dtype PRG_MXFP8): same shapes as the bf16 entry.  Returns 1 / 0 / negative.
 int try_launch_conv3x3_w256mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_CONV_W256MX");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int enabled = env_int("PRG_CONV_W256MX", 1);
   if (!enabled || !L.w_mx || !L.w_mx_scale) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
@@ -1250,12 +1199,11 @@ int try_launch_conv3x3_w256mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int* g
   const long total = (long)tiles_x * tiles_y * tiles_n * d.B;
   const int num_cus = device_cu_count();
   if (num_cus <= 0) return 0;
-  static const int min_fill = [] { const char* e = std::getenv("PRG_W256_MIN_TILES"); return e ? std::atoi(e) : 0; }();
   const int grid = num_cus & ~7;
   // Round 5: a launch with fewer tiles than CUs stays on the bf16 kernels (the network's level-3 convs: 128 tiles on 256 CUs — measured
   // at the configs[4] shape, same box, same positions: 25 / 29 us on conv3x3_ws_kernel against 28-29 / 38-40 us here,
   // profiles/r05_configs4_conv_per_launch_bf16_vs_mxfp8.txt); mx_pure (the conv-level tests) keeps the old half-a-wave threshold
-  if (grid < 8 || total < (min_fill > 0 ? min_fill : (L.mx_pure ? grid / 2 : grid))) return 0;
+  if (grid < 8 || !w256_fills(total, L.mx_pure ? grid / 2 : grid)) return 0;
   const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
   const int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 &&
                    tiles_x * tiles_y * 2 <= kGnMaxSplit;
@@ -1291,10 +1239,7 @@ int try_launch_conv3x3_w256mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int* g
 
 // Conv2d(C, Cout, 4, stride 2, pad 1) through the same kernel (MODE 1).  Returns 1 / 0 / negative like the entry above.
 int try_launch_conv4x4s2_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_CONV_DOWN_W256");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int enabled = env_int("PRG_CONV_DOWN_W256", 1);
   if (!enabled || !L.w_s2d) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad == 1 && d.ups == 0 && d.C1 == 0)) return 0;
@@ -1313,8 +1258,7 @@ int try_launch_conv4x4s2_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
   const int num_cus = device_cu_count();
   if (num_cus <= 0) return 0;
   const int grid = num_cus & ~7;
-  static const int min_fill = [] { const char* e = std::getenv("PRG_W256_MIN_TILES"); return e ? std::atoi(e) : 0; }();
-  if (grid < 8 || total < (min_fill > 0 ? min_fill : grid / 2)) return 0;   // the generic kernel for tiny launches
+  if (grid < 8 || !w256_fills(total, grid / 2)) return 0;   // the generic kernel for tiny launches
   const void* fn = tw == 32 ? reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 0, 1>)
                             : reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 0, 1>);
   const size_t lds = tw == 32 ? W2Geom<32>::LDS : W2Geom<16>::LDS;

@@ -33,10 +33,6 @@
 // Covers every 3x3 / stride 1 / pad 1 conv of the U-Nets at dim = 64 (widths multiples of 64): Block.proj, the last
 // down/up convs, Upsample's conv (x2 nearest gather folded into the halo load), skip concat as two sources.
 #include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "conv.h"
 
@@ -49,15 +45,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 namespace {
 
 constexpr int kCH = 64;   // channels per 128-byte pixel row (bf16)
-
-// Timing experiments only (results become garbage): -DPRG_WS_EXP=1 drops the weight waits, 2 the halo-unit waits,
-// 256 the producers' whole main loop, 512 the consumers' MFMA loop, 4 the fused prologue arithmetic, 8 the producers' LDS writes, 16 the whole tile epilogue, 32 its statistics.
-#ifndef PRG_WS_EXP
-#define PRG_WS_EXP 0
-#endif
-constexpr bool kExpNoWaitW = (PRG_WS_EXP & 1) != 0, kExpNoWaitU = (PRG_WS_EXP & 2) != 0;
-constexpr bool kExpNoPro = (PRG_WS_EXP & 4) != 0, kExpNoLdsWrite = (PRG_WS_EXP & 8) != 0;
-constexpr bool kExpNoEpilogue = (PRG_WS_EXP & 16) != 0, kExpNoStats = (PRG_WS_EXP & 32) != 0;
 
 __device__ inline float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ inline float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
@@ -79,44 +66,10 @@ __device__ inline float fast_silu(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 
-// Optional barrier trace (PRG_WS_TRACE=<launch index>): workgroup 0 records, per wave, the shader clock when it
-// arrives at and when it leaves every phase barrier of that launch (tools/ws_trace.py shows who the others wait for).
-// The record is stores only (device memory, count kept in a register): a load would put its latency into every phase
-// of the traced workgroup.  Stores raise vmcnt, which only makes the producers' counted waits stricter.
-// Compiled in only with -DPRG_WS_TRACE_BUILD=1 (`make trace` -> libprg_hip_trace.so): the checks alone are a dozen
-// instructions per phase and wave.
-#ifndef PRG_WS_TRACE_BUILD
-#define PRG_WS_TRACE_BUILD 0
-#endif
-constexpr bool kTrace = PRG_WS_TRACE_BUILD != 0;
-constexpr int kTraceStride = 4096;   // u64 slots per wave: [0] = count, then (arrive, leave) pairs
-
-struct TraceCtx {
-  unsigned long long* p;   // this wave's slots, or nullptr
-  int n;
-  __device__ __forceinline__ TraceCtx(unsigned long long* base)
-      : p(kTrace && base != nullptr && blockIdx.x == 0 && (threadIdx.x & 63) == 0 ? base + (threadIdx.x >> 6) * kTraceStride
-                                                                                   : nullptr),
-        n(0) {}
-  // two extra time stamps inside the phase that ends at barrier n (producers: after the weight wait, before the LDS drain)
-  __device__ __forceinline__ void mark(int which) {
-    if (kTrace && p != nullptr && n < 1000) p[kTraceStride / 2 + 2 * n + which] = clock64();
-  }
-};
-
 template <bool LDS_DONE = true>   // wait for this wave's own LDS operations first (writers always must)
-__device__ __forceinline__ void phase_barrier(TraceCtx& tr) {
+__device__ __forceinline__ void phase_barrier() {
   if constexpr (LDS_DONE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  const bool rec = kTrace && tr.p != nullptr && tr.n < (kTraceStride - 4) / 2;
-  if (rec) tr.p[1 + 2 * tr.n] = clock64();
-  if (!(PRG_WS_EXP & 4096)) __builtin_amdgcn_s_barrier();
-  if (rec) {
-    tr.p[2 + 2 * tr.n] = clock64();
-    if (tr.n == 0) tr.p[kTraceStride - 2] = wall_clock64();   // 100 MHz reference: the trace also yields the shader clock
-    tr.p[kTraceStride - 1] = wall_clock64();
-    ++tr.n;
-    tr.p[0] = tr.n;
-  }
+  __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
 
@@ -266,7 +219,6 @@ struct Producer {
   const TileMap& tm;
   char* Ah0;
   char* Bw0;
-  TraceCtx& trace;
   u32x4 wset[WD][NWL];
   u32x4 hreg[KU];
   u32x4 cf[2][4];            // [halo parity][a0..3, a4..7, b0..3, b4..7] as raw bits
@@ -299,8 +251,8 @@ struct Producer {
   int dr_r0;                 // ... and its row
 
   __device__ __forceinline__ Producer(const ConvLaunch<bf16_t>& L_, char* smem, int ptid, const TileMap& tm_, int nsteps_,
-                                      int nchunks_, TraceCtx& tr)
-      : L(L_), d(L_.d), tm(tm_), trace(tr), nsteps(nsteps_), nchunks(nchunks_) {
+                                      int nchunks_)
+      : L(L_), d(L_.d), tm(tm_), nsteps(nsteps_), nchunks(nchunks_) {
     Ah0 = smem + (ptid >> 3) * G::ROWB + (ptid & 7) * 16;            // this thread's unit of halo row `row`
     Bw0 = smem + 2 * G::AH_BYTES + (ptid >> 3) * G::ROWB + (ptid & 7) * 16;
     slot = ptid & 7;
@@ -355,9 +307,7 @@ struct Producer {
     }
   }
   __device__ __forceinline__ const char* w_tile(int tap, int chunk, int tn) const {
-    return reinterpret_cast<const char*>(L.w) +
-           ((PRG_WS_EXP & 1024) ? 0   // timing experiment: always the same (L1-resident) weight tile
-                                : ((size_t)(tap * d.kchunks + 2 * chunk) * d.CoutPad + tn * BN) * 64);
+    return reinterpret_cast<const char*>(L.w) + ((size_t)(tap * d.kchunks + 2 * chunk) * d.CoutPad + tn * BN) * 64;
   }
   template <int SET>
   __device__ __forceinline__ void w_issue(const char* base) {
@@ -371,25 +321,16 @@ struct Producer {
   template <int SET, int N>                                // N younger loads may stay in flight
   __device__ __forceinline__ void w_wait() {
     if constexpr (NWL == 2)
-      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(wset[SET][0]), "+v"(wset[SET][1]) : [n] "i"(kExpNoWaitW ? 63 : N) : "memory");
+      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(wset[SET][0]), "+v"(wset[SET][1]) : [n] "i"(N) : "memory");
     else
-      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(wset[SET][0]) : [n] "i"(kExpNoWaitW ? 63 : N) : "memory");
+      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(wset[SET][0]) : [n] "i"(N) : "memory");
     static_assert(NWL == 2 || NWL == 1, "weight units per thread");
   }
   template <int SET>
   __device__ __forceinline__ void w_write(int ring) {
-    if constexpr ((PRG_WS_EXP >> 16) != 0) {                       // timing experiment: stagger the weight writes
-      if (row & 32) __builtin_amdgcn_s_sleep(PRG_WS_EXP >> 16);    // odd producer waves start N * 64 clk later
-    }
 #pragma unroll
-    for (int j = 0; j < NWL; ++j) {    // weight row `row + 64 j`
-      // 16384: timing experiment, only half of the weight tile is written to LDS (what a 256-pixel tile would stage per MFMA)
-      const bool skip = (PRG_WS_EXP & 16384) && (NWL == 2 ? j == 1 : (row & 32) != 0);
-      if (!kExpNoLdsWrite && !skip) *reinterpret_cast<u32x4*>(Bw0 + ring * G::BW_BYTES + j * 64 * G::ROWB) = wset[SET][j];
-      if constexpr ((PRG_WS_EXP & 32768) != 0) {                 // timing experiment: gap between a wave's two stores
-        if (j + 1 < NWL) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-      }
-    }
+    for (int j = 0; j < NWL; ++j)    // weight row `row + 64 j`
+      *reinterpret_cast<u32x4*>(Bw0 + ring * G::BW_BYTES + j * 64 * G::ROWB) = wset[SET][j];
   }
 
   // ---- halo ----
@@ -426,7 +367,7 @@ struct Producer {
   __device__ __forceinline__ void issue_unit() {
     const bool ok = (hedge[K] & ld_tedge) == 0;
     // padding taps read the tile origin (always mapped) and are zeroed at write time
-    const unsigned pix = ok && !(PRG_WS_EXP & 2048) ? hpix[K] : ld_dummy;
+    const unsigned pix = ok ? hpix[K] : ld_dummy;
     const unsigned voff = __umul24(pix, ld_cs2) + (unsigned)(slot * 16);
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(hreg[K]) : "v"(voff), "s"(ld_base) : "memory");
     hvalid_nxt |= (ok ? 1u : 0u) << K;
@@ -436,10 +377,10 @@ struct Producer {
     if constexpr (PRO) {
       asm volatile("s_waitcnt vmcnt(%[n])"
                    : "+v"(hreg[K]), "+v"(cf[CS][0]), "+v"(cf[CS][1]), "+v"(cf[CS][2]), "+v"(cf[CS][3])
-                   : [n] "i"(kExpNoWaitU && N != 0 ? 63 : N)
+                   : [n] "i"(N)
                    : "memory");
     } else {
-      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(hreg[K]) : [n] "i"(kExpNoWaitU && N != 0 ? 63 : N) : "memory");
+      asm volatile("s_waitcnt vmcnt(%[n])" : "+v"(hreg[K]) : [n] "i"(N) : "memory");
     }
   }
   template <int K, int CS>
@@ -447,7 +388,7 @@ struct Producer {
     const int hp = K * RPP + row;
     if (hp < HALO && wr) {
       u32x4 v = hreg[K];
-      if constexpr (PRO && !kExpNoPro) {
+      if constexpr (PRO) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           // v[j] holds channels 2j (low half) and 2j+1 of this thread's 8: coefficients a[2j], a[2j+1] live in
@@ -462,8 +403,7 @@ struct Producer {
         }
       }
       if (!((hvalid >> K) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
-      if (!kExpNoLdsWrite) *reinterpret_cast<u32x4*>(Ah0 + (g_tgt & 1) * G::AH_BYTES + K * RPP * G::ROWB) = v;
-      else asm volatile("" ::"v"(v));
+      *reinterpret_cast<u32x4*>(Ah0 + (g_tgt & 1) * G::AH_BYTES + K * RPP * G::ROWB) = v;
     }
   }
   // Output drain: the consumers leave a finished tile as bf16 [wave][64 pixels][64 channels] in the LDS stage; during
@@ -492,22 +432,21 @@ struct Producer {
   template <int PH, int J, int CSW>
   __device__ __forceinline__ void units_wait() {
     if constexpr (J < UPH && PH * UPH + J < KU) {
-      if constexpr (!((PRG_WS_EXP & 8192) && (J & 1)))
-        wait_unit<PH * UPH + J, CSW, U_YOUNGER - NWL - J>();   // this phase's weight tile is issued after the LDS work
+      wait_unit<PH * UPH + J, CSW, U_YOUNGER - NWL - J>();   // this phase's weight tile is issued after the LDS work
       units_wait<PH, J + 1, CSW>();
     }
   }
   template <int PH, int J, int CSW>
   __device__ __forceinline__ void units_write(int g, bool wr) {
     if constexpr (J < UPH && PH * UPH + J < KU) {
-      if constexpr (!((PRG_WS_EXP & 8192) && (J & 1))) write_unit<PH * UPH + J, CSW>(g + 1, wr);
+      write_unit<PH * UPH + J, CSW>(g + 1, wr);
       units_write<PH, J + 1, CSW>(g, wr);
     }
   }
   template <int PH, int J>
   __device__ __forceinline__ void units_issue() {
     if constexpr (J < UPH && PH * UPH + J < KU) {
-      if constexpr (!((PRG_WS_EXP & 8192) && (J & 1))) issue_unit<PH * UPH + J>();
+      issue_unit<PH * UPH + J>();
       units_issue<PH, J + 1>();
     }
   }
@@ -529,7 +468,6 @@ struct Producer {
     }
     if constexpr (LIVE || PH >= WD) {
       w_wait<SET, w_younger(PH)>();
-      if constexpr (LIVE) trace.mark(0);
       w_write<SET>(RING);
     }
     if constexpr (LIVE && PH < 8) {
@@ -541,14 +479,13 @@ struct Producer {
     static_assert(TAPN < 18, "weight prefetch reaches at most into the next step");
     if constexpr (!LIVE) wptr = TAPN < 9 ? w_tile(TAPN, chunk0, tn0) : w_tile(TAPN - 9, chunk1, tn1);
     else if constexpr (TAPN == 9) wptr = w_tile(0, chunk1, tn1);
-    else if (!(PRG_WS_EXP & 1024)) wptr += w_tapb;
+    else wptr += w_tapb;
     w_issue<SET>(wptr);
     if constexpr (PH < 8) units_issue<PH, 0>();
     if constexpr (LIVE && PH < DRAIN_PHASES) {
       if (draining) drain_store<PH>(dv);
     }
-    if constexpr (LIVE) trace.mark(1);
-    if constexpr (LIVE) phase_barrier(trace);
+    if constexpr (LIVE) phase_barrier();
   }
   // GP = g & 1.  Writes halo g+1 (coefficient set (g+1)&1) and weight tiles 9g+2..9g+10; issues halo g+2 (set g&1) and
   // weight tiles 9g+5..9g+13.  LIVE = false is the issue-only "step -1" of the prologue: it puts exactly the loads a
@@ -625,12 +562,10 @@ struct Producer {
       keep_units<K + 1>();
     }
   }
-  __device__ __forceinline__ void finish(bool drain = true) {
+  __device__ __forceinline__ void finish() {
     // the last step always ends a tile: `dr` is that tile (consumers passed the last phase barrier: stage complete)
-    if (drain) {
-      drain_unit<0>(); drain_unit<1>(); drain_unit<2>(); drain_unit<3>();
-      static_assert(DRAIN_PHASES == 4, "one consumer wave's stage per drain phase");
-    }
+    drain_unit<0>(); drain_unit<1>(); drain_unit<2>(); drain_unit<3>();
+    static_assert(DRAIN_PHASES == 4, "one consumer wave's stage per drain phase");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int sidx = 0; sidx < WD; ++sidx)
@@ -643,7 +578,7 @@ struct Producer {
 #pragma unroll
         for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(cf[c][j])::"memory");
     }
-    phase_barrier(trace);
+    phase_barrier();
   }
 };
 
@@ -652,15 +587,13 @@ struct Producer {
 // =====================================================================================================
 template <int TH, int TW, int BN, bool PRO>
 __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t> L, const int tiles_x,
-                                                            const int tiles_y, const int tiles_n, const int fuse_stats,
-                                                            unsigned long long* const trace_buf) {
+                                                            const int tiles_y, const int tiles_n, const int fuse_stats) {
   using G = WsGeom<TH, TW, BN>;
   constexpr int HP = G::HP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROWB = G::ROWB;
   char* const stage = smem + 2 * G::AH_BYTES + 3 * G::BW_BYTES + G::RED_BYTES;
   float* const bias_lds = reinterpret_cast<float*>(stage + G::STG_BYTES);
-  TraceCtx trace(trace_buf);
 
   const ConvDesc& d = L.d;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -673,7 +606,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
 
   // ---------------------------------------------------------------------------------------------------
   if (wave < 4) {
-    __builtin_amdgcn_s_setprio((PRG_WS_EXP & 64) ? 0 : ((PRG_WS_EXP & 128) ? 1 : 3));   // the MFMA waves share each SIMD's issue port with one producer wave
+    __builtin_amdgcn_s_setprio(3);   // the MFMA waves share each SIMD's issue port with one producer wave
     // 8-channel chunks per GroupNorm group (a power of two <= 8 when the statistics are fused)
     const int gn_per = fuse_stats ? (d.Cout / L.gn_groups) >> 3 : 1;
     const int gn_per_sh = 31 - __builtin_clz(gn_per);
@@ -709,7 +642,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
     // ring slot / halo buffer that no producer touches before phase p+2.
     // the workgroup's channel tile never changes (one Cout tile, or pinned to one): its bias lives in LDS
     if (tid < BN) bias_lds[tid] = L.bias[(tmap.pinned ? tmap.tn_fixed : 0) * BN + tid];
-    phase_barrier<true>(trace);    // prologue barrier: first halo + weight tiles 0,1 are in LDS
+    phase_barrier<true>();    // prologue barrier: first halo + weight tiles 0,1 are in LDS
     // three fragment sets: the one being multiplied, the next call's, and the one being loaded two calls (256 MFMA
     // cycles) ahead; set of global call c is c % 3 (36 calls per step: the same code serves every step)
     bf16x8 fw[3][2], fx[3][2];
@@ -737,7 +670,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
         const int pn = p == 8 ? 0 : p + 1;
         const int toffN = (pn / 3) * HP + (pn % 3);
 #pragma unroll
-        for (int call = 0; call < ((PRG_WS_EXP & 512) ? 0 : 4); ++call) {
+        for (int call = 0; call < 4; ++call) {
           // set (call + 2) % 4 was consumed two calls ago: refill it for the call two ahead (this phase's calls 2,3
           // or the NEXT phase's calls 0,1 — its weight tile and halo are already visible in LDS)
           const int sl = (4 * p + call + 2) % 3, sm = (4 * p + call) % 3;   // set being loaded / multiplied
@@ -758,7 +691,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
             PRG_LW(sl, 1, (p + 1) % 3, call - 2); PRG_MM(sm, 1, 1); PRG_SB();
           }
         }
-        if (p == 8 && tile_end && !kExpNoEpilogue) {
+        if (p == 8 && tile_end) {
           // tile finished.  Lane holds pixel (pt*32 + l31), channels ct*32 + 8q + 4hi + {0..3}: bias, round, transpose
           // through the wave's LDS stage, 16-byte stores; the 8 channels of chunk (ct, q) are shared by the whole wave.
           char* const stg = stage + wave * (64 * 128);
@@ -791,7 +724,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
               V[8 + ct * 4 + q] = sq;
             }
           // the producer waves move the stage to HBM during the next step (Producer::drain_unit)
-          if (fuse_stats && !kExpNoStats) {
+          if (fuse_stats) {
             // 16 full-wave sums with 17 lane exchanges: each butterfly round halves the values a lane carries (it keeps
             // the half selected by its lane bit and sends the other half to its partner).  The rounds that move many
             // values use DPP quad permutes (VALU, no LDS crossbar); fixed order -> deterministic.
@@ -830,8 +763,8 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
 #pragma unroll
               for (int e = 0; e < 16; ++e) acc[ct][pt][e] = 0.0f;
         }
-        if (p == 8 && tile_end) phase_barrier<true>(trace);   // the stage must be visible to the producer waves
-        else phase_barrier<false>(trace);
+        if (p == 8 && tile_end) phase_barrier<true>();   // the stage must be visible to the producer waves
+        else phase_barrier<false>();
       }
       // next step
       { const char* t0 = xa[0]; xa[0] = xn[0]; xn[0] = t0; const char* t1 = xa[1]; xa[1] = xn[1]; xn[1] = t1; }
@@ -847,24 +780,15 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
 #undef PRG_LX
 #undef PRG_MM
 #undef PRG_SB
-    phase_barrier<false>(trace);   // matches the producers' finish()
+    phase_barrier<false>();   // matches the producers' finish()
     return;
   }
 
   // ---------------------------------------------------------------------------------------------------
   {
-    if (PRG_WS_EXP & (64 | 128)) __builtin_amdgcn_s_setprio((PRG_WS_EXP & 64) ? 3 : 1);
-    Producer<TH, TW, BN, PRO> Pv(L, smem, tid - 256, tmap, nsteps, nchunks, trace);
+    Producer<TH, TW, BN, PRO> Pv(L, smem, tid - 256, tmap, nsteps, nchunks);
     Pv.prologue();
-    phase_barrier(trace);
-    if constexpr ((PRG_WS_EXP & 256) != 0) {
-      // timing experiment: consumers alone.  The loads of the prologue stay owned until they have landed.
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      for (int g = 0; g < nsteps; ++g)
-        for (int p = 0; p < 9; ++p) phase_barrier(trace);
-      Pv.finish(false);
-      return;
-    }
+    phase_barrier();
 #pragma unroll 1
     for (int g = 0; g < nsteps; g += 2) {
       Pv.template step<0, true>(g);
@@ -895,31 +819,8 @@ int launch_ws_cfg2(const ConvLaunch<bf16_t>& L, hipStream_t s, int fuse_stats, i
   }
   if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y * G::WAVES_M : 0;
   if (L.probe) return PRG_OK;
-  static const int trace_at = [] { const char* e = std::getenv("PRG_WS_TRACE"); return e ? std::atoi(e) : -1; }();
-  static int launch_no = 0;
-  unsigned long long* tbuf = nullptr;
-  if (kTrace && trace_at >= 0 && launch_no++ == trace_at) {
-    if (hipMalloc(reinterpret_cast<void**>(&tbuf), 12 * kTraceStride * sizeof(unsigned long long)) == hipSuccess) {
-      (void)hipMemsetAsync(tbuf, 0, 12 * kTraceStride * sizeof(unsigned long long), s);
-      (void)hipStreamSynchronize(s);
-    }
-  }
-  conv3x3_ws_kernel<TH, TW, BN, PRO><<<dim3(grid), 768, G::LDS, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats, tbuf);
+  conv3x3_ws_kernel<TH, TW, BN, PRO><<<dim3(grid), 768, G::LDS, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
   PRG_LAUNCH_CHECK();
-  if (tbuf) {
-    (void)hipStreamSynchronize(s);
-    char path[256];
-    std::snprintf(path, sizeof(path), "%s/ws_trace_%d_%d_%d_cin%d_pro%d.bin",
-                  std::getenv("PRG_WS_TRACE_DIR") ? std::getenv("PRG_WS_TRACE_DIR") : "/tmp", TH, TW, BN, d.C0 + d.C1,
-                  (int)PRO);
-    std::vector<unsigned long long> host(12 * kTraceStride);
-    (void)hipMemcpy(host.data(), tbuf, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (FILE* f = std::fopen(path, "wb")) {
-      std::fwrite(host.data(), sizeof(unsigned long long), host.size(), f);
-      std::fclose(f);
-    }
-    (void)hipFree(tbuf);
-  }
   return PRG_OK;
 }
 
@@ -933,10 +834,7 @@ int launch_ws_cfg(const ConvLaunch<bf16_t>& L, hipStream_t s, int fuse_stats, in
 
 // Returns 1 when it launched, 0 when the shape is not covered (caller falls back), negative on error.
 int try_launch_conv3x3_ws(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = [] {
-    const char* e = std::getenv("PRG_CONV_WS");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int enabled = env_int("PRG_CONV_WS", 1);
   if (!enabled) return 0;
   const ConvDesc& d = L.d;
   if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
@@ -956,26 +854,12 @@ int try_launch_conv3x3_ws(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_ns
     // one partial per (tile, consumer wave row): a group must lie inside one wave's 64 channels
     return want && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && (W / TW) * (H / TH) * (4 / (BN / 64)) <= kGnMaxSplit ? 1 : 0;
   };
-  static const int cfg_mask = [] { const char* e = std::getenv("PRG_WS_CFGS"); return e ? std::atoi(e) : 7; }();   // debugging aid
   int rc = 0;
-  // PRG_WS_PREFER64: route wide convs through the 256-pixel x 64-channel tile where it fits (half the weight bytes
-  // staged per MFMA, the halo staged once per 64 output channels)
-  static const int prefer64 = [] { const char* e = std::getenv("PRG_WS_PREFER64"); return e ? std::atoi(e) : 0; }();
-  const int tn64 = d.Cout / 64;
-  if (prefer64 && d.Cout % 128 == 0 && W % 32 == 0 && H % 8 == 0 && (tn64 == 2 || tn64 == 4 || tn64 == 8) &&
-      (prefer64 >= 2 || tn64 == 2)) {
-    rc = launch_ws_cfg<8, 32, 64>(L, s, fuse_for(8, 32, 64), gn_nsplit_out, num_cus);
-    if (rc == kWsUnsupported) return 0;
-    if (rc == PRG_OK && acc_done) *acc_done = (L.gn_acc && gn_nsplit_out && *gn_nsplit_out > 0) ? 1 : 0;
-    return rc == PRG_OK ? 1 : rc;
-  }
   if (d.Cout % 128 == 0) {
-    if (!(cfg_mask & (W % 32 == 0 && H % 4 == 0 ? 1 : 2))) return 0;
     if (W % 32 == 0 && H % 4 == 0) rc = launch_ws_cfg<4, 32, 128>(L, s, fuse_for(4, 32, 128), gn_nsplit_out, num_cus);
     else if (W % 16 == 0 && H % 8 == 0) rc = launch_ws_cfg<8, 16, 128>(L, s, fuse_for(8, 16, 128), gn_nsplit_out, num_cus);
     else return 0;
   } else {
-    if (!(cfg_mask & 4)) return 0;
     if (W % 32 == 0 && H % 8 == 0) rc = launch_ws_cfg<8, 32, 64>(L, s, fuse_for(8, 32, 64), gn_nsplit_out, num_cus);
     else return 0;
   }

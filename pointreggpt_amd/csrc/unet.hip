@@ -45,26 +45,18 @@ int fail(int code, const std::string& m) {
 }
 const char* last_error() { return g_err.c_str(); }
 
-// PRG_GN_FOLD=1: the conv kernels that can (conv_c64.hip) fold the GroupNorm statistics into coefficients themselves (last
-// workgroup of an image, per-image ticket) instead of a gn_coeff_kernel launch.  Measured net-neutral (every workgroup of a
-// persistent launch finishes at the same time, so the fold lands on the kernel's tail: +5-6 us per conv against the 5 us
-// launch + 1.7 us boundary it removes): off by default, kept as a tested option.
 static bool head_fuse_enabled() {
-  static const int on = [] { const char* e = std::getenv("PRG_HEAD_FUSE"); return e ? std::atoi(e) : 1; }();
+  static const int on = env_int("PRG_HEAD_FUSE", 1);
   return on != 0;
 }
 static bool res_epilogue_enabled() {
-  static const int on = [] { const char* e = std::getenv("PRG_RES_EPILOGUE"); return e ? std::atoi(e) : 1; }();
+  static const int on = env_int("PRG_RES_EPILOGUE", 1);
   return on != 0;
 }
 // PRG_GN_ACC=0: GroupNorm statistics as per-tile slabs + one gn_coeff_kernel launch per norm (rounds 1-2) instead of the
 // fixed-point accumulators folded by the consumers (common.h, GnFold).  bf16 / mxfp8 handles only; fp32 always uses slabs.
 static bool gn_acc_enabled() {
-  static const int on = [] { const char* e = std::getenv("PRG_GN_ACC"); return e ? std::atoi(e) : 1; }();
-  return on != 0;
-}
-static bool gn_fold_enabled() {
-  static const int on = [] { const char* e = std::getenv("PRG_GN_FOLD"); return e ? std::atoi(e) : 0; }();
+  static const int on = env_int("PRG_GN_ACC", 1);
   return on != 0;
 }
 
@@ -312,7 +304,6 @@ struct prg_unet {
   uint16_t* d_split = nullptr;  // f16x3 mode (dtype PRG_F16X3): every conv weight as f16 hi / lo halves (conv_split.hip)
   uint16_t* d_h16 = nullptr;    // bf16 mode: f16 twins of the ResnetBlocks' second convs (the h16 format, conv.h)
   float* d_freqs = nullptr;     // SinusoidalPosEmb frequencies [dim/2] (sd:645-657), see prg_unet_set_time_freqs
-  int* d_tickets = nullptr;     // [kMaxTicketImages] per-image arrival counters of the conv kernels that fold GroupNorm coefficients (self-resetting)
   // fixed-point GroupNorm statistics (common.h, GnFold; bf16 / mxfp8 handles)
   long long* d_gnacc = nullptr; // [slots][resB][groups][2], zeroed by ONE memset at the start of every forward
   size_t gnacc_bytes = 0;
@@ -358,10 +349,6 @@ struct UnetImpl : prg_unet {
     int* gn_nsplit = nullptr;       // out: slabs written (0 = not fused for this shape)
     const float* pro_a = nullptr;   // fused GroupNorm+cond+SiLU on the input (halo kernel)
     const float* pro_b = nullptr;
-    const GnApply* gn = nullptr;    // fold the output's statistics into coefficients inside the conv kernel when it can
-    float* coef_a = nullptr;
-    float* coef_b = nullptr;
-    int* coef_done = nullptr;       // out: 1 = coef_a / coef_b are written by the conv launch (no gn_coeff launch needed)
     long long* gn_acc = nullptr;    // fixed-point statistics of the output (instead of gn_partials when the kernel can)
     int* acc_done = nullptr;        // out: 1 = the launch accumulated into gn_acc
     const GnFold* fold = nullptr;   // prologue coefficients folded by the consumer (pro_a / pro_b = scratch tables)
@@ -399,9 +386,6 @@ struct UnetImpl : prg_unet {
     L.split_kchunks = p.sp_kchunks;
     L.split_scale = (L.w_split && d_split_scale && p.sp_scale_off >= 0) ? d_split_scale + p.sp_scale_off : nullptr;
     L.split_scale_up = (L.w_up_split && d_split_scale && p.up_sp_scale_off >= 0) ? d_split_scale + p.up_sp_scale_off : nullptr;
-    L.gn = o.gn ? *o.gn : GnApply{};
-    L.gn_coef_a = o.gn ? o.coef_a : nullptr; L.gn_coef_b = o.gn ? o.coef_b : nullptr;
-    L.gn_tickets = (o.gn && gn_fold_enabled()) ? d_tickets : nullptr;
     L.gn_acc = o.gn_acc;
     L.pro_fold = o.fold ? *o.fold : GnFold{};
     L.res_fold = o.res_fold ? *o.res_fold : GnFold{};
@@ -416,7 +400,6 @@ struct UnetImpl : prg_unet {
     const ConvLaunch<T> L = make_launch(p, s0, C0, s1, C1, B, Hin, Win, stride, pad, ups, o, out);
     PRG_CHECK(C0 + C1 == p.Cin, "conv: channel mismatch");
     if (o.gn_nsplit) *o.gn_nsplit = 0;
-    if (o.coef_done) *o.coef_done = 0;
     if (o.acc_done) *o.acc_done = 0;
     if (arena.dry) return PRG_OK;
     if (prof && prof->on) {
@@ -428,7 +411,7 @@ struct UnetImpl : prg_unet {
       }
       auto& ev = prof->pool[prof->used++];
       PRG_HIP(hipEventRecord(ev.first, s));
-      int rc = launch_conv<T>(L, s, o.gn_nsplit, o.coef_done, o.acc_done);
+      int rc = launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
       PRG_HIP(hipEventRecord(ev.second, s));
       prof->conv_flops += conv_flops(L.d);
       prof->conv_flops_exec += conv_flops(L.d) * conv_last_exec_scale();
@@ -446,7 +429,7 @@ struct UnetImpl : prg_unet {
       prof->launches += 1;
       return rc;
     }
-    return launch_conv<T>(L, s, o.gn_nsplit, o.coef_done, o.acc_done);
+    return launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
   }
 
   // ---- fixed-point GroupNorm statistics (bf16 path) ----
@@ -503,7 +486,7 @@ struct UnetImpl : prg_unet {
     PRG_CHECK(arena.dry || (h1 && part1 && part2 && coefA && coefB && coefA2 && coefB2 && (!r.has_res || res)),
               "workspace exhausted (resblock)");
     const CondSrc* c1 = lay.cfg.conditional ? cs : nullptr;
-    int rc, ns1 = 0, ns2 = 0, cd1 = 0, cd2 = 0, ad1 = 0, ad2 = 0;
+    int rc, ns1 = 0, ns2 = 0, ad1 = 0, ad2 = 0;
     const GnApply g1 = gn_params(r.g1, r.b1, c1, r.ss_off);
     const GnApply g2 = gn_params(r.g2, r.b2, nullptr, 0);
     // bf16: statistics as fixed-point accumulators, coefficients folded by whoever consumes them (no gn_coeff launches)
@@ -511,20 +494,13 @@ struct UnetImpl : prg_unet {
     long long* acc2 = next_acc(B);
     ConvOpt o1;
     o1.gn_partials = part1; o1.gn_nsplit = &ns1;
-    o1.gn = &g1; o1.coef_a = coefA; o1.coef_b = coefB; o1.coef_done = &cd1;
     o1.gn_acc = acc1; o1.acc_done = &ad1;
     // conv2's own statistics fold into a second coefficient pair (coefA / coefB are still being read by its prologue)
     ConvOpt o2;
     o2.gn_partials = part2; o2.gn_nsplit = &ns2;
-    o2.gn = &g2; o2.coef_a = coefA2; o2.coef_b = coefB2; o2.coef_done = &cd2;
     o2.gn_acc = acc2; o2.acc_done = &ad2;
-    // PRG_FUSE_PRO: -1 (default) fuse wherever the conv supports it; 0 never; N > 0 only for widths >= N
-    static const int fuse_min = [] { const char* e = std::getenv("PRG_FUSE_PRO"); return e ? std::atoi(e) : -1; }();
-    // PRG_FUSE_PRO_MAX=N: widths above N apply GroupNorm + SiLU in one flat pass over h1 instead (a conv with several
-    // output-channel tiles transforms every input pixel once per tile in its prologue)
-    static const int fuse_max = [] { const char* e = std::getenv("PRG_FUSE_PRO_MAX"); return e ? std::atoi(e) : 1 << 30; }();
-    const bool fuse_pro = conv_supports_prologue<T>(make_desc(r.c2, r.cout, 0, B, H, Wd, 1, 1, 0)) &&
-                          (fuse_min < 0 || (fuse_min > 0 && r.cout >= fuse_min)) && r.cout <= fuse_max;
+    // conv2 applies GroupNorm + SiLU of h1 in its prologue wherever it supports one
+    const bool fuse_pro = conv_supports_prologue<T>(make_desc(r.c2, r.cout, 0, B, H, Wd, 1, 1, 0));
     GnFold f1{}, f2{};
     // h16 (conv.h): h1 only ever feeds conv2's fused prologue — stored as f16 when both launches land on kernels that implement it
     // (probed with the launches' own descriptors: PRG_H16=0, PRG_CONV_C64=0, ... and uncovered shapes fall back to bf16 h1)
@@ -554,7 +530,7 @@ struct UnetImpl : prg_unet {
           }
         }
       } else {
-        if (!cd1 && (rc = launch_gn_coeff(part1, ns1, g1, coefA, coefB, B, HW, r.cout, G, s))) return rc;
+        if ((rc = launch_gn_coeff(part1, ns1, g1, coefA, coefB, B, HW, r.cout, G, s))) return rc;
         if (fuse_pro) {
           o2.pro_a = coefA; o2.pro_b = coefB;
         } else if ((rc = launch_affine_silu<T>(h1, coefA, coefB, nullptr, h1, B, HW, r.cout, s))) {
@@ -586,7 +562,7 @@ struct UnetImpl : prg_unet {
       // GroupNorm + SiLU + skip.  Accumulator path: the tail kernels fold the coefficients themselves (the 1x1 res_conv's
       // epilogue reads tables: one gn_coeff_acc launch for those four blocks); slab path: gn_coeff launch, then the tables
       if (ad2) f2 = make_fold(acc2, r.cout, HW, false, 0, r.pq2);
-      else if (!cd2 && (rc = launch_gn_coeff(part2, ns2, g2, coefA2, coefB2, B, HW, r.cout, G, s))) return rc;
+      else if ((rc = launch_gn_coeff(part2, ns2, g2, coefA2, coefB2, B, HW, r.cout, G, s))) return rc;
       if constexpr (std::is_same<T, bf16_t>::value) {
         if (fused_tail) {
           rc = launch_resblock_tail_fused(out, coefA2, coefB2, s0, C0, s1, C1, d_attn + r.fw_res, F(r.res.b_off), out, B, HW,
@@ -897,7 +873,7 @@ struct UnetImpl : prg_unet {
 
 // ---- weight preparation (host) ---------------------------------------------------------------
 static bool fused_attention_enabled() {
-  static const int on = [] { const char* e = std::getenv("PRG_FUSED_ATTN"); return e ? std::atoi(e) : 1; }();
+  static const int on = env_int("PRG_FUSED_ATTN", 1);
   return on != 0;
 }
 
@@ -1079,7 +1055,7 @@ static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t
     }
     // Upsample convs: the sub-pixel decomposition's four 2 x 2-tap packings (conv_split.hip, UP form of the wave-specialised kernel)
     // (built only when the option is on — it is off by default, conv_split.hip: try_launch_conv_split — ADVICE round 4)
-    static const int split_up_on = [] { const char* e = std::getenv("PRG_SPLIT_UP2X2"); return e ? std::atoi(e) : 0; }();
+    static const int split_up_on = env_int("PRG_SPLIT_UP2X2", 0);
     for (auto& lv : u->lay.ups) {
       ConvP* p = &lv.resample;
       if (!split_up_on || !lv.strided || !(p->KH == 3 && p->KW == 3 && p->Cin % 32 == 0 && p->Cout % 128 == 0)) continue;
@@ -1104,8 +1080,7 @@ static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t
     if (hipMalloc(&u->d_split, data.size() * sizeof(uint16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split weights)");
     PRG_HIP(hipMemcpy(u->d_split, data.data(), data.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     // fused linear attention (attn_split.hip): to_qkv with the PreNorm gain folded in (q and k rows times log2 e: both only ever
-    // enter a softmax, evaluated with exp2) and to_out, each as f16 hi halves followed by the lo halves.  PRG_SPLIT_ATTN=0: unfused
-    static const int sa_on = [] { const char* e = std::getenv("PRG_SPLIT_ATTN"); return e ? std::atoi(e) : 1; }();
+    // enter a softmax, evaluated with exp2) and to_out, each as f16 hi halves followed by the lo halves
     std::vector<uint16_t> aw;
     auto f16bits = [](float v, uint16_t& h, uint16_t& l) {
       const _Float16 a = (_Float16)v, b = (_Float16)(v - (float)a);
@@ -1113,7 +1088,7 @@ static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t
       std::memcpy(&l, &b, 2);
     };
     auto add_attn = [&](AttnP& a) {
-      if (!sa_on || !a.linear || (a.C != 64 && a.C != 128)) return;   // (linattn_split_supported: C = 64 / 128; the token count is checked per call)
+      if (!a.linear || (a.C != 64 && a.C != 128)) return;   // (linattn_split_supported: C = 64 / 128; the token count is checked per call)
       aw.resize((aw.size() + 63) / 64 * 64);
       a.sp_qkv = (int64_t)aw.size();
       const size_t nq = (size_t)3 * kHidden * a.C;
@@ -1165,17 +1140,14 @@ static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t
       u->n_cond_entries = (int)ent.size();
     }
   }
-  if (hipMalloc(&u->d_tickets, kMaxTicketImages * sizeof(int)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(tickets)");
-  PRG_HIP(hipMemset(u->d_tickets, 0, kMaxTicketImages * sizeof(int)));
-  static const int stem3_on = [] { const char* e = std::getenv("PRG_STEM_MFMA3"); return e ? std::atoi(e) : 1; }();   // 0: MaskUnet's stem on the direct kernel
-  if (std::is_same<T, bf16_t>::value && (L.cfg.in_channels == 1 || (L.cfg.in_channels == 3 && stem3_on)) && L.cfg.dim == 64) {
+  if (std::is_same<T, bf16_t>::value && (L.cfg.in_channels == 1 || L.cfg.in_channels == 3) && L.cfg.dim == 64) {
     std::vector<bf16_t> sf;
     pack_stem_mfma_weights(weights + L.stem_w, L.cfg.in_channels, sf);
     if (hipMalloc(&u->d_stem_frag, sf.size() * sizeof(bf16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(stem fragments)");
     PRG_HIP(hipMemcpy(u->d_stem_frag, sf.data(), sf.size() * sizeof(bf16_t), hipMemcpyHostToDevice));
   }
   // f16x3 (round 5): the stem on the same MFMA kernel with f16 hi / lo halves (PRG_SPLIT_STEM=0: the direct fmaf kernel of the parity mode)
-  static const int split_stem_on = [] { const char* e = std::getenv("PRG_SPLIT_STEM"); return e ? std::atoi(e) : 1; }();
+  static const int split_stem_on = env_int("PRG_SPLIT_STEM", 1);
   if (split && split_stem_on && (L.cfg.in_channels == 1 || L.cfg.in_channels == 3) && L.cfg.dim == 64) {
     std::vector<uint16_t> sf;
     std::vector<float> sc;
@@ -1190,7 +1162,7 @@ static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t
     std::vector<bf16_t> aw;
     std::vector<float> ks;
     // PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every block
-    static const int kshift_on = [] { const char* e = std::getenv("PRG_LA_KSHIFT"); return e ? std::atoi(e) : 1; }();
+    static const int kshift_on = env_int("PRG_LA_KSHIFT", 1);
     auto add = [&](AttnP& a) {
       if (!a.linear || !linattn_fused_supported(a.C)) return;
       aw.resize((aw.size() + 63) / 64 * 64);
@@ -1425,7 +1397,6 @@ int prg_unet_destroy(prg_unet* h) {
   if (h->d_split_scale) (void)hipFree(h->d_split_scale);
   if (h->d_h16) (void)hipFree(h->d_h16);
   if (h->d_attn_split) (void)hipFree(h->d_attn_split);
-  if (h->d_tickets) (void)hipFree(h->d_tickets);
   if (h->d_gnacc) (void)hipFree(h->d_gnacc);
   if (h->d_pq_static) (void)hipFree(h->d_pq_static);
   if (h->d_cond_entries) (void)hipFree(h->d_cond_entries);
@@ -1709,8 +1680,8 @@ int prg_debug_block_pair(const float* x, const float* w1, const float* b1, const
     L1.out_f16 = 1;
     L2.in_f16 = 1;
   }
-  int ns = 0, cd = 0, ad = 0;
-  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L1, s, &ns, &cd, &ad);
+  int ns = 0, ad = 0;
+  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L1, s, &ns, &ad);
   if (rc == PRG_OK && !ad) rc = fail(PRG_E_INVALID, "prg_debug_block_pair: conv1's kernel does not accumulate fixed-point statistics for this shape");
   if (rc == PRG_OK) rc = launch_conv<bf16_t>(L2, s, nullptr);
   if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(reinterpret_cast<const bf16_t*>(d_y), out, B, H * W, C, s);

@@ -54,6 +54,25 @@ def test_product_has_no_cpu_path():
                 assert "import oracle" not in src and "from oracle" not in src, f
 
 
+def test_library_switches_are_the_tested_ones():
+    """Every PRG_* environment switch the HIP library reads pins an alternative schedule that a test compares against the default:
+    exactly these names, each read through env_int() (common.h).  No compile-time PRG_* experiment macro is left either."""
+    kept = {"PRG_CONV_WS", "PRG_CONV_C64", "PRG_CONV_W256", "PRG_CONV_DOWN_W256", "PRG_CONV_W256MX", "PRG_W256_MIN_TILES",
+            "PRG_UP2X2", "PRG_H16", "PRG_MX_PURE", "PRG_GN_ACC", "PRG_HEAD_FUSE", "PRG_RES_EPILOGUE", "PRG_FUSED_ATTN",
+            "PRG_LA_KSHIFT", "PRG_LA_PSUM", "PRG_SPLIT_UP2X2", "PRG_SPLIT_P64", "PRG_SPLIT_W512", "PRG_SPLIT_LA_ONLINE",
+            "PRG_SPLIT_STEM", "PRG_SPLIT_FULLATTN"}
+    csrc = os.path.join(ROOT, "pointreggpt_amd", "csrc")
+    read, macros = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        read |= set(re.findall(r"\b(?:getenv|env_int)\s*\(\s*\"(PRG_\w+)\"", src))
+        macros += [(f, m) for m in re.findall(r"^\s*#\s*(?:ifn?def|if|elif)\b.*\b(PRG_\w+)", src, flags=re.M)]
+    assert read == kept, {"unexpected": sorted(read - kept), "missing": sorted(kept - read)}
+    assert not macros, macros
+
+
 def test_host_geometry_against_reference_goldens(golden):
     g = golden("G2_intrinsic_transform")
     for S in (32, 64, 128, 256):

@@ -14,8 +14,6 @@ for FX in G21b_ddim250_256 G20_ddim250_128 G22_chain1000_ancestral_128; do
   run $FX 1 PRG_SPLIT_STEM=0
   run $FX 1 PRG_SPLIT_FULLATTN=0
   run $FX 1 PRG_SPLIT_P64=0
-  run $FX 1 PRG_SPLIT_WS=0
-  run $FX 1 PRG_SPLIT_ATTN_C128=0
   run $FX 1 PRG_SPLIT_UP2X2=1 PRG_SPLIT_P64=0
   run $FX 1 PRG_SPLIT_UP2X2=1 PRG_SPLIT_STEM=0
 done

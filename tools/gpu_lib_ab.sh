@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/gpu_lib_ab.sh <tag> <variant lib name> <rounds> [pytest -k expression]: same-box A/B of the product library against
-# pointreggpt_amd/libprg_<variant>.so (tools/variant_lib.sh): bf16 conv micro-bench (tools/split_bench.py), then the bf16 pipeline
+# pointreggpt_amd/libprg_<variant>.so (any other build of the library): bf16 conv micro-bench (tools/split_bench.py), then the bf16 pipeline
 # (bench.py, 200 transitions), arms alternating; first the parity tests named by the -k expression on the product library.
 cd $GRAFT_REPO_ROOT
 T=$1; V=$2; N=${3:-2}; K=$4

@@ -1,6 +1,7 @@
-"""Build profiles/rNN_conv_hbm_traffic.json from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of
+"""Build profiles/conv_hbm_traffic.json from two counter-only rocprofv3 passes (--pmc FETCH_SIZE, --pmc WRITE_SIZE; nothing else
+traced in the same run) of
 
-    bench.py --steps 1 --warmup 0 --sampling-steps 2 --no-cpu-baseline --no-roofline
+    bench.py --steps 1 --warmup 0 --streams 1 --sampling-steps 2
 
 Usage: python tools/hbm_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <out.json>
 Corrections as MI355X_MICROARCH.md's HBM/rocprofv3 section prescribes: separate passes, values in KB, FETCH_SIZE x2 on gfx950.
@@ -31,9 +32,8 @@ out = {
     "hbm_bytes_per_launch": (2.0 * f + w) * 1024.0,
     "correction": "FETCH_SIZE x2 (gfx950 counts 128-B requests as 64 B for wide coalesced reads, MI355X_MICROARCH.md HBM section); "
                   "WRITE_SIZE as reported; KB -> bytes x1024",
-    "command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace ... ; rocprofv3 --pmc WRITE_SIZE --kernel-trace ... -- python bench.py "
-               "--steps 1 --warmup 0 --streams 1 --sampling-steps 2 --no-cpu-baseline --no-roofline --no-configs4 (separate passes)",
-    "round": "r05",
+    "command": "rocprofv3 --pmc FETCH_SIZE ... ; rocprofv3 --pmc WRITE_SIZE ... -- python bench.py "
+               "--steps 1 --warmup 0 --streams 1 --sampling-steps 2 (separate counter-only passes)",
     "kernel_sources_sha256": __import__("hashlib").sha256(b"".join(
         open(__import__("os").path.join(__import__("os").path.dirname(__import__("os").path.abspath(__file__)), "..",
                                         "pointreggpt_amd", "csrc", f), "rb").read()
