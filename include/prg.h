@@ -114,6 +114,37 @@ int prg_occlusion_filter(const float* depth, const uint8_t* mask, float* out, in
 int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double radius,
                        int32_t* counts, void* stream);
 
+/* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
+ * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
+size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);
+
+/* PointCloud.voxel_down_sample for B ragged clouds in one call: per segment exactly prg_host_voxel_down_sample (below) —
+ * same bits, same output order — i.e. min over the valid rows, org = min - voxel/2, index = floor((p - org)/voxel) in
+ * float64, key = (ix*dy + iy)*dz + iz with dy,dz = max index + 1, voxels in ascending key order, each the sum of its rows
+ * taken one after the other in input order from the first row, divided by the count.
+ * pts (total,3) float64 DEVICE; valid (total) bytes DEVICE or NULL (= all rows); offsets (B+1) int64 DEVICE, ascending,
+ * within [0,total].  Rows with valid == 0, and rows outside [offsets[0], offsets[B]), are ignored entirely (they may hold
+ * NaN or nothing at all: `total` may be the capacity of a buffer whose tail is unused).  1 <= B <= 65535, total < 2^31.
+ * out (>= total rows,3) float64 DEVICE, compact CSR: segment b's voxel means occupy [out_offsets[b], out_offsets[b+1]),
+ *   out_offsets[0] = 0; rows of `out` from out_offsets[B] on are not written.  out_offsets (B+1) int64 DEVICE.
+ * status (B) int32 DEVICE: 0 ok; 1 a valid row is non-finite; 2 voxel grid too large: dx*dy*dz >= 2^46, the sort key's room
+ *   for one segment (this includes the host's "voxel_size is too small" condition, 2^62).  A segment with status != 0
+ *   produces 0 rows.  A segment's rows depend on that segment alone: not on B, on its neighbours or on the launch geometry.
+ * workspace: >= prg_voxel_grid_workspace_bytes(total, B) bytes, DEVICE, 8-byte aligned; contents are scratch.
+ * Asynchronous on `stream`; reads no device data on the host; allocates nothing.  voxel <= 0 fails with PRG_E_INVALID.  */
+int prg_voxel_grid_ragged(const double* pts, const uint8_t* valid, const int64_t* offsets, int B, int64_t total,
+                          double voxel, double* out, int64_t* out_offsets, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* The input of a scene-memory update (sd:2661-2680) without stream compaction, for prg_voxel_grid_ragged: segment b of
+ * `merged` = segment b of the float32 ragged cloud `memory` (memory_rows rows allocated, CSR memory_offsets (B+1) int64
+ * DEVICE) widened to float64 with valid = 1, followed by the HW rows of xyz[b] with valid[b] exactly as prg_unproject_f64
+ * leaves them (xyz (B,HW,3) float64, valid (B,HW) bytes).  merged (memory_rows + B*HW, 3) float64, merged_valid
+ * (memory_rows + B*HW) bytes, merged_offsets (B+1) int64, all DEVICE: merged_offsets[b] = memory_offsets[b] + b*HW.      */
+int prg_merge_memory_f64(const float* memory, const int64_t* memory_offsets, int64_t memory_rows, const double* xyz,
+                         const uint8_t* valid, int B, int HW, double* merged, uint8_t* merged_valid,
+                         int64_t* merged_offsets, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * U-Nets (MFMA kernels)
  * ---------------------------------------------------------------------------------------------------- */

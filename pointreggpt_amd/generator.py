@@ -114,7 +114,7 @@ class Generator:
     def generate(self, start_scene_index, stop_scene_index, num_samples, memory_voxel_size=0.002,
                  save_voxel_size=0.025, has_refine_step=False, depth_correction=None, mask_threshold=0.99,
                  noise_seed: Optional[int] = None, progress: bool = False, writer_threads: int = 0, stats: Optional[dict] = None,
-                 seed_poses: Optional[bool] = None, lanes: Optional[list] = None):
+                 seed_poses: Optional[bool] = None, lanes: Optional[list] = None, voxel_backend: str = "device"):
         """Same sequence as sd:2363-2694.  File output is asynchronous: every batch's clouds / images / text files are
         handed to the library's C++ writer pool (crop, voxel grid, PLY / PNG encoding on worker threads) and are
         produced while the GPU samples the next batch.  A batch's resume marker — the generated cloud of its LAST scene
@@ -129,7 +129,16 @@ class Generator:
         ``seed_poses`` (real-data input only): draw the poses from a local legacy stream per (job seed, batch, sample) so that
         a run can be re-sharded / resumed reproducibly; False = numpy's global stream like the reference (single lane only).
         Default: True when the caller passes a `noise_seed` (ANY value, 0 included: `None` is the "no seed" sentinel) or lanes,
-        False (the reference's unseeded behaviour) otherwise."""
+        False (the reference's unseeded behaviour) otherwise.
+        ``voxel_backend`` (num_samples > 1): where the scene memory lives between views.  "device" (the default on a HIP
+        device): one float32 ragged buffer on the GPU from the first upload on, updated by prg_merge_memory_f64 ->
+        prg_voxel_grid_ragged and read by the next view's z-buffer in place — no copy of the memory cloud to the host.
+        "host": the memory clouds are numpy arrays re-voxelised one by one in C++ on the calling thread (the only path of
+        a `device="cpu"` generator).  Both produce the same bytes."""
+        if voxel_backend not in ("device", "host"):
+            raise ValueError("voxel_backend must be 'device' or 'host'")
+        if self.device.type == "cpu":
+            voxel_backend = "host"
         if seed_poses is None:
             seed_poses = noise_seed is not None or (lanes is not None and len(lanes) > 0)
         noise_seed = 0 if noise_seed is None else int(noise_seed)
@@ -156,7 +165,7 @@ class Generator:
         pairs = pairs[:max(1, len(batches))]
         kw = dict(num_samples=num_samples, memory_voxel_size=memory_voxel_size, save_voxel_size=save_voxel_size,
                   has_refine_step=has_refine_step, mask_threshold=mask_threshold, noise_seed=noise_seed, progress=progress,
-                  seed_poses=seed_poses, info_train=info_train)
+                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend)
         n = len(pairs)
         wt = writer_threads if writer_threads <= 0 or n == 1 else max(1, writer_threads // n)
         results = [None] * n
@@ -196,7 +205,8 @@ class Generator:
     _pose_lock = threading.Lock()      # guards numpy's process-wide legacy stream (seed_poses=False)
 
     def _lane(self, batches, model, depth_correction, writer_threads, n_lanes, *, num_samples, memory_voxel_size,
-              save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None):
+              save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None,
+              voxel_backend="host"):
         """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream."""
         S, dev = self.image_size, self.device
         if writer_threads <= 0 and n_lanes > 1:
@@ -246,12 +256,18 @@ class Generator:
                 param_cond = self.G.param_vector(K_dev)
                 fragments: List[Optional[np.ndarray]] = [None] * batch
                 poses0 = None
+                on_device = voxel_backend == "device" and num_samples > 1
+                if on_device:                 # the ONE upload of the memory clouds; from here on they stay on the device
+                    mem_pts, mem_offs = self.G.upload_clouds(memory, dev)
                 for sample_idx in range(num_samples):
                     pose = self._poses(idxs, sample_idx, noise_seed if seed_poses else None)
                     if sample_idx == 0:
                         poses0 = pose
                     pose_dev = torch.from_numpy(pose).to(dev)
-                    rpj, hit = self.G.project_clouds(memory, pose, K, S, dev, depth_scale=0.1)
+                    if on_device:
+                        rpj, hit = self.G.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
+                    else:
+                        rpj, hit = self.G.project_clouds(memory, pose, K, S, dev, depth_scale=0.1)
                     prob = depth_correction(rpj)
                     rpj_c, hit_c, cond = self.G.apply_mask(prob, rpj, hit, mask_threshold)
                     seeds = [synthetic.noise_seed(noise_seed, i, sample_idx) for i in idxs]
@@ -260,11 +276,20 @@ class Generator:
                     prob2 = depth_correction(images)
                     images, _, _ = self.G.apply_mask(prob2, images, None, mask_threshold, want_cond=False)
                     xyz, valid = self.G.unproject_f64(images, K_dev, pose_dev)      # common frame, float64 (sd:2623-2628)
+                    last_sample = sample_idx == num_samples - 1
+                    vg_status = None
+                    if on_device and not last_sample:                               # memory update (sd:2661-2680), no host trip
+                        merged, mvalid, moffs = self.G.merge_memory(mem_pts, mem_offs, xyz, valid)
+                        vg_out, mem_offs, vg_status = self.G.voxel_grid_ragged(merged, mvalid, moffs, memory_voxel_size)
+                        mem_pts = vg_out.to(torch.float32)
                     # one blocking copy per tensor: the host waits here for the GPU while the pool writes the previous batch
                     rpj_host, crt_host, img_host = rpj.cpu().numpy(), rpj_c.cpu().numpy(), images.cpu().numpy()
                     xyz_host, valid_host = xyz.cpu().numpy(), valid.cpu().numpy()
+                    if vg_status is not None:     # B status words + the memory's row count: all the host learns of it
+                        st_n = torch.cat([vg_status.to(torch.int64), mem_offs[-1:]]).cpu().numpy()
+                        self.G.check_voxel_status(st_n[:-1], ["scene-{:0>6d}".format(i) for i in idxs])
+                        mem_pts = mem_pts[:max(int(st_n[-1]), 1)]
                     flush_marker()
-                    last_sample = sample_idx == num_samples - 1
                     for j, idx in enumerate(idxs):
                         sdir = sdirs[j]
                         pool.image01(str(sdir / "reprojected.image.png"), rpj_host[j])
@@ -278,7 +303,7 @@ class Generator:
                             pc = xyz_host[j][valid_host[j]]
                             fragments[j] = pc if sample_idx == 0 else np.concatenate([fragments[j], pc], axis=0)
                             frag, fvalid = fragments[j], None
-                            if not last_sample:                                         # memory update (sd:2661-2680)
+                            if not last_sample and not on_device:                       # memory update (sd:2661-2680)
                                 merged = np.concatenate([memory[j], pc], axis=0)
                                 memory[j] = PP.native_voxel_down_sample(merged, memory_voxel_size).astype(np.float32)
                         if last_sample:                                                 # sd:2640-2658
@@ -300,12 +325,12 @@ class Generator:
 
 
 def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int, num_samples: int,
-                root: str = ".", overlap: str = "hip", scenes_per_launch: int = 512) -> None:
+                root: str = ".", overlap: str = "hip", scenes_per_launch: int = 512, voxel: str = "device") -> None:
     """generate_gt.py:105-175 — per scene, every pair of .cloud.ply -> overlap ratios -> scene gt.log.
 
     The reference queries a KD-tree once per point in a Python loop (the wall-clock tail of a 10k-scene dataset); here the
-    clouds of up to `scenes_per_launch` scenes are voxel-down-sampled in C++ and all their pairs go through ONE
-    prg_overlap_counts launch.  `overlap='numpy-spec'` selects the numpy specification in postprocess.py instead — a test
+    clouds of up to `scenes_per_launch` scenes are voxel-down-sampled by ONE ragged device call (`voxel='device'`; 'host' =
+    one by one in C++ on the calling thread, same ratios) and all their pairs go through ONE prg_overlap_counts launch.  `overlap='numpy-spec'` selects the numpy specification in postprocess.py instead — a test
     hook for boxes without a GPU, never chosen implicitly."""
     from itertools import combinations
     if overlap not in ("hip", "numpy-spec"):
@@ -330,16 +355,16 @@ def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int
             cand.append((s, t, src, tgt))
         todo.append((scene_name, gt_path, cand))
         if len(todo) >= scenes_per_launch:
-            _finish_gt(todo, overlap)
+            _finish_gt(todo, overlap, voxel)
             todo = []
     if todo:
-        _finish_gt(todo, overlap)
+        _finish_gt(todo, overlap, voxel)
 
 
-def _finish_gt(todo, overlap: str) -> None:
+def _finish_gt(todo, overlap: str, voxel: str = "device") -> None:
     flat = [(src, tgt) for _n, _p, cand in todo for (_s, _t, src, tgt) in cand]
     if overlap == "hip":
-        ratios = PP.overlap_ratios_hip(flat)
+        ratios = PP.overlap_ratios_hip(flat, voxel=voxel)
     else:
         ratios = [PP.compute_overlap_ratio(a, b) for a, b in flat]
     k = 0

@@ -167,13 +167,28 @@ def project_clouds(clouds: Sequence[np.ndarray], poses: np.ndarray, intrinsic: n
                    device, depth_scale: float = 1.0):
     """Generator.generate's per-scene projection (sd:2531-2552) for a whole batch in one launch: ragged float32
     clouds (n_b,3) each moved by its (4,4) pose and z-buffered with its K; returns depth*depth_scale and mask."""
-    lib = _lib.load()
+    pts, d_offs = upload_clouds(clouds, device)
+    return project_cloud_buffer(pts, d_offs, poses, intrinsic, image_size, depth_scale=depth_scale)
+
+
+def upload_clouds(clouds: Sequence[np.ndarray], device, dtype=np.float32):
+    """A list of (n_b,3) host clouds as ONE ragged device buffer: (pts (max(total,1),3) `dtype`, offsets (B+1) int64)."""
     B = len(clouds)
     offs = np.zeros(B + 1, dtype=np.int64)
     offs[1:] = np.cumsum([len(c) for c in clouds])
-    pts = torch.from_numpy(np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds], 0)
-                           if offs[-1] else np.zeros((1, 3), np.float32)).to(device)
-    d_offs = torch.from_numpy(offs).to(device)
+    pts = torch.from_numpy(np.concatenate([np.asarray(c, dtype=dtype).reshape(-1, 3) for c in clouds], 0)
+                           if offs[-1] else np.zeros((1, 3), dtype)).to(device)
+    return pts, torch.from_numpy(offs).to(device)
+
+
+def project_cloud_buffer(pts: torch.Tensor, d_offs: torch.Tensor, poses: np.ndarray, intrinsic: np.ndarray,
+                         image_size: int, depth_scale: float = 1.0):
+    """`project_clouds` for a cloud that already lives on the device: pts (N,3) float32 ragged, d_offs (B+1) int64 CSR
+    offsets, both device tensors (rows beyond d_offs[B] are not read).  Nothing but the poses and intrinsics is uploaded."""
+    lib = _lib.load()
+    device = pts.device
+    assert pts.is_cuda and pts.dtype == torch.float32 and d_offs.dtype == torch.int64 and d_offs.device == device
+    B = d_offs.numel() - 1
     P = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float32)).to(device)
     K = torch.from_numpy(np.ascontiguousarray(intrinsic, dtype=np.float32)).to(device)
     S = int(image_size)
@@ -198,6 +213,76 @@ def unproject_f64(depth: torch.Tensor, intrinsic: torch.Tensor, pose: Optional[t
                                      float(depth_unit), float(clip[0]), float(clip[1]), _lib.stream_ptr()),
                "prg_unproject_f64")
     return xyz, valid.view(torch.bool)
+
+
+_VOXEL_WORKSPACE = {}     # (device index, stream) -> uint8 tensor: lanes of one device run on their own streams
+
+
+def _voxel_workspace(device, nbytes: int) -> torch.Tensor:
+    key = (device.index if device.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream(device).cuda_stream)
+    ws = _VOXEL_WORKSPACE.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+        _VOXEL_WORKSPACE[key] = ws
+    return ws
+
+
+def voxel_grid_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets: torch.Tensor, voxel: float):
+    """PointCloud.voxel_down_sample of B ragged clouds in one call, on the device (prg_voxel_grid_ragged): pts (total,3)
+    float64, valid (total) bool / uint8 or None, offsets (B+1) int64, all device tensors.  Returns (out (total,3) float64,
+    out_offsets (B+1) int64, status (B) int32) on the device: segment b's voxel means are out[out_offsets[b]:out_offsets[b+1]],
+    bit for bit what `postprocess.native_voxel_down_sample` returns for its valid rows; status 1 = non-finite row,
+    2 = grid too large (such a segment has no rows).  Nothing is copied to the host and nothing synchronises."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total, B = pts.shape[0], offsets.numel() - 1
+    v8 = None
+    if valid is not None:
+        v8 = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous().to(torch.uint8)
+        v8 = v8.view(-1)
+        assert v8.numel() == total
+    out = torch.empty((max(total, 1), 3), dtype=torch.float64, device=pts.device)
+    out_offsets = torch.empty((B + 1,), dtype=torch.int64, device=pts.device)
+    status = torch.empty((B,), dtype=torch.int32, device=pts.device)
+    nbytes = int(lib.prg_voxel_grid_workspace_bytes(total, B))
+    ws = _voxel_workspace(pts.device, nbytes)
+    _lib.check(lib.prg_voxel_grid_ragged(_lib.ptr(pts), _lib.ptr(v8), _lib.ptr(offsets), B, total, float(voxel),
+                                         _lib.ptr(out), _lib.ptr(out_offsets), _lib.ptr(status), _lib.ptr(ws), ws.numel(),
+                                         _lib.stream_ptr()), "prg_voxel_grid_ragged")
+    return out[:total], out_offsets, status
+
+
+def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
+    """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
+    float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as
+    `unproject_f64` returns them.  -> (merged (N + B*HW, 3) float64, merged_valid uint8, merged_offsets (B+1) int64)."""
+    lib = _lib.load()
+    assert memory.is_cuda and memory.dtype == torch.float32 and xyz.dtype == torch.float64
+    memory, xyz = memory.contiguous().view(-1, 3), xyz.contiguous()
+    B, HW, _ = xyz.shape
+    assert memory_offsets.numel() == B + 1 and memory_offsets.dtype == torch.int64
+    v8 = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous().to(torch.uint8)
+    rows = memory.shape[0] + B * HW
+    merged = torch.empty((rows, 3), dtype=torch.float64, device=xyz.device)
+    merged_valid = torch.empty((rows,), dtype=torch.uint8, device=xyz.device)
+    merged_offsets = torch.empty((B + 1,), dtype=torch.int64, device=xyz.device)
+    _lib.check(lib.prg_merge_memory_f64(_lib.ptr(memory), _lib.ptr(memory_offsets.contiguous()), memory.shape[0],
+                                        _lib.ptr(xyz), _lib.ptr(v8), B, HW, _lib.ptr(merged), _lib.ptr(merged_valid),
+                                        _lib.ptr(merged_offsets), _lib.stream_ptr()), "prg_merge_memory_f64")
+    return merged, merged_valid, merged_offsets
+
+
+def check_voxel_status(status, names: Sequence) -> None:
+    """Raise PrgError naming the first scene whose voxel grid failed (`status` already on the host)."""
+    for j, st in enumerate(np.asarray(status)):
+        if st:
+            raise _lib.PrgError("voxel_down_sample of {}: {}".format(
+                names[j], "non-finite point" if st == 1 else "voxel_size is too small"))
 
 
 def point_clouds(depth: torch.Tensor, intrinsic: torch.Tensor, pose: Optional[torch.Tensor] = None, *,

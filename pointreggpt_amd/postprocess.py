@@ -39,7 +39,8 @@ def transform(pts: np.ndarray, T: np.ndarray) -> np.ndarray:
 
 
 def voxel_down_sample(pts: np.ndarray, voxel_size: float) -> np.ndarray:
-    """PointCloud.voxel_down_sample: mean of the points of every occupied voxel (float64)."""
+    """PointCloud.voxel_down_sample: mean of the points of every occupied voxel (float64), voxels in ascending key order, each
+    mean = (sequential sum of its rows in input order) / count — bit for bit what the C++ and the device grid return."""
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
     if len(pts) == 0:
         return pts
@@ -55,7 +56,16 @@ def voxel_down_sample(pts: np.ndarray, voxel_size: float) -> np.ndarray:
     key_s = key[order]
     starts = np.flatnonzero(np.r_[True, key_s[1:] != key_s[:-1]])
     counts = np.diff(np.r_[starts, len(key_s)])
-    sums = np.add.reduceat(pts[order], starts, axis=0)
+    # the rows of a voxel are added ONE AFTER THE OTHER in input order, starting from the first (what csrc/hostpool.cpp and
+    # csrc/voxelgrid.hip do): np.add.reduceat would add a run of 8 or more rows pairwise and differ from them in the last bits
+    pts_s = pts[order]
+    sums = pts_s[starts].copy()
+    live = np.flatnonzero(counts > 1)
+    k = 1
+    while len(live):
+        sums[live] += pts_s[starts[live] + k]
+        k += 1
+        live = live[counts[live] > k]
     return sums / counts[:, None]
 
 
@@ -316,20 +326,44 @@ class WriterPool:
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# overlap ratios on the GPU (generate_gt.py:68-102): voxel grids in C++, neighbour-existence counts in one HIP launch
+# overlap ratios on the GPU (generate_gt.py:68-102): voxel grids of all clouds in one ragged device call (or one by one in
+# C++ on the host), neighbour-existence counts in one HIP launch
 # ------------------------------------------------------------------------------------------------------------------
 def overlap_ratios_hip(pairs, voxel_size: float = 0.025, overlap_factor: float = 1.5, is_down_sample: bool = True,
-                       device="cuda"):
+                       device="cuda", voxel: str = "device"):
     """[(src (n,3), tgt (m,3)), ...] -> [(overlap_src, overlap_tgt), ...] exactly as compute_overlap_ratio defines them:
     both clouds voxel-down-sampled, then the fraction of points with a point of the other cloud strictly within
-    overlap_factor * voxel_size.  One prg_overlap_counts launch for the whole list (float64 all-pairs test)."""
+    overlap_factor * voxel_size.  One prg_overlap_counts launch for the whole list (float64 all-pairs test).
+    `voxel`: "device" = all clouds uploaded once and down-sampled by one prg_voxel_grid_ragged call whose output feeds the
+    count kernel in place; "host" = each cloud through the C++ grid on the calling thread, then uploaded.  Same ratios."""
     import torch
 
     from . import _lib
     lib = _lib.load()
     _lib.require_gpu()
+    if voxel not in ("device", "host"):
+        raise ValueError("voxel must be 'device' or 'host'")
     if not pairs:
         return []
+    if voxel == "device" and is_down_sample:
+        from . import geometry as G
+        raw = [_f64(c) for pair in pairs for c in pair]
+        in_max = max(len(c) for c in raw)
+        if in_max == 0:
+            return [(float("nan"), float("nan"))] * len(pairs)
+        pts, d_offs = G.upload_clouds(raw, device, dtype=np.float64)
+        down, down_offs, status = G.voxel_grid_ragged(pts, None, d_offs, voxel_size)
+        counts = torch.empty((len(pairs), 2), dtype=torch.int32, device=device)
+        # max_cloud bounds the query slabs per cloud: the largest INPUT cloud is an upper bound of the largest down-sampled one
+        _lib.check(lib.prg_overlap_counts(_lib.ptr(down), _lib.ptr(down_offs), len(pairs), int(in_max),
+                                          float(voxel_size * overlap_factor), _lib.ptr(counts), _lib.stream_ptr()),
+                   "prg_overlap_counts")
+        G.check_voxel_status(status.cpu().numpy(), ["cloud {} of pair {}".format(k % 2, k // 2) for k in range(len(raw))])
+        sizes = np.diff(down_offs.cpu().numpy())
+        cnt = counts.cpu().numpy().astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return [(float(cnt[i, 0] / np.float64(sizes[2 * i])), float(cnt[i, 1] / np.float64(sizes[2 * i + 1])))
+                    for i in range(len(pairs))]
     clouds = []
     for a, b in pairs:
         for c in (a, b):
