@@ -1,22 +1,20 @@
-// unet.hip — host side of the two U-Nets and of the sampler: weight arena, layer walk, workspace, hipGraph.
+// unet.hip — host side of the two U-Nets and of the sampler: forward pass, workspace, hipGraph, C-ABI.  (The parameter layout
+// and the handle struct: unet_layout.h; weight preparation: unet_weights.hip; the prg_debug_* entries: unet_debug.hip.)
 //
 // Mirrors (structure only) Unet.forward sd:920-964, MaskUnet.forward dc:871-906, GaussianDiffusion.sample
 // sd:1283-1409.  Activations live as NHWC tensors of T (bf16_t or float) in a stack arena owned by the handle;
 // the skip `torch.cat` never materialises (two source pointers into the conv), `nn.Upsample` is folded into the
 // following conv's gather, weight standardisation is folded into the packed weights at load time.
-#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
 
-#include "blocks.h"
-#include "conv.h"
 #include "sampler.h"
+#include "unet_layout.h"
 
 namespace prg {
 
@@ -60,24 +58,6 @@ static bool gn_acc_enabled() {
   return on != 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// device stack arena
-// ---------------------------------------------------------------------------------------------
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, top = 0, high = 0;
-  bool dry = false;  // dry run: only measure
-  void* alloc(size_t bytes) {
-    size_t a = (top + 255) & ~(size_t)255;
-    top = a + bytes;
-    if (top > high) high = top;
-    if (dry) return reinterpret_cast<void*>((uintptr_t)0x1000 + a);  // never dereferenced
-    return (top <= cap) ? base + a : nullptr;
-  }
-  size_t mark() const { return top; }
-  void reset(size_t m) { top = m; }
-};
-
 struct ProfileSink {  // per-launch conv timing (bench roofline)
   bool on = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
@@ -106,225 +86,6 @@ struct ProfileSink {  // per-launch conv timing (bench roofline)
   double step_ms = 0;
   int64_t step_launches = 0;
 };
-
-// ---------------------------------------------------------------------------------------------
-// parameter walk: the flat float32 array is the reference state_dict in order (weights.param_spec)
-// ---------------------------------------------------------------------------------------------
-struct ConvP {
-  int Cout = 0, Cin = 0, KH = 0, KW = 0, CoutPad = 0, kchunks = 0;
-  size_t w_off = 0;        // element offset into the packed-T arena
-  int64_t b_off = -1;      // float offset of the bias in the flat array (-1: none)
-  int64_t w_flat = -1;     // float offset of the raw OIHW weight in the flat array
-  bool ws = false;         // weight-standardised (Block.proj)
-  int64_t mx_off = -1;     // byte offset of the MX-fp8 copy of the weights (-1: none) and of its block scales
-  int64_t mx_soff = -1;
-  int64_t s2d_off = -1;    // 4x4 / stride 2 convs (bf16): element offset of the equivalent 2x2-tap packing (ConvLaunch::w_s2d)
-  int s2d_kchunks = 0;
-  int64_t sp_off = -1;     // f16x3 mode: element offset of the hi / lo f16 split packing (ConvLaunch::w_split)
-  int sp_kchunks = 0;
-  int64_t h16_off = -1;    // bf16 mode, second conv of a ResnetBlock: element offset of the f16 twin of the packing (ConvLaunch::w_f16)
-  int64_t up_off = -1;     // bf16 mode, Upsample convs: element offset of the four pre-summed 2 x 2-tap packings (ConvLaunch::w_up)
-  int64_t sp_scale_off = -1, up_sp_scale_off = -1;   // f16x3 mode: offsets into d_split_scale (ConvLaunch::split_scale / split_scale_up)
-  int64_t up_sp_off = -1;  // f16x3 mode: the same in the split layout (ConvLaunch::w_up_split)
-};
-struct ResP {
-  int cin = 0, cout = 0;
-  int64_t mlp_w = -1, mlp_b = -1;  // Linear(2*emb -> 2*cout)
-  int ss_off = 0;                  // column offset of this block's (scale|shift) in the conditioning row
-  ConvP c1, c2, res;
-  int64_t g1 = 0, b1 = 0, g2 = 0, b2 = 0;
-  int64_t fw_res = -1;             // bf16 element offset of the raw res_conv weight in the fused-kernel arena (-1: unfused)
-  bool has_res = false;
-  int64_t pq1 = -1, pq2 = -1;      // float offsets into d_pq_static of (P = gamma | Q = beta) of norm 1 / 2, each cpad floats
-  int cpad = 0;                    // cout rounded up to 4 floats (16-byte aligned rows)
-};
-struct AttnP {
-  int C = 0;
-  bool linear = true;
-  ConvP qkv, out;
-  int64_t out_g = -1, norm_g = -1;
-  int64_t fw_qkv = -1, fw_out = -1;   // bf16 element offsets into the fused-attention weight arena (-1: unfused path)
-  int64_t kshift = -1;                // float offset of the 128 static softmax shifts in d_kshift (-1: measure the maxima)
-  int64_t sp_qkv = -1, sp_out = -1;   // f16x3 mode: element offsets into d_attn_split of the hi halves (the lo halves follow)
-};
-struct LevelP {
-  ResP r0, r1;
-  AttnP at;
-  ConvP resample;
-  bool strided = false;  // down: 4x4 s2 ; up: nearest x2 + 3x3
-};
-
-struct Cursor {
-  int64_t pos = 0;
-  int64_t take(int64_t n) {
-    int64_t p = pos;
-    pos += n;
-    return p;
-  }
-};
-
-static void walk_conv(Cursor& c, ConvP& p, int Cout, int Cin, int K, bool bias, bool ws) {
-  p.Cout = Cout; p.Cin = Cin; p.KH = K; p.KW = K; p.ws = ws;
-  p.w_flat = c.take((int64_t)Cout * Cin * K * K);
-  p.b_off = bias ? c.take(Cout) : -1;
-}
-static void walk_res(Cursor& c, ResP& r, int cin, int cout, bool cond, int emb, int& ss_total) {
-  r.cin = cin; r.cout = cout;
-  if (cond) {
-    r.mlp_w = c.take((int64_t)2 * cout * 2 * emb);
-    r.mlp_b = c.take(2 * cout);
-    r.ss_off = ss_total;
-    ss_total += 2 * cout;
-  }
-  walk_conv(c, r.c1, cout, cin, 3, true, true);
-  r.g1 = c.take(cout); r.b1 = c.take(cout);
-  walk_conv(c, r.c2, cout, cout, 3, true, true);
-  r.g2 = c.take(cout); r.b2 = c.take(cout);
-  r.has_res = cin != cout;
-  if (r.has_res) walk_conv(c, r.res, cout, cin, 1, true, false);
-}
-static void walk_attn(Cursor& c, AttnP& a, int C, bool linear) {
-  a.C = C; a.linear = linear;
-  walk_conv(c, a.qkv, 3 * kHidden, C, 1, false, false);
-  walk_conv(c, a.out, C, kHidden, 1, true, false);
-  if (linear) a.out_g = c.take(C);
-  a.norm_g = c.take(C);
-}
-
-struct Layout {
-  prg_unet_config cfg;
-  int emb = 0, ss_total = 0, L = 0;
-  std::vector<int> dims;
-  int64_t stem_w = 0, stem_b = 0;
-  int64_t tm1_w = 0, tm1_b = 0, tm3_w = 0, tm3_b = 0, pm0_w = 0, pm0_b = 0, pm2_w = 0, pm2_b = 0;
-  std::vector<LevelP> downs, ups;
-  ResP mid1, mid2, fin;
-  AttnP mid_at;
-  int64_t head_w = 0, head_b = 0;
-  int64_t total = 0;
-};
-
-static int build_layout(const prg_unet_config& cfg, Layout& L) {
-  PRG_CHECK(cfg.dim >= 8 && cfg.dim % 8 == 0, "config: dim must be a multiple of 8");
-  PRG_CHECK(cfg.n_levels >= 1 && cfg.n_levels <= 8, "config: n_levels out of range");
-  PRG_CHECK(cfg.in_channels == 1 || cfg.in_channels == 3, "config: in_channels must be 1 or 3");
-  PRG_CHECK(cfg.groups >= 1 && cfg.groups <= 64, "config: groups out of range");
-  L.cfg = cfg;
-  L.L = cfg.n_levels;
-  L.emb = cfg.dim * 4;
-  L.dims.assign(1, cfg.dim);
-  for (int i = 0; i < cfg.n_levels; ++i) {
-    PRG_CHECK(cfg.dim_mults[i] >= 1, "config: bad dim_mult");
-    L.dims.push_back(cfg.dim * cfg.dim_mults[i]);
-  }
-  for (size_t i = 0; i < L.dims.size(); ++i) PRG_CHECK(L.dims[i] % cfg.groups == 0, "config: width not divisible by groups");
-  for (size_t i = 0; i < L.dims.size(); ++i)
-    if (L.dims[i] > 1024)
-      return fail(PRG_E_INVALID, "config: dim * dim_mult = " + std::to_string(L.dims[i]) + " exceeds 1024 channels, the widest "
-                  "GroupNorm the coefficient kernels handle (gn_coeff_kernel / affine_silu_fold_kernel: four channels per thread)");
-  const bool cond = cfg.conditional != 0;
-  Cursor c;
-  const int d0 = cfg.dim, e = L.emb;
-  L.stem_w = c.take((int64_t)d0 * cfg.in_channels * 49);
-  L.stem_b = c.take(d0);
-  if (cond) {
-    L.tm1_w = c.take((int64_t)e * d0); L.tm1_b = c.take(e);
-    L.tm3_w = c.take((int64_t)e * e);  L.tm3_b = c.take(e);
-    L.pm0_w = c.take((int64_t)e * cfg.param_cond_dim); L.pm0_b = c.take(e);
-    L.pm2_w = c.take((int64_t)e * e);  L.pm2_b = c.take(e);
-  }
-  L.downs.resize(L.L);
-  L.ups.resize(L.L);
-  for (int i = 0; i < L.L; ++i) {
-    const int ci = L.dims[i], co = L.dims[i + 1];
-    LevelP& lv = L.downs[i];
-    walk_res(c, lv.r0, ci, ci, cond, e, L.ss_total);
-    walk_res(c, lv.r1, ci, ci, cond, e, L.ss_total);
-    walk_attn(c, lv.at, ci, true);
-    lv.strided = i != L.L - 1;
-    walk_conv(c, lv.resample, co, ci, lv.strided ? 4 : 3, true, false);
-  }
-  for (int i = 0; i < L.L; ++i) {
-    const int ci = L.dims[L.L - 1 - i], co = L.dims[L.L - i];
-    LevelP& lv = L.ups[i];
-    walk_res(c, lv.r0, co + ci, co, cond, e, L.ss_total);
-    walk_res(c, lv.r1, co + ci, co, cond, e, L.ss_total);
-    walk_attn(c, lv.at, co, true);
-    lv.strided = i != L.L - 1;  // here: "followed by x2 upsample"
-    walk_conv(c, lv.resample, ci, co, 3, true, false);
-  }
-  const int mid = L.dims.back();
-  walk_res(c, L.mid1, mid, mid, cond, e, L.ss_total);
-  walk_attn(c, L.mid_at, mid, false);
-  walk_res(c, L.mid2, mid, mid, cond, e, L.ss_total);
-  walk_res(c, L.fin, 2 * d0, d0, cond, e, L.ss_total);
-  L.head_w = c.take(d0);
-  L.head_b = c.take(1);
-  L.total = c.pos;
-  return PRG_OK;
-}
-
-// conditioning source for the ResnetBlocks of one forward
-struct CondSrc {
-  const float* ss_a = nullptr;
-  const float* ss_b = nullptr;
-  int64_t ss_a_stride = 0, ss_b_stride = 0;
-  const int* row = nullptr;
-  int64_t row_stride = 0;
-};
-
-struct Tap {
-  const void* ptr;
-  int C, H, W, B;
-  bool nchw_f32;
-};
-
-}  // namespace prg
-
-using namespace prg;
-
-// ---------------------------------------------------------------------------------------------
-// handle types
-// ---------------------------------------------------------------------------------------------
-struct prg_unet {
-  Layout lay;
-  int dtype = PRG_F32;
-  float* d_flat = nullptr;      // the float32 state_dict on device (biases, norm gains, MLPs read in place)
-  void* d_packed = nullptr;     // packed conv weights of T
-  float* d_stem = nullptr;      // stem weights [49*Cin][dim]
-  bf16_t* d_stem_frag = nullptr; // stem weights as MFMA fragments (bf16 path, Cin 1 -> 64)
-  uint16_t* d_stem_split = nullptr;    // f16x3 mode: the same fragments as f16 hi / lo halves (stem_mfma_kernel<CIN, true>)
-  float* d_stem_split_scale = nullptr; // ... and the inverse of the packer's per-channel power-of-two scale [64]
-  bf16_t* d_attn = nullptr;     // fused linear attention: gain-folded to_qkv and to_out weights (bf16 path only)
-  float* d_kshift = nullptr;    // fused linear attention: static softmax shifts of the k columns
-  uint8_t* d_mx = nullptr;      // MX-fp8 conv weights (dtype PRG_MXFP8): e4m3 data and E8M0 block scales
-  uint8_t* d_mx_scale = nullptr;
-  uint16_t* d_attn_split = nullptr;   // f16x3 mode: fused linear attention weights as f16 hi / lo halves (attn_split.hip)
-  float* d_split_scale = nullptr;   // f16x3 mode: the packer's per-output-channel power-of-two factors, undone in the epilogues
-  uint16_t* d_split = nullptr;  // f16x3 mode (dtype PRG_F16X3): every conv weight as f16 hi / lo halves (conv_split.hip)
-  uint16_t* d_h16 = nullptr;    // bf16 mode: f16 twins of the ResnetBlocks' second convs (the h16 format, conv.h)
-  float* d_freqs = nullptr;     // SinusoidalPosEmb frequencies [dim/2] (sd:645-657), see prg_unet_set_time_freqs
-  // fixed-point GroupNorm statistics (common.h, GnFold; bf16 / mxfp8 handles)
-  long long* d_gnacc = nullptr; // [slots][resB][groups][2], zeroed by ONE memset at the start of every forward
-  size_t gnacc_bytes = 0;
-  int gn_slots = 0, gn_slot = 0;
-  float* d_pq_static = nullptr; // (gamma | beta) of every norm, 16-byte aligned rows: P / Q of the unconditioned norms
-  CondFoldEntry* d_cond_entries = nullptr;   // one entry per conditioned norm (Block 1 of every ResnetBlock)
-  int n_cond_entries = 0;
-  Arena arena;
-  uint64_t arena_gen = 0;       // bumped whenever the workspace is reallocated: captured graphs bake its pointers in
-  int resB = 0, resS = 0;
-  bool taps_on = false;
-  std::map<std::string, Tap> taps;
-  ProfileSink* prof = nullptr;
-  virtual ~prg_unet() {}
-  virtual int measure(int B, int S, size_t* bytes) = 0;
-  virtual int forward(const float* x_nchw, const CondSrc& cond, float* out, int B, int S, hipStream_t s) = 0;
-  virtual int cond_general(const int64_t* time, const float* param_cond, int B, CondSrc* out, hipStream_t s) = 0;
-  virtual int tap_copy(const Tap& t, float* out, hipStream_t s) = 0;
-};
-
-namespace prg {
 
 template <typename T>
 struct UnetImpl : prg_unet {
@@ -850,11 +611,9 @@ struct UnetImpl : prg_unet {
       return launch_linear(cat, 2 * e, 0, F(r.mlp_w), 2 * e, 0, F(r.mlp_b), ss + r.ss_off, L.ss_total, B, 2 * e,
                            2 * r.cout, ACT_SILU, ACT_NONE, s);
     };
-    for (auto& lv : L.downs) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    for (auto& lv : L.ups) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    if ((rc = one(L.mid1))) return rc;
-    if ((rc = one(L.mid2))) return rc;
-    if ((rc = one(L.fin))) return rc;
+    rc = PRG_OK;
+    for_each_res(L, [&](const ResP& r) { if (rc == PRG_OK) rc = one(r); });
+    if (rc) return rc;
     out->ss_a = ss;
     out->ss_a_stride = L.ss_total;
     out->ss_b = nullptr;
@@ -870,371 +629,6 @@ struct UnetImpl : prg_unet {
     return launch_nhwc_to_nchw_f32<T>(reinterpret_cast<const T*>(t.ptr), out, t.B, t.H * t.W, t.C, s);
   }
 };
-
-// ---- weight preparation (host) ---------------------------------------------------------------
-static bool fused_attention_enabled() {
-  static const int on = env_int("PRG_FUSED_ATTN", 1);
-  return on != 0;
-}
-
-static void standardize(const float* w, int Cout, int K, std::vector<float>& out) {
-  out.resize((size_t)Cout * K);
-  for (int o = 0; o < Cout; ++o) {
-    double m = 0;
-    for (int k = 0; k < K; ++k) m += w[(size_t)o * K + k];
-    m /= K;
-    double v = 0;
-    for (int k = 0; k < K; ++k) { double d = w[(size_t)o * K + k] - m; v += d * d; }
-    v /= K;
-    const double rs = 1.0 / std::sqrt(v + 1e-5);
-    for (int k = 0; k < K; ++k) out[(size_t)o * K + k] = (float)((w[(size_t)o * K + k] - m) * rs);
-  }
-}
-
-template <typename T>
-static void pack_all(Layout& L, const float* flat, std::vector<T>& packed) {
-  std::vector<ConvP*> convs;
-  auto add_res = [&](ResP& r) { convs.push_back(&r.c1); convs.push_back(&r.c2); if (r.has_res) convs.push_back(&r.res); };
-  auto add_at = [&](AttnP& a) { convs.push_back(&a.qkv); convs.push_back(&a.out); };
-  for (auto& lv : L.downs) { add_res(lv.r0); add_res(lv.r1); add_at(lv.at); convs.push_back(&lv.resample); }
-  for (auto& lv : L.ups) { add_res(lv.r0); add_res(lv.r1); add_at(lv.at); convs.push_back(&lv.resample); }
-  add_res(L.mid1); add_at(L.mid_at); add_res(L.mid2); add_res(L.fin);
-  std::vector<float> tmp;
-  std::vector<T> one;
-  for (ConvP* p : convs) {
-    const float* w = flat + p->w_flat;
-    if (p->ws) { standardize(w, p->Cout, p->Cin * p->KH * p->KW, tmp); w = tmp.data(); }
-    pack_conv_weight<T>(w, p->Cout, p->Cin, p->KH, p->KW, one, &p->CoutPad, &p->kchunks);
-    size_t off = (packed.size() + 127) / 128 * 128;  // 256-byte aligned tiles
-    packed.resize(off + one.size());
-    std::memcpy(packed.data() + off, one.data(), one.size() * sizeof(T));
-    p->w_off = off;
-    if (std::is_same<T, bf16_t>::value && p->KH == 4 && p->KW == 4 && p->Cin % 64 == 0 && p->Cout % 64 == 0) {
-      // Downsample: second packing for the 256-pixel kernel's 2 x 2-tap mode (conv_w256.hip)
-      std::vector<float> eq;
-      s2d_equivalent_weights(w, p->Cout, p->Cin, eq);
-      int cp = 0;
-      pack_conv_weight<T>(eq.data(), p->Cout, 4 * p->Cin, 3, 3, one, &cp, &p->s2d_kchunks);
-      off = (packed.size() + 127) / 128 * 128;
-      packed.resize(off + one.size());
-      std::memcpy(packed.data() + off, one.data(), one.size() * sizeof(T));
-      p->s2d_off = (int64_t)off;
-    }
-  }
-  if (std::is_same<T, bf16_t>::value) {
-    // Upsample convs (up levels whose resample is nearest x2 + 3 x 3): third packing, the sub-pixel decomposition (conv_w256.hip MODE 2)
-    for (auto& lv : L.ups) {
-      ConvP* p = &lv.resample;
-      if (!lv.strided || !(p->KH == 3 && p->KW == 3 && p->Cin % 64 == 0 && (p->Cout == 64 || p->Cout % 128 == 0))) continue;
-      const float* w = flat + p->w_flat;
-      if (p->ws) { standardize(w, p->Cout, p->Cin * 9, tmp); w = tmp.data(); }
-      std::vector<float> eq;
-      up_equivalent_weights(w, p->Cout, p->Cin, eq);
-      size_t off = (packed.size() + 127) / 128 * 128;
-      p->up_off = (int64_t)off;
-      for (int ph = 0; ph < 4; ++ph) {
-        int cp = 0, kc = 0;
-        pack_conv_weight<T>(eq.data() + (size_t)ph * p->Cout * p->Cin * 4, p->Cout, p->Cin, 2, 2, one, &cp, &kc);
-        packed.resize(off + one.size());
-        std::memcpy(packed.data() + off, one.data(), one.size() * sizeof(T));
-        off += one.size();
-      }
-    }
-  }
-}
-
-static void collect_convs(Layout& L, std::vector<ConvP*>& convs) {
-  auto add_res = [&](ResP& r) { convs.push_back(&r.c1); convs.push_back(&r.c2); if (r.has_res) convs.push_back(&r.res); };
-  auto add_at = [&](AttnP& a) { convs.push_back(&a.qkv); convs.push_back(&a.out); };
-  for (auto& lv : L.downs) { add_res(lv.r0); add_res(lv.r1); add_at(lv.at); convs.push_back(&lv.resample); }
-  for (auto& lv : L.ups) { add_res(lv.r0); add_res(lv.r1); add_at(lv.at); convs.push_back(&lv.resample); }
-  add_res(L.mid1); add_at(L.mid_at); add_res(L.mid2); add_res(L.fin);
-}
-
-template <typename T>
-static int create_impl(const prg_unet_config* cfg, const float* weights, int64_t n, prg_unet** out, bool mx = false, bool split = false) {
-  std::unique_ptr<UnetImpl<T>> u(new UnetImpl<T>());
-  int rc = build_layout(*cfg, u->lay);
-  if (rc) return rc;
-  if (u->lay.total != n)
-    return fail(PRG_E_INVALID, "prg_unet_create: expected " + std::to_string(u->lay.total) + " floats, got " +
-                                   std::to_string(n));
-  std::vector<T> packed;
-  pack_all<T>(u->lay, weights, packed);
-  const Layout& L = u->lay;
-  std::vector<float> stem((size_t)49 * L.cfg.in_channels * L.cfg.dim);
-  for (int o = 0; o < L.cfg.dim; ++o)
-    for (int c = 0; c < L.cfg.in_channels; ++c)
-      for (int t = 0; t < 49; ++t)
-        stem[((size_t)t * L.cfg.in_channels + c) * L.cfg.dim + o] = weights[L.stem_w + ((size_t)o * L.cfg.in_channels + c) * 49 + t];
-  if (hipMalloc(&u->d_flat, (size_t)n * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(flat weights)");
-  if (hipMalloc(&u->d_packed, packed.size() * sizeof(T)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(packed weights)");
-  if (hipMalloc(&u->d_stem, stem.size() * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(stem weights)");
-  PRG_HIP(hipMemcpy(u->d_flat, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  PRG_HIP(hipMemcpy(u->d_packed, packed.data(), packed.size() * sizeof(T), hipMemcpyHostToDevice));
-  PRG_HIP(hipMemcpy(u->d_stem, stem.data(), stem.size() * sizeof(float), hipMemcpyHostToDevice));
-  {
-    // default frequency table: the reference's expression in float32 with this host's libm (the Python front-end
-    // replaces it with torch's own evaluation, which is what the reference would compute on the same host)
-    const int half = L.cfg.dim / 2;
-    std::vector<float> fr(half);
-    const float stepf = -(float)(9.210340371976184 / (double)(half - 1));
-    for (int i = 0; i < half; ++i) fr[i] = std::exp((float)i * stepf);
-    if (hipMalloc(&u->d_freqs, half * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(time frequencies)");
-    PRG_HIP(hipMemcpy(u->d_freqs, fr.data(), half * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (mx) {
-    // MX-fp8 copies of every 3x3 conv weight whose widths are 64-channel multiples (what conv3x3_mx_kernel covers); the
-    // 1x1 / 4x4 / stem convs and everything that is not a convolution stay bf16.
-    std::vector<ConvP*> convs;
-    collect_convs(u->lay, convs);
-    std::vector<uint8_t> data, scales, one, ones;
-    std::vector<float> tmp;
-    for (ConvP* p : convs) {
-      if (!(p->KH == 3 && p->KW == 3 && p->Cin % 64 == 0 && p->Cout % 64 == 0)) continue;
-      const float* w = weights + p->w_flat;
-      if (p->ws) { standardize(w, p->Cout, p->Cin * 9, tmp); w = tmp.data(); }
-      int cp = 0, kc = 0;
-      pack_conv_weight_mxfp8(w, p->Cout, p->Cin, 3, 3, one, ones, &cp, &kc);
-      p->mx_off = (int64_t)((data.size() + 255) / 256 * 256);
-      data.resize((size_t)p->mx_off + one.size());
-      std::memcpy(data.data() + p->mx_off, one.data(), one.size());
-      p->mx_soff = (int64_t)((scales.size() + 255) / 256 * 256);
-      scales.resize((size_t)p->mx_soff + ones.size());
-      std::memcpy(scales.data() + p->mx_soff, ones.data(), ones.size());
-    }
-    if (!data.empty()) {
-      if (hipMalloc(&u->d_mx, data.size()) != hipSuccess || hipMalloc(&u->d_mx_scale, scales.size()) != hipSuccess)
-        return fail(PRG_E_NOMEM, "hipMalloc(MX-fp8 weights)");
-      PRG_HIP(hipMemcpy(u->d_mx, data.data(), data.size(), hipMemcpyHostToDevice));
-      PRG_HIP(hipMemcpy(u->d_mx_scale, scales.data(), scales.size(), hipMemcpyHostToDevice));
-    }
-  }
-  if (std::is_same<T, bf16_t>::value) {
-    // h16 (conv.h): f16 twins of the ResnetBlocks' second convs (3 x 3, Cin = Cout, 64-channel multiples), standardised like the
-    // bf16 packing; conv2 takes them when the block's h1 tensor is stored as f16 (mxfp8 handles: the 64-channel pairs only —
-    // conv_h16_pair_ok — the wide convs run on their MX copies)
-    Layout& Lm = u->lay;
-    std::vector<ResP*> rs;
-    for (auto& lv : Lm.downs) { rs.push_back(&lv.r0); rs.push_back(&lv.r1); }
-    for (auto& lv : Lm.ups) { rs.push_back(&lv.r0); rs.push_back(&lv.r1); }
-    rs.push_back(&Lm.mid1); rs.push_back(&Lm.mid2); rs.push_back(&Lm.fin);
-    std::vector<uint16_t> data, one;
-    std::vector<float> tmp;
-    for (ResP* r : rs) {
-      ConvP* p = &r->c2;
-      if (!(p->KH == 3 && p->KW == 3 && p->Cin == p->Cout && p->Cin % 64 == 0)) continue;
-      const float* w = weights + p->w_flat;
-      if (p->ws) { standardize(w, p->Cout, p->Cin * 9, tmp); w = tmp.data(); }
-      pack_conv_weight_f16(w, p->Cout, p->Cin, 3, 3, one);
-      p->h16_off = (int64_t)((data.size() + 127) / 128 * 128);
-      data.resize((size_t)p->h16_off + one.size());
-      std::memcpy(data.data() + p->h16_off, one.data(), one.size() * sizeof(uint16_t));
-    }
-    if (!data.empty()) {
-      if (hipMalloc(&u->d_h16, data.size() * sizeof(uint16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(h16 weights)");
-      PRG_HIP(hipMemcpy(u->d_h16, data.data(), data.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-  }
-  if (split) {
-    // f16x3 mode: hi / lo f16 halves of every conv weight (standardised first where the Block does), conv_split.hip
-    std::vector<ConvP*> convs;
-    collect_convs(u->lay, convs);
-    std::vector<uint16_t> data, one;
-    std::vector<float> tmp, scales, sc1;
-    for (ConvP* p : convs) {
-      const float* w = weights + p->w_flat;
-      if (p->ws) { standardize(w, p->Cout, p->Cin * p->KH * p->KW, tmp); w = tmp.data(); }
-      int cp = 0;
-      pack_conv_weight_split(w, p->Cout, p->Cin, p->KH, p->KW, one, &cp, &p->sp_kchunks, &sc1);
-      p->sp_off = (int64_t)((data.size() + 127) / 128 * 128);
-      data.resize((size_t)p->sp_off + one.size());
-      std::memcpy(data.data() + p->sp_off, one.data(), one.size() * sizeof(uint16_t));
-      p->sp_scale_off = (int64_t)scales.size();
-      scales.insert(scales.end(), sc1.begin(), sc1.end());
-    }
-    // Upsample convs: the sub-pixel decomposition's four 2 x 2-tap packings (conv_split.hip, UP form of the wave-specialised kernel)
-    // (built only when the option is on — it is off by default, conv_split.hip: try_launch_conv_split — ADVICE round 4)
-    static const int split_up_on = env_int("PRG_SPLIT_UP2X2", 0);
-    for (auto& lv : u->lay.ups) {
-      ConvP* p = &lv.resample;
-      if (!split_up_on || !lv.strided || !(p->KH == 3 && p->KW == 3 && p->Cin % 32 == 0 && p->Cout % 128 == 0)) continue;
-      const float* w = weights + p->w_flat;
-      if (p->ws) { standardize(w, p->Cout, p->Cin * p->KH * p->KW, tmp); w = tmp.data(); }   // (as the bf16 twin in pack_all; no Upsample conv is)
-      std::vector<float> eq;
-      up_equivalent_weights(w, p->Cout, p->Cin, eq);
-      p->up_sp_off = (int64_t)((data.size() + 127) / 128 * 128);
-      p->up_sp_scale_off = (int64_t)scales.size();
-      size_t off = (size_t)p->up_sp_off;
-      for (int ph = 0; ph < 4; ++ph) {
-        int cp = 0, kc = 0;
-        pack_conv_weight_split(eq.data() + (size_t)ph * p->Cout * p->Cin * 4, p->Cout, p->Cin, 2, 2, one, &cp, &kc, &sc1);
-        data.resize(off + one.size());
-        std::memcpy(data.data() + off, one.data(), one.size() * sizeof(uint16_t));
-        off += one.size();
-        scales.insert(scales.end(), sc1.begin(), sc1.end());     // [phase][CoutPad]
-      }
-    }
-    if (hipMalloc(&u->d_split_scale, scales.size() * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split scales)");
-    PRG_HIP(hipMemcpy(u->d_split_scale, scales.data(), scales.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (hipMalloc(&u->d_split, data.size() * sizeof(uint16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split weights)");
-    PRG_HIP(hipMemcpy(u->d_split, data.data(), data.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    // fused linear attention (attn_split.hip): to_qkv with the PreNorm gain folded in (q and k rows times log2 e: both only ever
-    // enter a softmax, evaluated with exp2) and to_out, each as f16 hi halves followed by the lo halves
-    std::vector<uint16_t> aw;
-    auto f16bits = [](float v, uint16_t& h, uint16_t& l) {
-      const _Float16 a = (_Float16)v, b = (_Float16)(v - (float)a);
-      std::memcpy(&h, &a, 2);
-      std::memcpy(&l, &b, 2);
-    };
-    auto add_attn = [&](AttnP& a) {
-      if (!a.linear || (a.C != 64 && a.C != 128)) return;   // (linattn_split_supported: C = 64 / 128; the token count is checked per call)
-      aw.resize((aw.size() + 63) / 64 * 64);
-      a.sp_qkv = (int64_t)aw.size();
-      const size_t nq = (size_t)3 * kHidden * a.C;
-      aw.resize(aw.size() + 2 * nq);
-      for (int o = 0; o < 3 * kHidden; ++o)
-        for (int c = 0; c < a.C; ++c) {
-          const float v = weights[a.qkv.w_flat + (size_t)o * a.C + c] * weights[a.norm_g + c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f);
-          f16bits(v, aw[a.sp_qkv + (size_t)o * a.C + c], aw[a.sp_qkv + nq + (size_t)o * a.C + c]);
-        }
-      aw.resize((aw.size() + 63) / 64 * 64);
-      a.sp_out = (int64_t)aw.size();
-      const size_t no = (size_t)a.C * kHidden;
-      aw.resize(aw.size() + 2 * no);
-      for (size_t i = 0; i < no; ++i) f16bits(weights[a.out.w_flat + i], aw[a.sp_out + i], aw[a.sp_out + no + i]);
-    };
-    for (auto& lv : u->lay.downs) add_attn(lv.at);
-    for (auto& lv : u->lay.ups) add_attn(lv.at);
-    if (!aw.empty()) {
-      if (hipMalloc(&u->d_attn_split, aw.size() * sizeof(uint16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split attention weights)");
-      PRG_HIP(hipMemcpy(u->d_attn_split, aw.data(), aw.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-  }
-  if (std::is_same<T, bf16_t>::value) {
-    // fixed-point GroupNorm statistics (common.h, GnFold): P = gamma, Q = beta of every norm in 16-byte aligned rows (what
-    // the unconditioned norms use directly) and the table cond_fold_kernel walks for the conditioned ones
-    std::vector<float> pq;
-    std::vector<CondFoldEntry> ent;
-    auto add = [&](ResP& r) {
-      r.cpad = (r.cout + 3) & ~3;
-      auto put = [&](int64_t g_off, int64_t b_off) {
-        const int64_t o = (int64_t)pq.size();
-        pq.resize(pq.size() + 2 * (size_t)r.cpad, 0.0f);
-        std::memcpy(pq.data() + o, weights + g_off, sizeof(float) * r.cout);
-        std::memcpy(pq.data() + o + r.cpad, weights + b_off, sizeof(float) * r.cout);
-        return o;
-      };
-      r.pq1 = put(r.g1, r.b1);
-      r.pq2 = put(r.g2, r.b2);
-      if (L.cfg.conditional) ent.push_back(CondFoldEntry{r.ss_off, r.cout, (long long)r.g1, (long long)r.b1});
-    };
-    for (auto& lv : u->lay.downs) { add(lv.r0); add(lv.r1); }
-    for (auto& lv : u->lay.ups) { add(lv.r0); add(lv.r1); }
-    add(u->lay.mid1); add(u->lay.mid2); add(u->lay.fin);
-    if (hipMalloc(&u->d_pq_static, pq.size() * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(norm gains)");
-    PRG_HIP(hipMemcpy(u->d_pq_static, pq.data(), pq.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!ent.empty()) {
-      if (hipMalloc(&u->d_cond_entries, ent.size() * sizeof(CondFoldEntry)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(cond entries)");
-      PRG_HIP(hipMemcpy(u->d_cond_entries, ent.data(), ent.size() * sizeof(CondFoldEntry), hipMemcpyHostToDevice));
-      u->n_cond_entries = (int)ent.size();
-    }
-  }
-  if (std::is_same<T, bf16_t>::value && (L.cfg.in_channels == 1 || L.cfg.in_channels == 3) && L.cfg.dim == 64) {
-    std::vector<bf16_t> sf;
-    pack_stem_mfma_weights(weights + L.stem_w, L.cfg.in_channels, sf);
-    if (hipMalloc(&u->d_stem_frag, sf.size() * sizeof(bf16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(stem fragments)");
-    PRG_HIP(hipMemcpy(u->d_stem_frag, sf.data(), sf.size() * sizeof(bf16_t), hipMemcpyHostToDevice));
-  }
-  // f16x3 (round 5): the stem on the same MFMA kernel with f16 hi / lo halves (PRG_SPLIT_STEM=0: the direct fmaf kernel of the parity mode)
-  static const int split_stem_on = env_int("PRG_SPLIT_STEM", 1);
-  if (split && split_stem_on && (L.cfg.in_channels == 1 || L.cfg.in_channels == 3) && L.cfg.dim == 64) {
-    std::vector<uint16_t> sf;
-    std::vector<float> sc;
-    pack_stem_mfma_weights_split(weights + L.stem_w, L.cfg.in_channels, sf, sc);
-    if (hipMalloc(&u->d_stem_split, sf.size() * sizeof(uint16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split stem fragments)");
-    PRG_HIP(hipMemcpy(u->d_stem_split, sf.data(), sf.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    if (hipMalloc(&u->d_stem_split_scale, sc.size() * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(split stem scales)");
-    PRG_HIP(hipMemcpy(u->d_stem_split_scale, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (std::is_same<T, bf16_t>::value && fused_attention_enabled()) {
-    // fused linear attention (attn_fused.hip): to_qkv with the PreNorm gain folded in, to_out as is, both [out][in] bf16
-    std::vector<bf16_t> aw;
-    std::vector<float> ks;
-    // PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every block
-    static const int kshift_on = env_int("PRG_LA_KSHIFT", 1);
-    auto add = [&](AttnP& a) {
-      if (!a.linear || !linattn_fused_supported(a.C)) return;
-      aw.resize((aw.size() + 63) / 64 * 64);
-      a.fw_qkv = (int64_t)aw.size();
-      for (int o = 0; o < 3 * kHidden; ++o)
-        for (int c = 0; c < a.C; ++c)
-          // q and k only ever enter a softmax: their rows carry log2(e), so the kernels exponentiate with a bare v_exp_f32
-          aw.push_back(f32_to_bf16(weights[a.qkv.w_flat + (size_t)o * a.C + c] * weights[a.norm_g + c] *
-                                   (o < 2 * kHidden ? 1.4426950408889634f : 1.0f)));
-      // Softmax over pixels of k[n][d] = w_d . LN(x_n): a LayerNorm output has norm <= sqrt(C), so |k| <= ||w_d|| sqrt(C)
-      // (Cauchy-Schwarz; w_d = the bf16 weights the kernel multiplies with, 2 % slack for the bf16 rounding of LN(x)).
-      // exp(k - bound) >= exp(-2 bound): with bound <= 40 nothing underflows and the column maxima need not be measured.
-      // (k, hence the bound, in units of 1 / log2(e): the rows above are pre-scaled.)
-      float shifts[kHidden];
-      bool ok = kshift_on != 0;
-      for (int d = 0; d < kHidden; ++d) {
-        double n2 = 0;
-        for (int c = 0; c < a.C; ++c) {
-          const double w = bf16_to_f32(aw[(size_t)a.fw_qkv + (size_t)(kHidden + d) * a.C + c]);
-          n2 += w * w;
-        }
-        shifts[d] = (float)(1.02 * std::sqrt(n2 * a.C));
-        ok = ok && shifts[d] <= 40.0f * 1.4426950408889634f;
-      }
-      // the same bound for the q rows (softmax over the 32 d of a head, per pixel): one shift per head
-      float qsh[kHeads];
-      for (int h = 0; h < kHeads; ++h) {
-        double worst = 0;
-        for (int d = 0; d < kDimHead; ++d) {
-          double n2 = 0;
-          for (int c = 0; c < a.C; ++c) {
-            const double w = bf16_to_f32(aw[(size_t)a.fw_qkv + (size_t)(h * kDimHead + d) * a.C + c]);
-            n2 += w * w;
-          }
-          worst = std::max(worst, 1.02 * std::sqrt(n2 * a.C));
-        }
-        qsh[h] = (float)worst;
-        ok = ok && qsh[h] <= 40.0f * 1.4426950408889634f;
-      }
-      if (ok) {
-        a.kshift = (int64_t)ks.size();
-        ks.insert(ks.end(), shifts, shifts + kHidden);
-        ks.insert(ks.end(), qsh, qsh + kHeads);
-        ks.resize((ks.size() + 3) & ~(size_t)3);
-      }
-      a.fw_out = (int64_t)aw.size();
-      for (int c = 0; c < a.C; ++c)
-        for (int j = 0; j < kHidden; ++j) aw.push_back(f32_to_bf16(weights[a.out.w_flat + (size_t)c * kHidden + j]));
-    };
-    for (auto& lv : u->lay.downs) add(lv.at);
-    for (auto& lv : u->lay.ups) add(lv.at);
-    // fused ResnetBlock tail: raw res_conv weights [Cout][Cin] as bf16
-    auto add_res = [&](ResP& r) {
-      if (!r.has_res || r.res.b_off < 0 || !resblock_tail_fused_supported(r.cin / 2, r.cin - r.cin / 2, r.cout)) return;
-      aw.resize((aw.size() + 63) / 64 * 64);
-      r.fw_res = (int64_t)aw.size();
-      for (size_t i = 0; i < (size_t)r.cout * r.cin; ++i) aw.push_back(f32_to_bf16(weights[r.res.w_flat + i]));
-    };
-    for (auto& lv : u->lay.ups) { add_res(lv.r0); add_res(lv.r1); }
-    add_res(u->lay.fin);
-    if (!aw.empty()) {
-      if (hipMalloc(&u->d_attn, aw.size() * sizeof(bf16_t)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(attention weights)");
-      PRG_HIP(hipMemcpy(u->d_attn, aw.data(), aw.size() * sizeof(bf16_t), hipMemcpyHostToDevice));
-    }
-    if (!ks.empty()) {
-      if (hipMalloc(&u->d_kshift, ks.size() * sizeof(float)) != hipSuccess) return fail(PRG_E_NOMEM, "hipMalloc(softmax shifts)");
-      PRG_HIP(hipMemcpy(u->d_kshift, ks.data(), ks.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  }
-  *out = u.release();
-  return PRG_OK;
-}
 
 static int reserve(prg_unet* h, int B, int S) {
   if (B <= h->resB && S <= h->resS && h->arena.base) return PRG_OK;
@@ -1270,6 +664,8 @@ static int reserve(prg_unet* h, int B, int S) {
 
 }  // namespace prg
 
+using namespace prg;
+
 // =============================================================================================
 // sampler handle
 // =============================================================================================
@@ -1277,6 +673,7 @@ struct prg_sampler {
   prg_unet* unet = nullptr;
   int B = 0, S = 0, n_steps = 0;
   std::vector<prg_step> steps;
+  DeviceBuffers own;          // the d_* buffers below
   prg_step* d_steps = nullptr;
   float* d_tpart = nullptr;   // [n_steps][ss_total]  time half of every block's conditioning (+ bias)
   float* d_ppart = nullptr;   // [B][ss_total]        camera-parameter half
@@ -1296,6 +693,11 @@ struct prg_sampler {
   bool use_graph = true;
   ProfileSink prof;
   double last_total_ms = 0;
+  ~prg_sampler() {
+    for (auto& ev : prof.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    for (auto& ev : prof.step_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
 };
 
 namespace prg {
@@ -1376,33 +778,19 @@ int prg_unet_create(const prg_unet_config* cfg, const float* weights, int64_t n_
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PRG_E_HIP, "prg_unet_create: no HIP device");
   *out = nullptr;
-  int rc = (dtype == PRG_F32 || dtype == PRG_F16X3) ? create_impl<float>(cfg, weights, n_floats, out, false, dtype == PRG_F16X3)
-                                                     : create_impl<bf16_t>(cfg, weights, n_floats, out, dtype == PRG_MXFP8);
-  if (rc == PRG_OK) (*out)->dtype = dtype;
-  return rc;
+  std::unique_ptr<prg_unet> u;
+  if (dtype == PRG_F32 || dtype == PRG_F16X3) u.reset(new UnetImpl<float>());
+  else u.reset(new UnetImpl<bf16_t>());
+  int rc = prepare_unet_weights(*u, *cfg, weights, n_floats, dtype);
+  if (rc) return rc;
+  *out = u.release();
+  return PRG_OK;
 }
 
 int prg_unet_destroy(prg_unet* h) {
   if (!h) return PRG_OK;
   (void)hipDeviceSynchronize();
-  if (h->d_flat) (void)hipFree(h->d_flat);
-  if (h->d_packed) (void)hipFree(h->d_packed);
-  if (h->d_stem) (void)hipFree(h->d_stem);
-  if (h->d_attn) (void)hipFree(h->d_attn);
-  if (h->d_kshift) (void)hipFree(h->d_kshift);
-  if (h->d_freqs) (void)hipFree(h->d_freqs);
-  if (h->d_mx) (void)hipFree(h->d_mx);
-  if (h->d_mx_scale) (void)hipFree(h->d_mx_scale);
-  if (h->d_split) (void)hipFree(h->d_split);
-  if (h->d_split_scale) (void)hipFree(h->d_split_scale);
-  if (h->d_h16) (void)hipFree(h->d_h16);
-  if (h->d_attn_split) (void)hipFree(h->d_attn_split);
-  if (h->d_gnacc) (void)hipFree(h->d_gnacc);
-  if (h->d_pq_static) (void)hipFree(h->d_pq_static);
-  if (h->d_cond_entries) (void)hipFree(h->d_cond_entries);
-  if (h->d_stem_frag) (void)hipFree(h->d_stem_frag);
-  if (h->d_stem_split) (void)hipFree(h->d_stem_split);
-  if (h->d_stem_split_scale) (void)hipFree(h->d_stem_split_scale);
+  if (h->d_gnacc) (void)hipFree(h->d_gnacc);   // (reallocated by reserve, like the workspace; the weights: prg_unet::own)
   if (h->arena.base) (void)hipFree(h->arena.base);
   delete h;
   return PRG_OK;
@@ -1472,254 +860,6 @@ int prg_maskunet_forward(prg_unet* h, const float* depth, float* prob, int B, in
 }
 
 // ---------------------------------------------------------------------------------------------
-// float32-storage handles (PRG_F32: the exact-f32 kernels; PRG_F16X3: the split-operand kernels of conv_split.hip)
-static int debug_conv_f32(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                          int dtype, int K, int stride, int pad, hipStream_t s, int ups = 0) {
-  const size_t M = (size_t)B * H * W;
-  const int Ho = ups ? 2 * H : (H + 2 * pad - K) / stride + 1, Wo = ups ? 2 * W : (W + 2 * pad - K) / stride + 1;
-  const size_t Mo = (size_t)B * Ho * Wo;
-  std::vector<float> packed;
-  std::vector<uint16_t> sp;
-  int cp = 0, kc = 0, cp2 = 0, kc32 = 0;
-  pack_conv_weight<float>(w, Cout, Cin, K, K, packed, &cp, &kc);
-  std::vector<float> spsc;
-  if (dtype == PRG_F16X3) pack_conv_weight_split(w, Cout, Cin, K, K, sp, &cp2, &kc32, &spsc);
-  // Upsample (nearest x2, then the 3x3): the sub-pixel form's four 2 x 2-tap packings, as create_impl builds them (ADVICE round 4:
-  // the UP form of conv3x3_split_ws_kernel gets a kernel-level test)
-  std::vector<uint16_t> spu;
-  std::vector<float> spusc;
-  if (ups && dtype == PRG_F16X3 && K == 3 && Cin % 32 == 0 && Cout % 128 == 0) {
-    std::vector<float> eq, sc1;
-    std::vector<uint16_t> one;
-    up_equivalent_weights(w, Cout, Cin, eq);
-    for (int ph = 0; ph < 4; ++ph) {
-      int cpu_ = 0, kcu_ = 0;
-      pack_conv_weight_split(eq.data() + (size_t)ph * Cout * Cin * 4, Cout, Cin, 2, 2, one, &cpu_, &kcu_, &sc1);
-      spu.insert(spu.end(), one.begin(), one.end());
-      spusc.insert(spusc.end(), sc1.begin(), sc1.end());
-    }
-  }
-  std::vector<float> zb(Cout, 0.0f);
-  void *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr, *d_sp = nullptr, *d_sc = nullptr, *d_spu = nullptr, *d_scu = nullptr;
-  auto cleanup = [&]() { for (void* p : {d_in, d_out, d_w, d_b, d_sp, d_sc, d_spu, d_scu}) if (p) (void)hipFree(p); };
-  if (hipMalloc(&d_in, M * Cin * 4) != hipSuccess || hipMalloc(&d_out, Mo * Cout * 4) != hipSuccess ||
-      hipMalloc(&d_w, packed.size() * 4) != hipSuccess || hipMalloc(&d_b, Cout * 4) != hipSuccess ||
-      (!sp.empty() && (hipMalloc(&d_sp, sp.size() * 2) != hipSuccess || hipMalloc(&d_sc, spsc.size() * 4) != hipSuccess)) ||
-      (!spu.empty() && (hipMalloc(&d_spu, spu.size() * 2) != hipSuccess || hipMalloc(&d_scu, spusc.size() * 4) != hipSuccess))) {
-    cleanup();
-    return fail(PRG_E_NOMEM, "prg_debug_conv: hipMalloc failed");
-  }
-  if (d_spu && (hipMemcpy(d_spu, spu.data(), spu.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_scu, spusc.data(), spusc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
-    cleanup();
-    return fail(PRG_E_HIP, "prg_debug_conv: hipMemcpy failed");
-  }
-  if (hipMemcpy(d_w, packed.data(), packed.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_b, bias ? bias : zb.data(), Cout * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      (d_sp && (hipMemcpy(d_sp, sp.data(), sp.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_sc, spsc.data(), spsc.size() * 4, hipMemcpyHostToDevice) != hipSuccess))) {
-    cleanup();
-    return fail(PRG_E_HIP, "prg_debug_conv: hipMemcpy failed");
-  }
-  int rc = launch_nchw_f32_to_nhwc<float>(x, reinterpret_cast<float*>(d_in), B, H * W, Cin, s);
-  if (rc == PRG_OK) {
-    ConvLaunch<float> L{};
-    L.d.B = B; L.d.Hin = H; L.d.Win = W; L.d.C0 = Cin; L.d.C1 = 0; L.d.ups = ups; L.d.KH = K; L.d.KW = K; L.d.stride = stride; L.d.pad = pad;
-    L.d.Hout = Ho; L.d.Wout = Wo; L.d.Cout = Cout; L.d.CoutPad = cp; L.d.kchunks = kc;
-    L.src0 = reinterpret_cast<const float*>(d_in); L.w = reinterpret_cast<const float*>(d_w);
-    L.bias = reinterpret_cast<const float*>(d_b); L.out = reinterpret_cast<float*>(d_out);
-    L.gn_groups = 8;
-    L.w_split = reinterpret_cast<const uint16_t*>(d_sp); L.split_kchunks = kc32;
-    L.split_scale = reinterpret_cast<const float*>(d_sc);
-    L.w_up_split = reinterpret_cast<const uint16_t*>(d_spu);
-    L.split_scale_up = reinterpret_cast<const float*>(d_scu);
-    rc = launch_conv<float>(L, s, nullptr);
-  }
-  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<float>(reinterpret_cast<const float*>(d_out), out, B, Ho * Wo, Cout, s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_conv: stream synchronise failed");
-  cleanup();
-  return rc;
-}
-
-static int debug_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                      int dtype, int K, int stride, void* stream, int ups = 0) {
-  PRG_CHECK(x && w && out, "prg_debug_conv3x3: null pointer");
-  PRG_CHECK(B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0, "prg_debug_conv3x3: bad shape");
-  PRG_CHECK(dtype == PRG_BF16 || dtype == PRG_MXFP8 || dtype == PRG_F32 || dtype == PRG_F16X3, "prg_debug_conv3x3: bad dtype");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == PRG_F32 || dtype == PRG_F16X3) return debug_conv_f32(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, K == 1 ? 0 : 1, s, ups);
-  const size_t M = (size_t)B * H * W;
-  const int Ho = ups ? 2 * H : H / stride, Wo = ups ? 2 * W : W / stride;
-  const size_t Mo = (size_t)B * Ho * Wo;
-  std::vector<bf16_t> packed;
-  int cp = 0, kc = 0;
-  pack_conv_weight<bf16_t>(w, Cout, Cin, K, K, packed, &cp, &kc);
-  std::vector<bf16_t> packed_up;
-  if (ups && Cin % 64 == 0 && (Cout == 64 || Cout % 128 == 0)) {
-    std::vector<float> eq;
-    std::vector<bf16_t> one;
-    up_equivalent_weights(w, Cout, Cin, eq);
-    for (int ph = 0; ph < 4; ++ph) {
-      int cp2 = 0, kc2 = 0;
-      pack_conv_weight<bf16_t>(eq.data() + (size_t)ph * Cout * Cin * 4, Cout, Cin, 2, 2, one, &cp2, &kc2);
-      packed_up.insert(packed_up.end(), one.begin(), one.end());
-    }
-  }
-  std::vector<bf16_t> packed_s2d;
-  int kc_s2d = 0;
-  if (K == 4 && Cin % 64 == 0 && Cout % 64 == 0) {
-    std::vector<float> eq;
-    int cp2 = 0;
-    s2d_equivalent_weights(w, Cout, Cin, eq);
-    pack_conv_weight<bf16_t>(eq.data(), Cout, 4 * Cin, 3, 3, packed_s2d, &cp2, &kc_s2d);
-  }
-  std::vector<uint8_t> mxd, mxs;
-  if (dtype == PRG_MXFP8) {
-    PRG_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "prg_debug_conv3x3: MX-fp8 needs 64-channel multiples");
-    int cp2 = 0, kc2 = 0;
-    pack_conv_weight_mxfp8(w, Cout, Cin, 3, 3, mxd, mxs, &cp2, &kc2);
-  }
-  std::vector<float> zb(Cout, 0.0f);
-  void *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_b = nullptr, *d_mxd = nullptr, *d_mxs = nullptr, *d_w2 = nullptr, *d_wu = nullptr;
-  auto cleanup = [&]() { for (void* p : {d_in, d_out, d_w, d_b, d_mxd, d_mxs, d_w2, d_wu}) if (p) (void)hipFree(p); };
-  if (hipMalloc(&d_in, M * Cin * 2) != hipSuccess || hipMalloc(&d_out, Mo * Cout * 2) != hipSuccess ||
-      (!packed_up.empty() && (hipMalloc(&d_wu, packed_up.size() * 2) != hipSuccess ||
-                              hipMemcpy(d_wu, packed_up.data(), packed_up.size() * 2, hipMemcpyHostToDevice) != hipSuccess)) ||
-      (!packed_s2d.empty() && hipMalloc(&d_w2, packed_s2d.size() * 2) != hipSuccess) ||
-      hipMalloc(&d_w, packed.size() * 2) != hipSuccess || hipMalloc(&d_b, Cout * 4) != hipSuccess ||
-      (dtype == PRG_MXFP8 && (hipMalloc(&d_mxd, mxd.size()) != hipSuccess || hipMalloc(&d_mxs, mxs.size()) != hipSuccess))) {
-    cleanup();
-    return fail(PRG_E_NOMEM, "prg_debug_conv3x3: hipMalloc failed");
-  }
-  bool up = hipMemcpy(d_w, packed.data(), packed.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-            (!d_w2 || hipMemcpy(d_w2, packed_s2d.data(), packed_s2d.size() * 2, hipMemcpyHostToDevice) == hipSuccess) &&
-            hipMemcpy(d_b, bias ? bias : zb.data(), Cout * 4, hipMemcpyHostToDevice) == hipSuccess;
-  if (up && dtype == PRG_MXFP8)
-    up = hipMemcpy(d_mxd, mxd.data(), mxd.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(d_mxs, mxs.data(), mxs.size(), hipMemcpyHostToDevice) == hipSuccess;
-  if (!up) {
-    cleanup();
-    return fail(PRG_E_HIP, "prg_debug_conv3x3: hipMemcpy failed");
-  }
-  int rc = launch_nchw_f32_to_nhwc<bf16_t>(x, reinterpret_cast<bf16_t*>(d_in), B, H * W, Cin, s);
-  if (rc == PRG_OK) {
-    ConvLaunch<bf16_t> L{};
-    L.d.B = B; L.d.Hin = H; L.d.Win = W; L.d.C0 = Cin; L.d.C1 = 0; L.d.ups = ups; L.d.KH = K; L.d.KW = K; L.d.stride = stride; L.d.pad = 1;
-    L.d.Hout = Ho; L.d.Wout = Wo; L.d.Cout = Cout; L.d.CoutPad = cp; L.d.kchunks = kc;
-    L.src0 = reinterpret_cast<const bf16_t*>(d_in); L.w = reinterpret_cast<const bf16_t*>(d_w);
-    L.bias = reinterpret_cast<const float*>(d_b); L.out = reinterpret_cast<bf16_t*>(d_out);
-    L.gn_groups = 8;
-    L.w_up = reinterpret_cast<const bf16_t*>(d_wu);
-    L.w_s2d = reinterpret_cast<const bf16_t*>(d_w2); L.s2d_kchunks = kc_s2d;
-    L.w_mx = reinterpret_cast<const uint8_t*>(d_mxd); L.w_mx_scale = reinterpret_cast<const uint8_t*>(d_mxs);
-    L.mx_pure = 1;
-    rc = launch_conv<bf16_t>(L, s, nullptr);
-  }
-  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(reinterpret_cast<const bf16_t*>(d_out), out, B, Ho * Wo, Cout, s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_conv3x3: stream synchronise failed");
-  cleanup();
-  return rc;
-}
-
-// The two convolutions of a ResnetBlock's Block pair in bf16 mode, through the library's own dispatch (prg.h).
-int prg_debug_block_pair(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, const float* w2,
-                         const float* b2, float* out, int B, int Cin, int C, int H, int W, int groups, int h16, void* stream) {
-  PRG_CHECK(x && w1 && b1 && gamma && beta && w2 && b2 && out, "prg_debug_block_pair: null pointer");
-  PRG_CHECK(B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && C % 64 == 0 && groups > 0 && C % groups == 0 && (C / groups) % 8 == 0,
-            "prg_debug_block_pair: bad shape");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t M = (size_t)B * H * W;
-  std::vector<bf16_t> p1, p2;
-  std::vector<uint16_t> p2h;
-  int cp1 = 0, kc1 = 0, cp2 = 0, kc2 = 0;
-  pack_conv_weight<bf16_t>(w1, C, Cin, 3, 3, p1, &cp1, &kc1);
-  pack_conv_weight<bf16_t>(w2, C, C, 3, 3, p2, &cp2, &kc2);
-  pack_conv_weight_f16(w2, C, C, 3, 3, p2h);
-  std::vector<float> pq(2 * (size_t)C);
-  for (int c = 0; c < C; ++c) { pq[c] = gamma[c]; pq[C + c] = beta[c]; }
-  void *d_x = nullptr, *d_h = nullptr, *d_y = nullptr, *d_w1 = nullptr, *d_w2 = nullptr, *d_w2h = nullptr, *d_b1 = nullptr, *d_b2 = nullptr,
-       *d_pq = nullptr, *d_acc = nullptr, *d_part = nullptr, *d_coef = nullptr;
-  auto cleanup = [&]() { for (void* p : {d_x, d_h, d_y, d_w1, d_w2, d_w2h, d_b1, d_b2, d_pq, d_acc, d_part, d_coef}) if (p) (void)hipFree(p); };
-  const size_t acc_bytes = (size_t)B * groups * 2 * sizeof(long long);
-  if (hipMalloc(&d_x, M * Cin * 2) != hipSuccess || hipMalloc(&d_h, M * C * 2) != hipSuccess || hipMalloc(&d_y, M * C * 2) != hipSuccess ||
-      hipMalloc(&d_w1, p1.size() * 2) != hipSuccess || hipMalloc(&d_w2, p2.size() * 2) != hipSuccess || hipMalloc(&d_w2h, p2h.size() * 2) != hipSuccess ||
-      hipMalloc(&d_b1, C * 4) != hipSuccess || hipMalloc(&d_b2, C * 4) != hipSuccess || hipMalloc(&d_pq, pq.size() * 4) != hipSuccess ||
-      hipMalloc(&d_acc, acc_bytes) != hipSuccess || hipMalloc(&d_part, (size_t)B * kGnMaxSplit * groups * 2 * 4) != hipSuccess ||
-      hipMalloc(&d_coef, (size_t)2 * B * C * 4) != hipSuccess) {
-    cleanup();
-    return fail(PRG_E_NOMEM, "prg_debug_block_pair: hipMalloc failed");
-  }
-  if (hipMemcpy(d_w1, p1.data(), p1.size() * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_w2, p2.data(), p2.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_w2h, p2h.data(), p2h.size() * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_b1, b1, C * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_b2, b2, C * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_pq, pq.data(), pq.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemsetAsync(d_acc, 0, acc_bytes, s) != hipSuccess) {
-    cleanup();
-    return fail(PRG_E_HIP, "prg_debug_block_pair: upload failed");
-  }
-  int rc = launch_nchw_f32_to_nhwc<bf16_t>(x, reinterpret_cast<bf16_t*>(d_x), B, H * W, Cin, s);
-  ConvLaunch<bf16_t> L1{}, L2{};
-  auto desc = [&](ConvLaunch<bf16_t>& L, int cin, int cp, int kc) {
-    L.d.B = B; L.d.Hin = H; L.d.Win = W; L.d.C0 = cin; L.d.C1 = 0; L.d.ups = 0; L.d.KH = 3; L.d.KW = 3; L.d.stride = 1; L.d.pad = 1;
-    L.d.Hout = H; L.d.Wout = W; L.d.Cout = C; L.d.CoutPad = cp; L.d.kchunks = kc;
-    L.gn_groups = groups;
-  };
-  desc(L1, Cin, cp1, kc1);
-  L1.src0 = reinterpret_cast<const bf16_t*>(d_x); L1.w = reinterpret_cast<const bf16_t*>(d_w1); L1.bias = reinterpret_cast<const float*>(d_b1);
-  L1.out = reinterpret_cast<bf16_t*>(d_h);
-  L1.gn_partials = reinterpret_cast<float*>(d_part); L1.gn_acc = reinterpret_cast<long long*>(d_acc);
-  desc(L2, C, cp2, kc2);
-  L2.src0 = reinterpret_cast<const bf16_t*>(d_h); L2.w = reinterpret_cast<const bf16_t*>(d_w2); L2.w_f16 = reinterpret_cast<const uint16_t*>(d_w2h);
-  L2.bias = reinterpret_cast<const float*>(d_b2); L2.out = reinterpret_cast<bf16_t*>(d_y);
-  GnFold f{};
-  f.acc = reinterpret_cast<const long long*>(d_acc); f.P = reinterpret_cast<const float*>(d_pq); f.Q = f.P + C; f.pq_stride = 0;
-  f.G = groups; f.cpg = C / groups; f.inv_n = 1.0f / ((float)(H * W) * (float)f.cpg);
-  L2.pro_fold = f;
-  L2.pro_a = reinterpret_cast<const float*>(d_coef); L2.pro_b = L2.pro_a + (size_t)B * C;
-  if (rc == PRG_OK && h16) {
-    if (!conv_h16_pair_ok(L1, L2)) rc = fail(PRG_E_INVALID, "prg_debug_block_pair: the kernels this shape dispatches to do not implement the f16 format");
-    L1.out_f16 = 1;
-    L2.in_f16 = 1;
-  }
-  int ns = 0, ad = 0;
-  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L1, s, &ns, &ad);
-  if (rc == PRG_OK && !ad) rc = fail(PRG_E_INVALID, "prg_debug_block_pair: conv1's kernel does not accumulate fixed-point statistics for this shape");
-  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L2, s, nullptr);
-  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(reinterpret_cast<const bf16_t*>(d_y), out, B, H * W, C, s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_block_pair: stream synchronise failed");
-  cleanup();
-  return rc;
-}
-
-int prg_debug_conv3x3(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                      int dtype, void* stream) {
-  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, 3, 1, stream);
-}
-
-int prg_debug_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                   int dtype, int K, int stride, void* stream) {
-  PRG_CHECK((K == 1 || K == 3 || K == 4) && (stride == 1 || stride == 2), "prg_debug_conv: K must be 1, 3 or 4, stride 1 or 2");
-  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_F16X3 || K != 1, "prg_debug_conv: 1x1 convs only in the float32-storage modes");
-  PRG_CHECK(stride == 1 || (H % 2 == 0 && W % 2 == 0), "prg_debug_conv: odd image size");
-  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, stream);
-}
-
-int prg_debug_upsample_conv3x3(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                               void* stream) {
-  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, PRG_BF16, 3, 1, stream, 1);
-}
-
-int prg_debug_upsample_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                            int dtype, void* stream) {
-  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, 3, 1, stream, 1);
-}
-
-int prg_debug_conv4x4s2(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
-                        void* stream) {
-  PRG_CHECK(H % 2 == 0 && W % 2 == 0, "prg_debug_conv4x4s2: odd image size");
-  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, PRG_BF16, 4, 2, stream);
-}
-
-// ---------------------------------------------------------------------------------------------
 int prg_sampler_create(prg_unet* unet, const prg_step* steps, int n_steps, int B, int S, prg_sampler** out) {
   PRG_CHECK(unet && steps && out, "prg_sampler_create: null pointer");
   PRG_CHECK(unet->lay.cfg.conditional && unet->lay.cfg.in_channels == 1, "prg_sampler_create: needs the conditional U-Net");
@@ -1733,14 +873,16 @@ int prg_sampler_create(prg_unet* unet, const prg_step* steps, int n_steps, int B
   const int e = L.emb, d0 = L.cfg.dim, W = L.ss_total;
   const size_t HW = (size_t)S * S;
   const int R = n_steps > B ? n_steps : B;
-  if (hipMalloc(&h->d_steps, sizeof(prg_step) * n_steps) != hipSuccess ||
-      hipMalloc(&h->d_tpart, sizeof(float) * (size_t)n_steps * W) != hipSuccess ||
-      hipMalloc(&h->d_ppart, sizeof(float) * (size_t)B * W) != hipSuccess ||
-      hipMalloc(&h->d_scratch, sizeof(float) * (size_t)R * (d0 + 2 * e) + sizeof(int32_t) * n_steps) != hipSuccess ||
-      hipMalloc(&h->d_x, sizeof(float) * B * HW) != hipSuccess || hipMalloc(&h->d_u, sizeof(float) * B * HW) != hipSuccess ||
-      hipMalloc(&h->d_step, 2 * sizeof(int)) != hipSuccess || hipMalloc(&h->d_seeds, sizeof(uint64_t) * B) != hipSuccess)
-    return fail(PRG_E_NOMEM, "prg_sampler_create: hipMalloc failed");
-  PRG_HIP(hipMemcpy(h->d_steps, steps, sizeof(prg_step) * n_steps, hipMemcpyHostToDevice));
+  const char* nomem = "prg_sampler_create: hipMalloc failed";
+  h->d_steps = h->own.upload(steps, (size_t)n_steps, nomem);
+  h->d_tpart = h->own.alloc<float>((size_t)n_steps * W, nomem);
+  h->d_ppart = h->own.alloc<float>((size_t)B * W, nomem);
+  h->d_scratch = h->own.alloc<float>((size_t)R * (d0 + 2 * e) + n_steps, nomem);   // (+ n_steps int32 timesteps)
+  h->d_x = h->own.alloc<float>(B * HW, nomem);
+  h->d_u = h->own.alloc<float>(B * HW, nomem);
+  h->d_step = h->own.alloc<int>(2, nomem);
+  h->d_seeds = h->own.alloc<uint64_t>((size_t)B, nomem);
+  if (h->own.rc) return h->own.rc;
   PRG_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamDefault));
   // time half of the conditioning for every transition: Tpart[k] = W_t . SiLU(time_mlp(t_k)) + bias
   {
@@ -1760,11 +902,9 @@ int prg_sampler_create(prg_unet* unet, const prg_step* steps, int n_steps, int B
       return launch_linear(temb, e, 0, F + r.mlp_w, 2 * e, 0, F + r.mlp_b, h->d_tpart + r.ss_off, W, n_steps, e,
                            2 * r.cout, ACT_SILU, ACT_NONE, s);
     };
-    for (auto& lv : L.downs) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    for (auto& lv : L.ups) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    if ((rc = one(L.mid1))) return rc;
-    if ((rc = one(L.mid2))) return rc;
-    if ((rc = one(L.fin))) return rc;
+    rc = PRG_OK;
+    for_each_res(L, [&](const ResP& r) { if (rc == PRG_OK) rc = one(r); });
+    if (rc) return rc;
     PRG_HIP(hipStreamSynchronize(s));
   }
   *out = h.release();
@@ -1775,12 +915,7 @@ int prg_sampler_destroy(prg_sampler* h) {
   if (!h) return PRG_OK;
   (void)hipDeviceSynchronize();
   sampler_free(h);
-  for (auto& ev : h->prof.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-  for (auto& ev : h->prof.step_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  void* ptrs[] = {h->d_steps, h->d_tpart, h->d_ppart, h->d_scratch, h->d_x, h->d_u, h->d_step, h->d_seeds};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  delete h;
+  delete h;   // (events, stream and device buffers: ~prg_sampler)
   return PRG_OK;
 }
 
@@ -1863,11 +998,9 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
       return launch_linear(pemb, e, 0, F + r.mlp_w, 2 * e, e, nullptr, h->d_ppart + r.ss_off, W, B, e, 2 * r.cout,
                            ACT_SILU, ACT_NONE, s);
     };
-    for (auto& lv : L.downs) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    for (auto& lv : L.ups) { if ((rc = one(lv.r0))) return rc; if ((rc = one(lv.r1))) return rc; }
-    if ((rc = one(L.mid1))) return rc;
-    if ((rc = one(L.mid2))) return rc;
-    if ((rc = one(L.fin))) return rc;
+    rc = PRG_OK;
+    for_each_res(L, [&](const ResP& r) { if (rc == PRG_OK) rc = one(r); });
+    if (rc) return rc;
   }
   if ((rc = launch_sampler_init(h->d_x, noise, h->d_seeds, B, h->S * h->S, s))) return rc;
 

@@ -1,0 +1,153 @@
+// unet_debug.hip — the prg_debug_* entries (prg.h): single convolutions and a ResnetBlock's Block pair through the library's own
+// packer (pack_conv_host: what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own.
+#include <type_traits>
+
+#include "unet_layout.h"
+
+using namespace prg;
+
+namespace {
+
+// the launch of one single-source conv on the packings of `pk`; a packing the conv does not have leaves its pointer null
+template <typename T>
+struct DebugConv {
+  ConvLaunch<T> L{};
+  int Ho = 0, Wo = 0;
+  DebugConv(DeviceBuffers& own, const PackedConv<T>& pk, int B, int Cin, int Cout, int H, int W, int K, int stride, int pad, int ups,
+            int groups, const char* nomem) {
+    Ho = ups ? 2 * H : (H + 2 * pad - K) / stride + 1;
+    Wo = ups ? 2 * W : (W + 2 * pad - K) / stride + 1;
+    L.d.B = B; L.d.Hin = H; L.d.Win = W; L.d.C0 = Cin; L.d.C1 = 0; L.d.ups = ups; L.d.KH = K; L.d.KW = K; L.d.stride = stride; L.d.pad = pad;
+    L.d.Hout = Ho; L.d.Wout = Wo; L.d.Cout = Cout; L.d.CoutPad = pk.CoutPad; L.d.kchunks = pk.kchunks;
+    L.gn_groups = groups;
+    L.w = own.upload(pk.main, nomem);
+    L.w_s2d = own.upload(pk.s2d, nomem); L.s2d_kchunks = pk.s2d_kchunks;
+    L.w_up = own.upload(pk.up, nomem);
+    L.w_mx = own.upload(pk.mx, nomem); L.w_mx_scale = own.upload(pk.mx_scale, nomem);
+    L.w_f16 = own.upload(pk.h16, nomem);
+    L.w_split = own.upload(pk.split, nomem); L.split_kchunks = pk.split_kchunks;
+    L.split_scale = own.upload(pk.split_scale, nomem);
+    L.w_up_split = own.upload(pk.up_split, nomem);
+    L.split_scale_up = own.upload(pk.up_split_scale, nomem);
+  }
+};
+
+// float32-storage handles (PRG_F32: the exact-f32 kernels; PRG_F16X3: the split-operand kernels of conv_split.hip) and the bf16
+// ones (PRG_BF16, PRG_MXFP8).  pad = 1 except for the 1x1 convs.
+template <typename T>
+int debug_conv_t(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W, int dtype,
+                 int K, int stride, hipStream_t s, int ups) {
+  constexpr bool f32 = std::is_same<T, float>::value;
+  const char* nomem = f32 ? "prg_debug_conv: hipMalloc failed" : "prg_debug_conv3x3: hipMalloc failed";
+  if (dtype == PRG_MXFP8) PRG_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "prg_debug_conv3x3: MX-fp8 needs 64-channel multiples");
+  ConvRole role;
+  role.upsample = ups != 0;
+  const PackedConv<T> pk = pack_conv_host<T>(w, Cout, Cin, K, dtype, role);
+  DeviceBuffers own;
+  DebugConv<T> c(own, pk, B, Cin, Cout, H, W, K, stride, K == 1 ? 0 : 1, ups, 8, nomem);
+  const std::vector<float> zb(Cout, 0.0f);
+  T* d_in = own.alloc<T>((size_t)B * H * W * Cin, nomem);
+  c.L.src0 = d_in;
+  c.L.out = own.alloc<T>((size_t)B * c.Ho * c.Wo * Cout, nomem);
+  c.L.bias = own.upload(bias ? bias : zb.data(), (size_t)Cout, nomem);
+  c.L.mx_pure = f32 ? 0 : 1;
+  if (own.rc) return own.rc;
+  int rc = launch_nchw_f32_to_nhwc<T>(x, d_in, B, H * W, Cin, s);
+  if (rc == PRG_OK) rc = launch_conv<T>(c.L, s, nullptr);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(c.L.out, out, B, c.Ho * c.Wo, Cout, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK)
+    rc = fail(PRG_E_HIP, f32 ? "prg_debug_conv: stream synchronise failed" : "prg_debug_conv3x3: stream synchronise failed");
+  return rc;
+}
+
+int debug_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W, int dtype, int K,
+               int stride, void* stream, int ups = 0) {
+  PRG_CHECK(x && w && out, "prg_debug_conv3x3: null pointer");
+  PRG_CHECK(B > 0 && H > 0 && W > 0 && Cin % 8 == 0 && Cout % 8 == 0, "prg_debug_conv3x3: bad shape");
+  PRG_CHECK(dtype == PRG_BF16 || dtype == PRG_MXFP8 || dtype == PRG_F32 || dtype == PRG_F16X3, "prg_debug_conv3x3: bad dtype");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == PRG_F32 || dtype == PRG_F16X3) return debug_conv_t<float>(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, s, ups);
+  return debug_conv_t<bf16_t>(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, s, ups);
+}
+
+}  // namespace
+
+extern "C" {
+
+// The two convolutions of a ResnetBlock's Block pair in bf16 mode, through the library's own dispatch (prg.h).
+int prg_debug_block_pair(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, const float* w2,
+                         const float* b2, float* out, int B, int Cin, int C, int H, int W, int groups, int h16, void* stream) {
+  PRG_CHECK(x && w1 && b1 && gamma && beta && w2 && b2 && out, "prg_debug_block_pair: null pointer");
+  PRG_CHECK(B > 0 && H > 0 && W > 0 && Cin % 64 == 0 && C % 64 == 0 && groups > 0 && C % groups == 0 && (C / groups) % 8 == 0,
+            "prg_debug_block_pair: bad shape");
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_block_pair: hipMalloc failed";
+  const size_t M = (size_t)B * H * W;
+  ConvRole conv2;
+  conv2.conv2 = true;       // (with the f16 twin of its packing)
+  const PackedConv<bf16_t> p1 = pack_conv_host<bf16_t>(w1, C, Cin, 3, PRG_BF16, ConvRole{});
+  const PackedConv<bf16_t> p2 = pack_conv_host<bf16_t>(w2, C, C, 3, PRG_BF16, conv2);
+  std::vector<float> pq(2 * (size_t)C);
+  for (int c = 0; c < C; ++c) { pq[c] = gamma[c]; pq[C + c] = beta[c]; }
+  DeviceBuffers own;
+  DebugConv<bf16_t> c1(own, p1, B, Cin, C, H, W, 3, 1, 1, 0, groups, nomem), c2(own, p2, B, C, C, H, W, 3, 1, 1, 0, groups, nomem);
+  ConvLaunch<bf16_t>&L1 = c1.L, &L2 = c2.L;
+  const size_t acc_count = (size_t)B * groups * 2;
+  bf16_t* d_x = own.alloc<bf16_t>(M * Cin, nomem);
+  bf16_t* d_h = own.alloc<bf16_t>(M * C, nomem);
+  L1.src0 = d_x; L1.out = d_h; L1.bias = own.upload(b1, (size_t)C, nomem);
+  L1.gn_partials = own.alloc<float>((size_t)B * kGnMaxSplit * groups * 2, nomem);
+  L1.gn_acc = own.alloc<long long>(acc_count, nomem);
+  L2.src0 = d_h; L2.out = own.alloc<bf16_t>(M * C, nomem); L2.bias = own.upload(b2, (size_t)C, nomem);
+  GnFold f{};
+  f.acc = L1.gn_acc; f.P = own.upload(pq, nomem); f.Q = f.P + C; f.pq_stride = 0;
+  f.G = groups; f.cpg = C / groups; f.inv_n = 1.0f / ((float)(H * W) * (float)f.cpg);
+  L2.pro_fold = f;
+  L2.pro_a = own.alloc<float>((size_t)2 * B * C, nomem); L2.pro_b = L2.pro_a + (size_t)B * C;
+  if (own.rc) return own.rc;
+  if (hipMemsetAsync(L1.gn_acc, 0, acc_count * sizeof(long long), s) != hipSuccess) return fail(PRG_E_HIP, "prg_debug_block_pair: upload failed");
+  int rc = launch_nchw_f32_to_nhwc<bf16_t>(x, d_x, B, H * W, Cin, s);
+  if (rc == PRG_OK && h16) {
+    if (!conv_h16_pair_ok(L1, L2)) rc = fail(PRG_E_INVALID, "prg_debug_block_pair: the kernels this shape dispatches to do not implement the f16 format");
+    L1.out_f16 = 1;
+    L2.in_f16 = 1;
+  }
+  int ns = 0, ad = 0;
+  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L1, s, &ns, &ad);
+  if (rc == PRG_OK && !ad) rc = fail(PRG_E_INVALID, "prg_debug_block_pair: conv1's kernel does not accumulate fixed-point statistics for this shape");
+  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L2, s, nullptr);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(L2.out, out, B, H * W, C, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_block_pair: stream synchronise failed");
+  return rc;
+}
+
+int prg_debug_conv3x3(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                      int dtype, void* stream) {
+  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, 3, 1, stream);
+}
+
+int prg_debug_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                   int dtype, int K, int stride, void* stream) {
+  PRG_CHECK((K == 1 || K == 3 || K == 4) && (stride == 1 || stride == 2), "prg_debug_conv: K must be 1, 3 or 4, stride 1 or 2");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_F16X3 || K != 1, "prg_debug_conv: 1x1 convs only in the float32-storage modes");
+  PRG_CHECK(stride == 1 || (H % 2 == 0 && W % 2 == 0), "prg_debug_conv: odd image size");
+  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, stream);
+}
+
+int prg_debug_upsample_conv3x3(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                               void* stream) {
+  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, PRG_BF16, 3, 1, stream, 1);
+}
+
+int prg_debug_upsample_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                            int dtype, void* stream) {
+  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, dtype, 3, 1, stream, 1);
+}
+
+int prg_debug_conv4x4s2(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
+                        void* stream) {
+  PRG_CHECK(H % 2 == 0 && W % 2 == 0, "prg_debug_conv4x4s2: odd image size");
+  return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, PRG_BF16, 4, 2, stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""Outputs of the HIP library on a fixed case list, for bit-for-bit A/B of two builds (a refactor against its parent).
+
+  PRG_HIP_LIB=/path/to/libprg_hip.so python tools/lib_outputs.py OUT.npz     # every case, synthetic weights, fixed seeds
+  python tools/lib_outputs.py --compare A.npz B.npz                            # per case: identical or not; exit 1 on any difference
+
+The cases cover every weight packing a handle can build (the kernels are deterministic, so two builds that pack the same bytes
+give the same bits): the conditional dim-64 U-Net at 128 x 128 with B = 2 and 16 in all four modes, the switches read during
+weight preparation, the MaskUnet's 3-channel stems, a dim-16 network on the generic paths and an 8-step sampler chain with and
+without graph capture.  The library reads its PRG_* switches once per process: every switch setting runs in a child of its own."""
+import json
+import os
+import subprocess
+import sys
+
+MODES = ("fp32", "bf16", "mxfp8", "f16x3")
+
+# (environment of the child process, [(kind, dim, B, S, mode), ...])
+GROUPS = [
+    ({}, [("unet", 64, B, 128, m) for m in MODES for B in (2, 16)]
+         + [("maskunet", 64, 2, 128, m) for m in ("bf16", "f16x3")]
+         + [("unet", 16, 3, 32, m) for m in MODES]
+         + [("chain8_graph", 64, 2, 128, "bf16"), ("chain8_nograph", 64, 2, 128, "bf16")]),
+    ({"PRG_SPLIT_UP2X2": "1"}, [("unet", 64, B, 128, "f16x3") for B in (2, 16)]),
+    ({"PRG_LA_KSHIFT": "0"}, [("unet", 64, B, 128, "bf16") for B in (2, 16)]),
+    ({"PRG_FUSED_ATTN": "0"}, [("unet", 64, B, 128, "bf16") for B in (2, 16)]),
+]
+
+
+def case_name(env, case):
+    kind, dim, B, S, mode = case
+    tag = "".join(f"+{k}={v}" for k, v in sorted(env.items()))
+    return f"{kind}{dim}_B{B}_S{S}_{mode}{tag}"
+
+
+def run_group(index, out):
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from pointreggpt_amd import weights as W
+    from pointreggpt_amd.diffusion import GaussianDiffusion
+    from pointreggpt_amd.unet import MaskUnet, Unet
+    env, cases = GROUPS[index]
+    res = {}
+    for case in cases:
+        kind, dim, B, S, mode = case
+        g = torch.Generator().manual_seed(1000 + dim + B + S)
+        if kind == "maskunet":
+            net = MaskUnet(dim, dtype=mode).load_state_dict(W.synth_state_dict(W.maskunet_config(dim), 21))
+            y = net(torch.rand((B, 1, S, S), generator=g).cuda())
+        else:
+            net = Unet(dim, dtype=mode).load_state_dict(W.synth_state_dict(W.unet_config(dim), 20))
+            pc = torch.rand((B, 4), generator=g)
+            if kind == "unet":
+                x = torch.randn((B, 1, S, S), generator=g)
+                t = torch.randint(0, 1000, (B,), generator=g)
+                y = net(x.cuda(), t.cuda(), pc.cuda())
+            else:
+                d8 = GaussianDiffusion(net, image_size=S, timesteps=8)
+                cond = torch.rand((B, 2, S, S), generator=g) * 2 - 1
+                noise = torch.randn((d8.n_draws, B, 1, S, S), generator=g)
+                y = d8.sample(param_cond=pc, img_cond=cond, noise=noise, use_graph=kind == "chain8_graph")
+        torch.cuda.synchronize()
+        res[case_name(env, case)] = y.cpu().numpy()
+        net.close()
+    np.savez(out, **res)
+
+
+def run_all(out):
+    import numpy as np
+    merged = {}
+    for i, (env, _) in enumerate(GROUPS):
+        part = f"{out}.part{i}.npz"
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--group", str(i), part], env=dict(os.environ, **env),
+                       check=True, timeout=900)
+        with np.load(part) as z:
+            merged.update({k: z[k] for k in z.files})
+        os.remove(part)
+    np.savez(out, **merged)
+    print(json.dumps({"lib": os.environ.get("PRG_HIP_LIB", "default"), "cases": len(merged), "out": out}))
+
+
+def compare(a, b):
+    import numpy as np
+    za, zb = np.load(a), np.load(b)
+    bad = sorted(set(za.files) ^ set(zb.files))
+    for k in bad:
+        print(f"{k:56s} only in one file")
+    for k in sorted(set(za.files) & set(zb.files)):
+        same = za[k].shape == zb[k].shape and za[k].tobytes() == zb[k].tobytes()
+        finite = bool(np.isfinite(za[k]).all())
+        note = "" if same else f"  max |a - b| = {float(np.abs(za[k].astype(np.float64) - zb[k]).max()):.3e}" if za[k].shape == zb[k].shape else "  shapes differ"
+        print(f"{k:56s} {'identical' if same else 'DIFFERENT'}{'' if finite else '  (non-finite values)'}{note}")
+        if not same:
+            bad.append(k)
+    print(f"{len(za.files)} cases, {len(bad)} different")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    elif len(sys.argv) == 4 and sys.argv[1] == "--group":
+        run_group(int(sys.argv[2]), sys.argv[3])
+    elif len(sys.argv) == 2 and not sys.argv[1].startswith("-"):
+        run_all(sys.argv[1])
+    else:
+        sys.exit(__doc__)
