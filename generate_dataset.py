@@ -16,6 +16,9 @@ hard-coded literals, generate_dataset.py:32-55):
                       configs[0]'s plumbing run without a GPU; explicit only, the default never falls back to it
   --synthetic SEED    synthetic scenes instead of 3DMatch frames (no dataset needed)
   --noise_seed N      seed of the diffusion noise (default: fresh entropy, printed; synthetic runs default to SEED)
+  --with_gt           also write every scene's gt.log while generating: both clouds of a pair are finished on the GPU and go
+                      through generate_gt's voxel grid and overlap test in the batch that sampled them (same bytes as the
+                      two-pass run).  `generate_gt.py` afterwards finds every scene done and is the gather step only
   --resume synthetic[:SEED]   deterministic synthetic weights instead of ./successive_ddnm_diffusion_results/model-<resume>.pt
 Under `torchrun --nproc-per-node N` every rank takes a contiguous block of [-start, -stop) (no collectives).
 """
@@ -53,6 +56,9 @@ def main():
     p.add_argument("--noise_seed", default=None, type=int,
                    help="seed of the diffusion noise (and, with real data, of the pose stream); default: fresh entropy, "
                         "logged, like the reference's unseeded torch.randn")
+    p.add_argument("--with_gt", action="store_true",
+                   help="write each scene's gt.log in the batch that sampled it (clouds finished on the GPU; same bytes as "
+                        "generate_gt.py would write); generate_gt.py afterwards only gathers metadata/gt.log")
     args = p.parse_args()
 
     from pointreggpt_amd import sharding
@@ -61,6 +67,8 @@ def main():
     if args.device == "cpu":
         if args.dtype != "fp32":
             p.error("--device cpu computes in float32: use --dtype fp32")
+        if args.with_gt:
+            p.error("--with_gt needs the clouds on a HIP device: run generate_gt.py after a --device cpu run")
         from pointreggpt_amd.cpu import GaussianDiffusion, MaskUnet, Unet
         args.streams = 1
     else:
@@ -118,7 +126,8 @@ def main():
     if stop > start:
         generator.generate(start_scene_index=start, stop_scene_index=stop, num_samples=args.num_samples,
                            has_refine_step=False, depth_correction=depth_correction,
-                           mask_threshold=args.mask_threshold, noise_seed=args.noise_seed, lanes=lanes)
+                           mask_threshold=args.mask_threshold, noise_seed=args.noise_seed, lanes=lanes,
+                           gt_log=args.with_gt)
     if args.device == "cuda":
         torch.cuda.synchronize()
 

@@ -4,6 +4,8 @@
     python generate_gt.py --dataset_name=generated_dataset [-start 0] [-stop 1] [--num_samples 2] [--disable_tqdm]
 
 per scene `scene_name\\tsrc_idx\\ttgt_idx\\toverlap_src\\toverlap_tgt` (4 decimals), then ./<dataset>/metadata/gt.log.
+Scenes that already have a gt.log are skipped: after `generate_dataset.py --with_gt`, which writes them while it generates,
+this script reads no cloud and is the gather step only (the scene logs concatenated into metadata/gt.log).
 """
 import argparse
 

@@ -145,6 +145,28 @@ int prg_merge_memory_f64(const float* memory, const int64_t* memory_offsets, int
                          const uint8_t* valid, int B, int HW, double* merged, uint8_t* merged_valid,
                          int64_t* merged_offsets, void* stream);
 
+/* Rigid move + bounding-box crop of B ragged float64 clouds in one call: what the writer pool (prg_pool_submit_cloud below)
+ * does to a cloud before and after its voxel grid, on the device, so that pre-transform -> crop -> prg_voxel_grid_ragged ->
+ * post-transform never leaves the GPU.  pts (total,3) float64, valid (total) bytes or NULL (= all rows), offsets (B+1) int64,
+ * all DEVICE and meaning exactly what they mean for prg_voxel_grid_ragged; rows outside [offsets[0], offsets[B]) are neither
+ * read nor written.  1 <= B <= 65535, total < 2^31.
+ * T (B,16) float64 DEVICE, one row-major 4x4 per segment, or NULL (no segment is moved); has_T (B) bytes DEVICE: segment b is
+ *   moved iff has_T[b] != 0, NULL = every segment when T is given.  A moved row is x' = x*T[0] + y*T[1] + z*T[2] + T[3]
+ *   (y', z' from rows 1, 2), the products summed left to right in float64 without contraction: prg_pool_submit_cloud's
+ *   T_pre / T_post bit for bit.  The rows of a segment that is not moved are copied bit for bit (-0.0 stays -0.0, which a
+ *   product with an identity matrix would turn into +0.0).
+ * lo, hi: 3 doubles each, HOST, read during the call; both NULL = no crop.  With a crop valid_out[i] = valid[i] &&
+ *   lo <= p' <= hi on all three axes (inclusive, tested on the moved point, like prg_host_crop_aabb); without one
+ *   valid_out[i] = valid[i] (1 when valid is NULL).  The crop flags rows, it does not compact them: prg_voxel_grid_ragged
+ *   skips rows whose flag is 0.
+ * Rows with valid == 0 may hold NaN or garbage: their valid_out is 0, their `out` row is unspecified, nothing else follows.
+ * out (>= offsets[B] rows,3) float64 DEVICE, may be pts itself (one thread owns one row); valid_out (>= offsets[B]) bytes
+ *   DEVICE, may be valid itself, may be NULL only when there is no crop.
+ * Asynchronous on `stream`; reads no device data on the host; allocates nothing.                                          */
+int prg_rigid_crop_ragged_f64(const double* pts, const uint8_t* valid, const int64_t* offsets, int B, int64_t total,
+                              const double* T, const uint8_t* has_T, const double* lo, const double* hi, double* out,
+                              uint8_t* valid_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * U-Nets (MFMA kernels)
  * ---------------------------------------------------------------------------------------------------- */

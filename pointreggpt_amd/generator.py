@@ -114,7 +114,8 @@ class Generator:
     def generate(self, start_scene_index, stop_scene_index, num_samples, memory_voxel_size=0.002,
                  save_voxel_size=0.025, has_refine_step=False, depth_correction=None, mask_threshold=0.99,
                  noise_seed: Optional[int] = None, progress: bool = False, writer_threads: int = 0, stats: Optional[dict] = None,
-                 seed_poses: Optional[bool] = None, lanes: Optional[list] = None, voxel_backend: str = "device"):
+                 seed_poses: Optional[bool] = None, lanes: Optional[list] = None, voxel_backend: str = "device",
+                 gt_log: bool = False):
         """Same sequence as sd:2363-2694.  File output is asynchronous: every batch's clouds / images / text files are
         handed to the library's C++ writer pool (crop, voxel grid, PLY / PNG encoding on worker threads) and are
         produced while the GPU samples the next batch.  A batch's resume marker — the generated cloud of its LAST scene
@@ -134,9 +135,19 @@ class Generator:
         device): one float32 ragged buffer on the GPU from the first upload on, updated by prg_merge_memory_f64 ->
         prg_voxel_grid_ragged and read by the next view's z-buffer in place — no copy of the memory cloud to the host.
         "host": the memory clouds are numpy arrays re-voxelised one by one in C++ on the calling thread (the only path of
-        a `device="cpu"` generator).  Both produce the same bytes."""
+        a `device="cpu"` generator).  Both produce the same bytes.
+        ``gt_log`` (HIP device only, `voxel_backend="device"`): finish both clouds of every scene on the GPU and write the
+        scene's ``gt.log`` in the batch that sampled it — the line `generate_gt` would write after re-reading the two PLY files.
+        The memory clouds are uploaded once (also for num_samples == 1); the float64 views stay on the device; per batch ONE
+        ragged buffer of 2B segments [memory_j | views of scene j] goes through `finish_clouds` (the views with pre = pose0,
+        the crop box, post = pose0^-1; `save_voxel_size`), comes to the host once for the PLY writers (write-only jobs), and
+        through `voxel_grid_ragged` at generate_gt's 0.025 into one `prg_overlap_counts` launch.  Every file has the bytes of
+        the default path followed by `generate_gt`; a batch's gt.log files are on disk before its resume marker is submitted.
+        Afterwards `generate_gt` finds every scene done and only `gather_gt` is left."""
         if voxel_backend not in ("device", "host"):
             raise ValueError("voxel_backend must be 'device' or 'host'")
+        if gt_log and (self.device.type == "cpu" or voxel_backend != "device"):
+            raise ValueError("gt_log=True needs the clouds on a HIP device (device='cuda', voxel_backend='device')")
         if self.device.type == "cpu":
             voxel_backend = "host"
         if seed_poses is None:
@@ -165,7 +176,7 @@ class Generator:
         pairs = pairs[:max(1, len(batches))]
         kw = dict(num_samples=num_samples, memory_voxel_size=memory_voxel_size, save_voxel_size=save_voxel_size,
                   has_refine_step=has_refine_step, mask_threshold=mask_threshold, noise_seed=noise_seed, progress=progress,
-                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend)
+                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend, gt_log=gt_log)
         n = len(pairs)
         wt = writer_threads if writer_threads <= 0 or n == 1 else max(1, writer_threads // n)
         results = [None] * n
@@ -206,7 +217,7 @@ class Generator:
 
     def _lane(self, batches, model, depth_correction, writer_threads, n_lanes, *, num_samples, memory_voxel_size,
               save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None,
-              voxel_backend="host"):
+              voxel_backend="host", gt_log=False):
         """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream."""
         S, dev = self.image_size, self.device
         if writer_threads <= 0 and n_lanes > 1:
@@ -249,16 +260,21 @@ class Generator:
                     pool.image01(str(sdirs[j] / "sample-{:0>6d}.image.png".format(0)), depth0[j, 0])
                     job = (lambda path=str(sdirs[j] / "sample-{:0>6d}.cloud.ply".format(0)), pc=scene_pc:
                            pool.cloud(path, pc, None, crop=False, voxel=save_voxel_size))
-                    if j == batch - 1 and marker_index == 0:
+                    if gt_log:
+                        pass                          # written with the generated cloud, from the device-finished buffer
+                    elif j == batch - 1 and marker_index == 0:
                         marker_cur = job              # this batch's resume marker: written after everything else
                     else:
                         job()
                 param_cond = self.G.param_vector(K_dev)
                 fragments: List[Optional[np.ndarray]] = [None] * batch
                 poses0 = None
-                on_device = voxel_backend == "device" and num_samples > 1
+                on_device = (voxel_backend == "device" and num_samples > 1) or gt_log
                 if on_device:                 # the ONE upload of the memory clouds; from here on they stay on the device
                     mem_pts, mem_offs = self.G.upload_clouds(memory, dev)
+                mem_pts0, mem_offs0 = (mem_pts, mem_offs) if gt_log else (None, None)   # the source frame of the pair
+                views = []                    # gt_log: every sample's (xyz, valid) as unproject_f64 left them, on the device
+                finished = None
                 for sample_idx in range(num_samples):
                     pose = self._poses(idxs, sample_idx, noise_seed if seed_poses else None)
                     if sample_idx == 0:
@@ -282,9 +298,15 @@ class Generator:
                         merged, mvalid, moffs = self.G.merge_memory(mem_pts, mem_offs, xyz, valid)
                         vg_out, mem_offs, vg_status = self.G.voxel_grid_ragged(merged, mvalid, moffs, memory_voxel_size)
                         mem_pts = vg_out.to(torch.float32)
+                    if gt_log:
+                        views.append((xyz, valid))
+                        if last_sample:
+                            finished = self._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views, poses0,
+                                                                 save_voxel_size)
                     # one blocking copy per tensor: the host waits here for the GPU while the pool writes the previous batch
                     rpj_host, crt_host, img_host = rpj.cpu().numpy(), rpj_c.cpu().numpy(), images.cpu().numpy()
-                    xyz_host, valid_host = xyz.cpu().numpy(), valid.cpu().numpy()
+                    if not gt_log:
+                        xyz_host, valid_host = xyz.cpu().numpy(), valid.cpu().numpy()
                     if vg_status is not None:     # B status words + the memory's row count: all the host learns of it
                         st_n = torch.cat([vg_status.to(torch.int64), mem_offs[-1:]]).cpu().numpy()
                         self.G.check_voxel_status(st_n[:-1], ["scene-{:0>6d}".format(i) for i in idxs])
@@ -297,6 +319,8 @@ class Generator:
                         pool.image01(str(sdir / "corrected.image.png"), crt_host[j])
                         pool.image01(str(sdir / "sample-{:0>6d}.image.png".format(sample_idx + 1)), img_host[j])
                         pool.depth16(str(sdir / "sample-{:0>6d}.depth.png".format(sample_idx + 1)), img_host[j])
+                        if gt_log:
+                            continue                                                    # clouds: after the loop, from the device
                         if num_samples == 1:
                             frag, fvalid = xyz_host[j], valid_host[j]                  # compaction happens in the worker
                         else:
@@ -314,6 +338,8 @@ class Generator:
                                 marker_cur = job
                             else:
                                 job()
+                    if finished is not None:
+                        marker_cur = self._finish_pairs_write(pool, finished, idxs, sdirs, marker_index)
                     if progress:
                         print("batch {:0>6d}-{:0>6d}: sample {}/{}".format(idxs[0], idxs[-1], sample_idx + 1, num_samples))
                 n_pairs += batch
@@ -322,6 +348,80 @@ class Generator:
             flush_marker()
             jobs = pool.wait()
             return n_pairs, jobs, pool.threads
+
+
+    # -- gt_log: both clouds of a pair finished on the device, the scene's gt.log written with them ---------------------------
+    GT_VOXEL, GT_FACTOR, GT_MIN_POINTS = 0.025, 1.5, 1000      # generate_gt's fixed literals (generate_gt.py:68-102, 133-140)
+
+    def _finish_pairs_launch(self, mem_pts0, mem_offs0, mem_rows, views, poses0, save_voxel_size):
+        """Device work of a batch's pairs, nothing read back: -> (finished clouds, offsets (2B+1), statuses, overlap counts,
+        down-sampled offsets).  Segment 2j is scene j's source frame (its float32 memory widened to float64), segment 2j+1 its
+        views in view order; only the odd segments are moved by pose0 and back.  The crop box is applied to every segment and
+        is a no-op on the even ones: the memory IS `crop_aabb` of the source frame in float32, the bounds are float32 numbers,
+        and widening keeps every comparison."""
+        G_ = self.G
+        B = len(mem_rows)
+        dev = mem_pts0.device
+        xyz = views[0][0] if len(views) == 1 else torch.cat([v[0] for v in views], dim=1)         # (B, n_views*HW, 3)
+        valid = views[0][1] if len(views) == 1 else torch.cat([v[1] for v in views], dim=1)
+        rows_v = xyz.shape[1]
+        merged, mvalid, moffs = G_.merge_memory(mem_pts0, mem_offs0, xyz, valid)
+        shift = torch.arange(B, dtype=torch.int64, device=dev) * rows_v
+        offs2 = torch.empty((2 * B + 1,), dtype=torch.int64, device=dev)
+        offs2[0:2 * B:2] = moffs[:-1]
+        offs2[1:2 * B:2] = mem_offs0[1:] + shift
+        offs2[2 * B] = moffs[-1]
+        pre = np.zeros((2 * B, 4, 4), dtype=np.float64)
+        post = np.zeros((2 * B, 4, 4), dtype=np.float64)
+        has = np.zeros((2 * B,), dtype=np.uint8)
+        for j in range(B):
+            T = poses0[j].astype(np.float64)
+            pre[2 * j + 1], post[2 * j + 1], has[2 * j + 1] = T, np.linalg.inv(T), 1     # the same 16 doubles as the host path
+        fin, fin_offs, st_save = G_.finish_clouds(merged, mvalid, offs2, save_voxel_size, pre=pre, has_pre=has,
+                                                  crop=(PP.BBOX_MIN, PP.BBOX_MAX), post=post, has_post=has)
+        lib = G._lib.load()
+        down, down_offs, st_gt = G_.voxel_grid_ragged(fin, None, fin_offs, self.GT_VOXEL)
+        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        # max_cloud only bounds the query slabs: no finished cloud has more rows than went into it
+        G._lib.check(lib.prg_overlap_counts(G._lib.ptr(down), G._lib.ptr(down_offs), B, int(max(max(mem_rows), rows_v)),
+                                            float(self.GT_VOXEL * self.GT_FACTOR), G._lib.ptr(counts), G._lib.stream_ptr()),
+                     "prg_overlap_counts")
+        return fin, fin_offs, st_save, st_gt, counts, down_offs
+
+    def _finish_pairs_write(self, pool, finished, idxs, sdirs, marker_index):
+        """Host side: ONE copy of the finished clouds, the PLY files as write-only jobs, every scene's gt.log written before this
+        returns.  -> the batch's resume marker job (not yet submitted)."""
+        fin, fin_offs, st_save, st_gt, counts, down_offs = finished
+        B = len(idxs)
+        small = torch.cat([fin_offs, down_offs, st_save.to(torch.int64), st_gt.to(torch.int64), counts.view(-1).to(torch.int64)])
+        small = small.cpu().numpy()
+        offs, d_offs = small[:2 * B + 1], small[2 * B + 1:4 * B + 2]
+        st_save, st_gt, cnt = small[4 * B + 2:6 * B + 2], small[6 * B + 2:8 * B + 2], small[8 * B + 2:].reshape(B, 2)
+        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in (0, 1)]
+        self.G.check_voxel_status(st_save, names)
+        self.G.check_voxel_status(st_gt, names)
+        pts = fin[:max(int(offs[-1]), 0)].cpu().numpy()
+        marker = None
+        for j, sdir in enumerate(sdirs):
+            for k in (0, 1):
+                job = (lambda path=str(sdir / "sample-{:0>6d}.cloud.ply".format(k)), pc=pts[offs[2 * j + k]:offs[2 * j + k + 1]]:
+                       pool.cloud(path, pc, None, crop=False, voxel=0))
+                if j == B - 1 and k == marker_index:
+                    marker = job
+                else:
+                    job()
+        sizes, d_sizes = np.diff(offs), np.diff(d_offs)
+        for j, (idx, sdir) in enumerate(zip(idxs, sdirs)):
+            lines = []
+            if sizes[2 * j] >= self.GT_MIN_POINTS and sizes[2 * j + 1] >= self.GT_MIN_POINTS:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    o_s = float(np.float64(cnt[j, 0]) / np.float64(d_sizes[2 * j]))
+                    o_t = float(np.float64(cnt[j, 1]) / np.float64(d_sizes[2 * j + 1]))
+                if not (np.isnan(o_s) or np.isnan(o_t) or (o_s < 0.1 and o_t < 0.1)):
+                    lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), 0, 1, o_s, o_t))
+            with open(sdir / "gt.log", "w") as f:
+                f.writelines(lines)
+        return marker
 
 
 def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int, num_samples: int,

@@ -277,6 +277,102 @@ def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.
     return merged, merged_valid, merged_offsets
 
 
+def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.contiguous()
+    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).view(-1)
+
+
+def _transforms(T, B: int, device) -> Optional[torch.Tensor]:
+    """(B,4,4) / (B,16) float64, numpy or tensor -> (B,16) float64 on `device` (the 16 doubles are uploaded unchanged)."""
+    if T is None:
+        return None
+    if not torch.is_tensor(T):
+        T = torch.from_numpy(np.ascontiguousarray(T, dtype=np.float64))
+    assert T.dtype == torch.float64 and T.numel() == 16 * B, "one float64 4x4 per segment"
+    return T.to(device).contiguous().view(B, 16)
+
+
+def _flags(f, B: int, device) -> Optional[torch.Tensor]:
+    if f is None:
+        return None
+    if not torch.is_tensor(f):
+        f = torch.from_numpy(np.ascontiguousarray(f).astype(np.uint8))
+    assert f.numel() == B
+    return _u8(f.to(device))
+
+
+def rigid_crop_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets: torch.Tensor, *, T=None, has_T=None,
+                      crop=None, out: Optional[torch.Tensor] = None, valid_out: Optional[torch.Tensor] = None):
+    """prg_rigid_crop_ragged_f64: segment b of the ragged float64 cloud `pts` (CSR `offsets`, B+1 int64) moved by its row of
+    T ((B,4,4) float64; segments with has_T[b] == 0, or all of them when T is None, are copied bit for bit), and, with
+    crop = (lo, hi), valid_out = valid && lo <= p' <= hi.  `out` / `valid_out`: where to write (pts / valid themselves for
+    in-place use); default: fresh tensors (valid_out only when there is a crop or a mask).  -> (out, valid_out uint8 | None)."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total, B = pts.shape[0], offsets.numel() - 1
+    v8 = _u8(valid)
+    assert v8 is None or v8.numel() == total
+    Td, hd = _transforms(T, B, pts.device), _flags(has_T, B, pts.device)
+    lo = hi = None
+    if crop is not None:
+        lo, hi = (np.ascontiguousarray(c, dtype=np.float64).reshape(3) for c in crop)
+    if out is None:
+        out = torch.empty_like(pts)
+    if valid_out is None and (crop is not None or v8 is not None):
+        valid_out = torch.empty((total,), dtype=torch.uint8, device=pts.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 3 * total
+    assert valid_out is None or (valid_out.dtype == torch.uint8 and valid_out.is_contiguous() and valid_out.numel() == total)
+    if total == 0:                                  # no rows, and a tensor without elements has no address to pass
+        return out, valid_out
+    _lib.check(lib.prg_rigid_crop_ragged_f64(_lib.ptr(pts), _lib.ptr(v8), _lib.ptr(offsets), B, total, _lib.ptr(Td),
+                                             _lib.ptr(hd), None if lo is None else lo.ctypes.data, None if hi is None
+                                             else hi.ctypes.data, _lib.ptr(out), _lib.ptr(valid_out), _lib.stream_ptr()),
+               "prg_rigid_crop_ragged_f64")
+    return out, valid_out
+
+
+def finish_clouds(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets: torch.Tensor, voxel: float, *, pre=None,
+                  has_pre=None, crop=None, post=None, has_post=None):
+    """`WriterPool.cloud`'s pipeline for B ragged clouds at once, on the device: pre-transform -> crop -> voxel mean ->
+    post-transform.  pts (total,3) float64, valid (total) bool / uint8 or None, offsets (B+1) int64, device tensors as for
+    `voxel_grid_ragged`; pre / post: (B,4,4) float64 (numpy or tensor) or None, has_pre / has_post: (B) flags, None = every
+    segment; crop: (lo, hi) or None.  Returns (out (rows,3) float64, out_offsets (B+1) int64, status (B) int32) on the device:
+    out[out_offsets[b]:out_offsets[b+1]] is, bit for bit, the vertex payload of the PLY that `WriterPool.cloud(path, xyz_b,
+    valid_b, pre=, crop=, voxel=, post=)` writes (`postprocess.finish_cloud` is the numpy form); status as `voxel_grid_ragged`.
+    voxel <= 0 skips the grid: the kept rows stay in input order (compacted with torch on the device; that one path waits for
+    the row count).  `pts` and `valid` are left as they are."""
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total, B = pts.shape[0], offsets.numel() - 1
+    cur, cur_valid = pts, _u8(valid)
+    if pre is not None or crop is not None:
+        # a crop alone moves nothing: the kernel then only writes the flags and `out` may be the input itself
+        cur, cur_valid = rigid_crop_ragged(pts, cur_valid, offsets, T=pre, has_T=has_pre, crop=crop,
+                                           out=pts if pre is None else None)
+    if voxel > 0:
+        out, out_offsets, status = voxel_grid_ragged(cur, cur_valid, offsets, voxel)
+    else:
+        idx = torch.arange(total, device=pts.device)
+        keep = (idx >= offsets[0]) & (idx < offsets[-1])          # rows outside every segment hold nothing
+        if cur_valid is not None:
+            keep &= cur_valid != 0
+        csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=pts.device), torch.cumsum(keep.to(torch.int64), 0)])
+        out_offsets = csum[offsets.clamp(0, total)]
+        out_offsets = out_offsets - out_offsets[0]
+        out = cur[keep]
+        status = torch.zeros((B,), dtype=torch.int32, device=pts.device)
+    if post is not None and out.shape[0] > 0:
+        rigid_crop_ragged(out, None, out_offsets, T=post, has_T=has_post, out=out)
+    return out, out_offsets, status
+
+
 def check_voxel_status(status, names: Sequence) -> None:
     """Raise PrgError naming the first scene whose voxel grid failed (`status` already on the host)."""
     for j, st in enumerate(np.asarray(status)):

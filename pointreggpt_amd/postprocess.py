@@ -69,6 +69,39 @@ def voxel_down_sample(pts: np.ndarray, voxel_size: float) -> np.ndarray:
     return sums / counts[:, None]
 
 
+def rigid_move(pts: np.ndarray, T: np.ndarray) -> np.ndarray:
+    """p' = R p + t with every coordinate written out as x*T[r,0] + y*T[r,1] + z*T[r,2] + T[r,3], the products summed left to
+    right in float64 — bit for bit csrc/hostpool.cpp's transform() and prg_rigid_crop_ragged_f64.  (`transform` above goes
+    through the BLAS, which may fuse a product into the sum.)"""
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    out = np.empty_like(pts)
+    for r in range(3):
+        out[:, r] = x * T[r, 0] + y * T[r, 1] + z * T[r, 2] + T[r, 3]
+    return out
+
+
+def finish_cloud(xyz: np.ndarray, valid: Optional[np.ndarray] = None, *, pre: Optional[np.ndarray] = None, crop: bool = True,
+                 lo=BBOX_MIN, hi=BBOX_MAX, voxel: float = 0.025, post: Optional[np.ndarray] = None) -> np.ndarray:
+    """The numpy specification of a finished cloud: the (n,3) float64 vertex payload of the PLY that
+    `WriterPool.cloud(path, xyz, valid, pre=, crop=, voxel=, post=, lo=, hi=)` writes, bit for bit — rows with valid != 0 in
+    input order -> pre (4x4, None = not moved: the rows are copied, never multiplied by an identity) -> crop to lo <= p <= hi
+    (if crop) -> voxel mean (if voxel > 0) -> post.  What `geometry.finish_clouds` computes per segment on the device."""
+    pts = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    if valid is not None:
+        pts = pts[np.asarray(valid).reshape(-1) != 0]
+    if pre is not None:
+        pts = rigid_move(pts, pre)
+    if crop:
+        pts = crop_aabb(pts, np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64))
+    if voxel > 0:
+        pts = voxel_down_sample(pts, voxel)
+    if post is not None:
+        pts = rigid_move(pts, post)
+    return np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # PLY (what o3d.io.write_point_cloud / read_point_cloud exchange; the dataloaders only need the N x 3 points)
 # ------------------------------------------------------------------------------------------------------------------
