@@ -267,7 +267,9 @@ typedef struct prg_step {
   int32_t clip_pred;    /* bit 0: clamp the network output before deriving eps (DDIM rows = 1);
                            bit 1: clamp x0 after the DDNM replacement (ancestral rows = 2);
                            bit 2 (= 4, alone): refine row of has_refine_step (sd:1307-1314, 1374-1388):
-                                  x' = known ? clamp(u,-1,1) : x, no replacement, coefficients ignored */
+                                  x' = known ? clamp(u,-1,1) : x, no replacement, coefficients ignored.
+                           clamp is torch.clamp: +-Inf becomes +-1 and NaN stays NaN, so a non-finite network
+                           output is never turned into a plausible depth */
   float c_x0, c_x, c_eps, sigma;
   float sqrt_recip, sqrt_recipm1;
 } prg_step;

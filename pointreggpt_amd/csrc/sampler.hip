@@ -42,7 +42,8 @@ __device__ inline float4 philox_normal4(uint64_t key, uint32_t draw, uint32_t qu
   return make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
 }
 
-__device__ inline float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
+// torch.clamp: NaN stays NaN (fminf / fmaxf would return the bound and hide a non-finite network output as depth 0)
+__device__ inline float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
 // grid (chunks, B); each thread handles 4 consecutive pixels
 __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
