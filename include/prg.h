@@ -254,7 +254,8 @@ typedef struct prg_sampler prg_sampler;
 /* One denoising transition.  With u = Unet(x, t, param_cond):
  *     x0p = (clip_pred & 1) ? clamp(u,-1,1) : u                              (ddim_sample, sd:1199-1201)
  *     eps = (sqrt_recip * x - x0p) / sqrt_recipm1                            (sd:1158-1162; used iff c_eps != 0)
- *     x0  = known ? cond_depth : x0p                                         (DDNM replacement, sd:1210-1218)
+ *     x0  = (known && kept) ? cond_depth : x0p                               (DDNM replacement, sd:1210-1218; kept = true unless
+ *           the row has a keep threshold, prg_sampler_set_keep below)
  *     x0  = (clip_pred & 2) ? clamp(x0,-1,1) : x0                            (p_mean_variance, sd:1250-1251: the ancestral
  *           sampler clamps AFTER the replacement; ddim_sample does not, so known pixels > 1 enter the state as they are)
  *     x'  = c_x0 * x0 + c_x * x + c_eps * eps + sigma * noise                (sd:1173-1180,1280 / sd:1369-1373)
@@ -292,6 +293,22 @@ int prg_sampler_set_graph(prg_sampler* h, int enable);
 int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_cond, const float* noise,
                     int64_t noise_slabs, const uint64_t* seeds, float* out, void* stream);
 
+/* Stochastic DDNM (sd:1075-1094, 1210-1227: ddnm_sampling_dropout / ddnm_dropout_schedule, and denoise(), sd:1411-1427).
+ * keep_p: HOST array of n floats, one threshold per transition of the handle (n must equal its n_steps); NULL clears the table
+ * (the default: plain DDNM).  The handle owns the device copy.  In a run with an img_cond, transition k with
+ *     keep_p[k] <  0 : replaces every known pixel and draws nothing (exactly the run without a table);
+ *     keep_p[k] >= 0 : draws one float32 uniform u in [0,1) per pixel and replaces a known pixel iff u > keep_p[k], compared in
+ *                      float32 (`uniform_(0,1) > p`, sd:1214-1216).  0 is a threshold like any other: it draws, and drops the
+ *                      pixels whose u == 0; the reference draws nothing when its p is 0, so the host passes -1 there.
+ * The refine row (clip_pred == 4) ignores the table: no replacement, no draw, the full known mask (sd:1307-1314).            */
+int prg_sampler_set_keep(prg_sampler* h, const float* keep_p, int n);
+/* Where the uniforms come from.  NULL (default): on-device Philox4x32-10 with the per-scene key of prg_sampler_run's `seeds`
+ * (required then, also in a stored-noise run), counter {pixel quad q, k + 1, 0x6B656570, 0} — the normals use 0x70726721 as third
+ * word — word i >> 8 times 2^-24 for pixel 4q + i: exact, on the 2^-24 grid of torch's float32 uniform_, 0 included.
+ * Else u: DEVICE float32 (slabs, B, S, S), the caller's; slab k feeds transition k and is read only where keep_p[k] >= 0 (other
+ * slabs may hold anything); prg_sampler_run fails with PRG_E_INVALID if a drawing transition would read past `slabs`.          */
+int prg_sampler_set_keep_draws(prg_sampler* h, const float* u, int64_t slabs);
+
 /* Kernel unit-test / bandwidth hook (round 6): the transition update above ALONE (sampler_step_kernel: what p_sample / ddim_sample
  * do after model_predictions, sd:1257-1281 / sd:1369-1373) on caller tensors, `reps` launches back to back on `stream`:
  * x (B,HW) DEVICE, updated in place by every launch; u (B,HW) DEVICE = the network output; img_cond (B,2,HW) DEVICE or NULL;
@@ -299,6 +316,10 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
  * *avg_us (HOST, may be NULL) = HIP-event microseconds per launch.  Synchronises.                                            */
 int prg_debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, int B,
                            int HW, int reps, float* avg_us, void* stream);
+/* The same with a keep threshold on every launch (prg_sampler_set_keep): keep_p as above (< 0: no draw); keep_u DEVICE
+ * (reps, B, HW) stored uniforms, launch i reads slab i, or NULL: launch i takes Philox keep draw i + 1 of seeds[b].           */
+int prg_debug_sampler_step_keep(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step,
+                                float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream);
 
 /* Wall-clock free timing hook for bench.py: average duration in milliseconds of the dominant kernel class
  * (implicit-GEMM convolution launches) measured with HIP events on the run's own stream during the last

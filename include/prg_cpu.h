@@ -55,6 +55,13 @@ int prg_cpu_maskunet_forward(prg_cpu_unet* h, const float* depth, float* prob, i
  * replaced pixels).  sd:1283-1409.                                                                                      */
 int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* param_cond, const float* img_cond,
                         const float* noise, int64_t noise_slabs, const uint64_t* seeds, float* out, int B, int S);
+/* The same with the stochastic DDNM keep table of prg_sampler_set_keep / prg_sampler_set_keep_draws (prg.h): keep_p (n_steps)
+ * thresholds or NULL; keep_u stored uniforms (keep_slabs, B, S*S), slab k for transition k, read only where keep_p[k] >= 0, or
+ * NULL -> Philox with the device's counter layout and its exact 24-bit uniform (bit-identical masks; needs seeds).
+ * sd:1075-1094, 1210-1227, 1411-1427.                                                                                     */
+int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* param_cond, const float* img_cond,
+                             const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
+                             const float* keep_u, int64_t keep_slabs, float* out, int B, int S);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ PROTOTYPES = {
     "prg_cpu_unet_forward": (C.c_int, [_P, _P, _P, _P, _P, _I, _I]),
     "prg_cpu_maskunet_forward": (C.c_int, [_P, _P, _P, _I, _I]),
     "prg_cpu_sampler_run": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _I, _I]),
+    "prg_cpu_sampler_run_keep": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _I]),
 }
 
 _lib = None
@@ -174,9 +175,9 @@ class MaskUnet(_CpuNet):
 
 class GaussianDiffusion(_diff.GaussianDiffusion):
     """The GPU front-end's schedule / transition table (computed with torch on the host exactly like the reference) driving
-    prg_cpu_sampler_run."""
+    prg_cpu_sampler_run_keep (the keep table of stochastic DDNM included: never silently ignored here)."""
 
-    def _sampler(self, batch, refine=False):          # no device handle to keep
+    def _sampler(self, batch, refine=False, mode="sample"):          # no device handle to keep
         raise _hip.PrgError("the CPU sampler has no persistent handle")
 
     def close(self):
@@ -184,22 +185,37 @@ class GaussianDiffusion(_diff.GaussianDiffusion):
 
     @torch.no_grad()
     def sample(self, *, param_cond, img_cond=None, disable_tqdm=True, has_refine_step=False, noise=None,
-               seeds: Optional[Sequence[int]] = None, **_unused):
+               seeds: Optional[Sequence[int]] = None, keep_draws=None, **_unused):
+        return self._run("sample", param_cond, img_cond, has_refine_step, noise, seeds, keep_draws)
+
+    @torch.no_grad()
+    def denoise(self, *, param_cond, img_cond=None, disable_tqdm=True, has_refine_step=False, noise=None,
+                seeds: Optional[Sequence[int]] = None, keep_draws=None, **_unused):
+        return self._run("denoise", param_cond, img_cond, has_refine_step, noise, seeds, keep_draws)
+
+    def _run(self, mode, param_cond, img_cond, has_refine_step, noise, seeds, keep_draws):
         pc = _t(param_cond)
         B, S = pc.shape[0], self.image_size
-        cond = _t(img_cond) if (img_cond is not None and self.is_ddnm_sampling) else None
-        arr, n = self._steps_c(bool(has_refine_step) and cond is not None)
+        cond = _t(img_cond) if (img_cond is not None and (self.is_ddnm_sampling or mode == "denoise")) else None
+        refine = bool(has_refine_step) and cond is not None
+        arr, n = self._steps_c(refine)
+        keep = self._keep_c(mode, refine) if cond is not None else None
+        ku, kslabs = None, 0
+        if keep is not None and keep_draws is not None:
+            ku = _t(keep_draws)
+            kslabs = ku.numel() // (B * S * S)
         nz, seed_arr, slabs = None, None, 0
         if noise is not None:
             nz = _t(noise)
             slabs = nz.numel() // (B * S * S)
             assert slabs >= self.n_draws, f"stored noise needs {self.n_draws} draws of shape ({B},1,{S},{S})"
-        else:
+        if noise is None or (keep is not None and ku is None):
             seed_arr = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in (seeds if seeds is not None else range(B))])
         out = torch.empty((B, 1, S, S), dtype=torch.float32)
-        check(load().prg_cpu_sampler_run(self.model.handle, arr, n, _p(pc), _p(cond), _p(nz), slabs,
-                                         C.cast(seed_arr, C.c_void_p) if seed_arr is not None else None, _p(out), B, S),
-              "prg_cpu_sampler_run")
+        check(load().prg_cpu_sampler_run_keep(self.model.handle, arr, n, _p(pc), _p(cond), _p(nz), slabs,
+                                              C.cast(seed_arr, C.c_void_p) if seed_arr is not None else None,
+                                              C.cast(keep, C.c_void_p) if keep is not None else None, _p(ku), kslabs,
+                                              _p(out), B, S), "prg_cpu_sampler_run_keep")
         return out
 
 

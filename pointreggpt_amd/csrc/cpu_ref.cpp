@@ -496,6 +496,8 @@ int build(prg_cpu_unet& u, const prg_unet_config& cfg) {
 }
 
 // ---- Philox4x32-10, the device generator's counter layout (sampler.hip) ----
+// third counter word: the stream's name (sampler.h)
+constexpr uint32_t PHILOX_DOMAIN_NORMAL = 0x70726721u, PHILOX_DOMAIN_KEEP = 0x6B656570u;
 inline void philox4x32_10(uint32_t (&c)[4], uint64_t key) {
   uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   for (int r = 0; r < 10; ++r) {
@@ -507,7 +509,7 @@ inline void philox4x32_10(uint32_t (&c)[4], uint64_t key) {
   }
 }
 inline void philox_normal4(uint64_t key, uint32_t draw, uint32_t quad, float (&o)[4]) {
-  uint32_t c[4] = {quad, draw, 0x70726721u, 0u};
+  uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_NORMAL, 0u};
   philox4x32_10(c, key);
   const float k = 2.3283064365386963e-10f;
   const float u0 = ((float)c[0] + 0.5f) * k, u1 = ((float)c[1] + 0.5f) * k, u2 = ((float)c[2] + 0.5f) * k, u3 = ((float)c[3] + 0.5f) * k;
@@ -515,6 +517,12 @@ inline void philox_normal4(uint64_t key, uint32_t draw, uint32_t quad, float (&o
   const float r1 = std::sqrt(-2.0f * std::log(std::min(std::max(u2, 1e-12f), 1.0f)));
   o[0] = r0 * std::cos(6.283185307179586f * u1); o[1] = r0 * std::sin(6.283185307179586f * u1);
   o[2] = r1 * std::cos(6.283185307179586f * u3); o[3] = r1 * std::sin(6.283185307179586f * u3);
+}
+// the keep-mask uniforms of sampler.hip: third counter word "keep", word i >> 8 on the 2^-24 grid (exact: bit-identical to the device)
+inline void philox_keep4(uint64_t key, uint32_t draw, uint32_t quad, float (&o)[4]) {
+  uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_KEEP, 0u};
+  philox4x32_10(c, key);
+  for (int i = 0; i < 4; ++i) o[i] = (float)(c[i] >> 8) * 5.9604644775390625e-08f;
 }
 inline float clamp1(float v) { return std::min(std::max(v, -1.0f), 1.0f); }
 
@@ -747,6 +755,12 @@ int prg_cpu_maskunet_forward(prg_cpu_unet* h, const float* depth, float* prob, i
 
 int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* pc, const float* cond,
                         const float* noise, int64_t noise_slabs, const uint64_t* seeds, float* out, int B, int S) {
+  return prg_cpu_sampler_run_keep(h, steps, n_steps, pc, cond, noise, noise_slabs, seeds, nullptr, nullptr, 0, out, B, S);
+}
+
+int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* pc, const float* cond,
+                             const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
+                             const float* keep_u, int64_t keep_slabs, float* out, int B, int S) {
   CPU_CHECK(h && steps && pc && out && n_steps > 0 && B > 0 && S > 0, "prg_cpu_sampler_run: bad arguments");
   CPU_CHECK(noise || seeds, "prg_cpu_sampler_run: need stored noise or per-scene seeds");
   CPU_CHECK((S * S) % 4 == 0, "prg_cpu_sampler_run: H*W must be a multiple of 4");
@@ -757,6 +771,13 @@ int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, con
       if (steps[k].sigma != 0.0f) need = k + 2;
     CPU_CHECK(noise_slabs >= need, "prg_cpu_sampler_run: stored noise has too few slabs for this transition table");
   }
+  // a row draws a keep mask iff it has a threshold >= 0, there is a condition, and it is not the refine row (sampler.hip)
+  auto drops = [&](int k) { return keep_p && cond && keep_p[k] >= 0.0f && !(steps[k].clip_pred & 4); };
+  for (int k = 0; k < n_steps; ++k)
+    if (drops(k)) {
+      CPU_CHECK(keep_u || seeds, "prg_cpu_sampler_run: the keep mask needs stored uniforms or per-scene seeds");
+      CPU_CHECK(!keep_u || keep_slabs >= k + 1, "prg_cpu_sampler_run: stored keep-mask uniforms have too few slabs for this keep table");
+    }
   auto draw = [&](int k, int b, int q, float (&o)[4]) {        // slab k (0 = start image), pixel quad q of image b
     if (noise) std::memcpy(o, noise + ((size_t)k * B + b) * HW + (size_t)q * 4, sizeof(float) * 4);
     else philox_normal4(seeds[b], (uint32_t)k, (uint32_t)q, o);
@@ -778,6 +799,12 @@ int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, con
       for (int q = 0; q * 4 < HW; ++q) {
         float nz[4] = {0, 0, 0, 0};
         if (st.sigma != 0.0f) draw(k + 1, b, q, nz);
+        const bool drop = drops(k);
+        float ku[4] = {0, 0, 0, 0};
+        if (drop) {
+          if (keep_u) std::memcpy(ku, keep_u + ((size_t)k * B + b) * HW + (size_t)q * 4, sizeof(ku));
+          else philox_keep4(seeds[b], (uint32_t)(k + 1), (uint32_t)q, ku);
+        }
         for (int e = 0; e < 4; ++e) {
           const size_t o = (size_t)b * HW + (size_t)q * 4 + e;
           const float xs = x[o], us = u[o];
@@ -786,7 +813,8 @@ int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, con
           // arithmetic of sampler_step_kernel (sampler.hip) = the reference's order (sd:1158-1218, 1250-1280, 1369-1373)
           const float x0p = (st.clip_pred & 1) ? clamp1(us) : us;
           const bool known = cond && ((cm + 1.0f) * 0.5f > 0.5f);
-          float x0 = known ? cd : x0p;
+          const bool kept = !drop || ku[e] > keep_p[k];       // uniform_(0,1) > p in float32 (sd:1214-1216)
+          float x0 = (known && kept) ? cd : x0p;
           if (st.clip_pred & 2) x0 = clamp1(x0);
           float v = st.c_x0 * x0;
           if (st.clip_pred & 4) {

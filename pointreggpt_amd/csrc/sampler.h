@@ -4,6 +4,10 @@
 
 namespace prg {
 
+// third Philox counter word: the normals use 0x70726721, the keep-mask uniforms this one ("keep")
+constexpr uint32_t PHILOX_DOMAIN_NORMAL = 0x70726721u;
+constexpr uint32_t PHILOX_DOMAIN_KEEP = 0x6B656570u;
+
 struct SamplerStepArgs {
   float* x;                 // state (B, HW), updated in place
   const float* u;           // U-Net output (B, HW)
@@ -14,6 +18,9 @@ struct SamplerStepArgs {
   int* ticket;              // arrival counter of the workgroups of one launch (self-resetting)
   const uint64_t* seeds;    // device (B,) Philox keys (used when noise == null)
   float* final_out;         // (B, HW): written on the last transition as (x + 1) / 2
+  const float* keep_p;      // device (n_steps,) DDNM keep thresholds or null: row k with keep_p[k] >= 0 replaces a known pixel
+                            // iff its uniform > keep_p[k]; < 0 (and null): every known pixel, nothing drawn
+  const float* keep_u;      // stored uniforms (n_steps, B, HW), slab k feeds transition k, or null -> Philox (DOMAIN_KEEP)
   int B, HW, n_steps;
 };
 

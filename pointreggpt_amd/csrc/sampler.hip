@@ -29,7 +29,7 @@ __device__ inline void philox4x32_10(uint32_t (&c)[4], uint64_t key) {
 }
 // four standard normals for (scene key, draw index, pixel quad): two Box-Muller pairs
 __device__ inline float4 philox_normal4(uint64_t key, uint32_t draw, uint32_t quad) {
-  uint32_t c[4] = {quad, draw, 0x70726721u, 0u};
+  uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_NORMAL, 0u};
   philox4x32_10(c, key);
   const float k = 2.3283064365386963e-10f;  // 2^-32
   const float u0 = ((float)c[0] + 0.5f) * k, u1 = ((float)c[1] + 0.5f) * k;
@@ -42,17 +42,27 @@ __device__ inline float4 philox_normal4(uint64_t key, uint32_t draw, uint32_t qu
   return make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
 }
 
+// four uniforms in [0,1) on the 2^-24 grid (torch's float32 uniform_ grid, 0 included) for the DDNM keep mask of (scene key,
+// draw index, pixel quad): word i >> 8, exactly representable, serves pixel 4 * quad + i.  The third counter word separates
+// this stream from the normals' of the same (key, draw, quad).
+__device__ inline float4 philox_keep4(uint64_t key, uint32_t draw, uint32_t quad) {
+  uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_KEEP, 0u};
+  philox4x32_10(c, key);
+  const float k = 5.9604644775390625e-08f;  // 2^-24
+  return make_float4((float)(c[0] >> 8) * k, (float)(c[1] >> 8) * k, (float)(c[2] >> 8) * k, (float)(c[3] >> 8) * k);
+}
+
 // torch.clamp: NaN stays NaN (fminf / fmaxf would return the bound and hide a non-finite network output as depth 0)
 __device__ inline float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
-// grid (chunks, B); each thread handles 4 consecutive pixels
-__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
-  const int k = *a.step_idx;
-  const prg_step st = a.steps[k];
-  const int b = blockIdx.y;
-  const bool last = k == a.n_steps - 1;
+// One transition on image b.  DROP (stochastic DDNM, sd:1213-1216 / 1223-1225): a known pixel is replaced iff its uniform > keep_p
+// (float32 comparison, like torch's of a float32 tensor with a 0-dim float64 one).  DROP = false is the kernel as it was before the
+// keep mask existed: same instructions, same data.
+template <bool DROP>
+__device__ inline void sampler_step_image(const SamplerStepArgs& a, const prg_step& st, int k, int b, bool last, float keep_p,
+                                          int q0, int q_stride) {
   const size_t img = (size_t)b * a.HW;
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q * 4 < a.HW; q += gridDim.x * blockDim.x) {
+  for (int q = q0; q * 4 < a.HW; q += q_stride) {
     const size_t o = img + (size_t)q * 4;
     const float4 xv = *reinterpret_cast<const float4*>(a.x + o);
     const float4 uv = *reinterpret_cast<const float4*>(a.u + o);
@@ -70,12 +80,21 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
     const float cds[4] = {cd.x, cd.y, cd.z, cd.w}, cms[4] = {cm.x, cm.y, cm.z, cm.w};
     const float nzs[4] = {nz.x, nz.y, nz.z, nz.w};
+    bool kept[4] = {true, true, true, true};
+    if (DROP) {
+      float4 ku;
+      if (a.keep_u)
+        ku = *reinterpret_cast<const float4*>(a.keep_u + ((size_t)k * a.B + b) * a.HW + (size_t)q * 4);
+      else
+        ku = philox_keep4(a.seeds[b], (uint32_t)(k + 1), (uint32_t)q);
+      kept[0] = ku.x > keep_p; kept[1] = ku.y > keep_p; kept[2] = ku.z > keep_p; kept[3] = ku.w > keep_p;
+    }
     float r[4], f[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float x0p = (st.clip_pred & 1) ? clamp1(us[e]) : us[e];
       const bool known = a.cond && ((cms[e] + 1.0f) * 0.5f > 0.5f);  // get_mask_from_img_cond (sd:507-508)
-      float x0 = known ? cds[e] : x0p;
+      float x0 = (DROP ? known && kept[e] : known) ? cds[e] : x0p;   // keep_mask & mask_rpj (sd:1216): a dropped pixel stays in-painted
       if (st.clip_pred & 2) x0 = clamp1(x0);   // p_mean_variance clip_denoised (sd:1250); ddim_sample has no such clamp
       float v = st.c_x0 * x0;
       if (st.clip_pred & 4) {
@@ -97,6 +116,26 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
     *reinterpret_cast<float4*>(a.x + o) = make_float4(r[0], r[1], r[2], r[3]);
     if (last) *reinterpret_cast<float4*>(a.final_out + o) = make_float4(f[0], f[1], f[2], f[3]);
   }
+}
+
+// grid (chunks, B); each thread handles 4 consecutive pixels.  KEEP = false (no keep table: the host chooses it, launch_sampler_step) is
+// the kernel as it was before the keep mask existed; KEEP = true reads the row's threshold.
+template <bool KEEP>
+__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
+  const int k = *a.step_idx;
+  const prg_step st = a.steps[k];
+  const int b = blockIdx.y;
+  const bool last = k == a.n_steps - 1;
+  // The row decides whether a keep mask is drawn, so the branch is uniform across the launch.  No table, a negative threshold,
+  // no condition, or the refine row (which ignores the table): every known pixel is replaced and nothing is drawn.
+  const float keep_p = KEEP ? a.keep_p[k] : -1.0f;
+  // (the grid-stride bounds are taken here: read in the kernel itself, blockDim folds to the launch bound's uniform group size;
+  // read inside a device function it is the generic form, one more dependent load at the head of every launch)
+  const int q0 = blockIdx.x * blockDim.x + threadIdx.x, q_stride = gridDim.x * blockDim.x;
+  if (KEEP && keep_p >= 0.0f && a.cond && !(st.clip_pred & 4))
+    sampler_step_image<true>(a, st, k, b, last, keep_p, q0, q_stride);
+  else
+    sampler_step_image<false>(a, st, k, b, last, keep_p, q0, q_stride);
   // Every workgroup read the step counter at its first instruction; the last one to arrive here advances it for the
   // next launch and re-arms the ticket (kernel boundaries order this against the neighbouring launches).
   __syncthreads();
@@ -135,7 +174,10 @@ static inline dim3 step_grid(int HW, int B) {
 
 int launch_sampler_step(const SamplerStepArgs& a, hipStream_t s) {
   PRG_CHECK(a.HW % 4 == 0, "sampler: H*W must be a multiple of 4");
-  sampler_step_kernel<<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
+  if (a.keep_p)
+    sampler_step_kernel<true><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
+  else
+    sampler_step_kernel<false><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }
@@ -150,20 +192,23 @@ int launch_sampler_init(float* x, const float* noise, const uint64_t* seeds, int
 
 using namespace prg;
 
-extern "C" int prg_debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, int B,
-                                      int HW, int reps, float* avg_us, void* stream) {
+// has_keep: the launches also get a table of `reps` + 1 copies of keep_p (and keep_u); without it the table pointer is null
+static int debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, bool has_keep,
+                              float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream) {
   PRG_CHECK(x && u && seeds && step && B > 0 && HW > 0 && HW % 4 == 0 && reps > 0, "prg_debug_sampler_step: bad argument");
   hipStream_t s = (hipStream_t)stream;
   // a table of `reps` copies of the transition (+1 row so that no launch is the chain's last), the device step counter and the ticket
   std::vector<prg_step> rows((size_t)reps + 1, *step);
+  std::vector<float> keep(has_keep ? rows.size() : 0, keep_p);
   char* scratch = nullptr;
   const size_t tab = sizeof(prg_step) * rows.size();
-  PRG_HIP(hipMalloc(&scratch, tab + 2 * sizeof(int)));
+  PRG_HIP(hipMalloc(&scratch, tab + 2 * sizeof(int) + sizeof(float) * keep.size()));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = PRG_OK;
   auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == PRG_OK) { set_error(std::string("prg_debug_sampler_step: ") + hipGetErrorString(e)); rc = PRG_E_HIP; } };
   fail(hipMemcpyAsync(scratch, rows.data(), tab, hipMemcpyHostToDevice, s));
   fail(hipMemsetAsync(scratch + tab, 0, 2 * sizeof(int), s));
+  if (has_keep) fail(hipMemcpyAsync(scratch + tab + 2 * sizeof(int), keep.data(), sizeof(float) * keep.size(), hipMemcpyHostToDevice, s));
   fail(hipEventCreate(&e0));
   fail(hipEventCreate(&e1));
   if (rc == PRG_OK) {
@@ -171,6 +216,7 @@ extern "C" int prg_debug_sampler_step(float* x, const float* u, const float* img
     a.x = x; a.u = u; a.cond = img_cond; a.noise = nullptr; a.steps = reinterpret_cast<const prg_step*>(scratch);
     a.step_idx = reinterpret_cast<int*>(scratch + tab); a.ticket = a.step_idx + 1; a.seeds = seeds; a.final_out = x;
     a.B = B; a.HW = HW; a.n_steps = reps + 1;
+    if (has_keep) { a.keep_p = reinterpret_cast<const float*>(scratch + tab + 2 * sizeof(int)); a.keep_u = keep_u; }
     fail(hipEventRecord(e0, s));
     for (int i = 0; i < reps && rc == PRG_OK; ++i) rc = launch_sampler_step(a, s);
     fail(hipEventRecord(e1, s));
@@ -183,4 +229,14 @@ extern "C" int prg_debug_sampler_step(float* x, const float* u, const float* img
   if (e1) (void)hipEventDestroy(e1);
   (void)hipFree(scratch);
   return rc;
+}
+
+extern "C" int prg_debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, int B,
+                                      int HW, int reps, float* avg_us, void* stream) {
+  return debug_sampler_step(x, u, img_cond, seeds, step, false, -1.0f, nullptr, B, HW, reps, avg_us, stream);
+}
+
+extern "C" int prg_debug_sampler_step_keep(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step,
+                                           float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream) {
+  return debug_sampler_step(x, u, img_cond, seeds, step, true, keep_p, keep_u, B, HW, reps, avg_us, stream);
 }

@@ -682,11 +682,17 @@ struct prg_sampler {
   float* d_u = nullptr;       // network output
   int* d_step = nullptr;
   uint64_t* d_seeds = nullptr;
+  float* d_keep = nullptr;         // (n_steps) DDNM keep thresholds: uploaded by every run that has a table (prg_sampler_set_keep)
+  std::vector<float> keep;         // host copy; empty = no table: the kernel gets a null pointer
+  const float* keep_u = nullptr;   // caller's stored keep-mask uniforms (keep_slabs, B, S, S), null = Philox
+  int64_t keep_slabs = 0;
   hipStream_t own_stream = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   const float* g_cond = nullptr;   // pointers baked into the captured graph
   const float* g_noise = nullptr;
+  const float* g_keep = nullptr;   // d_keep or null
+  const float* g_keep_u = nullptr;
   float* g_out = nullptr;
   hipStream_t g_stream = nullptr;
   uint64_t g_arena_gen = 0;        // workspace generation the graph was captured against
@@ -723,6 +729,8 @@ static int sampler_one_step(prg_sampler* h, const float* cond, const float* nois
   a.x = h->d_x; a.u = h->d_u; a.cond = cond; a.noise = noise; a.steps = h->d_steps; a.step_idx = h->d_step;
   a.seeds = h->d_seeds; a.final_out = out; a.B = h->B; a.HW = h->S * h->S; a.n_steps = h->n_steps;
   a.ticket = h->d_step + 1;
+  a.keep_p = h->keep.empty() ? nullptr : h->d_keep;
+  a.keep_u = h->keep_u;
   if (h->prof.on) {
     ProfileSink& p = h->prof;
     if (p.step_used == p.step_pool.size()) {
@@ -882,6 +890,7 @@ int prg_sampler_create(prg_unet* unet, const prg_step* steps, int n_steps, int B
   h->d_u = h->own.alloc<float>(B * HW, nomem);
   h->d_step = h->own.alloc<int>(2, nomem);
   h->d_seeds = h->own.alloc<uint64_t>((size_t)B, nomem);
+  h->d_keep = h->own.alloc<float>((size_t)n_steps, nomem);
   if (h->own.rc) return h->own.rc;
   PRG_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamDefault));
   // time half of the conditioning for every transition: Tpart[k] = W_t . SiLU(time_mlp(t_k)) + bias
@@ -922,6 +931,22 @@ int prg_sampler_destroy(prg_sampler* h) {
 int prg_sampler_set_graph(prg_sampler* h, int enable) {
   PRG_CHECK(h, "prg_sampler_set_graph: null handle");
   h->use_graph = enable != 0;
+  return PRG_OK;
+}
+
+int prg_sampler_set_keep(prg_sampler* h, const float* keep_p, int n) {
+  PRG_CHECK(h, "prg_sampler_set_keep: null handle");
+  if (!keep_p) { h->keep.clear(); return PRG_OK; }
+  PRG_CHECK(n == h->n_steps, "prg_sampler_set_keep: the table needs one threshold per transition");
+  h->keep.assign(keep_p, keep_p + n);   // reaches d_keep on the stream of the next run, behind whatever still reads the old table
+  return PRG_OK;
+}
+
+int prg_sampler_set_keep_draws(prg_sampler* h, const float* u, int64_t slabs) {
+  PRG_CHECK(h, "prg_sampler_set_keep_draws: null handle");
+  PRG_CHECK(!u || slabs > 0, "prg_sampler_set_keep_draws: stored uniforms need at least one slab");
+  h->keep_u = u;
+  h->keep_slabs = u ? slabs : 0;
   return PRG_OK;
 }
 
@@ -978,6 +1003,14 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
       if (h->steps[k].sigma != 0.0f) need = k + 2;
     PRG_CHECK(noise_slabs >= need, "prg_sampler_run: stored noise has too few slabs for this transition table");
   }
+  // rows that draw a keep mask: a threshold >= 0, a condition to thin out, not the refine row (sampler_step_kernel's own test)
+  bool draws_keep = false;
+  for (int k = 0; k < h->n_steps && img_cond && !h->keep.empty(); ++k)
+    if (h->keep[k] >= 0.0f && !(h->steps[k].clip_pred & 4)) {
+      draws_keep = true;
+      PRG_CHECK(!h->keep_u || h->keep_slabs >= k + 1, "prg_sampler_run: stored keep-mask uniforms have too few slabs for this keep table");
+    }
+  PRG_CHECK(!draws_keep || h->keep_u || seeds, "prg_sampler_run: the keep mask needs stored uniforms or per-scene seeds");
   prg_unet* u = h->unet;
   PRG_CHECK(u->resB >= h->B && u->resS >= h->S, "prg_sampler_run: U-Net workspace was shrunk");
   hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
@@ -986,6 +1019,7 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
   int rc;
   if (seeds) PRG_HIP(hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, s));
   PRG_HIP(hipMemsetAsync(h->d_step, 0, 2 * sizeof(int), s));   // [step counter, arrival ticket]
+  if (!h->keep.empty()) PRG_HIP(hipMemcpyAsync(h->d_keep, h->keep.data(), sizeof(float) * h->n_steps, hipMemcpyHostToDevice, s));
   // camera half of the conditioning: Ppart[b] = W_p . SiLU(param_mlp(K_b))
   {
     float* h2 = h->d_scratch;
@@ -1016,8 +1050,9 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
     PRG_HIP(hipEventRecord(t0, s));
   }
   if (h->use_graph && !profiling && !u->taps_on) {
+    const float* keep_p = h->keep.empty() ? nullptr : h->d_keep;
     const bool stale = !h->exec || h->g_cond != img_cond || h->g_noise != noise || h->g_out != out || h->g_stream != s ||
-                       h->g_arena_gen != u->arena_gen;
+                       h->g_arena_gen != u->arena_gen || h->g_keep != keep_p || h->g_keep_u != h->keep_u;
     if (stale) {
       sampler_free(h);
       PRG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1029,6 +1064,7 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
       h->graph = g;
       PRG_HIP(hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0));
       h->g_cond = img_cond; h->g_noise = noise; h->g_out = out; h->g_stream = s; h->g_arena_gen = u->arena_gen;
+      h->g_keep = keep_p; h->g_keep_u = h->keep_u;
     }
     for (int k = 0; k < h->n_steps; ++k) PRG_HIP(hipGraphLaunch(h->exec, s));
   } else {

@@ -63,12 +63,14 @@ class GaussianDiffusion:
 
     def __init__(self, model: Unet, *, image_size, timesteps=1000, sampling_timesteps=None, loss_type="l1",
                  objective="pred_x0", beta_schedule="sigmoid", ddim_sampling_eta=1.0, is_ddnm_sampling=True,
-                 ddnm_sampling_dropout=0.0):
+                 ddnm_sampling_dropout=0.0, ddnm_dropout_schedule="none"):
         if objective != "pred_x0" or beta_schedule != "sigmoid":
             raise ValueError("this path implements the generator's configuration: objective='pred_x0', "
                              "beta_schedule='sigmoid' (generate_dataset.py:34-44)")
-        if ddnm_sampling_dropout != 0.0:
-            raise ValueError("ddnm_sampling_dropout must be 0 (the generator never enables it)")
+        if not 0.0 <= float(ddnm_sampling_dropout) <= 1.0:
+            raise ValueError(f"ddnm_sampling_dropout must lie in [0, 1], got {ddnm_sampling_dropout}")
+        if ddnm_dropout_schedule not in ("none", "linear"):
+            raise ValueError(f"unknown ddnm dropout schedule {ddnm_dropout_schedule}")
         assert not model.random_or_learned_sinusoidal_cond and model.channels == model.out_dim
         self.model, self.channels, self.image_size = model, model.channels, int(image_size)
         self.objective, self.is_ddnm_sampling = objective, bool(is_ddnm_sampling)
@@ -79,7 +81,14 @@ class GaussianDiffusion:
         self.ddim_sampling_eta = float(ddim_sampling_eta)
         for k, v in make_schedule(self.num_timesteps).items():
             setattr(self, k, v)
-        self._samplers = {}
+        # stochastic DDNM (sd:1075-1094): per-timestep probability of NOT replacing a known pixel, float64 like the reference's
+        self.ddnm_sampling_dropout = float(ddnm_sampling_dropout)
+        self.ddnm_dropout_schedule = ddnm_dropout_schedule
+        self.ddnm_dropouts = torch.linspace(self.ddnm_sampling_dropout,
+                                            self.ddnm_sampling_dropout if ddnm_dropout_schedule == "none" else 0.0,
+                                            self.num_timesteps, dtype=torch.float64)
+        self.denoise_dropouts = torch.linspace(1.0, 0.0, self.num_timesteps, dtype=torch.float64) ** 100
+        self._samplers = {}            # (batch, size, refine, mode) -> (handle, whether its keep table has a drawing row)
         dep = getattr(model, "_dependents", None)
         if dep is not None:
             dep.add(self)               # reloading / closing the network drops the samplers built on its old handle
@@ -123,6 +132,31 @@ class GaussianDiffusion:
                                 r["sqrt_recipm1"])
         return arr, len(rows)
 
+    def keep_table(self, mode: str = "sample", refine: bool = False) -> List[float]:
+        """One keep threshold per row of ``_steps_c(refine)`` for a run WITH a condition (prg_sampler_set_keep, include/prg.h):
+        >= 0: the row draws a uniform per pixel and replaces a known pixel iff ``u > threshold`` in float32; -1: it replaces
+        every known pixel and draws nothing.  ``sample`` and, on an ``is_ddnm_sampling`` model, ``denoise`` (whose own branch
+        is then never reached, sd:1210 / 1220): float32(ddnm_dropouts[t]) where that is > 0 in float64 -- the reference draws
+        nothing at p = 0 (sd:1213).  ``denoise`` otherwise: float32(denoise_dropouts[t]), always a draw; many of these
+        underflow to 0, which is still a draw (``u > 0``).  The refine row never draws (is_ban_ddnm, sd:1312 / 1386)."""
+        if mode not in ("sample", "denoise"):
+            raise ValueError(f"unknown sampler mode {mode}")
+        keep = []
+        for r in self.step_table():
+            if self.is_ddnm_sampling:
+                p = self.ddnm_dropouts[r["t"]]
+                keep.append(float(p.to(torch.float32)) if p > 0 else -1.0)
+            elif mode == "denoise":
+                keep.append(float(self.denoise_dropouts[r["t"]].to(torch.float32)))
+            else:
+                keep.append(-1.0)
+        return keep + ([-1.0] if refine else [])
+
+    def _keep_c(self, mode: str = "sample", refine: bool = False):
+        """The table as a C array, or None when no row draws: then none is set and the run is plain DDNM."""
+        keep = self.keep_table(mode, refine)
+        return (C.c_float * len(keep))(*keep) if any(k >= 0 for k in keep) else None
+
     @property
     def n_draws(self) -> int:
         """Noise slabs a stored-noise run consumes: the start image + one per transition that adds noise
@@ -130,20 +164,24 @@ class GaussianDiffusion:
         rows = self.step_table()
         return 1 + max([k + 1 for k, r in enumerate(rows) if r["sigma"] != 0.0], default=0)
 
-    def _sampler(self, batch: int, refine: bool = False):
-        key = (batch, self.image_size, bool(refine))
+    def _sampler(self, batch: int, refine: bool = False, mode: str = "sample"):
+        """One handle (and one captured graph) per mode: sample() and denoise() differ in their keep table."""
+        key = (batch, self.image_size, bool(refine), mode)
         if key not in self._samplers:
             lib = _lib.load()
             arr, n = self._steps_c(refine)
             h = C.c_void_p()
             _lib.check(lib.prg_sampler_create(self.model.handle, arr, n, batch, self.image_size, C.byref(h)),
                        "prg_sampler_create")
-            self._samplers[key] = h
-        return self._samplers[key]
+            keep = self._keep_c(mode, refine)
+            if keep is not None:
+                _lib.check(lib.prg_sampler_set_keep(h, keep, n), "prg_sampler_set_keep")
+            self._samplers[key] = (h, keep is not None)
+        return self._samplers[key][0]
 
     def close(self):
         lib = _lib.load()
-        for h in self._samplers.values():
+        for h, _draws in self._samplers.values():
             lib.prg_sampler_destroy(h)
         self._samplers.clear()
 
@@ -157,35 +195,57 @@ class GaussianDiffusion:
     @torch.no_grad()
     def sample(self, *, param_cond: torch.Tensor, img_cond: Optional[torch.Tensor] = None, disable_tqdm=True,
                has_refine_step=False, noise: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None,
-               use_graph: bool = True, profile: bool = False) -> torch.Tensor:
+               use_graph: bool = True, profile: bool = False, keep_draws: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(B,4) intrinsics vector, (B,2,S,S) condition in [-1,1] -> (B,1,S,S) depth in [0,1]  (sd:1394-1409).
 
         ``noise``: (n_draws,B,1,S,S) stored draws in the reference's order (parity runs); otherwise on-device
-        Philox keyed by ``seeds`` (one 64-bit key per scene, default 0..B-1)."""
+        Philox keyed by ``seeds`` (one 64-bit key per scene, default 0..B-1).  With ``ddnm_sampling_dropout`` > 0 every
+        transition whose ``keep_table`` entry is >= 0 thins the known pixels out with a keep mask (sd:1213-1216):
+        ``keep_draws`` (rows,B,1,S,S) stored uniforms, slab k for transition k, read only where the entry is >= 0 (parity
+        runs); otherwise on-device Philox keyed by the same ``seeds``."""
+        return self._run("sample", param_cond, img_cond, has_refine_step, noise, seeds, use_graph, profile, keep_draws)
+
+    @torch.no_grad()
+    def denoise(self, *, param_cond: torch.Tensor, img_cond: Optional[torch.Tensor] = None, disable_tqdm=True,
+                has_refine_step=False, noise: Optional[torch.Tensor] = None, seeds: Optional[Sequence[int]] = None,
+                use_graph: bool = True, profile: bool = False, keep_draws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``sample`` with is_denoise=True (sd:1411-1427): on a model with ``is_ddnm_sampling=False`` every transition replaces
+        the known pixels it keeps under ``denoise_dropouts`` (sd:1220-1227), so the condition reaches the device there too;
+        on an ``is_ddnm_sampling`` model it is ``sample``."""
+        return self._run("denoise", param_cond, img_cond, has_refine_step, noise, seeds, use_graph, profile, keep_draws)
+
+    def _run(self, mode, param_cond, img_cond, has_refine_step, noise, seeds, use_graph, profile, keep_draws):
         lib = _lib.load()
         pc = param_cond.to(device="cuda", dtype=torch.float32).contiguous()
         B, S = pc.shape[0], self.image_size
         cond = None
-        if img_cond is not None and self.is_ddnm_sampling:
+        if img_cond is not None and (self.is_ddnm_sampling or mode == "denoise"):
             cond = img_cond.to(device="cuda", dtype=torch.float32).contiguous()
             assert tuple(cond.shape) == (B, 2, S, S)
-        h = self._sampler(B, bool(has_refine_step) and cond is not None)
+        refine = bool(has_refine_step) and cond is not None
+        h = self._sampler(B, refine, mode)
         _lib.check(lib.prg_sampler_set_graph(h, int(use_graph)))
         _lib.check(lib.prg_sampler_set_profile(h, int(profile)))
+        drawing = cond is not None and self._samplers[(B, S, refine, mode)][1]
+        ku = None
+        if keep_draws is not None and drawing:
+            ku = keep_draws.to(device="cuda", dtype=torch.float32).contiguous()
+            assert ku.numel() % (B * S * S) == 0, f"stored keep draws are slabs of shape ({B},1,{S},{S})"
+        _lib.check(lib.prg_sampler_set_keep_draws(h, _lib.ptr(ku), 0 if ku is None else ku.numel() // (B * S * S)))
         nz = None
         seed_arr = None
         if noise is not None:
             nz = noise.to(device="cuda", dtype=torch.float32).contiguous()
             assert nz.numel() % (B * S * S) == 0 and nz.numel() // (B * S * S) >= self.n_draws, \
                 f"stored noise needs {self.n_draws} draws of shape ({B},1,{S},{S})"
-        else:
+        if noise is None or (drawing and ku is None):
             seed_arr = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in (seeds if seeds is not None else range(B))])
         out = torch.empty((B, 1, S, S), dtype=torch.float32, device="cuda")
         _lib.check(lib.prg_sampler_run(h, _lib.ptr(pc), _lib.ptr(cond), _lib.ptr(nz),
                                        0 if nz is None else nz.numel() // (B * S * S),
                                        C.cast(seed_arr, C.c_void_p) if seed_arr is not None else None,
                                        _lib.ptr(out), _lib.stream_ptr()), "prg_sampler_run")
-        self._keepalive = (pc, cond, nz)   # the run is asynchronous: keep inputs alive until the next call
+        self._keepalive = (pc, cond, nz, ku)   # the run is asynchronous: keep inputs alive until the next call
         return out
 
     def last_profile(self, batch: int, refine: bool = False) -> dict:

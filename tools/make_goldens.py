@@ -641,6 +641,93 @@ def g22_chain1000_128():
     long_chain_fixture("G22_chain1000_ancestral_128", 128, 1, 0, 2200, 1000)
 
 
+def recorded_draws(fn, d, seed, normal_seed):
+    """recorded_noise's sibling for chains that also draw keep masks: run fn() under torch.manual_seed(seed) and record, per
+    evaluation of the network d.model (= per transition, refine row included), the Tensor.uniform_ draw made after it and the
+    threshold the reference itself compares that draw with (the right-hand side of its `uniform_(0, 1) > p`, as float32: torch
+    compares a float32 tensor with a 0-dim float64 tensor in float32).  The normals come from a generator of their own
+    (normal_seed), so that chains of one sampler share them and the file stays small; they are recorded in order like
+    recorded_noise does.  Returns out, normals (n,B,1,S,S), uniforms (rows,B,1,S,S) with NaN slabs where nothing was drawn,
+    keep_p (rows,) float32 with -1 where nothing was drawn."""
+    normals, rows, last = [], [], [None]
+    gn = torch.Generator().manual_seed(normal_seed)
+    o_randn, o_like, o_uniform, o_gt = torch.randn, torch.randn_like, torch.Tensor.uniform_, torch.Tensor.__gt__
+
+    def randn(*a, **k):
+        t = o_randn(*a, generator=gn, **k)
+        normals.append(t.clone())
+        return t
+
+    def randn_like(x, **k):
+        t = o_randn(x.shape, generator=gn, dtype=x.dtype, device=x.device)
+        normals.append(t.clone())
+        return t
+
+    def uniform_(self, *a, **k):
+        t = o_uniform(self, *a, **k)
+        assert rows and rows[-1]["u"] is None, "a uniform_ draw outside a transition, or two in one"
+        rows[-1]["u"] = t.clone()
+        last[0] = t
+        return t
+
+    def gt(self, other):
+        if last[0] is not None and self is last[0]:
+            assert self.dtype == torch.float32
+            rows[-1]["p"] = np.float32(float(other))
+            last[0] = None
+        return o_gt(self, other)
+
+    hook = d.model.register_forward_hook(lambda *_: rows.append({"u": None, "p": np.float32(-1.0)}))
+    torch.manual_seed(seed)
+    torch.randn, torch.randn_like, torch.Tensor.uniform_, torch.Tensor.__gt__ = randn, randn_like, uniform_, gt
+    try:
+        out = fn()
+    finally:
+        torch.randn, torch.randn_like, torch.Tensor.uniform_, torch.Tensor.__gt__ = o_randn, o_like, o_uniform, o_gt
+        hook.remove()
+    assert last[0] is None and all((r["u"] is None) == (r["p"] < 0) for r in rows)
+    nan = torch.full_like(normals[0], float("nan"))
+    return out, torch.stack(normals), torch.stack([nan if r["u"] is None else r["u"] for r in rows]), \
+        np.array([r["p"] for r in rows], dtype=np.float32)
+
+
+def g23_ddnm_dropout():
+    """Stochastic DDNM (sd:1075-1094, 1210-1227) and denoise() (sd:1411-1427) on the G9_G10 network, pc and cond, p = 0.3:
+    per chain the output, the uniforms re-indexed to one slab per transition and the reference's own thresholds; the normals
+    per sampler (`T8_normals`, `ddim5_normals`: every chain of that sampler drew exactly these).  Every output has at least
+    60 % of its pixels strictly inside (0,1), so that the comparison is not one of clamped values."""
+    S, B, dim = 32, 2, 16
+    m = ref_unet(dim, 9)
+    pc = torch.tensor([[37.87, 38.02, 16.25, 16.0], [36.5, 36.7, 16.25, 16.0]])
+    cond = mixed_cond(B, S, 9)
+    out = {"pc": pc, "cond": cond, "p": np.float64(0.3)}
+    # name: (T, steps, schedule, is_ddnm_sampling, refine, method, seed of the uniforms)
+    chains = {"T8_linear": (8, None, "linear", True, False, "sample", 2301),
+              "T8_none_refine": (8, None, "none", True, True, "sample", 2302),
+              "ddim5_none": (1000, 5, "none", True, False, "sample", 2303),
+              "ddim5_linear_refine": (1000, 5, "linear", True, True, "sample", 2304),
+              "denoise_T8": (8, None, "none", False, False, "denoise", 2305),
+              "denoise_ddim5_refine": (1000, 5, "none", False, True, "denoise", 2306)}
+    shared = {}
+    for name, (T, steps, sched, ddnm, refine, method, seed) in chains.items():
+        d = sd.GaussianDiffusion(m, image_size=S, timesteps=T, sampling_timesteps=steps, loss_type="l1", objective="pred_x0",
+                                 beta_schedule="sigmoid", ddim_sampling_eta=1.0, is_ddnm_sampling=ddnm,
+                                 ddnm_sampling_dropout=0.3, ddnm_dropout_schedule=sched)
+        sampler = "T8" if steps is None else "ddim5"
+        img, nz, un, kp = recorded_draws(lambda: getattr(d, method)(param_cond=pc, img_cond=cond, disable_tqdm=True,
+                                                                    has_refine_step=refine), d, seed, 2300 if steps is None else 2350)
+        inside = float(((img > 0) & (img < 1)).float().mean())
+        print(f"  {name}: {int((kp >= 0).sum())} uniform draws over {len(kp)} rows, {inside:.2f} of the output inside (0,1)")
+        assert inside >= 0.6, "choose another seed: the chain's output is mostly clamped"
+        assert len(kp) == (T if steps is None else steps) + int(refine) and un.shape[0] == len(kp)
+        if sampler + "_normals" in shared:
+            assert torch.equal(shared[sampler + "_normals"], nz)
+        shared[sampler + "_normals"] = nz
+        out[name + "_out"], out[name + "_uniforms"], out[name + "_keep_p"] = img, un, kp
+    out.update(shared)
+    save("G23_ddnm_dropout", **out)
+
+
 def spec_fixture():
     import json
     spec = {"unet64": [[k, list(v.shape)] for k, v in sd.Unet(dim=64, param_cond_dim=4).state_dict().items()],
@@ -658,7 +745,8 @@ if __name__ == "__main__":
             ("g7", g7_unet_taps), ("g8", g8_unet_full), ("g9", g9_g10_sampler), ("g11", g11_maskunet),
             ("g12", g12_end_to_end), ("g12b", g12b_envelope), ("g13", g13_unet_128), ("g14", g14_chain_128),
             ("g15", g15_maskunet_128), ("g16", g16_unet_256), ("g17", g17_ddim_cond_gt1), ("g18", g18_refine_and_tester), ("g19", g19_chain1000_64),
-            ("g20", g20_ddim250_128), ("g21", g21_ddim250_256), ("g21b", g21b_ddim250_256), ("g22", g22_chain1000_128), ("spec", spec_fixture)]
+            ("g20", g20_ddim250_128), ("g21", g21_ddim250_256), ("g21b", g21b_ddim250_256), ("g22", g22_chain1000_128), ("g23", g23_ddnm_dropout),
+            ("spec", spec_fixture)]
     for name, fn in jobs:
         if not only or name in only:
             fn()
