@@ -21,6 +21,8 @@ hard-coded literals, generate_dataset.py:32-55):
                       two-pass run).  `generate_gt.py` afterwards finds every scene done and is the gather step only
   --resume synthetic[:SEED]   deterministic synthetic weights instead of ./successive_ddnm_diffusion_results/model-<resume>.pt
 Under `torchrun --nproc-per-node N` every rank takes a contiguous block of [-start, -stop) (no collectives).
+Two datasets generated from the same scenes (same --synthetic and --noise_seed, e.g. in two --dtype modes) are compared cloud
+by cloud and gt.log line by line by `compare_datasets.py A B -start I -stop J`.
 """
 import argparse
 import os

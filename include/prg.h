@@ -114,6 +114,19 @@ int prg_occlusion_filter(const float* depth, const uint8_t* mask, float* out, in
 int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double radius,
                        int32_t* counts, void* stream);
 
+/* Nearest point of the other cloud, for a batch of cloud pairs in the layout of prg_overlap_counts (pts (total,3) float64
+ * DEVICE, offsets (2*n_pairs+1) int64 DEVICE, offsets[0] may be > 0; max_cloud = largest cloud, < 2^31): d2 (total) float64
+ * and idx (total) int32, DEVICE, one entry per row of pts.  For row i of cloud 2p, d2[i] = the smallest squared distance to a
+ * row of cloud 2p+1 — prg_overlap_counts' expression, dx*dx + dy*dy + dz*dz in float64 summed left to right, so the number of
+ * d2 < r*r over a cloud is that call's count — and idx[i] = the lowest row of cloud 2p+1, counted from its first row, that
+ * attains it; the rows of cloud 2p+1 are answered the same way against cloud 2p by the same call.  Exact all-pairs search:
+ * a row starts at +inf / -1 and is replaced on a strict < only, visiting the other cloud in ascending row order, so an empty
+ * other cloud, a NaN row (query or candidate: it never wins) and distances that overflow leave +inf / -1.  Rows outside
+ * [offsets[0], offsets[2*n_pairs]) are neither read nor written, in pts, d2 or idx.  1 <= n_pairs <= 65535.
+ * Asynchronous on `stream`; reads no device data on the host; allocates nothing.                                            */
+int prg_nearest_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double* d2,
+                           int32_t* idx, void* stream);
+
 /* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
  * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
 size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);

@@ -44,6 +44,7 @@ PROTOTYPES = {
     "prg_apply_mask": (C.c_int, [_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
     "prg_occlusion_filter": (C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "prg_overlap_counts": (C.c_int, [_P, _P, _I, _L, C.c_double, _P, _P]),
+    "prg_nearest_ragged_f64": (C.c_int, [_P, _P, _I, _L, _P, _P, _P]),
     "prg_voxel_grid_workspace_bytes": (C.c_size_t, [_L, _I]),
     "prg_voxel_grid_ragged": (C.c_int, [_P, _P, _P, _I, _L, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
     "prg_merge_memory_f64": (C.c_int, [_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P]),

@@ -298,6 +298,73 @@ __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __rest
   if ((threadIdx.x & 63) == 0 && hits) atomicAdd(counts + 2 * pair + dir, (int32_t)__popcll(hits));
 }
 
+// ---- nearest point of the other cloud (dataset comparison) -----------------------------------------------------------
+// For every row of cloud A of a pair: the smallest squared distance to a row of cloud B (the overlap kernel's expression,
+// float64, left to right) and the lowest local row of B that attains it.  Exact all-pairs search, B streamed through LDS in
+// structure-of-arrays tiles like the overlap kernel, but with no early-out: the inner loop is the whole cost, and it is
+// bound by the float64 VALU — 3 subtractions, 3 products and 2 sums at 4 cycles each per wave, a compare and 3 selects on
+// top, some 44 cycles per (wave, candidate, query) — not by the LDS: a candidate is 3 ds_read_b64 at one address in every
+// lane (broadcast, 2 LDS cycles each).  With one query per thread the four SIMDs of a CU would ask for 24 LDS cycles per 44,
+// and 8-byte reads only reach their rate with about 4 waves per SIMD in flight; NN_Q = 2 queries per thread per LDS read
+// halves that (and the ds_read issue slots) for 12 more registers.  More queries per thread buy nothing once the VALU is
+// the bound, and would thin out the workgroups of a 10 k-row cloud.  (hipcc unrolls the candidate loop by four and reads two
+// candidates per ds_read_b128: 83 VGPRs, 5 waves per SIMD, which is plenty for a loop that waits on nothing but the VALU.)
+// The tile stays at the overlap kernel's 256 rows (6 KiB, one row per thread to stage): a tile is 256 * NN_Q * 44 = 22 k
+// cycles of arithmetic per wave against one global load and two barriers, and the next tile's rows are fetched into
+// registers before that arithmetic starts, so the load is hidden within one workgroup as well as across them.
+// Each query visits B in ascending row order and is replaced on a strict < only, so the blocking changes no bit: NaN
+// (query or candidate) and a distance that overflows to +inf never win, and such a row ends at +inf / -1.
+constexpr int NN_Q = 2;        // queries per thread
+constexpr int NN_TILE = 256;   // rows of the other cloud per LDS tile = threads per workgroup
+
+__global__ __launch_bounds__(NN_TILE) void nearest_ragged_kernel(const double* __restrict__ pts,
+                                                                 const int64_t* __restrict__ offs, double* __restrict__ d2_out,
+                                                                 int32_t* __restrict__ idx_out) {
+  __shared__ double tile[NN_TILE * 3];
+  const int pair = blockIdx.y, dir = blockIdx.z;
+  const int64_t a0 = offs[2 * pair + dir], a1 = offs[2 * pair + dir + 1];
+  const int64_t b0 = dir == 0 ? offs[2 * pair + 1] : offs[2 * pair], b1 = dir == 0 ? offs[2 * pair + 2] : offs[2 * pair + 1];
+  const int64_t slab = a0 + (int64_t)blockIdx.x * (NN_TILE * NN_Q);
+  if (slab >= a1) return;                                       // whole slab beyond this cloud (uniform exit)
+  double qx[NN_Q], qy[NN_Q], qz[NN_Q], best[NN_Q];
+  int32_t arg[NN_Q];
+#pragma unroll
+  for (int k = 0; k < NN_Q; ++k) {
+    const int64_t q = slab + k * NN_TILE + threadIdx.x;
+    qx[k] = qy[k] = qz[k] = 0;
+    if (q < a1) { qx[k] = pts[3 * q]; qy[k] = pts[3 * q + 1]; qz[k] = pts[3 * q + 2]; }
+    best[k] = __builtin_inf();
+    arg[k] = -1;
+  }
+  double nx = 0, ny = 0, nz = 0;                                // this thread's row of the next tile
+  if (b0 + threadIdx.x < b1) { nx = pts[3 * (b0 + threadIdx.x)]; ny = pts[3 * (b0 + threadIdx.x) + 1]; nz = pts[3 * (b0 + threadIdx.x) + 2]; }
+  for (int64_t t0 = b0; t0 < b1; t0 += NN_TILE) {
+    const int n = (int)min((int64_t)NN_TILE, b1 - t0);
+    __syncthreads();                                            // the previous tile has been read by every wave
+    tile[threadIdx.x] = nx;
+    tile[NN_TILE + threadIdx.x] = ny;
+    tile[2 * NN_TILE + threadIdx.x] = nz;
+    __syncthreads();
+    const int64_t r = t0 + NN_TILE + threadIdx.x;
+    if (r < b1) { nx = pts[3 * r]; ny = pts[3 * r + 1]; nz = pts[3 * r + 2]; }
+    const int32_t base = (int32_t)(t0 - b0);
+    for (int j = 0; j < n; ++j) {
+      const double bx = tile[j], by = tile[NN_TILE + j], bz = tile[2 * NN_TILE + j];
+#pragma unroll
+      for (int k = 0; k < NN_Q; ++k) {
+        const double dx = bx - qx[k], dy = by - qy[k], dz = bz - qz[k];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        if (d2 < best[k]) { best[k] = d2; arg[k] = base + j; }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NN_Q; ++k) {
+    const int64_t q = slab + k * NN_TILE + threadIdx.x;
+    if (q < a1) { d2_out[q] = best[k]; idx_out[q] = arg[k]; }
+  }
+}
+
 // ---- mask application + condition assembly (sd:2564-2570, sd:2579-2581) --------------------------
 __global__ void apply_mask_kernel(const float* __restrict__ prob, const float* __restrict__ depth,
                                   const uint8_t* __restrict__ hit, float thr, float* __restrict__ depth_out,
@@ -439,6 +506,18 @@ int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, i
   PRG_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * 2 * (size_t)n_pairs, (hipStream_t)stream));
   const dim3 grid((unsigned)((max_cloud + 255) / 256), (unsigned)n_pairs, 2);
   overlap_count_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pts, offsets, radius * radius, counts);
+  PRG_LAUNCH_CHECK();
+  return PRG_OK;
+}
+
+int prg_nearest_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double* d2,
+                           int32_t* idx, void* stream) {
+  PRG_CHECK(pts && offsets && d2 && idx, "prg_nearest_ragged_f64: null pointer");
+  PRG_CHECK(n_pairs > 0 && n_pairs <= 65535 && max_cloud > 0 && max_cloud < ((int64_t)1 << 31),
+            "prg_nearest_ragged_f64: bad arguments");
+  const int64_t slab = NN_TILE * NN_Q;
+  const dim3 grid((unsigned)((max_cloud + slab - 1) / slab), (unsigned)n_pairs, 2);
+  nearest_ragged_kernel<<<grid, NN_TILE, 0, (hipStream_t)stream>>>(pts, offsets, d2, idx);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }

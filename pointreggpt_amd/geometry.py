@@ -257,6 +257,27 @@ def voxel_grid_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     return out[:total], out_offsets, status
 
 
+def nearest_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_cloud: int):
+    """Nearest point of the other cloud for `n_pairs` cloud pairs in one launch (prg_nearest_ragged_f64): pts (total,3)
+    float64 and offsets (2*n_pairs+1) int64 as `prg_overlap_counts` takes them, both device tensors.  Returns (d2 (total)
+    float64, idx (total) int32) on the device: per row the smallest squared distance to a row of its pair's other cloud and
+    the lowest local row that attains it, bit for bit `postprocess.nearest`; +inf / -1 where there is none.  Entries of rows
+    outside every segment are +inf / -1 as allocated here (the kernel does not touch them).  Nothing synchronises."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    assert offsets.numel() == 2 * int(n_pairs) + 1
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total = pts.shape[0]
+    d2 = torch.full((total,), float("inf"), dtype=torch.float64, device=pts.device)
+    idx = torch.full((total,), -1, dtype=torch.int32, device=pts.device)
+    _lib.check(lib.prg_nearest_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), int(max_cloud), _lib.ptr(d2),
+                                          _lib.ptr(idx), _lib.stream_ptr()), "prg_nearest_ragged_f64")
+    return d2, idx
+
+
 def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
     """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
     float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as

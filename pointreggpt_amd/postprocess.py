@@ -210,6 +210,85 @@ def compute_overlap_ratio(pc1: np.ndarray, pc2: np.ndarray, voxel_size: float = 
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# nearest point of another cloud and the distance metrics between two clouds (dataset comparison, compare.py)
+# ------------------------------------------------------------------------------------------------------------------
+DISTANCE_THRESHOLDS = (1e-4, 1e-3, 0.0125, 0.0375)   # north-star tolerance, 1 mm, half the save voxel, generate_gt's radius
+
+
+def nearest(a: np.ndarray, b: np.ndarray, chunk: int = 1024) -> Tuple[np.ndarray, np.ndarray]:
+    """For every row of `a`: (d2, idx) = the smallest squared distance to a row of `b` and the lowest row of `b` that attains
+    it — the numpy specification of prg_nearest_ragged_f64, bit for bit.  d2 = dx*dx + dy*dy + dz*dz in float64 with the
+    three products written out and summed left to right (as `rigid_move` writes its products out: nothing here goes through
+    the BLAS or a pairwise sum).  A NaN never wins; a row with no finite candidate — `b` empty, NaN, or every distance
+    overflowing — ends at +inf / -1.  The query rows are processed `chunk` at a time to bound the (chunk, len(b)) temporaries."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    d2 = np.full(len(a), np.inf, dtype=np.float64)
+    idx = np.full(len(a), -1, dtype=np.int32)
+    if len(a) == 0 or len(b) == 0:
+        return d2, idx
+    bx, by, bz = b[None, :, 0], b[None, :, 1], b[None, :, 2]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(0, len(a), chunk):
+            q = a[s:s + chunk]
+            dx, dy, dz = bx - q[:, 0:1], by - q[:, 1:2], bz - q[:, 2:3]
+            d = dx * dx + dy * dy + dz * dz
+            d[np.isnan(d)] = np.inf
+            j = np.argmin(d, axis=1)                      # the first occurrence of the minimum = the lowest row
+            m = d[np.arange(len(q)), j]
+            d2[s:s + chunk] = m
+            idx[s:s + chunk] = np.where(np.isinf(m), -1, j)
+    return d2, idx
+
+
+def nearest_hip(pairs, device="cuda"):
+    """[(a (n,3), b (m,3)), ...] -> [(d2_ab, idx_ab, d2_ba, idx_ba), ...] as `nearest(a, b)` and `nearest(b, a)` define them:
+    all clouds uploaded once as one ragged float64 buffer, ONE prg_nearest_ragged_f64 launch for the whole list."""
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    if not pairs:
+        return []
+    clouds = [_f64(c) for pair in pairs for c in pair]
+    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    offs = np.zeros(len(clouds) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(sizes)
+    if sizes.max() == 0:
+        d2 = np.full(0, np.inf)
+        idx = np.full(0, -1, dtype=np.int32)
+    else:
+        pts, d_offs = G.upload_clouds(clouds, device, dtype=np.float64)
+        d2_d, idx_d = G.nearest_ragged(pts, d_offs, len(pairs), int(sizes.max()))
+        d2, idx = d2_d.cpu().numpy(), idx_d.cpu().numpy()
+    out = []
+    for p in range(len(pairs)):
+        o0, o1, o2 = offs[2 * p], offs[2 * p + 1], offs[2 * p + 2]
+        out.append((d2[o0:o1].copy(), idx[o0:o1].copy(), d2[o1:o2].copy(), idx[o1:o2].copy()))
+    return out
+
+
+def cloud_distance_metrics(d2_ab: np.ndarray, d2_ba: np.ndarray, thresholds=DISTANCE_THRESHOLDS) -> dict:
+    """Distances between two clouds from the squared nearest-neighbour distances of both directions (host float64, over
+    d = sqrt(d2)): n_a, n_b, chamfer = (mean d_ab + mean d_ba) / 2, hausdorff = the largest d, p50 / p95 / p99 of all the
+    distances of both directions together (np.percentile), within[t] = the share of those distances <= t.  If either cloud
+    is empty there is nothing to measure: every metric is NaN and empty = True."""
+    d_ab = np.sqrt(np.asarray(d2_ab, dtype=np.float64).reshape(-1))
+    d_ba = np.sqrt(np.asarray(d2_ba, dtype=np.float64).reshape(-1))
+    thresholds = tuple(float(t) for t in thresholds)
+    m = {"n_a": int(len(d_ab)), "n_b": int(len(d_ba)), "empty": len(d_ab) == 0 or len(d_ba) == 0}
+    if m["empty"]:
+        nan = float("nan")
+        m.update(chamfer=nan, hausdorff=nan, p50=nan, p95=nan, p99=nan, within={t: nan for t in thresholds})
+        return m
+    both = np.concatenate([d_ab, d_ba])
+    p50, p95, p99 = np.percentile(both, [50, 95, 99])
+    m.update(chamfer=float((d_ab.mean() + d_ba.mean()) / 2), hausdorff=float(both.max()), p50=float(p50), p95=float(p95),
+             p99=float(p99), within={t: float((both <= t).mean()) for t in thresholds})
+    return m
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # image side files (torchvision.utils.save_image / cv2.imwrite equivalents; real-data parity unpinned)
 # ------------------------------------------------------------------------------------------------------------------
 def save_image01(img01: np.ndarray, path: str) -> None:
