@@ -127,6 +127,37 @@ int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, i
 int prg_nearest_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double* d2,
                            int32_t* idx, void* stream);
 
+/* All pairs within a radius, as a ragged list: the ground-truth correspondences of a batch of cloud pairs, in the layout of
+ * prg_overlap_counts (pts (total,3) float64 DEVICE, offsets (2*n_pairs+1) int64 DEVICE, offsets[0] may be > 0).  Pair p is the
+ * QUERY cloud A = segment 2p against the CANDIDATE cloud B = segment 2p+1 (one direction: the list of B against A is this one
+ * with its columns swapped).  Row i of A and row j of B correspond iff dx*dx + dy*dy + dz*dz < radius*radius with dx = b.x - a.x
+ * ... in float64, products written out, summed left to right, strict < — the expression of prg_overlap_counts and
+ * prg_nearest_ragged_f64, so on one buffer a row of A has matches iff that call's d2 < radius*radius, and the rows with matches
+ * are the first call's count.  Exact all-pairs search; a NaN row never matches; an empty A or B yields nothing.
+ * The size of the list is data-dependent, hence two calls; both are asynchronous on `stream`, read no device data on the host
+ * and allocate nothing.  1 <= n_pairs <= 65535, 0 < max_cloud < 2^31 (largest cloud), 0 <= total < 2^31, radius finite and > 0;
+ * anything else, a null pointer or a workspace that is too small fails with PRG_E_INVALID before any device call.
+ *
+ * prg_radius_pairs_workspace_bytes: bytes of device workspace pass 1 needs for `total` rows (positive, non-decreasing).
+ * Host-only arithmetic: no device call, usable without a GPU; returns the size, not a PRG_E_* code.                          */
+size_t prg_radius_pairs_workspace_bytes(int64_t total);
+
+/* Pass 1: per query row the number of matches, then an exclusive scan over buffer rows.  row_start (total+1) int64 DEVICE,
+ * written in full: row_start[r] = number of list rows produced by query rows (rows of the even segments) with buffer row < r;
+ * rows of odd segments and rows outside [offsets[0], offsets[2*n_pairs]) contribute 0.  row_start[total] is the size of the
+ * list, and row_start[offsets[2p]] the first list row of pair p.  workspace: >= prg_radius_pairs_workspace_bytes(total) bytes,
+ * DEVICE, 8-byte aligned; contents are scratch.  pts is not written.                                                          */
+int prg_radius_count_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t total, int64_t max_cloud,
+                                double radius, int64_t* row_start, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Pass 2, with pass 1's row_start and the same pts / offsets / n_pairs / max_cloud / radius: corr (capacity,2) int32 DEVICE;
+ * the matches of query row r occupy rows [row_start[r], row_start[r+1]) as (i, j) = (row of A counted from A's first row, row
+ * of B counted from B's first row), j ascending — so the list is ordered by pair, then i, then j, the same on every run.  A list
+ * row whose position is >= capacity is not written (nothing past the buffer, ever): the caller compares row_start[total] with
+ * capacity.  capacity == 0 writes nothing (corr may then be NULL).  Rows of pts outside the segments are not read.           */
+int prg_radius_fill_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double radius,
+                               const int64_t* row_start, int64_t capacity, int32_t* corr, void* stream);
+
 /* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
  * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
 size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);

@@ -391,15 +391,9 @@ class Generator:
     def _finish_pairs_write(self, pool, finished, idxs, sdirs, marker_index):
         """Host side: ONE copy of the finished clouds, the PLY files as write-only jobs, every scene's gt.log written before this
         returns.  -> the batch's resume marker job (not yet submitted)."""
-        fin, fin_offs, st_save, st_gt, counts, down_offs = finished
+        fin = finished[0]
         B = len(idxs)
-        small = torch.cat([fin_offs, down_offs, st_save.to(torch.int64), st_gt.to(torch.int64), counts.view(-1).to(torch.int64)])
-        small = small.cpu().numpy()
-        offs, d_offs = small[:2 * B + 1], small[2 * B + 1:4 * B + 2]
-        st_save, st_gt, cnt = small[4 * B + 2:6 * B + 2], small[6 * B + 2:8 * B + 2], small[8 * B + 2:].reshape(B, 2)
-        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in (0, 1)]
-        self.G.check_voxel_status(st_save, names)
-        self.G.check_voxel_status(st_gt, names)
+        offs, d_offs, cnt = self._finish_pairs_words(finished, idxs)
         pts = fin[:max(int(offs[-1]), 0)].cpu().numpy()
         marker = None
         for j, sdir in enumerate(sdirs):
@@ -410,18 +404,43 @@ class Generator:
                     marker = job
                 else:
                     job()
-        sizes, d_sizes = np.diff(offs), np.diff(d_offs)
         for j, (idx, sdir) in enumerate(zip(idxs, sdirs)):
             lines = []
-            if sizes[2 * j] >= self.GT_MIN_POINTS and sizes[2 * j + 1] >= self.GT_MIN_POINTS:
-                with np.errstate(invalid="ignore", divide="ignore"):
-                    o_s = float(np.float64(cnt[j, 0]) / np.float64(d_sizes[2 * j]))
-                    o_t = float(np.float64(cnt[j, 1]) / np.float64(d_sizes[2 * j + 1]))
-                if not (np.isnan(o_s) or np.isnan(o_t) or (o_s < 0.1 and o_t < 0.1)):
-                    lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), 0, 1, o_s, o_t))
+            ratios, _why = self._pair_ratios(offs, d_offs, cnt, j)
+            if ratios is not None:
+                lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), 0, 1, ratios[0], ratios[1]))
             with open(sdir / "gt.log", "w") as f:
                 f.writelines(lines)
         return marker
+
+    def _finish_pairs_words(self, finished, idxs):
+        """The small words of a finished batch in ONE copy, voxel statuses checked: -> (offsets (2B+1), down-sampled offsets (2B+1),
+        overlap counts (B,2)) on the host."""
+        _fin, fin_offs, st_save, st_gt, counts, down_offs = finished
+        B = len(idxs)
+        small = torch.cat([fin_offs, down_offs, st_save.to(torch.int64), st_gt.to(torch.int64), counts.view(-1).to(torch.int64)])
+        small = small.cpu().numpy()
+        offs, d_offs = small[:2 * B + 1], small[2 * B + 1:4 * B + 2]
+        st_save, st_gt, cnt = small[4 * B + 2:6 * B + 2], small[6 * B + 2:8 * B + 2], small[8 * B + 2:].reshape(B, 2)
+        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in (0, 1)]
+        self.G.check_voxel_status(st_save, names)
+        self.G.check_voxel_status(st_gt, names)
+        return offs, d_offs, cnt
+
+    @classmethod
+    def _pair_ratios(cls, offs, d_offs, cnt, j):
+        """generate_gt's filter on pair j of a finished batch: -> ((overlap of the source, of the target), None) when the pair gets
+        a gt.log line, (None, reason) when it does not."""
+        if offs[2 * j + 1] - offs[2 * j] < cls.GT_MIN_POINTS or offs[2 * j + 2] - offs[2 * j + 1] < cls.GT_MIN_POINTS:
+            return None, "a cloud has fewer than {} points".format(cls.GT_MIN_POINTS)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            o_s = float(np.float64(cnt[j, 0]) / np.float64(d_offs[2 * j + 1] - d_offs[2 * j]))
+            o_t = float(np.float64(cnt[j, 1]) / np.float64(d_offs[2 * j + 2] - d_offs[2 * j + 1]))
+        if np.isnan(o_s) or np.isnan(o_t):
+            return None, "an overlap ratio is NaN"
+        if o_s < 0.1 and o_t < 0.1:
+            return None, "both overlap ratios are below 0.1"
+        return (o_s, o_t), None
 
 
 def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int, num_samples: int,

@@ -278,6 +278,35 @@ def nearest_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_c
     return d2, idx
 
 
+def radius_pairs_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_cloud: int, radius: float):
+    """All pairs within `radius` for `n_pairs` cloud pairs (prg_radius_count_ragged_f64 / prg_radius_fill_ragged_f64): pts
+    (total,3) float64 and offsets (2*n_pairs+1) int64 as `prg_overlap_counts` takes them, both device tensors; pair p queries
+    segment 2p against segment 2p+1.  Returns (corr (K,2) int32, pair_offsets (n_pairs+1) int64) on the device: pair p's
+    correspondences are corr[pair_offsets[p]:pair_offsets[p+1]], rows (i, j) local to the two clouds, ordered by i then j, bit for
+    bit `postprocess.radius_pairs`.  Count, ONE 8-byte read-back (the size of the list — the only synchronisation), an
+    allocation of exactly K rows, fill."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    assert offsets.numel() == 2 * int(n_pairs) + 1
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total = pts.shape[0]
+    row_start = torch.empty((total + 1,), dtype=torch.int64, device=pts.device)
+    ws = _voxel_workspace(pts.device, int(lib.prg_radius_pairs_workspace_bytes(total)))
+    _lib.check(lib.prg_radius_count_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), total, int(max_cloud),
+                                               float(radius), _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "prg_radius_count_ragged_f64")
+    K = int(row_start[total].item())
+    corr = torch.empty((K, 2), dtype=torch.int32, device=pts.device)
+    if K:
+        _lib.check(lib.prg_radius_fill_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), int(max_cloud), float(radius),
+                                                  _lib.ptr(row_start), K, _lib.ptr(corr), _lib.stream_ptr()),
+                   "prg_radius_fill_ragged_f64")
+    return corr, row_start[offsets[0::2]]
+
+
 def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
     """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
     float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as

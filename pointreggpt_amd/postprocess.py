@@ -268,6 +268,48 @@ def nearest_hip(pairs, device="cuda"):
     return out
 
 
+def radius_pairs(a: np.ndarray, b: np.ndarray, radius: float, chunk: int = 1024) -> np.ndarray:
+    """Every (i, j) with row j of `b` strictly within `radius` of row i of `a`, as a (K,2) int32 array ordered by i, then j — the
+    numpy specification of prg_radius_count_ragged_f64 / prg_radius_fill_ragged_f64, bit for bit.  The test is `nearest`'s
+    expression: dx*dx + dy*dy + dz*dz < radius*radius in float64 with dx = b.x - a.x, the products written out and summed left to
+    right, so a row of `a` has matches iff `nearest(a, b)` gives it d2 < radius*radius, and its nearest row is among them.  A NaN
+    row never matches; an empty `a` or `b` gives shape (0,2).  The query rows are processed `chunk` at a time, which bounds the
+    (chunk, len(b)) temporaries and changes nothing else."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    r2 = np.float64(radius) * np.float64(radius)
+    out = [np.zeros((0, 2), dtype=np.int32)]
+    if len(a) and len(b):
+        bx, by, bz = b[None, :, 0], b[None, :, 1], b[None, :, 2]
+        with np.errstate(over="ignore", invalid="ignore"):
+            for s in range(0, len(a), chunk):
+                q = a[s:s + chunk]
+                dx, dy, dz = bx - q[:, 0:1], by - q[:, 1:2], bz - q[:, 2:3]
+                i, j = np.nonzero(dx * dx + dy * dy + dz * dz < r2)      # row-major: i ascending, then j
+                out.append(np.stack([i + s, j], axis=1).astype(np.int32))
+    return np.concatenate(out, axis=0)
+
+
+def radius_pairs_hip(pairs, radius: float, device="cuda"):
+    """[(a (n,3), b (m,3)), ...] -> [corr_p (K_p,2) int32, ...] as `radius_pairs(a, b, radius)` defines them, for clouds that
+    are on the host (a loader's collate step on a batch of PLY pairs): all clouds uploaded once as one ragged float64 buffer,
+    ONE count / fill (`geometry.radius_pairs_ragged`) for the whole list, one copy back."""
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    if not pairs:
+        return []
+    clouds = [_f64(c) for pair in pairs for c in pair]
+    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    if sizes.max() == 0:
+        return [np.zeros((0, 2), dtype=np.int32) for _ in pairs]
+    pts, d_offs = G.upload_clouds(clouds, device, dtype=np.float64)
+    corr_d, po_d = G.radius_pairs_ragged(pts, d_offs, len(pairs), int(sizes.max()), radius)
+    corr, po = corr_d.cpu().numpy(), po_d.cpu().numpy()
+    return [corr[po[p]:po[p + 1]].copy() for p in range(len(pairs))]
+
+
 def cloud_distance_metrics(d2_ab: np.ndarray, d2_ba: np.ndarray, thresholds=DISTANCE_THRESHOLDS) -> dict:
     """Distances between two clouds from the squared nearest-neighbour distances of both directions (host float64, over
     d = sqrt(d2)): n_a, n_b, chamfer = (mean d_ab + mean d_ba) / 2, hausdorff = the largest d, p50 / p95 / p99 of all the

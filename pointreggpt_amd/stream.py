@@ -1,0 +1,134 @@
+"""`PairStream`: finished cloud pairs straight from the GPU, with their ground-truth correspondences, and no file in between.
+
+A registration network (Predator, CoFiNet, GeoTransformer) trains at batch size 1, a few iterations per second; one MI355X
+generates more pairs than that.  Instead of ~13 files per scene on disk and a KD-tree per item in the loader
+(`get_correspondences` of the example loaders), iterate a `PairStream`: it runs `Generator.generate`'s device sequence for
+`num_samples = 1` batch by batch and yields, per surviving scene, the two finished clouds — the rows `generate(gt_log=True)`
+writes to `sample-000000.cloud.ply` / `sample-000001.cloud.ply` — the two overlap ratios behind the scene's `gt.log` line, and
+`corr`, every (row of src, row of tgt) within `matching_radius` (`geometry.radius_pairs_ragged`; INTEGRATION.md says how the
+loaders' lists map onto it).
+
+    stream = PairStream(generator, mask_unet, start=0, stop=100000, noise_seed=7, matching_radius=0.0375, to="torch")
+    for item in stream:
+        item["scene"], item["src"], item["tgt"], item["overlap_src"], item["overlap_tgt"], item["corr"]
+
+Reproducibility: a scene's item has the bits of the file path (`generate(start, stop, 1, gt_log=True, noise_seed=...)`) for the
+same `batch_size`, `start` and seeds.  `noise_seed` is required: besides the diffusion noise it seeds, with real-data input, the
+pose stream per (job seed, first scene of the batch) exactly as `generate(noise_seed=...)` does — the batches, and so the
+poses, are the same only for the same `start` and `batch_size`.  There is no unseeded mode here.
+
+The stream runs on the calling thread's current HIP stream.  It uses no writer pool and no lanes, writes no file and creates
+nothing under the generator's `samples_folder` (the folder itself is `Generator.__init__`'s doing).
+"""
+from __future__ import annotations
+
+import pickle
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import postprocess as PP
+from . import synthetic
+from .sharding import num_to_groups
+
+
+class PairStream:
+    def __init__(self, generator, depth_correction, *, start: int, stop: int, noise_seed: int,
+                 matching_radius: Optional[float] = None, mask_threshold: float = 0.99, has_refine_step: bool = False,
+                 save_voxel_size: float = 0.025, to: str = "numpy"):
+        if to not in ("numpy", "torch"):
+            raise ValueError("to must be 'numpy' or 'torch'")
+        if generator.device.type == "cpu":
+            raise ValueError("PairStream needs the clouds on a HIP device (Generator(device='cuda'))")
+        if noise_seed is None:
+            raise ValueError("PairStream needs a noise_seed (it also seeds the real-data pose stream per batch)")
+        if matching_radius is not None and not (np.isfinite(matching_radius) and matching_radius > 0):
+            raise ValueError("matching_radius must be finite and > 0 (or None for no correspondences)")
+        self.generator = generator
+        self.depth_correction = depth_correction
+        self.start, self.stop = int(start), int(stop)
+        self.noise_seed = int(noise_seed)
+        self.matching_radius = None if matching_radius is None else float(matching_radius)
+        self.mask_threshold = mask_threshold
+        self.has_refine_step = has_refine_step
+        self.save_voxel_size = save_voxel_size
+        self.to = to
+        self.skipped: List[Tuple[int, str]] = []     # (scene, reason) of the scenes generate_gt's filter drops
+
+    # -- the device sequence of one batch: Generator._lane for num_samples = 1 and gt_log=True, minus every file ---------------
+    @torch.no_grad()
+    def _batch(self, idxs, info_train):
+        gen = self.generator
+        G_, S, dev = gen.G, gen.image_size, gen.device
+        batch = len(idxs)
+        K = np.zeros((batch, 3, 3), dtype=np.float32)
+        depth0 = np.zeros((batch, 1, S, S), dtype=np.float32)
+        for j, idx in enumerate(idxs):
+            depth0[j, 0], K[j] = gen._scene_inputs(idx, info_train, None)
+        K_dev = torch.from_numpy(K).to(dev)
+        frames = G_.point_clouds(torch.from_numpy(depth0).to(dev), K_dev, None)
+        memory = [PP.crop_aabb(f.astype(np.float32)).astype(np.float32) for f in frames]      # the scene "memory" (sd:2484-2490)
+        param_cond = G_.param_vector(K_dev)
+        mem_pts, mem_offs = G_.upload_clouds(memory, dev)
+        pose = gen._poses(idxs, 0, self.noise_seed)
+        pose_dev = torch.from_numpy(pose).to(dev)
+        rpj, hit = G_.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
+        prob = self.depth_correction(rpj)
+        _rpj_c, _hit_c, cond = G_.apply_mask(prob, rpj, hit, self.mask_threshold)
+        seeds = [synthetic.noise_seed(self.noise_seed, i, 0) for i in idxs]
+        images = gen.model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds, has_refine_step=self.has_refine_step)
+        prob2 = self.depth_correction(images)
+        images, _, _ = G_.apply_mask(prob2, images, None, self.mask_threshold, want_cond=False)
+        xyz, valid = G_.unproject_f64(images, K_dev, pose_dev)
+        return gen._finish_pairs_launch(mem_pts, mem_offs, [len(m) for m in memory], [(xyz, valid)], pose, self.save_voxel_size)
+
+    def __iter__(self):
+        gen = self.generator
+        self.skipped = []
+        info_train = None
+        if gen.synthetic_seed is None:
+            with open("./dataset/indoor/metadata/train_info.pkl", "rb") as f:
+                info_train = pickle.load(f)
+        first = self.start
+        for batch in num_to_groups(self.stop - self.start, gen.batch_size):
+            idxs = list(range(first, first + batch))
+            first += batch
+            finished = self._batch(idxs, info_train)
+            fin = finished[0]
+            offs, d_offs, cnt = gen._finish_pairs_words(finished, idxs)          # the one copy of the small words
+            keep, ratios = [], []
+            for j, idx in enumerate(idxs):
+                r, why = gen._pair_ratios(offs, d_offs, cnt, j)
+                if r is None:
+                    self.skipped.append((idx, why))
+                else:
+                    keep.append(j)
+                    ratios.append(r)
+            if not keep:
+                continue
+            # one ragged buffer of the surviving pairs: segments (2k, 2k+1) = (source frame, generated view) of keep[k]
+            sizes = np.array([offs[2 * j + k + 1] - offs[2 * j + k] for j in keep for k in (0, 1)], dtype=np.int64)
+            k_offs = np.zeros(len(sizes) + 1, dtype=np.int64)
+            k_offs[1:] = np.cumsum(sizes)
+            if len(keep) == batch:
+                pts = fin[int(offs[0]):int(offs[-1])]
+            else:
+                pts = torch.cat([fin[int(offs[2 * j]):int(offs[2 * j + 2])] for j in keep], dim=0)
+            corr = c_offs = None
+            if self.matching_radius is not None:
+                corr, c_offs = gen.G.radius_pairs_ragged(pts.contiguous(), torch.from_numpy(k_offs).to(pts.device), len(keep),
+                                                         int(sizes.max()), self.matching_radius)
+                c_offs = c_offs.cpu().numpy()
+            if self.to == "numpy":
+                pts = pts.cpu().numpy()
+                corr = None if corr is None else corr.cpu().numpy()
+                own = np.copy
+            else:
+                own = torch.clone
+            for k, j in enumerate(keep):
+                item = dict(scene=idxs[j], src=own(pts[k_offs[2 * k]:k_offs[2 * k + 1]]), tgt=own(pts[k_offs[2 * k + 1]:k_offs[2 * k + 2]]),
+                            overlap_src=ratios[k][0], overlap_tgt=ratios[k][1])
+                if corr is not None:
+                    item["corr"] = own(corr[c_offs[k]:c_offs[k + 1]])
+                yield item
