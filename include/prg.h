@@ -288,6 +288,27 @@ int prg_debug_conv(const float* x, const float* w, const float* bias, float* out
  * wave-specialised kernel when Cout % 128 == 0; round 5).  out: (B, Cout, 2H, 2W) float32. */
 int prg_debug_upsample_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
                             int dtype, void* stream);
+/* Kernel unit-test hook: an attention core alone on a given to_qkv output.  qkv (B, 384, N) float32 DEVICE in the reference's
+ * layout (q | k | v, each 4 heads x 32, head-major), out (B, 128, N) float32 DEVICE; dtype PRG_F32, PRG_BF16 or PRG_F16X3 is the
+ * storage the values are converted to first.  linear = 1: the LinearAttention core (sd:755-768; kernel = 0, not PRG_F16X3).
+ * linear = 0: the bottleneck core (sd:789-795); kernel = 0 the generic kernel (PRG_F16X3: the float32 one, as the library would
+ * run), kernel = 1 the matrix-pipe kernel of the dtype (bf16 MFMA / split-f16 MFMA).  A token count the chosen kernel does not
+ * take, PRG_F32 with kernel = 1 and every other bad argument fail with PRG_E_INVALID before any device call.  Synchronises.   */
+int prg_debug_attention_core(const float* qkv, float* out, int B, int N, int dtype, int linear, int kernel, void* stream);
+/* Kernel unit-test hook: channel LayerNorm with gain (sd:619-628) plus an optional residual on pixel-major rows.  x, residual
+ * (or NULL), out (M, C) float32 DEVICE, g (C) float32 HOST; dtype PRG_F32 or PRG_BF16.  C a multiple of 4 (PRG_F32) or 8
+ * (PRG_BF16) and of at most 256 such vectors.  Bad arguments fail with PRG_E_INVALID before any device call.  Synchronises.   */
+int prg_debug_layernorm(const float* x, const float* g, const float* residual, float* out, int64_t M, int C, int dtype, void* stream);
+/* Kernel unit-test hook: out = x + LN_out_g(to_out(LinearAttention(to_qkv(LN_norm_g(x))))) (sd:583-589, 631-639, 737-769) through
+ * the fused kernels, on the weights packed as a handle packs them.  x, out (B, C, N) float32 DEVICE; norm_g (C), w_qkv (384, C),
+ * w_out (C, 128), b_out (C), out_g (C) float32 HOST, as the state dict holds them.  dtype PRG_BF16: the bf16 kernels (C = 64, 128,
+ * 256); shift_mode 1 = the static softmax shifts (PRG_E_INVALID when their bound does not hold for these weights), 0 = measured
+ * maxima, -1 = what a handle would choose; psum 1 / 0 = the row sums of p on the matrix pipe or not, -1 = the library's choice.
+ * dtype PRG_F16X3: the split-f16 kernels (C = 64, 128; N a multiple of 64); shift_mode and psum must be -1.  *used_static (may be
+ * NULL) receives 1 when the static shifts were used.  Bad arguments fail with PRG_E_INVALID before any device call.  Synchronises. */
+int prg_debug_linear_attention_block(const float* x, const float* norm_g, const float* w_qkv, const float* w_out, const float* b_out,
+                                     const float* out_g, float* out, int B, int C, int N, int dtype, int shift_mode, int psum,
+                                     int* used_static, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Sampler: GaussianDiffusion.sample / p_sample_loop / ddim_sample (sd:1283-1409), DDNM replacement included

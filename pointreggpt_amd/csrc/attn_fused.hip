@@ -857,7 +857,7 @@ constexpr bool kPsumDefault = C >= 128;   // (measured: C = 64 58 against 70 us 
 
 template <int C>
 int launch_c(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const float* bias, const float* out_g, bf16_t* out,
-             float* ws, int B, int N, const float* kshift, hipStream_t s) {
+             float* ws, int B, int N, const float* kshift, hipStream_t s, int psum_override) {
   static DeviceOnce attr;   // one-time opt-in; atomic: lanes launch from several host threads (idempotent call)
   if (!attr.done()) {
     int rc;
@@ -882,7 +882,8 @@ int launch_c(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const floa
   }
   // PRG_LA_PSUM: sum_n p on the matrix pipe: -1 (default) where measured faster, 0 never, 1 always
   static const int psum_env = env_int("PRG_LA_PSUM", -1);
-  const bool psum = psum_env > 0 || (psum_env < 0 && kPsumDefault<C>);
+  const int psum_sel = psum_override >= 0 ? psum_override : psum_env;
+  const bool psum = psum_sel > 0 || (psum_sel < 0 && kPsumDefault<C>);
 #define PRG_LA_CTX_GO(PS, KS) la_ctx_fused_kernel<C, PS, KS><<<grid, 256, lds_kmax<C>(), s>>>(x, wqkv, pmax, ctxp, sump, N, nslab)
   if (kshift) { if (psum) PRG_LA_CTX_GO(true, true); else PRG_LA_CTX_GO(false, true); }
   else { if (psum) PRG_LA_CTX_GO(true, false); else PRG_LA_CTX_GO(false, false); }
@@ -965,12 +966,12 @@ size_t linattn_fused_ws_floats(int B, int N) {
 // x, out: (B, N, C) bf16.  wqkv: [384][C] with the PreNorm gain folded in (q | k | v rows, head-major); wout: [C][128].
 int launch_linear_attention_fused(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const float* bias,
                                   const float* out_g, bf16_t* out, float* ws, int B, int N, int C, const float* kshift,
-                                  hipStream_t s) {
+                                  hipStream_t s, int psum_override) {
   PRG_CHECK(linattn_fused_supported(C), "fused linear attention: unsupported width");
   PRG_CHECK(la_slabs(N) <= 4096, "fused linear attention: too many slabs");
-  if (C == 64) return launch_c<64>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s);
-  if (C == 256) return launch_c<256>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s);
-  return launch_c<128>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s);
+  if (C == 64) return launch_c<64>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);
+  if (C == 256) return launch_c<256>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);
+  return launch_c<128>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);
 }
 
 }  // namespace prg

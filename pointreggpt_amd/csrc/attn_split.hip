@@ -550,6 +550,10 @@ __global__ __launch_bounds__(256) void full_attn_split_kernel(const float* __res
         for (int j = 0; j < 8; ++j) {
           _Float16 sh_, sl_;
           split1(vv[j], sh_, sl_);
+          // an infinite v: hi = Inf leaves lo = Inf - Inf = NaN, and Inf times an exact-zero lo half of p is NaN as well.  Carried
+          // by the lo half alone it meets only p's hi half: the column comes out infinite, as the reference's, for as long as that
+          // half is not zero — p >= 2^-25, i.e. a key within ~17 nats of its row's maximum; below that f16 has no p and Inf * 0 = NaN
+          if (__builtin_isinf(vv[j])) { sl_ = sh_; sh_ = (_Float16)0.0f; }
           Vh[(u * 8 + j) * LDV + pos] = sh_;
           Vl[(u * 8 + j) * LDV + pos] = sl_;
         }

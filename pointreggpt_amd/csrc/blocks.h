@@ -65,10 +65,10 @@ int launch_full_attention_split(const float* qkv, float* out, int B, int N, hipS
 bool linattn_fused_supported(int C);
 size_t linattn_fused_ws_floats(int B, int N);
 // kshift: [128 + 4] static softmax shifts — a bound on |k| per column, then a bound on |q| per head (see unet.hip) — or
-// null = measure the maxima.
+// null = measure the maxima.  psum_override: sum_n p on the matrix pipe: 1 always, 0 never, -1 the library's choice.
 int launch_linear_attention_fused(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const float* bias,
                                   const float* out_g, bf16_t* out, float* ws, int B, int N, int C, const float* kshift,
-                                  hipStream_t s);
+                                  hipStream_t s, int psum_override = -1);
 
 // ResnetBlock tail with the 1x1 res_conv folded in (attn_fused.hip), bf16 path.  wres: [Cout][C0+C1] bf16.
 bool resblock_tail_fused_supported(int C0, int C1, int Cout);

@@ -1,5 +1,7 @@
 // unet_debug.hip — the prg_debug_* entries (prg.h): single convolutions and a ResnetBlock's Block pair through the library's own
-// packer (pack_conv_host: what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own.
+// packer (pack_conv_host: what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own;
+// the attention cores, the channel LayerNorm and the fused linear-attention blocks (pack_fused_attention / pack_split_attention)
+// through the launch functions the forward calls, with the kernel chosen by argument.
 #include <type_traits>
 
 #include "unet_layout.h"
@@ -70,9 +72,147 @@ int debug_conv(const float* x, const float* w, const float* bias, float* out, in
   return debug_conv_t<bf16_t>(x, w, bias, out, B, Cin, Cout, H, W, dtype, K, stride, s, ups);
 }
 
+// the attention cores on a qkv tensor of their own: T is the storage type, `mp` selects the matrix-pipe kernel of `dtype`
+template <typename T>
+int debug_attention_core_t(const float* qkv, float* out, int B, int N, int linear, int mp, hipStream_t s) {
+  const char* nomem = "prg_debug_attention_core: hipMalloc failed";
+  DeviceBuffers own;
+  T* d_qkv = own.alloc<T>((size_t)B * N * 3 * kHidden, nomem);
+  T* d_out = own.alloc<T>((size_t)B * N * kHidden, nomem);
+  float* ws = linear ? own.alloc<float>(linattn_ws_floats(B, N), nomem) : nullptr;
+  if (own.rc) return own.rc;
+  int rc = launch_nchw_f32_to_nhwc<T>(qkv, d_qkv, B, N, 3 * kHidden, s);
+  if (rc == PRG_OK) {
+    if (linear) {
+      rc = launch_linear_attention<T>(d_qkv, d_out, ws, B, N, s);
+    } else if (!mp) {
+      rc = launch_full_attention<T>(d_qkv, d_out, B, N, s);
+    } else if constexpr (std::is_same<T, float>::value) {
+      rc = launch_full_attention_split(d_qkv, d_out, B, N, s);
+    } else {
+      rc = launch_full_attention_mfma(d_qkv, d_out, B, N, s);
+    }
+  }
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(d_out, out, B, N, kHidden, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_attention_core: stream synchronise failed");
+  return rc;
+}
+
+// (M, C) float32 -> T and back without a change of layout: the NCHW <-> NHWC kernels with one channel are plain conversions
+template <typename T>
+int debug_layernorm_t(const float* x, const float* g, const float* residual, float* out, int64_t M, int C, hipStream_t s) {
+  const char* nomem = "prg_debug_layernorm: hipMalloc failed";
+  const size_t n = (size_t)M * C;
+  DeviceBuffers own;
+  T* d_x = own.alloc<T>(n, nomem);
+  T* d_r = residual ? own.alloc<T>(n, nomem) : nullptr;
+  T* d_o = own.alloc<T>(n, nomem);
+  const float* d_g = own.upload(g, (size_t)C, nomem);
+  if (own.rc) return own.rc;
+  int rc = launch_nchw_f32_to_nhwc<T>(x, d_x, 1, (int)n, 1, s);
+  if (rc == PRG_OK && residual) rc = launch_nchw_f32_to_nhwc<T>(residual, d_r, 1, (int)n, 1, s);
+  if (rc == PRG_OK) rc = launch_layernorm<T>(d_x, d_g, d_r, d_o, M, C, s);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(d_o, out, 1, (int)n, 1, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_layernorm: stream synchronise failed");
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The linear-attention core and the three bottleneck attention cores on a given qkv (prg.h).
+int prg_debug_attention_core(const float* qkv, float* out, int B, int N, int dtype, int linear, int kernel, void* stream) {
+  PRG_CHECK(qkv && out, "prg_debug_attention_core: null pointer");
+  PRG_CHECK(B > 0 && B <= 65535 && N > 0 && (int64_t)B * N <= (int64_t)1 << 22, "prg_debug_attention_core: bad shape");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16 || dtype == PRG_F16X3, "prg_debug_attention_core: bad dtype");
+  PRG_CHECK((linear == 0 || linear == 1) && (kernel == 0 || kernel == 1), "prg_debug_attention_core: linear and kernel are 0 or 1");
+  PRG_CHECK(!linear || (dtype != PRG_F16X3 && kernel == 0),
+            "prg_debug_attention_core: the linear core has one kernel, in PRG_F32 and PRG_BF16");
+  if (kernel) {
+    PRG_CHECK(dtype != PRG_F32, "prg_debug_attention_core: PRG_F32 has no matrix-pipe kernel");
+    PRG_CHECK(dtype == PRG_BF16 ? full_attention_mfma_supported(N) : full_attention_split_supported(N),
+              "prg_debug_attention_core: the matrix-pipe kernel does not take this token count");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == PRG_BF16) return debug_attention_core_t<bf16_t>(qkv, out, B, N, linear, kernel, s);
+  return debug_attention_core_t<float>(qkv, out, B, N, linear, kernel, s);
+}
+
+// Residual(PreNorm(LinearAttention)) through the fused bf16 kernels or the split-f16 ones, on what a handle would pack (prg.h).
+int prg_debug_linear_attention_block(const float* x, const float* norm_g, const float* w_qkv, const float* w_out, const float* b_out,
+                                     const float* out_g, float* out, int B, int C, int N, int dtype, int shift_mode, int psum,
+                                     int* used_static, void* stream) {
+  PRG_CHECK(x && norm_g && w_qkv && w_out && b_out && out_g && out, "prg_debug_linear_attention_block: null pointer");
+  PRG_CHECK(dtype == PRG_BF16 || dtype == PRG_F16X3, "prg_debug_linear_attention_block: bad dtype");
+  // (N <= 2^21: at most 4096 slabs of eight 64-pixel tiles, the limit of launch_linear_attention_fused)
+  PRG_CHECK(B > 0 && B <= 65535 && N > 0 && N <= 1 << 21 && C > 0 && (int64_t)B * N <= (int64_t)1 << 22,
+            "prg_debug_linear_attention_block: bad shape");
+  PRG_CHECK(dtype == PRG_BF16 ? linattn_fused_supported(C) : linattn_split_supported(C, N),
+            "prg_debug_linear_attention_block: the kernels of this dtype do not take this width and token count");
+  PRG_CHECK(shift_mode >= -1 && shift_mode <= 1 && psum >= -1 && psum <= 1, "prg_debug_linear_attention_block: shift_mode and psum are -1, 0 or 1");
+  PRG_CHECK(dtype == PRG_BF16 || (shift_mode == -1 && psum == -1),
+            "prg_debug_linear_attention_block: shift_mode and psum choose among the bf16 kernels only");
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_linear_attention_block: hipMalloc failed";
+  const char* nosync = "prg_debug_linear_attention_block: stream synchronise failed";
+  const size_t M = (size_t)B * N;
+  int rc;
+  if (dtype == PRG_F16X3) {
+    SplitAttnPack pk;
+    pack_split_attention(w_qkv, norm_g, w_out, C, pk);
+    if (used_static) *used_static = 0;
+    DeviceBuffers own;
+    const uint16_t* qh = own.upload(pk.qkv, nomem);
+    const uint16_t* oh = own.upload(pk.out, nomem);
+    const float* d_bias = own.upload(b_out, (size_t)C, nomem);
+    const float* d_outg = own.upload(out_g, (size_t)C, nomem);
+    float* d_x = own.alloc<float>(M * C, nomem);
+    float* d_out = own.alloc<float>(M * C, nomem);
+    float* ws = own.alloc<float>(linattn_split_ws_floats(B, N), nomem);
+    if (own.rc) return own.rc;
+    rc = launch_nchw_f32_to_nhwc<float>(x, d_x, B, N, C, s);
+    if (rc == PRG_OK)
+      rc = launch_linear_attention_split(d_x, qh, qh + (size_t)3 * kHidden * C, oh, oh + (size_t)C * kHidden, d_bias, d_outg, d_out, ws, B, N, C, s);
+    if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<float>(d_out, out, B, N, C, s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, nosync);
+    return rc;
+  }
+  FusedAttnPack pk;
+  pack_fused_attention(w_qkv, norm_g, w_out, C, pk);
+  PRG_CHECK(shift_mode != 1 || pk.ok, "prg_debug_linear_attention_block: the static softmax bound does not hold for these weights");
+  // shift_mode -1: what a handle does with this block (unet_weights.hip)
+  const bool stat = shift_mode == 1 || (shift_mode == -1 && pk.ok && env_int("PRG_LA_KSHIFT", 1) != 0);
+  if (used_static) *used_static = stat ? 1 : 0;
+  DeviceBuffers own;
+  const bf16_t* d_wqkv = own.upload(pk.qkv, nomem);
+  const bf16_t* d_wout = own.upload(pk.out, nomem);
+  const float* d_shift = own.upload(pk.shifts, (size_t)(kHidden + kHeads), nomem);
+  const float* d_bias = own.upload(b_out, (size_t)C, nomem);
+  const float* d_outg = own.upload(out_g, (size_t)C, nomem);
+  bf16_t* d_x = own.alloc<bf16_t>(M * C, nomem);
+  bf16_t* d_out = own.alloc<bf16_t>(M * C, nomem);
+  float* ws = own.alloc<float>(linattn_fused_ws_floats(B, N), nomem);
+  if (own.rc) return own.rc;
+  rc = launch_nchw_f32_to_nhwc<bf16_t>(x, d_x, B, N, C, s);
+  if (rc == PRG_OK) rc = launch_linear_attention_fused(d_x, d_wqkv, d_wout, d_bias, d_outg, d_out, ws, B, N, C, stat ? d_shift : nullptr, s, psum);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(d_out, out, B, N, C, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, nosync);
+  return rc;
+}
+
+// Channel LayerNorm (+ residual) on pixel-major rows (prg.h).
+int prg_debug_layernorm(const float* x, const float* g, const float* residual, float* out, int64_t M, int C, int dtype, void* stream) {
+  PRG_CHECK(x && g && out, "prg_debug_layernorm: null pointer");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16, "prg_debug_layernorm: bad dtype");
+  const int vec = dtype == PRG_F32 ? 4 : 8;
+  // (launch_layernorm: at most four 16-byte vectors in each of 64 lanes)
+  PRG_CHECK(C > 0 && C % vec == 0 && C / vec <= 256, "prg_debug_layernorm: C must be a multiple of the vector width, at most 256 vectors");
+  PRG_CHECK(M > 0 && M <= (int64_t)0x7fffffff / C, "prg_debug_layernorm: bad row count");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == PRG_BF16) return debug_layernorm_t<bf16_t>(x, g, residual, out, M, C, s);
+  return debug_layernorm_t<float>(x, g, residual, out, M, C, s);
+}
 
 // The two convolutions of a ResnetBlock's Block pair in bf16 mode, through the library's own dispatch (prg.h).
 int prg_debug_block_pair(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, const float* w2,

@@ -137,6 +137,23 @@ struct PackedConv {
 template <typename T>
 PackedConv<T> pack_conv_host(const float* w, int Cout, int Cin, int K, int dtype, ConvRole role);
 
+// ---------------------------------------------------------------------------------------------
+// What a handle packs for ONE fused Residual(PreNorm(LinearAttention)) block from the state dict's float32 tensors
+// (unet_weights.hip; the debug entry of unet_debug.hip packs through the same functions).  w_qkv [384][C], norm_g [C], w_out [C][128].
+// ---------------------------------------------------------------------------------------------
+struct FusedAttnPack {                 // bf16 (attn_fused.hip)
+  std::vector<bf16_t> qkv;             // [384][C]: PreNorm gain folded in, q and k rows times log2 e
+  std::vector<bf16_t> out;             // [C][128]
+  float shifts[kHidden + kHeads];      // static softmax shifts: a bound on |k| per column, then on |q| per head (log2 units)
+  bool ok = false;                     // every bound is small enough for the kernels to skip the measured maxima
+};
+void pack_fused_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, FusedAttnPack& p);
+struct SplitAttnPack {                 // f16x3 (attn_split.hip): the f16 hi halves, then the lo halves
+  std::vector<uint16_t> qkv;           // 2 x [384][C]
+  std::vector<uint16_t> out;           // 2 x [C][128]
+};
+void pack_split_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, SplitAttnPack& p);
+
 // appends `one` to `arena` at the next multiple of `align` elements (zero filled gap); returns its element offset
 template <typename U>
 size_t append_aligned(std::vector<U>& arena, const std::vector<U>& one, size_t align) {

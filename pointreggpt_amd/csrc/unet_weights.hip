@@ -267,28 +267,33 @@ static int upload_time_freqs(prg_unet& u) {
 
 // f16x3: fused linear attention (attn_split.hip): to_qkv with the PreNorm gain folded in (q and k rows times log2 e: both only ever
 // enter a softmax, evaluated with exp2) and to_out, each as f16 hi halves followed by the lo halves
-static int upload_split_attention(prg_unet& u, const float* weights) {
-  std::vector<uint16_t> aw, one;
+void pack_split_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, SplitAttnPack& p) {
   auto f16bits = [](float v, uint16_t& h, uint16_t& l) {
     const _Float16 a = (_Float16)v, b = (_Float16)(v - (float)a);
     std::memcpy(&h, &a, 2);
     std::memcpy(&l, &b, 2);
   };
+  const size_t nq = (size_t)3 * kHidden * C;
+  p.qkv.assign(2 * nq, 0);
+  for (int o = 0; o < 3 * kHidden; ++o)
+    for (int c = 0; c < C; ++c) {
+      const float v = w_qkv[(size_t)o * C + c] * norm_g[c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f);
+      f16bits(v, p.qkv[(size_t)o * C + c], p.qkv[nq + (size_t)o * C + c]);
+    }
+  const size_t no = (size_t)C * kHidden;
+  p.out.assign(2 * no, 0);
+  for (size_t i = 0; i < no; ++i) f16bits(w_out[i], p.out[i], p.out[no + i]);
+}
+
+static int upload_split_attention(prg_unet& u, const float* weights) {
+  std::vector<uint16_t> aw;
+  SplitAttnPack one;
   for_each_attn(u.lay, [&](AttnP& a) {
     // mid_at is not linear; linattn_split_supported: C = 64 / 128 (the token count is checked per call)
     if (!a.linear || (a.C != 64 && a.C != 128)) return;
-    const size_t nq = (size_t)3 * kHidden * a.C;
-    one.assign(2 * nq, 0);
-    for (int o = 0; o < 3 * kHidden; ++o)
-      for (int c = 0; c < a.C; ++c) {
-        const float v = weights[a.qkv.w_flat + (size_t)o * a.C + c] * weights[a.norm_g + c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f);
-        f16bits(v, one[(size_t)o * a.C + c], one[nq + (size_t)o * a.C + c]);
-      }
-    a.sp_qkv = (int64_t)append_aligned(aw, one, 64);
-    const size_t no = (size_t)a.C * kHidden;
-    one.assign(2 * no, 0);
-    for (size_t i = 0; i < no; ++i) f16bits(weights[a.out.w_flat + i], one[i], one[no + i]);
-    a.sp_out = (int64_t)append_aligned(aw, one, 64);
+    pack_split_attention(weights + a.qkv.w_flat, weights + a.norm_g, weights + a.out.w_flat, a.C, one);
+    a.sp_qkv = (int64_t)append_aligned(aw, one.qkv, 64);
+    a.sp_out = (int64_t)append_aligned(aw, one.out, 64);
   });
   u.d_attn_split = u.own.upload(aw, "hipMalloc(split attention weights)");
   return u.own.rc;
@@ -318,62 +323,65 @@ static int upload_norm_rows(prg_unet& u, const float* weights) {
   return u.own.rc;
 }
 
-// bf16: fused linear attention (attn_fused.hip): to_qkv with the PreNorm gain folded in, to_out as is, both [out][in] bf16; the
-// static softmax shifts; the raw res_conv weights of the fused ResnetBlock tail.  64-element alignment, shifts padded to 4 floats.
+// bf16: fused linear attention (attn_fused.hip): to_qkv with the PreNorm gain folded in, to_out as is, both [out][in] bf16, and the
+// static softmax shifts
+void pack_fused_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, FusedAttnPack& p) {
+  p.qkv.clear();
+  for (int o = 0; o < 3 * kHidden; ++o)
+    for (int c = 0; c < C; ++c)
+      // q and k only ever enter a softmax: their rows carry log2(e), so the kernels exponentiate with a bare v_exp_f32
+      p.qkv.push_back(f32_to_bf16(w_qkv[(size_t)o * C + c] * norm_g[c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f)));
+  // Softmax over pixels of k[n][d] = w_d . LN(x_n): a LayerNorm output has norm <= sqrt(C), so |k| <= ||w_d|| sqrt(C)
+  // (Cauchy-Schwarz; w_d = the bf16 weights the kernel multiplies with, 2 % slack for the bf16 rounding of LN(x)).
+  // exp(k - bound) >= exp(-2 bound): with bound <= 40 nothing underflows and the column maxima need not be measured.
+  // (k, hence the bound, in units of 1 / log2(e): the rows above are pre-scaled.)
+  p.ok = true;
+  for (int d = 0; d < kHidden; ++d) {
+    double n2 = 0;
+    for (int c = 0; c < C; ++c) {
+      const double w = bf16_to_f32(p.qkv[(size_t)(kHidden + d) * C + c]);
+      n2 += w * w;
+    }
+    p.shifts[d] = (float)(1.02 * std::sqrt(n2 * C));
+    p.ok = p.ok && p.shifts[d] <= 40.0f * 1.4426950408889634f;
+  }
+  // the same bound for the q rows (softmax over the 32 d of a head, per pixel): one shift per head
+  for (int h = 0; h < kHeads; ++h) {
+    double worst = 0;
+    for (int d = 0; d < kDimHead; ++d) {
+      double n2 = 0;
+      for (int c = 0; c < C; ++c) {
+        const double w = bf16_to_f32(p.qkv[(size_t)(h * kDimHead + d) * C + c]);
+        n2 += w * w;
+      }
+      worst = std::max(worst, 1.02 * std::sqrt(n2 * C));
+    }
+    p.shifts[kHidden + h] = (float)worst;
+    p.ok = p.ok && p.shifts[kHidden + h] <= 40.0f * 1.4426950408889634f;
+  }
+  p.out.clear();
+  for (int c = 0; c < C; ++c)
+    for (int j = 0; j < kHidden; ++j) p.out.push_back(f32_to_bf16(w_out[(size_t)c * kHidden + j]));
+}
+
+// bf16: the fused linear-attention blocks and the raw res_conv weights of the fused ResnetBlock tail.  64-element alignment, shifts
+// padded to 4 floats.
 static int upload_fused_attention(prg_unet& u, const float* weights) {
   std::vector<bf16_t> aw, one;
   std::vector<float> ks;
+  FusedAttnPack pk;
   // PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every block
   static const int kshift_on = env_int("PRG_LA_KSHIFT", 1);
   for_each_attn(u.lay, [&](AttnP& a) {
     if (!a.linear || !linattn_fused_supported(a.C)) return;   // (mid_at is not linear)
-    one.clear();
-    for (int o = 0; o < 3 * kHidden; ++o)
-      for (int c = 0; c < a.C; ++c)
-        // q and k only ever enter a softmax: their rows carry log2(e), so the kernels exponentiate with a bare v_exp_f32
-        one.push_back(f32_to_bf16(weights[a.qkv.w_flat + (size_t)o * a.C + c] * weights[a.norm_g + c] *
-                                  (o < 2 * kHidden ? 1.4426950408889634f : 1.0f)));
-    a.fw_qkv = (int64_t)append_aligned(aw, one, 64);
-    // Softmax over pixels of k[n][d] = w_d . LN(x_n): a LayerNorm output has norm <= sqrt(C), so |k| <= ||w_d|| sqrt(C)
-    // (Cauchy-Schwarz; w_d = the bf16 weights the kernel multiplies with, 2 % slack for the bf16 rounding of LN(x)).
-    // exp(k - bound) >= exp(-2 bound): with bound <= 40 nothing underflows and the column maxima need not be measured.
-    // (k, hence the bound, in units of 1 / log2(e): the rows above are pre-scaled.)
-    float shifts[kHidden];
-    bool ok = kshift_on != 0;
-    for (int d = 0; d < kHidden; ++d) {
-      double n2 = 0;
-      for (int c = 0; c < a.C; ++c) {
-        const double w = bf16_to_f32(aw[(size_t)a.fw_qkv + (size_t)(kHidden + d) * a.C + c]);
-        n2 += w * w;
-      }
-      shifts[d] = (float)(1.02 * std::sqrt(n2 * a.C));
-      ok = ok && shifts[d] <= 40.0f * 1.4426950408889634f;
-    }
-    // the same bound for the q rows (softmax over the 32 d of a head, per pixel): one shift per head
-    float qsh[kHeads];
-    for (int h = 0; h < kHeads; ++h) {
-      double worst = 0;
-      for (int d = 0; d < kDimHead; ++d) {
-        double n2 = 0;
-        for (int c = 0; c < a.C; ++c) {
-          const double w = bf16_to_f32(aw[(size_t)a.fw_qkv + (size_t)(h * kDimHead + d) * a.C + c]);
-          n2 += w * w;
-        }
-        worst = std::max(worst, 1.02 * std::sqrt(n2 * a.C));
-      }
-      qsh[h] = (float)worst;
-      ok = ok && qsh[h] <= 40.0f * 1.4426950408889634f;
-    }
-    if (ok) {
+    pack_fused_attention(weights + a.qkv.w_flat, weights + a.norm_g, weights + a.out.w_flat, a.C, pk);
+    a.fw_qkv = (int64_t)append_aligned(aw, pk.qkv, 64);
+    if (kshift_on != 0 && pk.ok) {
       a.kshift = (int64_t)ks.size();
-      ks.insert(ks.end(), shifts, shifts + kHidden);
-      ks.insert(ks.end(), qsh, qsh + kHeads);
+      ks.insert(ks.end(), pk.shifts, pk.shifts + kHidden + kHeads);
       ks.resize((ks.size() + 3) & ~(size_t)3);
     }
-    one.clear();
-    for (int c = 0; c < a.C; ++c)
-      for (int j = 0; j < kHidden; ++j) one.push_back(f32_to_bf16(weights[a.out.w_flat + (size_t)c * kHidden + j]));
-    a.fw_out = (int64_t)append_aligned(aw, one, 1);
+    a.fw_out = (int64_t)append_aligned(aw, pk.out, 1);
   });
   // fused ResnetBlock tail: raw res_conv weights [Cout][Cin] as bf16.  (has_res: the blocks of the up levels and the final one)
   for_each_res(u.lay, [&](ResP& r) {
