@@ -158,6 +158,23 @@ int prg_radius_count_ragged_f64(const double* pts, const int64_t* offsets, int n
 int prg_radius_fill_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double radius,
                                const int64_t* row_start, int64_t capacity, int32_t* corr, void* stream);
 
+/* Neighbour tables from the list of passes 1 and 2: per query row its `limit` nearest candidates within the radius, nearest
+ * first — the K-nearest-within-a-radius tables of a KPConv pyramid (neighbours, sub-sampling, up-sampling).  pts / offsets /
+ * n_pairs / max_cloud: the buffer passes 1 and 2 ran on; row_start (total+1) and corr (list_rows,2): their complete output,
+ * list_rows = row_start[total].  corr is never read at or beyond list_rows; list_rows == 0 allows corr == NULL.
+ * table int32 DEVICE: query row i of pair p owns the `limit` slots from (table_offsets[p] + i) * limit on (table_offsets
+ * (n_pairs) int64 DEVICE: the first table row of every pair).  Its matches are ordered by (dx*dx + dy*dy + dz*dz ascending, the
+ * expression of passes 1 and 2 recomputed from pts, then j ascending); the first `limit` are written as index_base[p] + j
+ * (index_base (n_pairs) int32 DEVICE, NULL = 0), every remaining slot as pad[p] (pad (n_pairs) int32 DEVICE, NULL = the number
+ * of rows of the candidate cloud).  Every slot of every query row is written exactly once and nothing else is; pts, row_start
+ * and corr are not written.  1 <= n_pairs <= 65535, 0 < max_cloud < 2^31, list_rows >= 0, 1 <= limit <= 1024; anything else or
+ * a null pointer fails with PRG_E_INVALID before any device call.  Asynchronous on `stream`; reads no device data on the host;
+ * allocates nothing.                                                                                                          */
+int prg_radius_select_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud,
+                                 const int64_t* row_start, const int32_t* corr, int64_t list_rows, int limit,
+                                 const int64_t* table_offsets, const int32_t* index_base, const int32_t* pad, int32_t* table,
+                                 void* stream);
+
 /* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
  * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
 size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);

@@ -307,6 +307,155 @@ def radius_pairs_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, 
     return corr, row_start[offsets[0::2]]
 
 
+def _neighbor_tables(pts, offsets, n_pairs, max_cloud, radius, limit, index_base, pad, query_rows=None):
+    """count / fill / select on one pair buffer -> (table, table_offsets, count).  `query_rows`: the total number of query rows
+    when the caller already has it on the host; then the read-back is the 8 bytes of the list size alone."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    n_pairs, limit = int(n_pairs), int(limit)
+    assert offsets.numel() == 2 * n_pairs + 1
+    if not 1 <= limit <= 1024:
+        raise _lib.PrgError("radius_neighbors_ragged: limit must be in 1..1024")
+    dev = pts.device
+    pts = pts.contiguous().view(-1, 3)
+    offsets = offsets.contiguous()
+    total = pts.shape[0]
+    if total == 0:                                  # no rows: a tensor without elements has no address to pass
+        pts, total = torch.zeros((1, 3), dtype=torch.float64, device=dev), 1
+    for t in (index_base, pad):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.numel() == n_pairs)
+    row_start = torch.empty((total + 1,), dtype=torch.int64, device=dev)
+    ws = _voxel_workspace(dev, int(lib.prg_radius_pairs_workspace_bytes(total)))
+    _lib.check(lib.prg_radius_count_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, total, int(max_cloud), float(radius),
+                                               _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "prg_radius_count_ragged_f64")
+    table_offsets = torch.zeros((n_pairs + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(offsets[1::2] - offsets[0:-1:2], 0, out=table_offsets[1:])
+    if query_rows is None:
+        K, Q = (int(v) for v in torch.stack([row_start[total], table_offsets[n_pairs]]).tolist())   # THE synchronisation
+    else:
+        K, Q = int(row_start[total].item()), int(query_rows)                                        # THE synchronisation
+    table = torch.empty((Q, limit), dtype=torch.int32, device=dev)
+    count = torch.empty((Q,), dtype=torch.int32, device=dev)
+    if Q == 0:
+        return table, table_offsets, count
+    corr = None
+    if K:
+        corr = torch.empty((K, 2), dtype=torch.int32, device=dev)
+        _lib.check(lib.prg_radius_fill_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, int(max_cloud), float(radius),
+                                                  _lib.ptr(row_start), K, _lib.ptr(corr), _lib.stream_ptr()),
+                   "prg_radius_fill_ragged_f64")
+    _lib.check(lib.prg_radius_select_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, int(max_cloud), _lib.ptr(row_start),
+                                                _lib.ptr(corr), K, limit, _lib.ptr(table_offsets),
+                                                _lib.ptr(None if index_base is None else index_base.contiguous()),
+                                                _lib.ptr(None if pad is None else pad.contiguous()), _lib.ptr(table),
+                                                _lib.stream_ptr()), "prg_radius_select_ragged_f64")
+    # count = row_start differences over the query rows: table row t belongs to pair p = the last p with table_offsets[p] <= t
+    t = torch.arange(Q, dtype=torch.int64, device=dev)
+    p = torch.searchsorted(table_offsets[1:].contiguous(), t, right=True)
+    q = offsets[0::2][p] + (t - table_offsets[p])
+    torch.sub(row_start[q + 1], row_start[q], out=count)
+    return table, table_offsets, count
+
+
+def radius_neighbors_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_cloud: int, radius: float, limit: int,
+                            index_base: Optional[torch.Tensor] = None, pad: Optional[torch.Tensor] = None):
+    """Neighbour tables for `n_pairs` cloud pairs: per query row its `limit` nearest candidates within `radius`, nearest first
+    (prg_radius_count_ragged_f64 / prg_radius_fill_ragged_f64, then prg_radius_select_ragged_f64).  pts (total,3) float64 and
+    offsets (2*n_pairs+1) int64 as `radius_pairs_ragged` takes them, both device tensors; pair p queries segment 2p against
+    segment 2p+1.  index_base / pad: (n_pairs) int32 device tensors or None — a match j of pair p is written as index_base[p] + j
+    (None: j), an empty slot as pad[p] (None: the rows of the candidate cloud).
+    Returns (table (Q, limit) int32, table_offsets (n_pairs+1) int64, count (Q) int32) on the device, Q = all query rows: pair p's
+    table is table[table_offsets[p]:table_offsets[p+1]], bit for bit `postprocess.radius_neighbors` of its two clouds, and count
+    the matches per row before truncation (row_start differences).  Count, ONE read-back (the size of the list and Q, 16 bytes in
+    one copy — the only synchronisation), allocations of exactly K and Q rows, fill, select."""
+    return _neighbor_tables(pts, offsets, n_pairs, max_cloud, radius, limit, index_base, pad)
+
+
+def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_size: float, radius: float, neighbor_limits):
+    """The KPConv pyramid of a stack of C clouds on the device, bit for bit `postprocess.neighbor_pyramid` (which states the
+    definition): points (N,3) float64 or float32 device tensor — float32 is widened, which is exact — the clouds one after the
+    other, lengths (C,) their rows (device tensor, numpy or a list).  Returns {"points", "lengths", "neighbors", "subsampling",
+    "upsampling": lists of device tensors per level, "counts": {"neighbors", "subsampling", "upsampling"}}: points float64,
+    lengths int64, tables int32 indices into the candidate level's stack with that level's row count as the pad.
+
+    Level l+1 is `voxel_grid_ragged` of level l at voxel_size * 2**(l+1); a non-zero status raises through `check_voxel_status`.
+    Two select launches per level: neighbors[l] and subsampling[l] share the radius r_l and the candidates, so they are the 2C
+    pairs of ONE count / fill / select; upsampling[l] (radius 2 r_l) is a second one of C pairs; the last level has neighbors only.
+    A pair's query and candidate segments are adjacent in the pair buffer, so a level searched against itself needs every cloud
+    twice: the buffer [c, c for every cloud, then next-level c, c for every cloud] is assembled by ONE device `cat` of row
+    slices per launch — no kernel of its own, 3 N_l + N_{l+1} rows for the first launch, N_l + N_{l+1} for the second.
+    Host synchronisations: one for `lengths` if it is a device tensor; then per level l < num_stages - 1 three — one read of
+    the next level's offsets and status (C+1 and C numbers in one copy, needed for the slices) and the 8-byte list size of each
+    of the two launches; the last level has one (its list size)."""
+    if not points.is_cuda:
+        raise _lib.PrgError("expected a tensor on the HIP device (this package has no CPU path)")
+    if points.dtype not in (torch.float64, torch.float32):
+        raise _lib.PrgError("neighbor_pyramid: points must be float64 or float32")
+    num_stages = int(num_stages)
+    limits = [int(k) for k in neighbor_limits]
+    if num_stages < 1 or len(limits) != num_stages:
+        raise ValueError("num_stages >= 1 and one neighbor limit per stage")
+    if not (np.isfinite(radius) and radius > 0 and np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("radius and voxel_size must be finite and > 0")
+    dev = points.device
+    pts = points.contiguous().view(-1, 3).to(torch.float64)
+    lens = (lengths.cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)).astype(np.int64).reshape(-1)
+    C = len(lens)
+    if C < 1 or (lens < 0).any() or int(lens.sum()) != pts.shape[0]:
+        raise ValueError("lengths do not add up to the rows of points")
+    max_cloud = max(1, int(lens.max()))             # a level never has more rows per cloud than the one above it
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)       # noqa: E731
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)       # noqa: E731
+
+    def launch(segs, n_pairs, r, limit, base, pad):
+        """segs: [(level points, start, stop), ...], 2 per pair -> the tables of the launch."""
+        sizes = np.array([b - a for _, a, b in segs], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        rows = [P[a:b] for P, a, b in segs if b > a]
+        buf = torch.cat(rows, 0) if rows else torch.zeros((1, 3), dtype=torch.float64, device=dev)
+        table, _, count = _neighbor_tables(buf, i64(offs), n_pairs, max_cloud, r, limit, i32(base), i32(pad),
+                                           query_rows=int(sizes[0::2].sum()))
+        return table, count
+
+    out = {"points": [pts], "lengths": [i64(lens)], "neighbors": [], "subsampling": [], "upsampling": [],
+           "counts": {"neighbors": [], "subsampling": [], "upsampling": []}}
+    P, o = pts, np.concatenate([[0], np.cumsum(lens)])                  # this level: points, host offsets
+    for l in range(num_stages):
+        r, N = float(radius) * 2 ** l, int(o[-1])
+        segs = [(P, o[c], o[c + 1]) for c in range(C) for _ in range(2)]
+        base, pad = list(o[:C]), [N] * C
+        if l == num_stages - 1:
+            table, count = launch(segs, C, r, limits[l], base, pad)
+            out["neighbors"].append(table)
+            out["counts"]["neighbors"].append(count)
+            break
+        if N:
+            down, d_offs, status = voxel_grid_ragged(P, None, i64(o), float(voxel_size) * 2 ** (l + 1))
+            host = torch.cat([d_offs, status.to(torch.int64)]).cpu().numpy()
+            on = host[:C + 1]
+            check_voxel_status(host[C + 1:], ["cloud {} of level {}".format(c, l) for c in range(C)])
+        else:                                       # a stack without rows stays one
+            down, on = P, o
+        Pn, Nn = down[:int(on[-1])], int(on[-1])
+        segs += [(Pk, ok[c], ok[c + 1]) for c in range(C) for Pk, ok in ((Pn, on), (P, o))]
+        table, count = launch(segs, 2 * C, r, limits[l], base + base, pad + pad)
+        out["neighbors"].append(table[:N])
+        out["subsampling"].append(table[N:])
+        out["counts"]["neighbors"].append(count[:N])
+        out["counts"]["subsampling"].append(count[N:])
+        segs = [(Pk, ok[c], ok[c + 1]) for c in range(C) for Pk, ok in ((P, o), (Pn, on))]
+        table, count = launch(segs, C, 2 * r, limits[l + 1], list(on[:C]), [Nn] * C)
+        out["upsampling"].append(table)
+        out["counts"]["upsampling"].append(count)
+        out["points"].append(Pn)
+        out["lengths"].append(i64(np.diff(on)))
+        P, o = Pn, on
+    return out
+
+
 def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
     """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
     float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as

@@ -310,6 +310,124 @@ def radius_pairs_hip(pairs, radius: float, device="cuda"):
     return [corr[po[p]:po[p + 1]].copy() for p in range(len(pairs))]
 
 
+def _check_radius_limit(radius, limit) -> None:
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and > 0")
+    if int(limit) != limit or limit < 1:
+        raise ValueError("limit must be an integer >= 1")
+
+
+def radius_neighbors(a: np.ndarray, b: np.ndarray, radius: float, limit: int) -> Tuple[np.ndarray, np.ndarray]:
+    """For every row of `a` its `limit` nearest rows of `b` within `radius`, nearest first: (idx (len(a), limit) int32, count
+    (len(a),) int32) — the numpy specification of prg_radius_select_ragged_f64 on count / fill's list, bit for bit, and the
+    neighbour table of a KPConv collate step.  The rows j that match row i are `radius_pairs`' (dx*dx + dy*dy + dz*dz <
+    radius*radius in float64, dx = b.x - a.x, products written out and summed left to right, strict <); they are ordered by that
+    squared distance ascending, then by j ascending; the first `limit` are kept and the remaining slots hold len(b), the index
+    of the shadow row those networks append.  count[i] is the number of matches BEFORE truncation (what a neighbour limit is
+    calibrated from).  A NaN row never matches and is never matched; an empty `a` gives shapes (0, limit) and (0,); an empty `b`
+    gives all pads, and the pad is 0.  `limit` < 1, or a radius that is not finite and > 0, raises ValueError."""
+    _check_radius_limit(radius, limit)
+    limit = int(limit)
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    idx = np.full((len(a), limit), len(b), dtype=np.int32)
+    corr = radius_pairs(a, b, radius)
+    i, j = corr[:, 0].astype(np.int64), corr[:, 1].astype(np.int64)
+    count = np.bincount(i, minlength=len(a)).astype(np.int32)
+    if len(corr):
+        dx, dy, dz = b[j, 0] - a[i, 0], b[j, 1] - a[i, 1], b[j, 2] - a[i, 2]
+        d2 = dx * dx + dy * dy + dz * dz
+        order = np.lexsort((j, d2, i))                               # by i, then d2, then j
+        i, j = i[order], j[order]
+        first = np.cumsum(count, dtype=np.int64) - count             # where row i's matches begin in the ordered list
+        rank = np.arange(len(i), dtype=np.int64) - first[i]
+        keep = rank < limit
+        idx[i[keep], rank[keep]] = j[keep]
+    return idx, count
+
+
+def radius_neighbors_hip(pairs, radius: float, limit: int, device="cuda"):
+    """[(a (n,3), b (m,3)), ...] -> [(idx_p (n,limit) int32, count_p (n,) int32), ...] as `radius_neighbors(a, b, radius, limit)`
+    defines them, for clouds that are on the host: all clouds uploaded once as one ragged float64 buffer, ONE count / fill /
+    select (`geometry.radius_neighbors_ragged`) for the whole list, one copy back."""
+    from . import _lib
+    from . import geometry as G
+    _check_radius_limit(radius, limit)
+    _lib.load()
+    _lib.require_gpu()
+    if not pairs:
+        return []
+    clouds = [_f64(c) for pair in pairs for c in pair]
+    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    pts, d_offs = G.upload_clouds(clouds, device, dtype=np.float64)
+    table_d, to_d, count_d = G.radius_neighbors_ragged(pts, d_offs, len(pairs), max(1, int(sizes.max())), radius, int(limit))
+    table, to, count = table_d.cpu().numpy(), to_d.cpu().numpy(), count_d.cpu().numpy()
+    return [(table[to[p]:to[p + 1]].copy(), count[to[p]:to[p + 1]].copy()) for p in range(len(pairs))]
+
+
+def neighbor_pyramid(points: np.ndarray, lengths, num_stages: int, voxel_size: float, radius: float, neighbor_limits) -> dict:
+    """The KPConv pyramid of a stack of C clouds, host specification of `geometry.neighbor_pyramid`, built from
+    `radius_neighbors` and `voxel_down_sample` only.  points (N,3): the clouds one after the other, lengths (C,) their rows.
+    Level 0 is the input stack, unchanged; level l+1 is `voxel_down_sample(cloud, voxel_size * 2**(l+1))` of every cloud of
+    level l, re-stacked in cloud order.  With r_l = radius * 2**l:
+      neighbors[l]    level l against itself,                   radius r_l,     limit neighbor_limits[l]
+      subsampling[l]  query level l+1, candidates level l,      radius r_l,     limit neighbor_limits[l]      (l < num_stages - 1)
+      upsampling[l]   query level l,   candidates level l+1,    radius 2 * r_l, limit neighbor_limits[l+1]    (l < num_stages - 1)
+    Searches never cross clouds.  An index counts rows of the candidate level's STACK (cloud start + local j) and the pad is
+    that level's total row count, the shadow row.  Returns {"points": [(N_l,3) float64], "lengths": [(C,) int64], "neighbors",
+    "subsampling", "upsampling": [(rows, limit) int32], "counts": {"neighbors", "subsampling", "upsampling": [(rows,) int32]}}."""
+    num_stages = int(num_stages)
+    if num_stages < 1:
+        raise ValueError("num_stages must be >= 1")
+    limits = [int(k) for k in neighbor_limits]
+    if len(limits) != num_stages:
+        raise ValueError("one neighbor limit per stage")
+    for k in limits:
+        _check_radius_limit(radius, k)
+    if not (np.isfinite(voxel_size) and voxel_size > 0):
+        raise ValueError("voxel_size must be finite and > 0")
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lens.sum() != len(pts) or (lens < 0).any():
+        raise ValueError("lengths do not add up to the rows of points")
+
+    def split(p, n):
+        o = np.concatenate([[0], np.cumsum(n)])
+        return [p[o[c]:o[c + 1]] for c in range(len(n))], o
+
+    def tables(query, q_lens, cand, c_lens, r, limit):
+        qs, _ = split(query, q_lens)
+        cs, co = split(cand, c_lens)
+        idx, cnt = [np.zeros((0, limit), dtype=np.int32)], [np.zeros(0, dtype=np.int32)]
+        for c in range(len(qs)):
+            t, k = radius_neighbors(qs[c], cs[c], r, limit)
+            hit = t < len(cs[c])
+            t = np.where(hit, t + np.int32(co[c]), np.int32(len(cand))).astype(np.int32)
+            idx.append(t)
+            cnt.append(k)
+        return np.concatenate(idx, 0), np.concatenate(cnt, 0)
+
+    out = {"points": [pts], "lengths": [lens], "neighbors": [], "subsampling": [], "upsampling": [],
+           "counts": {"neighbors": [], "subsampling": [], "upsampling": []}}
+    for l in range(1, num_stages):
+        clouds, _ = split(out["points"][-1], out["lengths"][-1])
+        down = [voxel_down_sample(c, voxel_size * 2 ** l) for c in clouds]
+        out["points"].append(np.concatenate([np.zeros((0, 3))] + down, 0))
+        out["lengths"].append(np.array([len(d) for d in down], dtype=np.int64))
+    for l in range(num_stages):
+        r = radius * 2 ** l
+        P, n = out["points"][l], out["lengths"][l]
+        jobs = [("neighbors", P, n, P, n, r, limits[l])]
+        if l < num_stages - 1:
+            Pn, nn = out["points"][l + 1], out["lengths"][l + 1]
+            jobs += [("subsampling", Pn, nn, P, n, r, limits[l]), ("upsampling", P, n, Pn, nn, 2 * r, limits[l + 1])]
+        for name, q, ql, c, cl, rr, k in jobs:
+            t, cnt = tables(q, ql, c, cl, rr, k)
+            out[name].append(t)
+            out["counts"][name].append(cnt)
+    return out
+
+
 def cloud_distance_metrics(d2_ab: np.ndarray, d2_ba: np.ndarray, thresholds=DISTANCE_THRESHOLDS) -> dict:
     """Distances between two clouds from the squared nearest-neighbour distances of both directions (host float64, over
     d = sqrt(d2)): n_a, n_b, chamfer = (mean d_ab + mean d_ba) / 2, hausdorff = the largest d, p50 / p95 / p99 of all the
