@@ -175,6 +175,50 @@ int prg_radius_select_ragged_f64(const double* pts, const int64_t* offsets, int 
                                  const int64_t* table_offsets, const int32_t* index_base, const int32_t* pad, int32_t* table,
                                  void* stream);
 
+/* Node patches: the point-to-node partition of a coarse-to-fine registration network as per-node tables.  d2 (total) float64 and
+ * assign (total) int32, DEVICE: the d2 and idx prg_nearest_ragged_f64 wrote for the buffer [points_0 | nodes_0 | points_1 |
+ * nodes_1 | ...] with these `offsets` (2*n_pairs+1 int64 DEVICE, offsets[0] may be > 0) — "pair" c is cloud c: segment 2c its
+ * points, segment 2c+1 its nodes, so assign[r] of a point row r is its nearest node, counted from the cloud's first node, or -1
+ * (a NaN point, no node).  Only the entries of point rows are read; an assign outside [0, nodes of the cloud) counts as -1.
+ * table int32 DEVICE: node k of cloud c owns the `limit` slots from (table_offsets[c] + k) * limit on, and sizes[table_offsets[c]
+ * + k] (table_offsets (n_pairs) int64 DEVICE: the first table row of every cloud).  The node's members, the points with assign ==
+ * k, are ordered by (d2 ascending, then row ascending); the first `limit` are written as index_base[c] + i, i the point's row
+ * counted from the cloud's first point (index_base (n_pairs) int32 DEVICE, NULL = 0), every remaining slot as pad[c] (pad
+ * (n_pairs) int32 DEVICE, NULL = the number of point rows of the cloud); sizes = the number of members BEFORE truncation, 0 for a
+ * node without members.  A node may own any number of points.  Every slot and every size of every node is written, the same
+ * bytes on every run (a pad pass, then one writer per slot: no atomics, no sort), and nothing else is; d2 and assign are not
+ * written.  The d2 of an assigned row must not be NaN (prg_nearest_ragged_f64 never produces one).  max_cloud / max_nodes: the
+ * largest number of points / nodes of a cloud.  1 <= n_pairs <= 65535, 0 < max_cloud < 2^31, 0 < max_nodes < 2^31, 1 <= limit <=
+ * 256; anything else or a null pointer fails with PRG_E_INVALID before any device call.  Asynchronous on `stream`; reads no
+ * device data on the host; allocates nothing.                                                                                 */
+int prg_patch_tables_ragged(const double* d2, const int32_t* assign, const int64_t* offsets, int n_pairs, int64_t max_cloud,
+                            int64_t max_nodes, int limit, const int64_t* table_offsets, const int32_t* index_base,
+                            const int32_t* pad, int32_t* table, int32_t* sizes, void* stream);
+
+/* Patch against patch: the coarse ground truth of n_pairs items.  pts / offsets: the layout of prg_overlap_counts, segment 2p the
+ * fine points of item p's source cloud, segment 2p+1 of its target cloud.  tables (rows, limit) int32 DEVICE: the patch tables of
+ * all 2*n_pairs clouds with LOCAL point rows (index_base NULL) and pad = the cloud's rows (pad NULL); table_offsets (2*n_pairs+1)
+ * int64 DEVICE: the first table row of every cloud, and the end.  A patch is the entries of its table row inside [0, rows of the
+ * cloud); anything else is a pad.  For source node a and target node b of item p, with ms / mt nodes in the two clouds,
+ *   hits[2 * (hit_offsets[p] + a * mt + b)]     = points i of patch a that have a point j of patch b with dx*dx + dy*dy + dz*dz <
+ *                                                 radius*radius (the expression and the strict < of prg_radius_count_ragged_f64),
+ *   hits[2 * (hit_offsets[p] + a * mt + b) + 1] = points j of patch b that have such a point i of patch a
+ * (hit_offsets (n_pairs+1) int64 DEVICE, the exclusive sums of ms * mt; hits (total_node_pairs, 2) int32 DEVICE, dense): every
+ * node pair of every item is written exactly once, zeros included, the same bytes on every run; a position outside [0,
+ * total_node_pairs) is not written.  A NaN point never matches.  max_nodes: the most nodes of a cloud; max_item_pairs: the
+ * largest ms * mt of an item.
+ * boxes: NULL, or (rows, 6) float64 DEVICE scratch: the call then writes every patch's bounding box there first and skips (writes
+ * zeros for) a node pair whose boxes are at least `radius` apart along an axis, the gap taken as fl(lo_b - hi_a) >= radius in
+ * float64.  That is exact (rounding is monotonic: every dx*dx of such a pair is >= radius*radius), so hits is the same with and
+ * without it.
+ * 1 <= n_pairs <= 65535, 0 < max_nodes < 2^31, 1 <= max_item_pairs <= total_node_pairs <= 2^28, 1 <= limit <= 256, radius finite
+ * and > 0; anything else or a null pointer (other than boxes) fails with PRG_E_INVALID before any device call.  Asynchronous on
+ * `stream`; reads no device data on the host; allocates nothing; pts and tables are not written.                              */
+int prg_patch_overlap_ragged_f64(const double* pts, const int64_t* offsets, int n_pairs, const int32_t* tables,
+                                 const int64_t* table_offsets, int64_t max_nodes, int limit, double radius,
+                                 const int64_t* hit_offsets, int64_t total_node_pairs, int64_t max_item_pairs, double* boxes,
+                                 int32_t* hits, void* stream);
+
 /* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
  * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
 size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);

@@ -456,6 +456,165 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
     return out
 
 
+def _host_offsets(o, what: str) -> np.ndarray:
+    """CSR offsets as a host int64 array; a device tensor is copied back (one synchronisation)."""
+    o = (o.cpu().numpy() if torch.is_tensor(o) else np.asarray(o)).astype(np.int64).reshape(-1)
+    if len(o) < 2 or (np.diff(o) < 0).any() or o[0] < 0:
+        raise ValueError("{}: ascending offsets with at least two entries".format(what))
+    return o
+
+
+def _check_patch_limit(limit, what: str) -> int:
+    if int(limit) != limit or not 1 <= limit <= 256:
+        raise _lib.PrgError("{}: limit must be in 1..256".format(what))
+    return int(limit)
+
+
+def node_patches_ragged(points: torch.Tensor, point_offsets, nodes: torch.Tensor, node_offsets, limit: int,
+                        index_base: Optional[torch.Tensor] = None, pad: Optional[torch.Tensor] = None):
+    """The point-to-node partition of C clouds and its per-node tables, bit for bit `postprocess.node_patches` per cloud: points
+    (N,3) and nodes (M,3) float64 device tensors, point_offsets / node_offsets (C+1) CSR offsets (numpy, a list or tensors); cloud
+    c's points are points[point_offsets[c]:point_offsets[c+1]], its nodes likewise.  index_base / pad: (C) int32 device tensors or
+    None — a member i of cloud c is written as index_base[c] + i (None: i, the row counted from the cloud's first point), an empty
+    slot as pad[c] (None: the rows of the cloud).
+    Returns (assign (N) int32 — per point its node counted from the cloud's first node, -1 for none and for rows outside every
+    cloud; table (rows, limit) int32 and sizes (rows) int32, rows = node_offsets[C] - node_offsets[0]: node k of cloud c is row
+    node_offsets[c] - node_offsets[0] + k) on the device.
+    One device `cat` of row slices into the pair layout [points_c | nodes_c], `nearest_ragged` on it (prg_nearest_ragged_f64),
+    a gather of the point rows' assignment, prg_patch_tables_ragged.  Host synchronisations: none when both offsets are on the
+    host; one copy back per offsets tensor that is on the device."""
+    lib = _lib.load()
+    if not (points.is_cuda and nodes.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert points.dtype == torch.float64 and nodes.dtype == torch.float64
+    limit = _check_patch_limit(limit, "node_patches_ragged")
+    dev = points.device
+    points, nodes = points.contiguous().view(-1, 3), nodes.contiguous().view(-1, 3)
+    po, no = _host_offsets(point_offsets, "point_offsets"), _host_offsets(node_offsets, "node_offsets")
+    C = len(po) - 1
+    if len(no) != C + 1 or po[-1] > points.shape[0] or no[-1] > nodes.shape[0]:
+        raise ValueError("offsets do not fit the clouds")
+    for t in (index_base, pad):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.numel() == C)
+    rows = int(no[-1] - no[0])
+    assign = torch.full((points.shape[0],), -1, dtype=torch.int32, device=dev)
+    table = torch.empty((rows, limit), dtype=torch.int32, device=dev)
+    sizes = torch.empty((rows,), dtype=torch.int32, device=dev)
+    if rows == 0:                                   # no node anywhere: nothing to write, every point stays at -1
+        return assign, table, sizes
+    seg = np.stack([np.diff(po), np.diff(no)], 1).reshape(-1)                       # rows of [points_0, nodes_0, points_1, ...]
+    offs = np.concatenate([[0], np.cumsum(seg)]).astype(np.int64)
+    parts = [t[int(o[c]):int(o[c + 1])] for c in range(C) for t, o in ((points, po), (nodes, no)) if o[c + 1] > o[c]]
+    buf = torch.cat(parts, 0)
+    d_offs = torch.from_numpy(offs).to(dev)
+    max_cloud, max_nodes = max(1, int(seg[0::2].max())), max(1, int(seg[1::2].max()))
+    d2, idx = nearest_ragged(buf, d_offs, C, max(max_cloud, max_nodes))
+    t_offs = torch.from_numpy(np.ascontiguousarray(no[:-1] - no[0])).to(dev)
+    base = None if index_base is None else index_base.contiguous()      # named: a temporary's block could be handed out again
+    padv = None if pad is None else pad.contiguous()                    # before the launch
+    _lib.check(lib.prg_patch_tables_ragged(_lib.ptr(d2), _lib.ptr(idx), _lib.ptr(d_offs), C, max_cloud, max_nodes, limit,
+                                           _lib.ptr(t_offs), _lib.ptr(base), _lib.ptr(padv), _lib.ptr(table), _lib.ptr(sizes),
+                                           _lib.stream_ptr()), "prg_patch_tables_ragged")
+    if po[-1] > po[0]:
+        assign[int(po[0]):int(po[-1])] = torch.cat([idx[int(offs[2 * c]):int(offs[2 * c + 1])] for c in range(C) if seg[2 * c]], 0)
+    return assign, table, sizes
+
+
+def patch_overlaps_ragged(pts: torch.Tensor, offsets, tables: torch.Tensor, table_offsets, radius: float, *,
+                          prefilter: bool = True):
+    """Which node patches overlap, for n items at once, bit for bit `postprocess.patch_overlaps` per item: pts (total,3) float64
+    device tensor and offsets (2n+1) as `prg_overlap_counts` takes them — segment 2p the fine points of item p's source cloud,
+    segment 2p+1 of its target; tables (rows, limit) int32 device tensor, the patch tables of all 2n clouds with LOCAL point rows
+    and the cloud's row count as the pad (`node_patches_ragged` with index_base = pad = None), table_offsets (2n+1) the first
+    table row of every cloud and the end.  Both offsets: numpy, a list or tensors.
+    Returns (node_corr (P,2) int32 — (source node, target node) counted from each cloud's first node, ordered by item, a, b;
+    hits (P,2) int32; overlap (P,) float64; corr_offsets (n+1) int64: item p's rows are [corr_offsets[p], corr_offsets[p+1])) on
+    the device.  prg_patch_overlap_ragged_f64 writes the two hit counts of EVERY node pair (dense, 8 bytes per pair, at most 2^28
+    pairs per call); `nonzero` over them, a gather and the float64 overlap in torch follow.  prefilter: the kernel's exact
+    bounding-box test (False runs every patch pair; the result is the same).
+    Host synchronisations: ONE, the number of listed node pairs inside `nonzero`; one more per offsets tensor that is on the
+    device."""
+    lib = _lib.load()
+    if not (pts.is_cuda and tables.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and tables.dtype == torch.int32 and tables.dim() == 2
+    if not (np.isfinite(radius) and radius > 0):
+        raise _lib.PrgError("patch_overlaps_ragged: radius must be finite and > 0")
+    dev = pts.device
+    pts, tables = pts.contiguous().view(-1, 3), tables.contiguous()
+    limit = _check_patch_limit(tables.shape[1], "patch_overlaps_ragged")
+    o, to = _host_offsets(offsets, "offsets"), _host_offsets(table_offsets, "table_offsets")
+    n = (len(o) - 1) // 2
+    if len(o) != 2 * n + 1 or n < 1 or len(to) != len(o) or o[-1] > pts.shape[0] or to[-1] > tables.shape[0]:
+        raise ValueError("offsets do not fit the clouds or the tables")
+    m = np.diff(to)
+    per_item = m[0::2] * m[1::2]
+    ho = np.concatenate([[0], np.cumsum(per_item)]).astype(np.int64)
+    total = int(ho[-1])
+    if total > 1 << 28:
+        raise _lib.PrgError("patch_overlaps_ragged: more than 2^28 node pairs in one call")
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)       # noqa: E731
+    hits = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    d_o, d_to, d_ho, d_m = i64(o), i64(to), i64(ho), i64(m)     # named: a temporary's block could be handed out again at once
+    if total:
+        if pts.shape[0] == 0:                       # no rows: a tensor without elements has no address to pass
+            pts = torch.zeros((1, 3), dtype=torch.float64, device=dev)
+        boxes = torch.empty((tables.shape[0], 6), dtype=torch.float64, device=dev) if prefilter else None
+        _lib.check(lib.prg_patch_overlap_ragged_f64(_lib.ptr(pts), _lib.ptr(d_o), n, _lib.ptr(tables), _lib.ptr(d_to),
+                                                    int(m.max()), limit, float(radius), _lib.ptr(d_ho), total,
+                                                    int(per_item.max()), _lib.ptr(boxes), _lib.ptr(hits), _lib.stream_ptr()),
+                   "prg_patch_overlap_ragged_f64")
+    g = torch.nonzero(hits[:, 0] > 0).view(-1)                                    # THE synchronisation; ascending = (item, a, b)
+    p = torch.searchsorted(d_ho[1:].contiguous(), g, right=True)                  # the item of every listed node pair
+    local = g - d_ho[p]
+    mt = d_m[2 * p + 1]
+    a, b = torch.div(local, mt, rounding_mode="floor"), torch.remainder(local, mt)
+    listed = hits[g]
+    # |patch| = the entries of a table row that are not the pad, i.e. not the row count of the row's cloud
+    rows_of = torch.repeat_interleave(i64(np.diff(o)), d_m, output_size=int(to[-1] - to[0]))
+    size = (tables[int(to[0]):int(to[-1])] != rows_of[:, None].to(torch.int32)).sum(1).to(torch.float64)
+    size_a, size_b = size[d_to[2 * p] - int(to[0]) + a], size[d_to[2 * p + 1] - int(to[0]) + b]
+    overlap = (listed[:, 0].to(torch.float64) / size_a + listed[:, 1].to(torch.float64) / size_b) / 2
+    corr_offsets = torch.searchsorted(g, d_ho)
+    return torch.stack([a, b], 1).to(torch.int32), listed, overlap, corr_offsets
+
+
+def coarse_ground_truth(pyr: dict, *, fine_level: int, limit: int, radius: float) -> dict:
+    """The patch-level ground truth of a coarse-to-fine network on the dict `neighbor_pyramid` returns, bit for bit
+    `postprocess.coarse_ground_truth` (which states the definition and the returned keys): the stack is [src_0, tgt_0, src_1,
+    tgt_1, ...], the nodes are the last level, the fine points level `fine_level`.  One `node_patches_ragged` over all clouds
+    (local tables), one `patch_overlaps_ragged` over all items, then the stack indices with torch on the device.
+    Host synchronisations: one copy back of the two levels' `lengths` (the pyramid keeps them on the device) and the ONE of
+    `patch_overlaps_ragged`."""
+    limit = _check_patch_limit(limit, "coarse_ground_truth")
+    levels = len(pyr["points"])
+    if int(fine_level) != fine_level or not 0 <= fine_level < levels:
+        raise ValueError("fine_level must be in 0..num_stages-1")
+    fine, nodes = pyr["points"][int(fine_level)], pyr["points"][-1]
+    if not (fine.is_cuda and nodes.is_cuda):
+        raise _lib.PrgError("expected a pyramid on the HIP device (this package has no CPU path)")
+    dev = fine.device
+    lens = torch.stack([pyr["lengths"][int(fine_level)].to(torch.int64), pyr["lengths"][-1].to(torch.int64)]).cpu().numpy()
+    fl, nl = lens[0], lens[1]
+    if len(fl) % 2 or len(fl) < 2:
+        raise ValueError("the stack must hold an even number of clouds: [src_0, tgt_0, src_1, tgt_1, ...]")
+    fo, no = np.concatenate([[0], np.cumsum(fl)]), np.concatenate([[0], np.cumsum(nl)])
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)       # noqa: E731
+    assign, local, sizes = node_patches_ragged(fine, fo, nodes, no, limit)
+    corr, hits, overlap, corr_offsets = patch_overlaps_ragged(fine, fo, local, no, radius)
+    # local rows -> rows of the level's stack, as the pyramid's tables are indexed
+    node_base = torch.repeat_interleave(i32(no[:-1]), torch.from_numpy(fl).to(dev), output_size=int(fo[-1]))
+    point_base = torch.repeat_interleave(i32(fo[:-1]), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
+    rows_of = torch.repeat_interleave(i32(fl), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
+    assign = torch.where(assign >= 0, assign + node_base, assign)
+    table = torch.where(local != rows_of[:, None], local + point_base[:, None], torch.full_like(local, int(fo[-1])))
+    item = torch.searchsorted(corr_offsets[1:].contiguous(), torch.arange(corr.shape[0], device=dev), right=True)
+    d_no = i32(no)
+    node_corr = corr + torch.stack([d_no[2 * item], d_no[2 * item + 1]], 1)
+    return {"assign": assign, "table": table, "sizes": sizes, "node_corr": node_corr, "hits": hits, "overlap": overlap,
+            "corr_offsets": corr_offsets}
+
+
 def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
     """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
     float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as

@@ -428,6 +428,173 @@ def neighbor_pyramid(points: np.ndarray, lengths, num_stages: int, voxel_size: f
     return out
 
 
+def _check_patch_limit(limit) -> int:
+    if int(limit) != limit or not 1 <= limit <= 256:
+        raise ValueError("limit must be an integer in 1..256")
+    return int(limit)
+
+
+def node_patches(points: np.ndarray, nodes: np.ndarray, limit: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The point-to-node partition of a coarse-to-fine network and its inverse: (assign (n,) int32, table (m, limit) int32, sizes
+    (m,) int32) — the numpy specification of prg_patch_tables_ragged on prg_nearest_ragged_f64's output, bit for bit.
+    `d2, assign = nearest(points, nodes)`: every point belongs to its nearest node (dx*dx + dy*dy + dz*dz in float64, summed left
+    to right; the lowest node row wins a tie); a NaN point, and every point when `nodes` is empty, gets -1 and is in no patch.
+    sizes[k] is the number of points with assign == k.  Row k of table holds those points ordered by (d2 ascending, row ascending)
+    — a strict total order, so the table is unique; the first `limit` are kept and the remaining slots hold n = len(points), the
+    shadow row.  1 <= limit <= 256, else ValueError."""
+    limit = _check_patch_limit(limit)
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    nodes = np.asarray(nodes, dtype=np.float64).reshape(-1, 3)
+    n, m = len(points), len(nodes)
+    d2, assign = nearest(points, nodes)
+    table = np.full((m, limit), n, dtype=np.int32)
+    sizes = np.zeros(m, dtype=np.int32)
+    live = np.flatnonzero(assign >= 0)
+    if len(live):
+        k = assign[live].astype(np.int64)
+        sizes = np.bincount(k, minlength=m).astype(np.int32)
+        order = np.lexsort((live, d2[live], k))                      # by node, then d2, then row
+        k, i = k[order], live[order]
+        first = np.cumsum(sizes, dtype=np.int64) - sizes             # where node k's members begin in the ordered list
+        rank = np.arange(len(i), dtype=np.int64) - first[k]
+        keep = rank < limit
+        table[k[keep], rank[keep]] = i[keep]
+    return assign, table, sizes
+
+
+def patch_overlaps(src_points: np.ndarray, src_table: np.ndarray, tgt_points: np.ndarray, tgt_table: np.ndarray,
+                   radius: float, chunk: int = 1 << 20) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Which node patches of two clouds overlap, and by how much: (node_corr (P,2) int32, hits (P,2) int32, overlap (P,) float64)
+    — the numpy specification of prg_patch_overlap_ragged_f64 and of the Python layer on top of it, bit for bit.  Patch a of the
+    source is the entries of src_table[a] that are not the pad len(src_points) (`node_patches`' table), patch b of the target
+    likewise.  For every (a, b): hits_src = the points i of patch a that have a point j of patch b with dx*dx + dy*dy + dz*dz <
+    radius*radius — `radius_pairs`' expression and strict <, float64, dx = tgt.x - src.x, products written out and summed left to
+    right — and hits_tgt = the points j of patch b that have such an i.  node_corr lists every (a, b) with hits_src > 0 (which is
+    hits_tgt > 0) ordered by a, then b; hits its (hits_src, hits_tgt); overlap = (hits_src / |patch a| + hits_tgt / |patch b|) / 2
+    with float64 division and addition in exactly this order.  A NaN row never matches.  The target nodes are processed in blocks
+    of about `chunk` distance tests per source node, which bounds the temporaries and changes nothing else."""
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and > 0")
+    a = np.asarray(src_points, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(tgt_points, dtype=np.float64).reshape(-1, 3)
+    ta, tb = np.asarray(src_table, dtype=np.int64), np.asarray(tgt_table, dtype=np.int64)
+    if ta.ndim != 2 or tb.ndim != 2:
+        raise ValueError("patch tables must be (nodes, limit)")
+    ms, mt = len(ta), len(tb)
+    in_a, in_b = ta != len(a), tb != len(b)
+    r2 = np.float64(radius) * np.float64(radius)
+    bp = np.full((mt, tb.shape[1], 3), np.nan)                        # the target patches' points, NaN in the pad slots
+    bp[in_b] = b[tb[in_b]]
+    hs, ht = np.zeros((ms, mt), dtype=np.int32), np.zeros((ms, mt), dtype=np.int32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s in range(ms):
+            q = a[ta[s][in_a[s]]]
+            if not len(q) or not mt:
+                continue
+            step = max(1, int(chunk) // max(1, len(q) * tb.shape[1]))
+            for t in range(0, mt, step):
+                c = bp[None, t:t + step]
+                dx, dy, dz = c[..., 0] - q[:, None, None, 0], c[..., 1] - q[:, None, None, 1], c[..., 2] - q[:, None, None, 2]
+                w = dx * dx + dy * dy + dz * dz < r2                  # (points of patch a, target nodes, slots of patch b)
+                hs[s, t:t + step] = w.any(axis=2).sum(axis=0)
+                ht[s, t:t + step] = w.any(axis=0).sum(axis=1)
+    A, B = np.nonzero(hs > 0)                                         # row-major: a ascending, then b
+    hits = np.stack([hs[A, B], ht[A, B]], axis=1).astype(np.int32)
+    size_a, size_b = in_a.sum(axis=1).astype(np.float64), in_b.sum(axis=1).astype(np.float64)
+    overlap = (hits[:, 0].astype(np.float64) / size_a[A] + hits[:, 1].astype(np.float64) / size_b[B]) / np.float64(2)
+    return np.stack([A, B], axis=1).astype(np.int32), hits, overlap
+
+
+def coarse_ground_truth(pyramid: dict, *, fine_level: int, limit: int, radius: float) -> dict:
+    """The patch-level ground truth of a coarse-to-fine network from a `neighbor_pyramid` whose stack is [src_0, tgt_0, src_1,
+    tgt_1, ...] (an even number of clouds; item p is clouds 2p and 2p+1): host specification of `geometry.coarse_ground_truth`.
+    The nodes are the last level, the fine points level `fine_level` (0 <= fine_level < num_stages; with the last level every
+    node is its own patch).  Per cloud `node_patches(fine points, nodes, limit)`, per item `patch_overlaps(..., radius)` of its
+    two clouds.  Returns {"assign": (N_f,) int32 — per fine point its node as a row of the node level's STACK, -1 for none;
+    "table": (M, limit) int32 — per node its patch as rows of the fine level's stack, the pad is N_f, the level's row count,
+    exactly as the pyramid's neighbour tables are indexed; "sizes": (M,) int32; "node_corr": (P,2) int32 — (source node, target
+    node) as rows of the node level's stack, ordered by item, then source, then target; "hits": (P,2) int32; "overlap": (P,)
+    float64; "corr_offsets": (items+1,) int64 — item p's pairs are rows [corr_offsets[p], corr_offsets[p+1])}."""
+    limit = _check_patch_limit(limit)
+    levels = len(pyramid["points"])
+    if int(fine_level) != fine_level or not 0 <= fine_level < levels:
+        raise ValueError("fine_level must be in 0..num_stages-1")
+    fine = np.asarray(pyramid["points"][int(fine_level)], dtype=np.float64).reshape(-1, 3)
+    nodes = np.asarray(pyramid["points"][-1], dtype=np.float64).reshape(-1, 3)
+    fl = np.asarray(pyramid["lengths"][int(fine_level)], dtype=np.int64).reshape(-1)
+    nl = np.asarray(pyramid["lengths"][-1], dtype=np.int64).reshape(-1)
+    if len(fl) % 2 or len(fl) != len(nl):
+        raise ValueError("the stack must hold an even number of clouds: [src_0, tgt_0, src_1, tgt_1, ...]")
+    fo, no = np.concatenate([[0], np.cumsum(fl)]), np.concatenate([[0], np.cumsum(nl)])
+    assign, table, sizes, local = [np.zeros(0, np.int32)], [np.zeros((0, limit), np.int32)], [np.zeros(0, np.int32)], []
+    for c in range(len(fl)):
+        a, t, s = node_patches(fine[fo[c]:fo[c + 1]], nodes[no[c]:no[c + 1]], limit)
+        local.append(t)
+        assign.append(np.where(a >= 0, a + np.int32(no[c]), np.int32(-1)).astype(np.int32))
+        table.append(np.where(t < fl[c], t + np.int32(fo[c]), np.int32(len(fine))).astype(np.int32))
+        sizes.append(s)
+    corr, hits, overlap, co = [np.zeros((0, 2), np.int32)], [np.zeros((0, 2), np.int32)], [np.zeros(0)], [0]
+    for p in range(len(fl) // 2):
+        s, t = 2 * p, 2 * p + 1
+        nc, h, o = patch_overlaps(fine[fo[s]:fo[s + 1]], local[s], fine[fo[t]:fo[t + 1]], local[t], radius)
+        corr.append((nc + np.array([no[s], no[t]], dtype=np.int32)).astype(np.int32))
+        hits.append(h)
+        overlap.append(o)
+        co.append(co[-1] + len(nc))
+    return {"assign": np.concatenate(assign), "table": np.concatenate(table, 0), "sizes": np.concatenate(sizes),
+            "node_corr": np.concatenate(corr, 0), "hits": np.concatenate(hits, 0), "overlap": np.concatenate(overlap),
+            "corr_offsets": np.asarray(co, dtype=np.int64)}
+
+
+def node_patches_hip(clouds, limit: int, device="cuda"):
+    """[(points (n,3), nodes (m,3)), ...] -> [(assign, table, sizes), ...] as `node_patches(points, nodes, limit)` defines them,
+    for clouds that are on the host: everything uploaded once, ONE `geometry.node_patches_ragged` for the whole list, one copy
+    back."""
+    import torch
+
+    from . import _lib
+    from . import geometry as G
+    limit = _check_patch_limit(limit)
+    _lib.load()
+    _lib.require_gpu()
+    if not clouds:
+        return []
+    pts, nds = [_f64(p) for p, _ in clouds], [_f64(q) for _, q in clouds]
+    po = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
+    no = np.concatenate([[0], np.cumsum([len(q) for q in nds])]).astype(np.int64)
+    up = lambda rows: torch.from_numpy(np.concatenate(rows, 0)).to(device)       # noqa: E731
+    assign_d, table_d, sizes_d = G.node_patches_ragged(up(pts), po, up(nds), no, limit)
+    assign, table, sizes = assign_d.cpu().numpy(), table_d.cpu().numpy(), sizes_d.cpu().numpy()
+    return [(assign[po[c]:po[c + 1]].copy(), table[no[c]:no[c + 1]].copy(), sizes[no[c]:no[c + 1]].copy())
+            for c in range(len(clouds))]
+
+
+def patch_overlaps_hip(items, radius: float, device="cuda", prefilter: bool = True):
+    """[(src_points, src_table, tgt_points, tgt_table), ...] -> [(node_corr, hits, overlap), ...] as `patch_overlaps` defines them,
+    for clouds and tables that are on the host: everything uploaded once, ONE `geometry.patch_overlaps_ragged` for the whole
+    list, one copy back.  All tables must have the same number of columns."""
+    import torch
+
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    if not items:
+        return []
+    clouds = [_f64(c) for it in items for c in (it[0], it[2])]
+    tabs = [np.ascontiguousarray(t, dtype=np.int32) for it in items for t in (it[1], it[3])]
+    limit = _check_patch_limit(tabs[0].shape[1])
+    if any(t.ndim != 2 or t.shape[1] != limit for t in tabs):
+        raise ValueError("all patch tables must be (nodes, limit) with one limit")
+    offs = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+    toffs = np.concatenate([[0], np.cumsum([len(t) for t in tabs])]).astype(np.int64)
+    pts = torch.from_numpy(np.concatenate(clouds, 0)).to(device)
+    tables = torch.from_numpy(np.concatenate(tabs, 0)).to(device)
+    corr_d, hits_d, ov_d, co_d = G.patch_overlaps_ragged(pts, offs, tables, toffs, radius, prefilter=prefilter)
+    corr, hits, ov, co = corr_d.cpu().numpy(), hits_d.cpu().numpy(), ov_d.cpu().numpy(), co_d.cpu().numpy()
+    return [(corr[co[p]:co[p + 1]].copy(), hits[co[p]:co[p + 1]].copy(), ov[co[p]:co[p + 1]].copy()) for p in range(len(items))]
+
+
 def cloud_distance_metrics(d2_ab: np.ndarray, d2_ba: np.ndarray, thresholds=DISTANCE_THRESHOLDS) -> dict:
     """Distances between two clouds from the squared nearest-neighbour distances of both directions (host float64, over
     d = sqrt(d2)): n_a, n_b, chamfer = (mean d_ab + mean d_ba) / 2, hausdorff = the largest d, p50 / p95 / p99 of all the
