@@ -219,6 +219,24 @@ int prg_patch_overlap_ragged_f64(const double* pts, const int64_t* offsets, int 
                                  const int64_t* hit_offsets, int64_t total_node_pairs, int64_t max_item_pairs, double* boxes,
                                  int32_t* hits, void* stream);
 
+/* Fine-level ground truth: the label matrices of n_sel selected patch pairs.  pts (rows, 3) float64 DEVICE: the fine level's
+ * stack; table (nodes, limit) int32 DEVICE: every node's patch as rows of that stack — an entry outside [0, rows) is a pad, and
+ * the valid slots need not form a prefix; pairs (n_sel, 2) int32 DEVICE: rows of `table` as (a, b) = (source node, target node).
+ * labels (n_sel, limit+1, limit+1) uint8 DEVICE, values 0 / 1; with i = table[a][u], j = table[b][v] and K = limit:
+ *   labels[s][u][v] = both slots valid and dx*dx + dy*dy + dz*dz < radius*radius, dx = pts[j].x - pts[i].x (the expression and
+ *                     the strict < of prg_radius_count_ragged_f64 and prg_patch_overlap_ragged_f64)
+ *   labels[s][u][K] = slot u valid and row u holds no match;   labels[s][K][v] = slot v valid and column v holds no match
+ *   labels[s][K][K] = 0
+ * Validity is by index only: a valid slot that points at a NaN row matches nothing and has its slack label set.  A pair with a
+ * or b outside [0, nodes) stands for two empty patches: its matrix is all zero, and nothing of `table` is read for it.  Every
+ * byte of labels is written exactly once, the same byte on every run (one writer per byte: no atomics), and nothing else is;
+ * pts, table and pairs are not written.
+ * 0 <= rows < 2^31 (pts may be NULL only when rows == 0), 1 <= nodes < 2^31, 1 <= limit <= 256, 1 <= n_sel <= 2^24, radius
+ * finite and > 0; anything else or another null pointer fails with PRG_E_INVALID before any device call.  Asynchronous on
+ * `stream`; reads no device data on the host; allocates nothing.                                                               */
+int prg_patch_corr_labels_f64(const double* pts, int64_t rows, const int32_t* table, int64_t nodes, int limit,
+                              const int32_t* pairs, int64_t n_sel, double radius, uint8_t* labels, void* stream);
+
 /* Bytes of device workspace prg_voxel_grid_ragged needs for `total` input rows in `B` segments (non-decreasing in both).
  * Host-only arithmetic: no device call, usable without a GPU; this one returns the size, not a PRG_E_* code.            */
 size_t prg_voxel_grid_workspace_bytes(int64_t total, int B);

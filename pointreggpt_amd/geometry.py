@@ -615,6 +615,96 @@ def coarse_ground_truth(pyr: dict, *, fine_level: int, limit: int, radius: float
             "corr_offsets": corr_offsets}
 
 
+def patch_corr_labels(points: torch.Tensor, table: torch.Tensor, pairs: torch.Tensor, radius: float) -> torch.Tensor:
+    """The fine-level label matrices of S selected patch pairs, bit for bit `postprocess.patch_corr_labels` (which states the
+    definition): points (N,3) float64 device tensor (float32 is converted), the fine level's stack; table (M,K) int32 device
+    tensor, the patches as rows of that stack, an entry outside [0, N) a pad (`coarse_ground_truth`'s "table"); pairs (S,2) int32
+    device tensor, rows of `table` as (source node, target node).  Returns (S, K+1, K+1) torch.bool on the device, a view of the
+    uint8 buffer prg_patch_corr_labels_f64 wrote (one launch per 2^24 pairs).  S == 0 returns the empty tensor without a launch.
+    Host synchronisations: none."""
+    lib = _lib.load()
+    if not (points.is_cuda and table.is_cuda and pairs.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    if not (np.isfinite(radius) and radius > 0):
+        raise _lib.PrgError("patch_corr_labels: radius must be finite and > 0")
+    assert table.dtype == torch.int32 and table.dim() == 2 and pairs.dtype == torch.int32
+    limit = _check_patch_limit(table.shape[1], "patch_corr_labels")
+    points = points.to(torch.float64).contiguous().view(-1, 3)
+    table, pairs = table.contiguous(), pairs.contiguous().view(-1, 2)
+    N, M, S = points.shape[0], table.shape[0], pairs.shape[0]
+    if N >= 1 << 31 or M >= 1 << 31:
+        raise _lib.PrgError("patch_corr_labels: 2^31 or more rows")
+    if S == 0 or M == 0:                            # no pair, or no node: every pair stands for two empty patches
+        return torch.zeros((S, limit + 1, limit + 1), dtype=torch.bool, device=points.device)
+    labels = torch.empty((S, limit + 1, limit + 1), dtype=torch.uint8, device=points.device)
+    step = 1 << 24
+    for s0 in range(0, S, step):
+        part, out = pairs[s0:s0 + step], labels[s0:s0 + step]   # named: contiguous views of tensors that outlive the launch
+        _lib.check(lib.prg_patch_corr_labels_f64(_lib.ptr(points) if N else None, N, _lib.ptr(table), M, limit, _lib.ptr(part),
+                                                 part.shape[0], float(radius), _lib.ptr(out), _lib.stream_ptr()),
+                   "prg_patch_corr_labels_f64")
+    return labels.view(torch.bool)
+
+
+def select_node_corr(gt: dict, *, min_overlap: float = 0.1, num_targets: int = 128, keys: Optional[torch.Tensor] = None,
+                     generator: Optional[torch.Generator] = None):
+    """Which ground-truth node pairs the fine level trains on, bit for bit `postprocess.select_node_corr` on gt["overlap"] and
+    gt["corr_offsets"] (`coarse_ground_truth`'s dict, on the device): per item the rows with overlap > min_overlap, and of more
+    than `num_targets` of them the `num_targets` with the smallest (keys[r], r).  keys: (P,) float64 device tensor, one per row
+    of gt["node_corr"]; None draws torch.rand(P, dtype=float64, generator=generator) on the device — a uniform sample without
+    replacement.  Returns (rows (S,) int64 ascending, sel_offsets (items+1,) int64) on the device.  Two stable sorts (by key, then
+    by item and candidate flag) rank every candidate within its item; no kernel of this project's.
+    Host synchronisations: ONE, the number of selected rows inside `nonzero`."""
+    if int(num_targets) != num_targets or num_targets < 1:
+        raise ValueError("num_targets must be an integer >= 1")
+    overlap, co = gt["overlap"], gt["corr_offsets"]
+    if not (overlap.is_cuda and co.is_cuda):
+        raise _lib.PrgError("expected a ground truth on the HIP device (this package has no CPU path)")
+    dev = overlap.device
+    overlap, co = overlap.to(torch.float64).view(-1), co.to(torch.int64).view(-1)
+    P = overlap.shape[0]
+    if keys is None:
+        keys = torch.rand(P, dtype=torch.float64, device=dev, generator=generator)
+    keys = keys.to(device=dev, dtype=torch.float64).view(-1)
+    if keys.shape[0] != P:
+        raise ValueError("one key per listed node pair")
+    r = torch.arange(P, device=dev)
+    item = torch.searchsorted(co[1:].contiguous(), r, right=True)
+    cand = (overlap > min_overlap) & (r >= co[0]) & (r < co[-1])                  # rows outside every item are no candidates
+    by_key = torch.sort(keys, stable=True).indices                                # (key, row): rows arrive ascending
+    group = 2 * item + (~cand).to(torch.int64)                                    # per item its candidates first
+    grouped = torch.sort(group[by_key], stable=True)
+    order = by_key[grouped.indices]
+    rank = torch.empty_like(r)
+    rank[order] = r
+    keep = cand & (rank - torch.searchsorted(grouped.values, 2 * item) < int(num_targets))
+    rows = torch.nonzero(keep).view(-1)                                           # THE synchronisation; ascending
+    csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(keep.to(torch.int64), 0)])
+    return rows, csum[co]
+
+
+def fine_ground_truth(pyr: dict, gt: dict, *, fine_level: int, radius: float, min_overlap: float = 0.1, num_targets: int = 128,
+                      keys: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None) -> dict:
+    """The fine-level ground truth of a coarse-to-fine network on the dicts `neighbor_pyramid` and `coarse_ground_truth` return
+    (the same `fine_level`), bit for bit `postprocess.fine_ground_truth` (which states the definition and the returned keys):
+    `select_node_corr` picks the node pairs, two gathers give their patch tables and masks, ONE prg_patch_corr_labels_f64 writes
+    their label matrices.  Everything returned is on the device.
+    Host synchronisations: ONE, the number of selected node pairs inside `select_node_corr`."""
+    levels = len(pyr["points"])
+    if int(fine_level) != fine_level or not 0 <= fine_level < levels:
+        raise ValueError("fine_level must be in 0..num_stages-1")
+    fine, table = pyr["points"][int(fine_level)], gt["table"]
+    if not (fine.is_cuda and table.is_cuda):
+        raise _lib.PrgError("expected a pyramid and a ground truth on the HIP device (this package has no CPU path)")
+    rows, sel_offsets = select_node_corr(gt, min_overlap=min_overlap, num_targets=num_targets, keys=keys, generator=generator)
+    node_corr = gt["node_corr"][rows]
+    src_table, tgt_table = table[node_corr[:, 0].to(torch.int64)], table[node_corr[:, 1].to(torch.int64)]
+    n_fine = fine.view(-1, 3).shape[0]
+    return {"rows": rows, "sel_offsets": sel_offsets, "node_corr": node_corr, "src_table": src_table, "tgt_table": tgt_table,
+            "src_mask": src_table != n_fine, "tgt_mask": tgt_table != n_fine,
+            "labels": patch_corr_labels(fine, table, node_corr, radius)}
+
+
 def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.Tensor, valid: torch.Tensor):
     """Input of a scene-memory update for `voxel_grid_ragged`, without compaction (prg_merge_memory_f64): per scene the
     float32 ragged `memory` rows widened to float64 (valid) followed by the HW rows of xyz[b] with valid[b] as

@@ -546,6 +546,115 @@ def coarse_ground_truth(pyramid: dict, *, fine_level: int, limit: int, radius: f
             "corr_offsets": np.asarray(co, dtype=np.int64)}
 
 
+def patch_corr_labels(points: np.ndarray, table: np.ndarray, pairs: np.ndarray, radius: float, chunk: int = 1 << 22) -> np.ndarray:
+    """The fine-level ground truth of a coarse-to-fine network: per selected patch pair the (K+1, K+1) label matrix of its
+    optimal-transport loss, (S, K+1, K+1) bool — the numpy specification of prg_patch_corr_labels_f64, bit for bit.
+    `points` (N,3) float64 is the fine level's stack, `table` (M,K) int32 the patches as rows of that stack (`coarse_ground_truth`'s
+    "table"; an entry outside [0, N) is a pad, and the valid slots need not form a prefix), `pairs` (S,2) int32 rows of `table` as
+    (a, b) = (source node, target node).  With i = table[a, u] and j = table[b, v]: labels[s, u, v] = both slots valid and
+    dx*dx + dy*dy + dz*dz < radius*radius — `radius_pairs`' expression and strict <, float64, dx = points[j].x - points[i].x,
+    products written out and summed left to right; labels[s, u, K] = slot u valid and row u holds no match; labels[s, K, v] =
+    slot v valid and column v holds no match; labels[s, K, K] = False.  Validity is by index only: a valid slot that points at a
+    NaN row matches nothing, so its slack label is True.  A pair whose a or b lies outside [0, M) stands for two empty patches:
+    its matrix is all False.  1 <= K <= 256, radius finite and > 0, else ValueError.  The pairs are processed in blocks of about
+    `chunk` distance tests, which bounds the temporaries and changes nothing else."""
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and > 0")
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    tab = np.asarray(table, dtype=np.int64)
+    if tab.ndim != 2:
+        raise ValueError("the patch table must be (nodes, limit)")
+    K = _check_patch_limit(tab.shape[1])
+    prs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n, m, S = len(pts), len(tab), len(prs)
+    labels = np.zeros((S, K + 1, K + 1), dtype=bool)
+    if S == 0 or m == 0:
+        return labels
+    valid = (tab >= 0) & (tab < n)
+    pp = np.full((m, K, 3), np.nan)                                   # the patches' points, NaN in the pad slots
+    pp[valid] = pts[tab[valid]]
+    r2 = np.float64(radius) * np.float64(radius)
+    real = ((prs >= 0) & (prs < m)).all(axis=1)
+    step = max(1, int(chunk) // (K * K))
+    with np.errstate(over="ignore", invalid="ignore"):
+        for s0 in range(0, S, step):
+            sel = np.flatnonzero(real[s0:s0 + step]) + s0
+            if not len(sel):
+                continue
+            a, b = prs[sel, 0], prs[sel, 1]
+            A, B = pp[a][:, :, None, :], pp[b][:, None, :, :]
+            dx, dy, dz = B[..., 0] - A[..., 0], B[..., 1] - A[..., 1], B[..., 2] - A[..., 2]
+            w = dx * dx + dy * dy + dz * dz < r2                      # (pairs, slots of patch a, slots of patch b)
+            labels[sel, :K, :K] = w
+            labels[sel, :K, K] = valid[a] & ~w.any(axis=2)
+            labels[sel, K, :K] = valid[b] & ~w.any(axis=1)
+    return labels
+
+
+def select_node_corr(overlap: np.ndarray, corr_offsets: np.ndarray, keys: np.ndarray, *, min_overlap: float,
+                     num_targets: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Which ground-truth node pairs a coarse-to-fine consumer trains its fine level on: (rows (S,) int64, sel_offsets (items+1,)
+    int64) — host specification of `geometry.select_node_corr`.  The candidates of item p are the rows r in [corr_offsets[p],
+    corr_offsets[p+1]) with overlap[r] > min_overlap (strict); an item with more than `num_targets` candidates keeps the
+    `num_targets` with the smallest (keys[r], r) — with independent uniform keys a uniform sample without replacement.  `rows` is
+    ascending within each item, the items in order; item p's rows are rows[sel_offsets[p]:sel_offsets[p+1]].  keys is (P,)
+    float64; num_targets >= 1, else ValueError."""
+    if int(num_targets) != num_targets or num_targets < 1:
+        raise ValueError("num_targets must be an integer >= 1")
+    ov = np.asarray(overlap, dtype=np.float64).reshape(-1)
+    co = np.asarray(corr_offsets, dtype=np.int64).reshape(-1)
+    ky = np.asarray(keys, dtype=np.float64).reshape(-1)
+    if len(ky) != len(ov):
+        raise ValueError("one key per listed node pair")
+    rows, so = [np.zeros(0, dtype=np.int64)], [0]
+    for p in range(len(co) - 1):
+        r = np.arange(co[p], co[p + 1], dtype=np.int64)
+        r = r[ov[r] > min_overlap]
+        if len(r) > num_targets:
+            r = np.sort(r[np.lexsort((r, ky[r]))[:int(num_targets)]])
+        rows.append(r)
+        so.append(so[-1] + len(r))
+    return np.concatenate(rows), np.asarray(so, dtype=np.int64)
+
+
+def fine_ground_truth(pyramid: dict, gt: dict, *, fine_level: int, radius: float, keys, min_overlap: float = 0.1,
+                      num_targets: int = 128) -> dict:
+    """The fine-level ground truth of a coarse-to-fine network from a `neighbor_pyramid` and the `coarse_ground_truth` dict `gt`
+    of the same `fine_level`: host specification of `geometry.fine_ground_truth`.  `select_node_corr(gt["overlap"],
+    gt["corr_offsets"], keys, ...)` picks the node pairs, `patch_corr_labels(points[fine_level], gt["table"], node_corr, radius)`
+    labels them.  Returns {"rows": (S,) int64 — indices into gt["node_corr"]; "sel_offsets": (items+1,) int64; "node_corr": (S,2)
+    int32 = gt["node_corr"][rows]; "src_table", "tgt_table": (S,K) int32 = gt["table"] at the two columns of node_corr;
+    "src_mask", "tgt_mask": (S,K) bool — True where the table entry is not the pad; "labels": (S,K+1,K+1) bool}."""
+    levels = len(pyramid["points"])
+    if int(fine_level) != fine_level or not 0 <= fine_level < levels:
+        raise ValueError("fine_level must be in 0..num_stages-1")
+    fine = np.asarray(pyramid["points"][int(fine_level)], dtype=np.float64).reshape(-1, 3)
+    table = np.asarray(gt["table"], dtype=np.int32)
+    rows, sel_offsets = select_node_corr(gt["overlap"], gt["corr_offsets"], keys, min_overlap=min_overlap, num_targets=num_targets)
+    node_corr = np.asarray(gt["node_corr"], dtype=np.int32).reshape(-1, 2)[rows]
+    src_table, tgt_table = table[node_corr[:, 0]], table[node_corr[:, 1]]
+    return {"rows": rows, "sel_offsets": sel_offsets, "node_corr": node_corr, "src_table": src_table, "tgt_table": tgt_table,
+            "src_mask": src_table != len(fine), "tgt_mask": tgt_table != len(fine),
+            "labels": patch_corr_labels(fine, table, node_corr, radius)}
+
+
+def patch_corr_labels_hip(points, table, pairs, radius: float, device="cuda") -> np.ndarray:
+    """`patch_corr_labels(points, table, pairs, radius)` for arrays that are on the host: uploaded once, ONE
+    `geometry.patch_corr_labels`, one copy back."""
+    import torch
+
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    tab = np.ascontiguousarray(table, dtype=np.int32)
+    if tab.ndim != 2:
+        raise ValueError("the patch table must be (nodes, limit)")
+    up = lambda a: torch.tensor(a, device=device)                                # noqa: E731 (a copy: `a` may be read-only)
+    labels = G.patch_corr_labels(up(_f64(points)), up(tab), up(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)), radius)
+    return labels.cpu().numpy()
+
+
 def node_patches_hip(clouds, limit: int, device="cuda"):
     """[(points (n,3), nodes (m,3)), ...] -> [(assign, table, sizes), ...] as `node_patches(points, nodes, limit)` defines them,
     for clouds that are on the host: everything uploaded once, ONE `geometry.node_patches_ragged` for the whole list, one copy
