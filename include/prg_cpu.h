@@ -63,6 +63,13 @@ int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps
                              const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
                              const float* keep_u, int64_t keep_slabs, float* out, int B, int S);
 
+/* ---- conv3x3_c64_kernel's step schedule (pointreggpt_amd/csrc/c64_schedule.h, shared with the kernel) as event rows ----
+ * One role's instruction stream in program order: role 0 = producer waves, 1 = consumer waves; depth = halo register sets (2 or
+ * 3).  Row = 6 int32 {role, kind (0 issue loads, 1 write LDS, 2 read LDS, 3 barrier), halo, register set, LDS buffer, tile
+ * step}, -1 where a field does not apply.  capacity = 0 only counts.  tests/test_c64_schedule.py proves the barrier counts and
+ * the buffer / register lifetimes from these rows for every step count before a kernel built on them is launched.           */
+int prg_cpu_c64_schedule(int nsteps, int depth, int role, int32_t* events, int64_t capacity, int64_t* n_events);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ PROTOTYPES = {
     "prg_cpu_maskunet_forward": (C.c_int, [_P, _P, _P, _I, _I]),
     "prg_cpu_sampler_run": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _I, _I]),
     "prg_cpu_sampler_run_keep": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _I]),
+    "prg_cpu_c64_schedule": (C.c_int, [_I, _I, _I, _P, _L, C.POINTER(_L)]),
 }
 
 _lib = None

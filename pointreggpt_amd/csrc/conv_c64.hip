@@ -14,18 +14,26 @@
 //   waves 0-3  CONSUMERS (2 pixel halves x 2 channel halves of a 8 x 32 pixel x 64 channel tile): 144 MFMAs per tile,
 //              fragments prefetched three reads ahead; epilogue = bias, GroupNorm partial sums (the deterministic butterfly
 //              of conv_ws.hip), bf16 and DIRECT stores: a v_permlane32_swap pairs the two lane halves' channel quads, so
-//              every lane stores 16 contiguous bytes (no LDS stage, nothing for the producers to drain);
+//              every lane stores 16 contiguous bytes (no LDS stage, nothing for the producers to drain).  The four pixel
+//              rows' accumulators finish one halo row apart (the row-reuse skew): rows 0-2 are packed, summed and stored
+//              INSIDE the MFMA stream, in the shadows of the next halo row's MFMAs; only row 3, the butterfly and the
+//              atomics come after the tile's last MFMA;
 //   waves 4-7  PRODUCERS: write halo s+1 (loaded a whole step earlier; optional fused GroupNorm + (scale+1, shift) + SiLU
 //              prologue of the previous Block, sd:690-696), re-issue the registers for halo s+2.  A step is ~5000 cycles,
-//              so plain loads with compiler-managed waits are enough: every load has a full step to land.
+//              so plain loads with compiler-managed waits are enough: every load has a full step to land.  (A third
+//              register set, loads two steps ahead, was built and measured 9-22 % SLOWER per launch: at 254 registers
+//              hipcc puts an s_waitcnt vmcnt(0) at the top of the three-step body.  DESIGN.md 4.1.)
 //
-// ONE barrier per tile, between the consumers' MFMAs and their epilogue: "halo s+1 written; buffer s & 1 no longer read".
-// The epilogue of tile s therefore runs while the producers already write halo s+2 (round 2 had two barriers and an LDS
+// ONE barrier per tile, behind the consumers' MFMAs: "halo s+1 written; buffer s & 1 no longer read".  The step schedule
+// (which halo is issued, written and read in which step, in which register set and LDS buffer, and how many barriers each
+// wave class executes for a given step count) is c64_schedule.h; tests/test_c64_schedule.py proves it on the CPU.
+// The rest of the epilogue of tile s runs while the producers already write halo s+2 (round 2 had two barriers and an LDS
 // stage: producers idle during the epilogue, consumers idle during the drain — the two were additive, 81 / 122 us).
 // LDS: 2 halos x 340 rows x 144 B (padded rows: conflict-free ds_read_b128 with immediate tap offsets).
 #include <atomic>
 #include <cstdlib>
 
+#include "c64_schedule.h"
 #include "conv.h"
 
 namespace prg {
@@ -166,6 +174,9 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
   const int nsteps = inter ? (widx < nx ? (nx - widx + wpx - 1) / wpx : 0) : qx + (widx < rx ? 1 : 0);
   const int stride = inter ? wpx : 1;
   if (nsteps == 0) return;
+  // halo register sets of the producers (c64_schedule.h).  A third set (loads two steps ahead) was built and measured slower:
+  // profiles/c64_pipeline_stamps_and_variants.txt.
+  constexpr int DEPTH = 2;
 
   // ---------------------------------------------------------------------------------------------------
   if (wave < 4) {
@@ -196,7 +207,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     };
     c64_barrier();                                         // halo 0 is in LDS (producers' prologue)
     for (int s = 0; s < nsteps; ++s) {
-      const char* const xb = smem + (size_t)(s & 1) * AH_BYTES + x0off;
+      const char* const xb = smem + (size_t)c64_lds_buf(s) * AH_BYTES + x0off;
       // Round 5: the accumulators START at the bias (16 values per lane, re-read from LDS per tile: they are dead again before the
       // fragment sets fill up) instead of at zero — the epilogue's 64 bias additions per tile and wave are gone; the sum's rounding
       // order changes (bias first), far below the bf16 / f16 output rounding.
@@ -207,12 +218,53 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 #pragma unroll
         for (int pt = 0; pt < 4; ++pt) { acc[pt][4 * q] = b4.x; acc[pt][4 * q + 1] = b4.y; acc[pt][4 * q + 2] = b4.z; acc[pt][4 * q + 3] = b4.w; }
       }
+      // ---- epilogue state, ahead of the MFMAs: lane holds pixel (row 4 wm + pt, col l31), channels wn*32 + 8 q + 4 hi + {0..3}
+      int tb, ty0, tx0;
+      c64_tile(first + s * stride, tiles_x, tiles_y, tb, ty0, tx0);
+      char* const obase = reinterpret_cast<char*>(L.out) +
+                          ((((size_t)tb * d.Hout + ty0 + wm * 4) * d.Wout + tx0 + l31) * 64 + wn * 32 + 8 * hi) * 2;
+      const size_t orow = (size_t)d.Wout * 128;          // output bytes per image row
+      float V[8];                                          // [sum | sumsq][q]
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        V[q] = 0.0f;
+        V[4 + q] = 0.0f;
+      }
+      uint32_t pk[8];
+      // 8-channel chunk q of pixel row pt: statistics (per q the sums run pt-major, then r: the order they have always had, so the
+      // float sums keep their bits) and packing.  `pin`: inside the MFMA stream the results are made opaque where they are
+      // computed, or the compiler sinks the arithmetic behind the loop again (it did: 167 of 206 VALU instructions).
+      auto pack_chunk = [&](const int pt, const int q, const bool pin) __attribute__((always_inline)) {
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          v[r] = acc[pt][4 * q + r];   // (the bias rode in as the accumulators' initial value)
+          V[q] += v[r];
+          V[4 + q] = fmaf(v[r], v[r], V[4 + q]);
+        }
+        pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : c64_pack(v[0], v[1]);
+        pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : c64_pack(v[2], v[3]);
+        if (pin) asm volatile("" : "+v"(V[q]), "+v"(V[4 + q]), "+v"(pk[2 * q]), "+v"(pk[2 * q + 1]));
+      };
+      // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper half
+      // of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m, half 1 with
+      // those of chunk 2m+1: one 16-byte store each
+      auto store_half = [&](const int pt, const int m) __attribute__((always_inline)) {
+        const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
+        const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
+        const c64_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
+        *reinterpret_cast<c64_u32x4*>(obase + pt * orow + m * 32) = o;
+      };
       // Round 6: ROW REUSE.  Tap (dy, dx) of pixel row pt reads halo row pt + dy: the twelve (pt, dy) pairs of one (dx, k-step) touch
       // only SIX halo rows.  The four accumulators are independent chains, so they are skewed by one tap row: fragment (halo row r,
       // dx, c) is read ONCE and feeds acc[r] at tap (0, dx), acc[r-1] at (1, dx) and acc[r-2] at (2, dx) back to back — 72 reads
       // per tile instead of 144 (0.5 ds_read_b128 per MFMA), no extra registers, and every accumulator still sees its MFMAs in
       // tap-major order: the outputs are bit-identical.  Measured -1.0 ... -1.5 % per launch (profiles/r06_ab_c64_row_reuse.txt): the
       // fragment reads are a small term of this kernel (profiles/r06_c64_half_reads_bound.txt).  Ring of four fragments, three ahead.
+      //
+      // The skew also finishes the accumulators one halo row apart: acc[pt] has its last MFMA at the end of halo row pt + 2.  Its
+      // epilogue (no LDS in it, so it needs no barrier) is issued in the MFMA shadows of halo row pt + 3: chunk q at fragments 1, 3,
+      // 5, 7 of that row, the two stores at fragments 9 and 10.  Only acc[3] is finished behind the barrier.
       constexpr int FD = 3, FR = 4, NF = 72;
       c64_bf16x8 fr[FR];
       auto foff = [](int n) { return ((n / 12) * HP + (n / 4) % 3) * ROWB + (n & 3) * 32; };   // n = (r * 3 + dx) * 4 + c
@@ -227,49 +279,21 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
           const int pt = r - dy;
           if (pt >= 0 && pt < 4) acc[pt] = mma(wf[dy * 3 + dx][c], fr[n % FR], acc[pt]);
         }
+        if (r >= 3) {
+          const int j = n % 12;
+          if ((j & 1) && j < 8) pack_chunk(r - 3, j >> 1, true);
+          if (j == 9) store_half(r - 3, 0);
+          if (j == 10) store_half(r - 3, 1);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
-      // ---- epilogue: lane holds pixel (row 4 wm + pt, col l31), channels wn*32 + 8 q + 4 hi + {0..3}
-      int tb, ty0, tx0;
-      c64_tile(first + s * stride, tiles_x, tiles_y, tb, ty0, tx0);
       // the partial sums of the previous tile have left this CU before the barrier its ticket is taken behind
       if (fuse_stats && L.gn_tickets) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       c64_barrier();                                       // halo s+1 is written; nobody reads buffer s & 1 any more
-      float V[8];                                          // [sum | sumsq][q]
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        V[q] = 0.0f;
-        V[4 + q] = 0.0f;
-      }
-      char* const obase = reinterpret_cast<char*>(L.out) +
-                          ((((size_t)tb * d.Hout + ty0 + wm * 4) * d.Wout + tx0 + l31) * 64 + wn * 32 + 8 * hi) * 2;
-      const size_t orow = (size_t)d.Wout * 128;          // output bytes per image row
+      for (int q = 0; q < 4; ++q) pack_chunk(3, q, false);
 #pragma unroll
-      for (int pt = 0; pt < 4; ++pt) {
-        uint32_t pk[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            v[r] = acc[pt][4 * q + r];   // (the bias rode in as the accumulators' initial value)
-            V[q] += v[r];
-            V[4 + q] = fmaf(v[r], v[r], V[4 + q]);
-          }
-          pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : c64_pack(v[0], v[1]);
-          pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : c64_pack(v[2], v[3]);
-        }
-        // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper half
-        // of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m, half 1 with
-        // those of chunk 2m+1: one 16-byte store each
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-          const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-          const c64_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-          *reinterpret_cast<c64_u32x4*>(obase + pt * orow + m * 32) = o;
-        }
-      }
+      for (int m = 0; m < 2; ++m) store_half(3, m);
       if (fuse_stats) {
         // 8 full-wave sums with a halving butterfly (conv_ws.hip's, one level shorter): fixed order, deterministic
         const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
@@ -310,7 +334,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       }
     }
     if (fuse_stats && L.gn_tickets) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (nsteps & 1) c64_barrier();                         // the producers' padding step
+    for (int p = c64_consumer_pad_barriers(nsteps, DEPTH); p > 0; --p) c64_barrier();   // the producers' padding steps
     c64_barrier();                                         // matches the producers' final barrier (ticket of the last tile)
     return;
   }
@@ -359,7 +383,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     longlong2 fs_n = make_longlong2(0, 0);                  // PRO == 2: (sum, sumsq) of the 8-channel unit's group, fixed point
     auto issue = [&](int s, c64_u32x4(&h)[KU]) {           // loads of halo s (clamped to the last tile: harmless reloads)
       int b, y0, x0;
-      c64_tile(first + min(s, nsteps - 1) * stride, tiles_x, tiles_y, b, y0, x0);
+      c64_tile(first + c64_tile_of_halo(s, nsteps) * stride, tiles_x, tiles_y, b, y0, x0);
       okmask_nxt = m_valid & ~((y0 == 0 ? m_top : 0u) | (y0 + TH == Hl ? m_bot : 0u) | (x0 == 0 ? m_left : 0u) |
                                (x0 + TW == Wl ? m_right : 0u));
       const int soff = __builtin_amdgcn_readfirstlane((((b * d.Hin + (y0 >> d.ups)) * d.Win) + (x0 >> d.ups)) * 128);   // the SGPR offset
@@ -388,7 +412,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       }
     };
     auto write = [&](int s, c64_u32x4(&h)[KU]) {           // halo s -> LDS buffer s & 1
-      char* dst = ah + (size_t)(s & 1) * AH_BYTES;
+      char* dst = ah + (size_t)c64_lds_buf(s) * AH_BYTES;
       const float a8[8] = {ca[0].x, ca[0].y, ca[0].z, ca[0].w, ca[1].x, ca[1].y, ca[1].z, ca[1].w};
       const float b8[8] = {cb[0].x, cb[0].y, cb[0].z, cb[0].w, cb[1].x, cb[1].y, cb[1].z, cb[1].w};
 #pragma unroll
@@ -436,7 +460,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
         }
       }
     };
-    issue(0, hA);
+    static_assert(c64_reg_set(0, DEPTH) == 0 && c64_reg_set(1, DEPTH) == 1 && c64_issued_in_step(0, DEPTH) == 2);
+    issue(0, hA);                                          // (c64_schedule.h: halo 0, write 0, halo 1)
     adopt();
     write(0, hA);
     issue(1, hB);
@@ -461,8 +486,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     };
     // Two steps per iteration (the register set of a halo is a compile-time choice); an odd step count is padded with
     // one step of clamped reloads that nobody reads, so the loop body stays branch-free between a load and its use and
-    // the compiler's s_waitcnt vmcnt(N) counts stay exact.
-    const int n2 = (nsteps + 1) & ~1;
+    // the compiler's s_waitcnt vmcnt(N) counts stay exact.  The consumers execute the padding step as a bare barrier.
+    const int n2 = c64_padded_steps(nsteps, DEPTH);
 #pragma unroll 1
     for (int s = 0; s < n2; s += 2) {
       // during the consumers' MFMAs of step s and their epilogue of step s-1: the loads of halo s+2, then halo s+1 into

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/prg_cpu.h"
+#include "c64_schedule.h"
 
 namespace {
 
@@ -832,6 +833,24 @@ int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps
       }
   }
   for (size_t i = 0; i < x.size(); ++i) out[i] = (x[i] + 1.0f) * 0.5f;
+  return PRG_OK;
+}
+
+// The step schedule of conv3x3_c64_kernel (c64_schedule.h: the helper the kernel itself uses), written out as event rows.
+int prg_cpu_c64_schedule(int nsteps, int depth, int role, int32_t* events, int64_t capacity, int64_t* n_events) {
+  CPU_CHECK(nsteps >= 1 && (depth == 2 || depth == 3) && (role == prg::C64_PRODUCER || role == prg::C64_CONSUMER) && n_events &&
+                capacity >= 0 && (events || capacity == 0),
+            "prg_cpu_c64_schedule: bad arguments");
+  int64_t n = 0;
+  prg::c64_emit_schedule(role, nsteps, depth, [&](int r, int kind, int halo, int set, int buf, int tile) {
+    if (n < capacity) {
+      int32_t* e = events + n * prg::C64_EVENT_INTS;
+      e[0] = r; e[1] = kind; e[2] = halo; e[3] = set; e[4] = buf; e[5] = tile;
+    }
+    ++n;
+  });
+  *n_events = n;
+  CPU_CHECK(n <= capacity || capacity == 0, "prg_cpu_c64_schedule: the event buffer is too small");
   return PRG_OK;
 }
 
