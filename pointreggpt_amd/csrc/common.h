@@ -29,6 +29,12 @@ int fail(int code, const std::string& msg);
     if (!(cond)) return ::prg::fail(PRG_E_INVALID, std::string(msg) + " [" #cond "]");           \
   } while (0)
 
+// the two checks every ragged pair-buffer entry point repeats; fn = the entry point's name, a string literal.  The arguments are
+// plain identifiers and are not parenthesised, so the condition quoted in the message reads as it would written out.
+#define PRG_CHECK_PAIRS(fn, n_pairs) PRG_CHECK(n_pairs > 0 && n_pairs <= 65535, fn ": n_pairs out of range")   // gridDim.y
+#define PRG_CHECK_RADIUS(fn, radius) \
+  PRG_CHECK(radius > 0 && radius <= 1.79769313486231570815e308, fn ": radius must be finite and > 0")
+
 #define PRG_LAUNCH_CHECK()                                                                       \
   do {                                                                                           \
     hipError_t _e = hipGetLastError();                                                           \

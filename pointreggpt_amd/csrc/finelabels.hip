@@ -3,12 +3,11 @@
 // with a slack row and a slack column for the patch points without a partner — the target of the consumers' optimal-transport
 // loss.  postprocess.patch_corr_labels states it in numpy; everything here is bit for bit that.
 //
-// The test is rp_within's (radiuspairs.hip) and po_hits_kernel's (patches.hip): b - a, dx*dx + dy*dy + dz*dz < r*r in float64,
-// products written out, summed left to right, strict <, -ffp-contract=off — so a patch pair that prg_patch_overlap_ragged_f64
-// lists as overlapping has a match in its matrix, and one it does not list has none.
+// The test is allpairs.h's dist2 < r * r on slots read by its load_patch_slot, as in po_hits_kernel (patches.hip) — so a patch
+// pair that prg_patch_overlap_ragged_f64 lists as overlapping has a match in its matrix, and one it does not list has none.
 //
 // fl_labels_kernel is po_hits_kernel's idiom turned by 90 degrees: ONE WAVE per selected pair, four waves per workgroup that never
-// wait for each other (no __syncthreads; a wavefront-wide fence around the staging as in ns_select_kernel).  The SOURCE patch is
+// wait for each other (no __syncthreads; allpairs.h's wave_lds_fence behind the staging).  The SOURCE patch is
 // staged in this wave's LDS (structure of arrays, NCH * 1.5 KB per wave; NCH = ceil(limit / 64) chunks, a template parameter so the
 // chunk loops unroll), the TARGET patch sits in registers, one point per lane and chunk: the lanes run along v, so one store
 // instruction writes 64 consecutive bytes of a label row.  One sweep over u, the source point broadcast from LDS to all lanes:
@@ -23,7 +22,7 @@
 // Memory safety does not lean on device data being well-formed: a pair row outside [0, nodes) gives an all-zero matrix and reads
 // nothing of `table`; a table entry outside [0, rows) is a pad and reads nothing of `pts`.
 // hipcc (gfx950, -O3): register and LDS use are listed in DESIGN.md §4.11 (tools/kernel_regs.sh); no scratch, no fma.
-#include "common.h"
+#include "allpairs.h"
 
 namespace prg {
 
@@ -47,7 +46,6 @@ __global__ __launch_bounds__(64 * FL_WAVES) void fl_labels_kernel(const double* 
   }
   const int32_t* ta = table + (int64_t)pa * limit;
   const int32_t* tb = table + (int64_t)pb * limit;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double* sx = s_a[wave][0];
   double* sy = s_a[wave][1];
   double* sz = s_a[wave][2];
@@ -57,23 +55,14 @@ __global__ __launch_bounds__(64 * FL_WAVES) void fl_labels_kernel(const double* 
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int slot = c * 64 + lane;
-    double x = nan, y = nan, z = nan;
-    bool ok = false;
-    bx[c] = by[c] = bz[c] = nan;
-    ok_b[c] = false;
+    const bool in = slot < limit;                               // a slot beyond the patch is a pad
+    double x, y, z;
+    ok_a[c] = __ballot(load_patch_slot(pts, 0, rows, in ? ta[slot] : -1, x, y, z));
+    ok_b[c] = load_patch_slot(pts, 0, rows, in ? tb[slot] : -1, bx[c], by[c], bz[c]);
     found[c] = false;
-    if (slot < limit) {
-      const int32_t i = ta[slot], j = tb[slot];
-      ok = i >= 0 && i < rows;
-      if (ok) { x = pts[3 * (int64_t)i]; y = pts[3 * (int64_t)i + 1]; z = pts[3 * (int64_t)i + 2]; }
-      ok_b[c] = j >= 0 && j < rows;
-      if (ok_b[c]) { bx[c] = pts[3 * (int64_t)j]; by[c] = pts[3 * (int64_t)j + 1]; bz[c] = pts[3 * (int64_t)j + 2]; }
-    }
     sx[slot] = x; sy[slot] = y; sz[slot] = z;
-    ok_a[c] = __ballot(ok);
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");        // the source patch is written before any lane reads it
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_fence();                                             // the source patch is written before any lane reads it
 #pragma unroll
   for (int cu = 0; cu < NCH; ++cu) {
     const int nu = min(64, limit - cu * 64);
@@ -85,8 +74,7 @@ __global__ __launch_bounds__(64 * FL_WAVES) void fl_labels_kernel(const double* 
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int v = c * 64 + lane;
-        const double dx = bx[c] - ax, dy = by[c] - ay, dz = bz[c] - az;
-        const bool w = dx * dx + dy * dy + dz * dz < r2;
+        const bool w = dist2(bx[c], by[c], bz[c], ax, ay, az) < r2;
         found[c] |= w;
         any |= __ballot(w);
         if (v < limit) row[v] = (uint8_t)w;
@@ -116,16 +104,13 @@ int prg_patch_corr_labels_f64(const double* pts, int64_t rows, const int32_t* ta
   PRG_CHECK(nodes >= 1 && nodes < ((int64_t)1 << 31), "prg_patch_corr_labels_f64: nodes out of range");
   PRG_CHECK(limit >= 1 && limit <= 256, "prg_patch_corr_labels_f64: limit out of range (1..256)");
   PRG_CHECK(n_sel >= 1 && n_sel <= ((int64_t)1 << 24), "prg_patch_corr_labels_f64: n_sel out of range (1..2^24)");
-  PRG_CHECK(radius > 0 && radius <= 1.79769313486231570815e308, "prg_patch_corr_labels_f64: radius must be finite and > 0");
+  PRG_CHECK_RADIUS("prg_patch_corr_labels_f64", radius);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((n_sel + FL_WAVES - 1) / FL_WAVES), 1, 1);
   const double r2 = radius * radius;
-  switch ((limit + 63) / 64) {
-    case 1: fl_labels_kernel<1><<<grid, 64 * FL_WAVES, 0, s>>>(pts, rows, table, nodes, limit, pairs, n_sel, r2, labels); break;
-    case 2: fl_labels_kernel<2><<<grid, 64 * FL_WAVES, 0, s>>>(pts, rows, table, nodes, limit, pairs, n_sel, r2, labels); break;
-    case 3: fl_labels_kernel<3><<<grid, 64 * FL_WAVES, 0, s>>>(pts, rows, table, nodes, limit, pairs, n_sel, r2, labels); break;
-    default: fl_labels_kernel<4><<<grid, 64 * FL_WAVES, 0, s>>>(pts, rows, table, nodes, limit, pairs, n_sel, r2, labels); break;
-  }
+  dispatch_chunks(limit, [&](auto nch) {
+    fl_labels_kernel<decltype(nch)::value><<<grid, 64 * FL_WAVES, 0, s>>>(pts, rows, table, nodes, limit, pairs, n_sel, r2, labels);
+  });
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }

@@ -5,7 +5,7 @@
 // pixel indices and the float32 depths come out bit-identical to the reference.
 //
 // sd = denoising_diffusion_pytorch/successive_ddnm_diffusion.py, dc = depth_correction_pytorch/depth_correction.py
-#include "common.h"
+#include "allpairs.h"
 
 namespace prg {
 
@@ -266,19 +266,21 @@ __global__ void occlusion_filter_kernel(const float* __restrict__ depth, const u
 // float64, < r^2 like the KD-tree radius search)?  Clouds are a few thousand points after the 0.025 voxel grid, so
 // the exact all-pairs test with B streamed through LDS is microseconds per pair on one CU and needs no grid or tree;
 // one workgroup per (pair, direction, 256-query slab), a count per (pair, direction) by atomicAdd of integers (exact).
+// The distance and the segment decode are allpairs.h's.  The loop stays its own, not sweep<1>: one query per thread, no prefetch,
+// and an early-out once a row is found, which the sweep would drop (68 VGPRs and 7 waves per SIMD against 60 and 8 here).
 __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offs,
                                                             double r2, int32_t* __restrict__ counts) {
   __shared__ double tile[256 * 3];
   const int pair = blockIdx.y, dir = blockIdx.z;
-  const int64_t a0 = offs[2 * pair + dir], a1 = offs[2 * pair + dir + 1];
-  const int64_t b0 = dir == 0 ? offs[2 * pair + 1] : offs[2 * pair], b1 = dir == 0 ? offs[2 * pair + 2] : offs[2 * pair + 1];
-  const int64_t q = a0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (a0 + (int64_t)blockIdx.x * 256 >= a1) return;            // whole slab beyond this cloud (uniform exit)
+  const PairSegments g = pair_segments(offs, pair, dir);
+  const int64_t a1 = g.a1, b1 = g.b1;
+  const int64_t q = g.a0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g.a0 + (int64_t)blockIdx.x * 256 >= a1) return;          // whole slab beyond this cloud (uniform exit)
   const bool live = q < a1;
   double qx = 0, qy = 0, qz = 0;
   if (live) { qx = pts[3 * q]; qy = pts[3 * q + 1]; qz = pts[3 * q + 2]; }
   bool found = false;
-  for (int64_t t0 = b0; t0 < b1; t0 += 256) {
+  for (int64_t t0 = g.b0; t0 < b1; t0 += 256) {
     const int64_t n = min((int64_t)256, b1 - t0);
     __syncthreads();
     if (threadIdx.x < n) {
@@ -288,10 +290,8 @@ __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __rest
     }
     __syncthreads();
     if (!found) {
-      for (int j = 0; j < (int)n; ++j) {
-        const double dx = tile[j] - qx, dy = tile[256 + j] - qy, dz = tile[512 + j] - qz;
-        if (dx * dx + dy * dy + dz * dz < r2) found = true;
-      }
+      for (int j = 0; j < (int)n; ++j)
+        if (dist2(tile[j], tile[256 + j], tile[512 + j], qx, qy, qz) < r2) found = true;
     }
   }
   const unsigned long long hits = __ballot(live && found);
@@ -299,9 +299,9 @@ __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __rest
 }
 
 // ---- nearest point of the other cloud (dataset comparison) -----------------------------------------------------------
-// For every row of cloud A of a pair: the smallest squared distance to a row of cloud B (the overlap kernel's expression,
-// float64, left to right) and the lowest local row of B that attains it.  Exact all-pairs search, B streamed through LDS in
-// structure-of-arrays tiles like the overlap kernel, but with no early-out: the inner loop is the whole cost, and it is
+// For every row of cloud A of a pair: the smallest squared distance to a row of cloud B (allpairs.h's dist2) and the lowest
+// local row of B that attains it.  Exact all-pairs search, B streamed through LDS in structure-of-arrays tiles like the overlap
+// kernel, but with no early-out: the inner loop is the whole cost, and it is
 // bound by the float64 VALU — 3 subtractions, 3 products and 2 sums at 4 cycles each per wave, a compare and 3 selects on
 // top, some 44 cycles per (wave, candidate, query) — not by the LDS: a candidate is 3 ds_read_b64 at one address in every
 // lane (broadcast, 2 LDS cycles each).  With one query per thread the four SIMDs of a CU would ask for 24 LDS cycles per 44,
@@ -314,23 +314,24 @@ __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __rest
 // registers before that arithmetic starts, so the load is hidden within one workgroup as well as across them.
 // Each query visits B in ascending row order and is replaced on a strict < only, so the blocking changes no bit: NaN
 // (query or candidate) and a distance that overflows to +inf never win, and such a row ends at +inf / -1.
+// The loop is allpairs.h's sweep and stays written out: through sweep<NN_Q> and a lambda hipcc keeps the running minimum twice,
+// as a 2-vector and as scalars (5 selects per candidate and query for 3, 87 VGPRs): 4.48 ms against 3.88 ms on 250 pairs of ~4.5 k
+// rows (profiles/allpairs_refactor_ab.txt).  A dead query lane holds 0 here and the store below is guarded.
 constexpr int NN_Q = 2;        // queries per thread
-constexpr int NN_TILE = 256;   // rows of the other cloud per LDS tile = threads per workgroup
 
-__global__ __launch_bounds__(NN_TILE) void nearest_ragged_kernel(const double* __restrict__ pts,
+__global__ __launch_bounds__(AP_TILE) void nearest_ragged_kernel(const double* __restrict__ pts,
                                                                  const int64_t* __restrict__ offs, double* __restrict__ d2_out,
                                                                  int32_t* __restrict__ idx_out) {
-  __shared__ double tile[NN_TILE * 3];
-  const int pair = blockIdx.y, dir = blockIdx.z;
-  const int64_t a0 = offs[2 * pair + dir], a1 = offs[2 * pair + dir + 1];
-  const int64_t b0 = dir == 0 ? offs[2 * pair + 1] : offs[2 * pair], b1 = dir == 0 ? offs[2 * pair + 2] : offs[2 * pair + 1];
-  const int64_t slab = a0 + (int64_t)blockIdx.x * (NN_TILE * NN_Q);
+  __shared__ double tile[AP_TILE * 3];
+  const PairSegments g = pair_segments(offs, blockIdx.y, blockIdx.z);
+  const int64_t a1 = g.a1, b0 = g.b0, b1 = g.b1;
+  const int64_t slab = g.a0 + (int64_t)blockIdx.x * (AP_TILE * NN_Q);
   if (slab >= a1) return;                                       // whole slab beyond this cloud (uniform exit)
   double qx[NN_Q], qy[NN_Q], qz[NN_Q], best[NN_Q];
   int32_t arg[NN_Q];
 #pragma unroll
   for (int k = 0; k < NN_Q; ++k) {
-    const int64_t q = slab + k * NN_TILE + threadIdx.x;
+    const int64_t q = slab + k * AP_TILE + threadIdx.x;
     qx[k] = qy[k] = qz[k] = 0;
     if (q < a1) { qx[k] = pts[3 * q]; qy[k] = pts[3 * q + 1]; qz[k] = pts[3 * q + 2]; }
     best[k] = __builtin_inf();
@@ -338,29 +339,28 @@ __global__ __launch_bounds__(NN_TILE) void nearest_ragged_kernel(const double* _
   }
   double nx = 0, ny = 0, nz = 0;                                // this thread's row of the next tile
   if (b0 + threadIdx.x < b1) { nx = pts[3 * (b0 + threadIdx.x)]; ny = pts[3 * (b0 + threadIdx.x) + 1]; nz = pts[3 * (b0 + threadIdx.x) + 2]; }
-  for (int64_t t0 = b0; t0 < b1; t0 += NN_TILE) {
-    const int n = (int)min((int64_t)NN_TILE, b1 - t0);
+  for (int64_t t0 = b0; t0 < b1; t0 += AP_TILE) {
+    const int n = (int)min((int64_t)AP_TILE, b1 - t0);
     __syncthreads();                                            // the previous tile has been read by every wave
     tile[threadIdx.x] = nx;
-    tile[NN_TILE + threadIdx.x] = ny;
-    tile[2 * NN_TILE + threadIdx.x] = nz;
+    tile[AP_TILE + threadIdx.x] = ny;
+    tile[2 * AP_TILE + threadIdx.x] = nz;
     __syncthreads();
-    const int64_t r = t0 + NN_TILE + threadIdx.x;
+    const int64_t r = t0 + AP_TILE + threadIdx.x;
     if (r < b1) { nx = pts[3 * r]; ny = pts[3 * r + 1]; nz = pts[3 * r + 2]; }
     const int32_t base = (int32_t)(t0 - b0);
     for (int j = 0; j < n; ++j) {
-      const double bx = tile[j], by = tile[NN_TILE + j], bz = tile[2 * NN_TILE + j];
+      const double bx = tile[j], by = tile[AP_TILE + j], bz = tile[2 * AP_TILE + j];
 #pragma unroll
       for (int k = 0; k < NN_Q; ++k) {
-        const double dx = bx - qx[k], dy = by - qy[k], dz = bz - qz[k];
-        const double d2 = dx * dx + dy * dy + dz * dz;
+        const double d2 = dist2(bx, by, bz, qx[k], qy[k], qz[k]);
         if (d2 < best[k]) { best[k] = d2; arg[k] = base + j; }
       }
     }
   }
 #pragma unroll
   for (int k = 0; k < NN_Q; ++k) {
-    const int64_t q = slab + k * NN_TILE + threadIdx.x;
+    const int64_t q = slab + k * AP_TILE + threadIdx.x;
     if (q < a1) { d2_out[q] = best[k]; idx_out[q] = arg[k]; }
   }
 }
@@ -515,9 +515,9 @@ int prg_nearest_ragged_f64(const double* pts, const int64_t* offsets, int n_pair
   PRG_CHECK(pts && offsets && d2 && idx, "prg_nearest_ragged_f64: null pointer");
   PRG_CHECK(n_pairs > 0 && n_pairs <= 65535 && max_cloud > 0 && max_cloud < ((int64_t)1 << 31),
             "prg_nearest_ragged_f64: bad arguments");
-  const int64_t slab = NN_TILE * NN_Q;
+  const int64_t slab = AP_TILE * NN_Q;
   const dim3 grid((unsigned)((max_cloud + slab - 1) / slab), (unsigned)n_pairs, 2);
-  nearest_ragged_kernel<<<grid, NN_TILE, 0, (hipStream_t)stream>>>(pts, offsets, d2, idx);
+  nearest_ragged_kernel<<<grid, AP_TILE, 0, (hipStream_t)stream>>>(pts, offsets, d2, idx);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }

@@ -9,15 +9,15 @@
 // Rank by counting — no sort, no atomics.  (d2, j) is a strict total order on a row's matches (j is unique within a row), so
 //   rank(t) = #{ u : (d2_u, j_u) < (d2_t, j_t) }
 // is a permutation of 0 .. m-1: match t goes to slot rank(t) if that is below `limit`, slots min(m, limit) .. limit-1 take the
-// pad, and every slot of the row has exactly one writer.  d2 is recomputed from pts with radiuspairs.hip's expression (b - a,
-// the three products written out and summed left to right in float64, -ffp-contract=off: no fma), so the order is the one
-// postprocess.radius_neighbors states in numpy, bit for bit; the list does not carry distances, and three gathered rows per
-// match are cheaper than 8 more bytes per list row written by fill and read again here.
+// pad, and every slot of the row has exactly one writer.  d2 is recomputed from pts with allpairs.h's dist2, the expression that
+// produced the list, and compared with its `before`, so the order is the one postprocess.radius_neighbors states in numpy, bit
+// for bit; the list does not carry distances, and three gathered rows per match are cheaper than 8 more bytes per list row
+// written by fill and read again here.
 //
 // Launch shape: one wave per query row, NB_ROWS = 4 rows per 256-thread workgroup, grid (ceil(max_cloud / 4), n_pairs).  A wave
 // owns NB_CHUNK (d2, j) slots of LDS (structure of arrays, 12 bytes per match, 24 KB per workgroup: six workgroups per CU) and
-// never waits for another wave: there is no __syncthreads, the waves of a workgroup have different m.  Within a wave the LDS
-// returns in order, so a wavefront-wide fence (which pins the compiler) is all a staged chunk needs before it is read.
+// never waits for another wave: there is no __syncthreads, the waves of a workgroup have different m; a staged chunk needs
+// allpairs.h's wave_lds_fence before it is read, and no more.
 //   for every 64 matches t (one per lane: the targets)        -- iterates, m is unbounded
 //     for every chunk of NB_CHUNK matches u                   -- iterates, m is unbounded
 //       stage the chunk (lane-strided: j from corr, the row from pts, d2) unless it is the row's only chunk and already there
@@ -34,17 +34,12 @@
 // corr is never read at or beyond list_rows, and a j outside the candidate cloud is clamped into it before pts is read.  On
 // count / fill's output neither clamp changes anything.
 // hipcc (gfx950, -O3): ns_select_kernel 56 VGPRs, 60 SGPRs, 24576 bytes LDS, 6 waves per SIMD, no scratch, no fma.
-#include "common.h"
+#include "allpairs.h"
 
 namespace prg {
 
 constexpr int NB_ROWS = 4;       // query rows (waves) per workgroup
 constexpr int NB_CHUNK = 512;    // matches staged in LDS per wave
-
-// (du, ju) < (dt, jt) as 0 / 1, without a branch
-__device__ __forceinline__ int32_t before(double du, int32_t ju, double dt, int32_t jt) {
-  return (int32_t)(du < dt) | ((int32_t)(du == dt) & (int32_t)(ju < jt));
-}
 
 __global__ __launch_bounds__(64 * NB_ROWS) void ns_select_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offs,
                                                                  const int64_t* __restrict__ row_start,
@@ -56,11 +51,12 @@ __global__ __launch_bounds__(64 * NB_ROWS) void ns_select_kernel(const double* _
   __shared__ __attribute__((aligned(16))) int32_t s_j[NB_ROWS][NB_CHUNK];
   const int pair = blockIdx.y;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t a0 = offs[2 * pair], b0 = offs[2 * pair + 1], b1 = offs[2 * pair + 2];
+  const PairSegments g = pair_segments(offs, pair);
+  const int64_t b0 = g.b0;
   const int64_t i = (int64_t)blockIdx.x * NB_ROWS + wave;       // query row, local; the same in every lane of the wave
-  const int64_t q = a0 + i;
-  if (q >= b0) return;                                          // beyond this query cloud (wave-uniform: no barrier below)
-  const int32_t nb = (int32_t)(b1 - b0);
+  const int64_t q = g.a0 + i;
+  if (q >= g.a1) return;                                        // beyond this query cloud (wave-uniform: no barrier below)
+  const int32_t nb = (int32_t)(g.b1 - b0);
   const int32_t base = index_base ? index_base[pair] : 0;
   const int32_t padv = pad ? pad[pair] : nb;
   int32_t* __restrict__ out = table + (table_offsets[pair] + i) * (int64_t)limit;
@@ -79,8 +75,7 @@ __global__ __launch_bounds__(64 * NB_ROWS) void ns_select_kernel(const double* _
   auto match = [&](int64_t t, double& d2, int32_t& j) {
     j = corr[2 * (s + t) + 1];
     const int64_t r = b0 + min(max(j, 0), nb - 1);
-    const double dx = pts[3 * r] - ax, dy = pts[3 * r + 1] - ay, dz = pts[3 * r + 2] - az;
-    d2 = dx * dx + dy * dy + dz * dz;
+    d2 = dist2(pts[3 * r], pts[3 * r + 1], pts[3 * r + 2], ax, ay, az);
   };
 
   for (int64_t t0 = 0; t0 < m; t0 += 64) {
@@ -93,8 +88,7 @@ __global__ __launch_bounds__(64 * NB_ROWS) void ns_select_kernel(const double* _
       const int n = (int)min((int64_t)NB_CHUNK, m - c0);
       const int n4 = (n + 3) & ~3;                              // the walk below takes four at a time
       if (t0 == 0 || m > NB_CHUNK) {                            // a row of one chunk stages it once
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the previous chunk has been read by every lane
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_fence();                                       // the previous chunk has been read by every lane
         for (int u = lane; u < n4; u += 64) {
           double d2 = inf;                                      // filler up to a multiple of four: below no match, equal to none
           int32_t j = 0;
@@ -102,8 +96,7 @@ __global__ __launch_bounds__(64 * NB_ROWS) void ns_select_kernel(const double* _
           sd[u] = d2;
           sj[u] = j;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // ... and this one written before any lane reads it
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_fence();                                       // ... and this one written before any lane reads it
       }
       for (int u = 0; u < n4; u += 4) {                         // every lane reads the same address: LDS broadcasts
         const double2 d01 = *reinterpret_cast<const double2*>(sd + u), d23 = *reinterpret_cast<const double2*>(sd + u + 2);
@@ -130,7 +123,7 @@ int prg_radius_select_ragged_f64(const double* pts, const int64_t* offsets, int 
                                  void* stream) {
   PRG_CHECK(pts && offsets && row_start && table_offsets && table && (corr || list_rows == 0),
             "prg_radius_select_ragged_f64: null pointer");
-  PRG_CHECK(n_pairs > 0 && n_pairs <= 65535, "prg_radius_select_ragged_f64: n_pairs out of range");
+  PRG_CHECK_PAIRS("prg_radius_select_ragged_f64", n_pairs);
   PRG_CHECK(max_cloud > 0 && max_cloud < ((int64_t)1 << 31) && list_rows >= 0, "prg_radius_select_ragged_f64: bad sizes");
   PRG_CHECK(limit >= 1 && limit <= 1024, "prg_radius_select_ragged_f64: limit out of range (1..1024)");
   const dim3 grid((unsigned)((max_cloud + NB_ROWS - 1) / NB_ROWS), (unsigned)n_pairs, 1);

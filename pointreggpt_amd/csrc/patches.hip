@@ -10,16 +10,16 @@
 //    is a permutation of 0 .. members-1, member i goes to slot rank(i) if that is below `limit`, and the member of rank 0 writes
 //    the node's size: every written slot has one writer — no sort, no atomics, the same bytes on every run.  The slots no member
 //    reaches, and the sizes of nodes without members, come from pt_pad_kernel, launched first on the same stream.
-//    Launch shape of pt_rank_kernel — the all-pairs siblings' (nearest_ragged_kernel, rp_sweep): one thread per point, the (d2,
-//    assign) of the thread's own cloud streamed through LDS in 256-row tiles, the next tile fetched into registers before the
-//    arithmetic on the current one starts.  Both loops iterate, so a node may own any number of points (a whole cloud).  Per (i,
+//    Launch shape of pt_rank_kernel — that of allpairs.h's sweep, with its own loop because it streams (d2, assign) and not
+//    points: one thread per point, the (d2, assign) of the thread's own cloud through LDS in 256-row tiles, the next tile fetched
+//    into registers before the arithmetic on the current one starts; the order is allpairs.h's `before`.  Both loops iterate,
+//    so a node may own any number of points (a whole cloud).  Per (i,
 //    u): an int32 compare, two float64 compares, an int32 compare and two conditional increments against 12 bytes of LDS broadcast;
 //    O(rows^2) per cloud like the nearest-node sweep that produced its input, with about a third of that sweep's arithmetic.
 //
 // 2. prg_patch_overlap_ragged_f64 tests patch against patch for every (source node, target node) of every item and writes the
 //    two hit counts densely, (a, b) row-major: the Python layer's nonzero is then already ordered by (a, b), and no count / scan /
-//    fill is needed.  The test is rp_within's (radiuspairs.hip): b - a, dx*dx + dy*dy + dz*dz < r*r in float64, products written
-//    out, summed left to right, strict <, -ffp-contract=off.
+//    fill is needed.  The test is allpairs.h's dist2 < r * r, the one of radiuspairs.hip; a slot is read by its load_patch_slot.
 //    One THREAD per node pair decides whether the pair needs the test at all; one WAVE then runs the test for each surviving
 //    pair of its 64 (ballot, then a wave-uniform loop over the set bits).  The pre-filter — optional: `boxes` NULL switches it
 //    off — compares the patches' bounding boxes, which po_box_kernel wrote to caller-provided scratch first: a pair is skipped
@@ -31,7 +31,7 @@
 //    chunks, a template parameter so the chunk loops unroll), the target patch staged in this wave's LDS (structure of arrays,
 //    NCH * 1.5 KB per wave); one sweep over the target points, each broadcast to all lanes, gives both counts: a lane's sticky
 //    "found" is hits_src after ballot + popcount, and a non-zero ballot of the test itself means target point j was hit.
-//    Waves never wait for each other: no __syncthreads, a wavefront-wide fence around the staging as in ns_select_kernel.
+//    Waves never wait for each other: no __syncthreads, allpairs.h's wave_lds_fence around the staging.
 //
 // Memory safety does not lean on device data being well-formed: an assign outside [0, nodes) counts as -1; a table entry outside
 // [0, rows of its cloud) is a pad (its point never matches); a dense output position outside [0, total_node_pairs) is not
@@ -40,18 +40,13 @@
 // pt_pad_kernel 24 and po_box_kernel 32 VGPRs; no scratch, no fma.
 // Measured: 250 items of two ~4.6 k-row clouds with ~400 nodes each, limit 64: tables 1.95 ms next to the nearest
 // sweep's 1.26 ms; overlap 0.70 ms for 4.1e7 node pairs with the pre-filter, 11.9 ms without it.
-#include "common.h"
+#include "allpairs.h"
 
 namespace prg {
 
 constexpr int PT_TILE = 256;     // rows per LDS tile = threads per workgroup of pt_rank_kernel
 constexpr int PT_ROWS = 4;       // table rows (waves) per workgroup of the pad and box kernels
 constexpr int PO_THREADS = 256;  // node pairs per workgroup of po_hits_kernel
-
-// (du, u) < (dt, t) as 0 / 1, without a branch
-__device__ __forceinline__ int32_t pt_before(double du, int32_t u, double dt, int32_t t) {
-  return (int32_t)(du < dt) | ((int32_t)(du == dt) & (int32_t)(u < t));
-}
 
 // every slot of every node of every cloud = pad, every size = 0
 __global__ __launch_bounds__(64 * PT_ROWS) void pt_pad_kernel(const int64_t* __restrict__ offs, int limit,
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(PT_TILE) void pt_rank_kernel(const double* __restri
     for (int j = 0; j < n; ++j) {
       const int32_t same = (int32_t)(s_a[j] == ai);
       cnt += same;
-      rank += same & pt_before(s_d[j], base + j, di, li);
+      rank += same & before(s_d[j], base + j, di, li);
     }
   }
   if (ai >= 0) {
@@ -141,9 +136,8 @@ __global__ __launch_bounds__(64 * PT_ROWS) void po_box_kernel(const double* __re
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   double lx = inf, ly = inf, lz = inf, hx = -inf, hy = -inf, hz = -inf;
   for (int s = lane; s < limit; s += 64) {
-    const int32_t j = tables[row * limit + s];
-    if (j >= 0 && j < nc) {
-      const double x = pts[3 * (c0 + j)], y = pts[3 * (c0 + j) + 1], z = pts[3 * (c0 + j) + 2];
+    double x, y, z;
+    if (load_patch_slot(pts, c0, nc, tables[row * limit + s], x, y, z)) {
       lx = fmin(lx, x); ly = fmin(ly, y); lz = fmin(lz, z);
       hx = fmax(hx, x); hy = fmax(hy, y); hz = fmax(hz, z);
     }
@@ -189,7 +183,6 @@ __global__ __launch_bounds__(PO_THREADS) void po_hits_kernel(const double* __res
   if (!todo) return;                                            // wave-uniform, and there is no barrier below
   const int64_t a0 = offs[2 * item], b0 = offs[2 * item + 1];
   const int64_t na = b0 - a0, nb = offs[2 * item + 2] - b0;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double* sx = s_b[wave][0];
   double* sy = s_b[wave][1];
   double* sz = s_b[wave][2];
@@ -203,35 +196,26 @@ __global__ __launch_bounds__(PO_THREADS) void po_hits_kernel(const double* __res
     double ax[NCH], ay[NCH], az[NCH];
     bool found[NCH];
     int kb = 0;                                                 // 1 + the last slot of the target patch that holds a point
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the previous pair's patch has been read by every lane
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();                                           // the previous pair's patch has been read by every lane
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int s = c * 64 + lane;
-      ax[c] = ay[c] = az[c] = nan;
+      const bool in = s < limit;                                // a slot beyond the patch is a pad
+      double x, y, z;
+      load_patch_slot(pts, a0, na, in ? ta[s] : -1, ax[c], ay[c], az[c]);
+      const unsigned long long has = __ballot(load_patch_slot(pts, b0, nb, in ? tb[s] : -1, x, y, z));
       found[c] = false;
-      double x = nan, y = nan, z = nan;
-      bool ok = false;
-      if (s < limit) {
-        const int32_t i = ta[s], j = tb[s];
-        if (i >= 0 && i < na) { ax[c] = pts[3 * (a0 + i)]; ay[c] = pts[3 * (a0 + i) + 1]; az[c] = pts[3 * (a0 + i) + 2]; }
-        ok = j >= 0 && j < nb;
-        if (ok) { x = pts[3 * (b0 + j)]; y = pts[3 * (b0 + j) + 1]; z = pts[3 * (b0 + j) + 2]; }
-      }
       sx[s] = x; sy[s] = y; sz[s] = z;
-      const unsigned long long has = __ballot(ok);
       if (has) kb = c * 64 + 64 - __builtin_clzll(has);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // ... and this one written before any lane reads it
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();                                           // ... and this one written before any lane reads it
     int32_t hit_tgt = 0;
     for (int j = 0; j < kb; ++j) {                              // every lane reads the same address: LDS broadcasts
       const double bx = sx[j], by = sy[j], bz = sz[j];
       unsigned long long any = 0;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        const double dx = bx - ax[c], dy = by - ay[c], dz = bz - az[c];
-        const bool w = dx * dx + dy * dy + dz * dz < r2;
+        const bool w = dist2(bx, by, bz, ax[c], ay[c], az[c]) < r2;
         found[c] |= w;
         any |= __ballot(w);
       }
@@ -258,7 +242,7 @@ int prg_patch_tables_ragged(const double* d2, const int32_t* assign, const int64
                             int64_t max_nodes, int limit, const int64_t* table_offsets, const int32_t* index_base,
                             const int32_t* pad, int32_t* table, int32_t* sizes, void* stream) {
   PRG_CHECK(d2 && assign && offsets && table_offsets && table && sizes, "prg_patch_tables_ragged: null pointer");
-  PRG_CHECK(n_pairs > 0 && n_pairs <= 65535, "prg_patch_tables_ragged: n_pairs out of range");
+  PRG_CHECK_PAIRS("prg_patch_tables_ragged", n_pairs);
   PRG_CHECK(max_cloud > 0 && max_cloud < ((int64_t)1 << 31) && max_nodes > 0 && max_nodes < ((int64_t)1 << 31),
             "prg_patch_tables_ragged: bad sizes");
   PRG_CHECK(limit >= 1 && limit <= 256, "prg_patch_tables_ragged: limit out of range (1..256)");
@@ -277,13 +261,13 @@ int prg_patch_overlap_ragged_f64(const double* pts, const int64_t* offsets, int 
                                  const int64_t* hit_offsets, int64_t total_node_pairs, int64_t max_item_pairs, double* boxes,
                                  int32_t* hits, void* stream) {
   PRG_CHECK(pts && offsets && tables && table_offsets && hit_offsets && hits, "prg_patch_overlap_ragged_f64: null pointer");
-  PRG_CHECK(n_pairs > 0 && n_pairs <= 65535, "prg_patch_overlap_ragged_f64: n_pairs out of range");
+  PRG_CHECK_PAIRS("prg_patch_overlap_ragged_f64", n_pairs);
   PRG_CHECK(max_nodes > 0 && max_nodes < ((int64_t)1 << 31), "prg_patch_overlap_ragged_f64: bad sizes");
   PRG_CHECK(total_node_pairs > 0 && total_node_pairs <= ((int64_t)1 << 28) && max_item_pairs > 0 &&
                 max_item_pairs <= total_node_pairs,
             "prg_patch_overlap_ragged_f64: node pairs out of range (1..2^28)");
   PRG_CHECK(limit >= 1 && limit <= 256, "prg_patch_overlap_ragged_f64: limit out of range (1..256)");
-  PRG_CHECK(radius > 0 && radius <= 1.79769313486231570815e308, "prg_patch_overlap_ragged_f64: radius must be finite and > 0");
+  PRG_CHECK_RADIUS("prg_patch_overlap_ragged_f64", radius);
   hipStream_t s = (hipStream_t)stream;
   if (boxes) {
     const dim3 box_grid((unsigned)((max_nodes + PT_ROWS - 1) / PT_ROWS), (unsigned)n_pairs, 2);
@@ -292,16 +276,10 @@ int prg_patch_overlap_ragged_f64(const double* pts, const int64_t* offsets, int 
   }
   const dim3 grid((unsigned)((max_item_pairs + PO_THREADS - 1) / PO_THREADS), (unsigned)n_pairs, 1);
   const double r2 = radius * radius;
-  switch ((limit + 63) / 64) {
-    case 1: po_hits_kernel<1><<<grid, PO_THREADS, 0, s>>>(pts, offsets, tables, table_offsets, limit, radius, r2, hit_offsets,
-                                                          total_node_pairs, boxes, hits); break;
-    case 2: po_hits_kernel<2><<<grid, PO_THREADS, 0, s>>>(pts, offsets, tables, table_offsets, limit, radius, r2, hit_offsets,
-                                                          total_node_pairs, boxes, hits); break;
-    case 3: po_hits_kernel<3><<<grid, PO_THREADS, 0, s>>>(pts, offsets, tables, table_offsets, limit, radius, r2, hit_offsets,
-                                                          total_node_pairs, boxes, hits); break;
-    default: po_hits_kernel<4><<<grid, PO_THREADS, 0, s>>>(pts, offsets, tables, table_offsets, limit, radius, r2, hit_offsets,
-                                                           total_node_pairs, boxes, hits); break;
-  }
+  dispatch_chunks(limit, [&](auto nch) {
+    po_hits_kernel<decltype(nch)::value><<<grid, PO_THREADS, 0, s>>>(pts, offsets, tables, table_offsets, limit, radius, r2,
+                                                                     hit_offsets, total_node_pairs, boxes, hits);
+  });
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }

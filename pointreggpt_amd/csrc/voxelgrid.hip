@@ -11,7 +11,7 @@
 //   2. vg_dims_kernel     per-segment dx,dy,dz = max index + 1 by integer atomic max.
 //   3. vg_keys_kernel     sort key (segment << 46 | voxel key) per valid row, all-ones for the rest; per-segment status.
 //   4. rocprim::radix_sort_pairs (key, row) — stable, so equal keys stay in input order.  The only library primitive.
-//   5. vg_count_heads / vg_scan_blocks / vg_reduce_runs: head flags where the key changes, a two-level exclusive scan gives
+//   5. vg_count_heads / scan.h's scan_blocks / vg_reduce_runs: head flags where the key changes, a two-level exclusive scan gives
 //      every voxel its output slot, and the thread that owns a run's head walks the run and sums it in order.  No float atomics:
 //      the output is a pure function of the input whatever the launch geometry and whatever else is in the call.
 #include <cstring>
@@ -19,6 +19,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
+#include "scan.h"
 
 namespace prg {
 
@@ -175,38 +176,6 @@ __global__ __launch_bounds__(256) void vg_count_heads(const unsigned long long* 
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;   // n is wave-uniform
   __syncthreads();
   if (threadIdx.x == 0) block_heads[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// exclusive scan of block_heads[0..n) in place by ONE workgroup; block_heads[n] = number of voxels of the whole call
-__global__ __launch_bounds__(1024) void vg_scan_blocks(uint32_t* __restrict__ block_heads, int n) {
-  __shared__ uint32_t wtot[16];
-  __shared__ uint32_t carry_s;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + threadIdx.x;
-    const uint32_t v = i < n ? block_heads[i] : 0u;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    uint32_t woff = 0, all = 0;
-    for (int k = 0; k < 16; ++k) {
-      if (k < w) woff += wtot[k];
-      all += wtot[k];
-    }
-    const uint32_t carry = carry_s;
-    if (i < n) block_heads[i] = carry + woff + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 0) carry_s = carry + all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) block_heads[n] = carry_s;
 }
 
 __global__ __launch_bounds__(256) void vg_reduce_runs(const double* __restrict__ pts, const unsigned long long* __restrict__ keys,
@@ -371,7 +340,7 @@ int prg_voxel_grid_ragged(const double* pts, const uint8_t* valid, const int64_t
 
   vg_count_heads<<<L.n_blocks, 256, 0, s>>>(dk.current(), total, heads);
   PRG_LAUNCH_CHECK();
-  vg_scan_blocks<<<1, 1024, 0, s>>>(heads, L.n_blocks);
+  scan_blocks<uint32_t, true><<<1, kScanThreads, 0, s>>>(heads, L.n_blocks);   // heads[n_blocks] = voxels of the whole call
   PRG_LAUNCH_CHECK();
   vg_reduce_runs<<<L.n_blocks, 256, 0, s>>>(pts, dk.current(), dv.current(), total, B, heads, L.n_blocks, out, out_offsets);
   PRG_LAUNCH_CHECK();

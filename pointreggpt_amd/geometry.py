@@ -116,6 +116,37 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().to(torch.float32)
 
 
+def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """bool (reinterpreted) or any other dtype (converted) -> flat contiguous uint8; None stays None."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).view(-1)
+
+
+def _dev_i32(a, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+
+def _dev_i64(a, device) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)
+
+
+def _ragged_f64(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: Optional[int] = None):
+    """What every ragged float64 function starts with: both tensors on the device, float64 / int64, contiguous, pts as
+    (total,3); with `n_pairs`, offsets must be the 2*n_pairs+1 of a pair buffer.  -> (pts, offsets, total).  A buffer without
+    rows comes back as one row of zeros, with total == 0: a tensor without elements has no address to pass."""
+    if not (pts.is_cuda and offsets.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
+    assert n_pairs is None or offsets.numel() == 2 * int(n_pairs) + 1
+    pts = pts.contiguous().view(-1, 3)
+    total = pts.shape[0]
+    if total == 0:
+        pts = torch.zeros((1, 3), dtype=torch.float64, device=pts.device)
+    return pts, offsets.contiguous(), total
+
+
 def depth2pc_tensor(depth: torch.Tensor, intrinsic: torch.Tensor, *, clip=(0, 10), invalid_num=None):
     """(B,1,H,W) depth, (B,3,3) K -> pc (B,HW,3) (invalid -> NaN / invalid_num), valid (B,HW) bool  (sd:176-209)."""
     lib = _lib.load()
@@ -138,7 +169,7 @@ def pc2depth_tensor(pc: torch.Tensor, valid: Optional[torch.Tensor], intrinsic: 
     pc, K = _f32(pc), _f32(intrinsic)
     B, N, _ = pc.shape
     H, W = int(image_size[0]), int(image_size[1])
-    v8 = None if valid is None else valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous().to(torch.uint8)
+    v8 = _u8(valid)
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=pc.device)
     mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=pc.device)
     _lib.check(lib.prg_pc2depth(_lib.ptr(pc), _lib.ptr(v8), _lib.ptr(K), _lib.ptr(depth), _lib.ptr(mask), B, N, H, W,
@@ -235,17 +266,10 @@ def voxel_grid_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     bit for bit what `postprocess.native_voxel_down_sample` returns for its valid rows; status 1 = non-finite row,
     2 = grid too large (such a segment has no rows).  Nothing is copied to the host and nothing synchronises."""
     lib = _lib.load()
-    if not (pts.is_cuda and offsets.is_cuda):
-        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
-    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
-    pts = pts.contiguous().view(-1, 3)
-    offsets = offsets.contiguous()
-    total, B = pts.shape[0], offsets.numel() - 1
-    v8 = None
-    if valid is not None:
-        v8 = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous().to(torch.uint8)
-        v8 = v8.view(-1)
-        assert v8.numel() == total
+    pts, offsets, total = _ragged_f64(pts, offsets)
+    B = offsets.numel() - 1
+    v8 = _u8(valid)
+    assert v8 is None or v8.numel() == total
     out = torch.empty((max(total, 1), 3), dtype=torch.float64, device=pts.device)
     out_offsets = torch.empty((B + 1,), dtype=torch.int64, device=pts.device)
     status = torch.empty((B,), dtype=torch.int32, device=pts.device)
@@ -264,13 +288,7 @@ def nearest_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_c
     the lowest local row that attains it, bit for bit `postprocess.nearest`; +inf / -1 where there is none.  Entries of rows
     outside every segment are +inf / -1 as allocated here (the kernel does not touch them).  Nothing synchronises."""
     lib = _lib.load()
-    if not (pts.is_cuda and offsets.is_cuda):
-        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
-    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
-    assert offsets.numel() == 2 * int(n_pairs) + 1
-    pts = pts.contiguous().view(-1, 3)
-    offsets = offsets.contiguous()
-    total = pts.shape[0]
+    pts, offsets, total = _ragged_f64(pts, offsets, n_pairs)
     d2 = torch.full((total,), float("inf"), dtype=torch.float64, device=pts.device)
     idx = torch.full((total,), -1, dtype=torch.int32, device=pts.device)
     _lib.check(lib.prg_nearest_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), int(max_cloud), _lib.ptr(d2),
@@ -285,68 +303,54 @@ def radius_pairs_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, 
     correspondences are corr[pair_offsets[p]:pair_offsets[p+1]], rows (i, j) local to the two clouds, ordered by i then j, bit for
     bit `postprocess.radius_pairs`.  Count, ONE 8-byte read-back (the size of the list — the only synchronisation), an
     allocation of exactly K rows, fill."""
+    pts, offsets, total = _ragged_f64(pts, offsets, n_pairs)
+    row_start, corr, _ = _count_fill(pts, offsets, int(n_pairs), total, max_cloud, radius)
+    return corr, row_start[offsets[0::2]]
+
+
+def _count_fill(pts, offsets, n_pairs: int, total: int, max_cloud, radius, also: Optional[torch.Tensor] = None):
+    """prg_radius_count_ragged_f64, the read-back of the list size K — THE synchronisation: 8 bytes, or 16 in one copy with
+    `also`, a device int64 scalar the caller wants on the host as well —, an allocation of exactly K rows, and
+    prg_radius_fill_ragged_f64 unless K == 0.  -> (row_start (total+1) int64, corr (K,2) int32, `also` as an int or None)."""
     lib = _lib.load()
-    if not (pts.is_cuda and offsets.is_cuda):
-        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
-    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
-    assert offsets.numel() == 2 * int(n_pairs) + 1
-    pts = pts.contiguous().view(-1, 3)
-    offsets = offsets.contiguous()
-    total = pts.shape[0]
-    row_start = torch.empty((total + 1,), dtype=torch.int64, device=pts.device)
-    ws = _voxel_workspace(pts.device, int(lib.prg_radius_pairs_workspace_bytes(total)))
-    _lib.check(lib.prg_radius_count_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), total, int(max_cloud),
-                                               float(radius), _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+    dev = pts.device
+    row_start = torch.empty((total + 1,), dtype=torch.int64, device=dev)
+    ws = _voxel_workspace(dev, int(lib.prg_radius_pairs_workspace_bytes(total)))
+    _lib.check(lib.prg_radius_count_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, total, int(max_cloud), float(radius),
+                                               _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
                "prg_radius_count_ragged_f64")
-    K = int(row_start[total].item())
-    corr = torch.empty((K, 2), dtype=torch.int32, device=pts.device)
+    if also is None:
+        K = int(row_start[total].item())
+    else:
+        K, also = (int(v) for v in torch.stack([row_start[total], also]).tolist())
+    corr = torch.empty((K, 2), dtype=torch.int32, device=dev)
     if K:
-        _lib.check(lib.prg_radius_fill_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), int(n_pairs), int(max_cloud), float(radius),
+        _lib.check(lib.prg_radius_fill_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, int(max_cloud), float(radius),
                                                   _lib.ptr(row_start), K, _lib.ptr(corr), _lib.stream_ptr()),
                    "prg_radius_fill_ragged_f64")
-    return corr, row_start[offsets[0::2]]
+    return row_start, corr, also
 
 
 def _neighbor_tables(pts, offsets, n_pairs, max_cloud, radius, limit, index_base, pad, query_rows=None):
     """count / fill / select on one pair buffer -> (table, table_offsets, count).  `query_rows`: the total number of query rows
     when the caller already has it on the host; then the read-back is the 8 bytes of the list size alone."""
     lib = _lib.load()
-    if not (pts.is_cuda and offsets.is_cuda):
-        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
-    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
-    n_pairs, limit = int(n_pairs), int(limit)
-    assert offsets.numel() == 2 * n_pairs + 1
+    pts, offsets, total = _ragged_f64(pts, offsets, n_pairs)
+    n_pairs, limit, total = int(n_pairs), int(limit), max(total, 1)     # the stand-in row of an empty buffer counts as a row
     if not 1 <= limit <= 1024:
         raise _lib.PrgError("radius_neighbors_ragged: limit must be in 1..1024")
     dev = pts.device
-    pts = pts.contiguous().view(-1, 3)
-    offsets = offsets.contiguous()
-    total = pts.shape[0]
-    if total == 0:                                  # no rows: a tensor without elements has no address to pass
-        pts, total = torch.zeros((1, 3), dtype=torch.float64, device=dev), 1
     for t in (index_base, pad):
         assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.numel() == n_pairs)
-    row_start = torch.empty((total + 1,), dtype=torch.int64, device=dev)
-    ws = _voxel_workspace(dev, int(lib.prg_radius_pairs_workspace_bytes(total)))
-    _lib.check(lib.prg_radius_count_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, total, int(max_cloud), float(radius),
-                                               _lib.ptr(row_start), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
-               "prg_radius_count_ragged_f64")
     table_offsets = torch.zeros((n_pairs + 1,), dtype=torch.int64, device=dev)
     torch.cumsum(offsets[1::2] - offsets[0:-1:2], 0, out=table_offsets[1:])
-    if query_rows is None:
-        K, Q = (int(v) for v in torch.stack([row_start[total], table_offsets[n_pairs]]).tolist())   # THE synchronisation
-    else:
-        K, Q = int(row_start[total].item()), int(query_rows)                                        # THE synchronisation
+    row_start, corr, Q = _count_fill(pts, offsets, n_pairs, total, max_cloud, radius,
+                                     also=table_offsets[n_pairs] if query_rows is None else None)
+    K, Q = corr.shape[0], int(query_rows if query_rows is not None else Q)
     table = torch.empty((Q, limit), dtype=torch.int32, device=dev)
     count = torch.empty((Q,), dtype=torch.int32, device=dev)
     if Q == 0:
         return table, table_offsets, count
-    corr = None
-    if K:
-        corr = torch.empty((K, 2), dtype=torch.int32, device=dev)
-        _lib.check(lib.prg_radius_fill_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, int(max_cloud), float(radius),
-                                                  _lib.ptr(row_start), K, _lib.ptr(corr), _lib.stream_ptr()),
-                   "prg_radius_fill_ragged_f64")
     _lib.check(lib.prg_radius_select_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), n_pairs, int(max_cloud), _lib.ptr(row_start),
                                                 _lib.ptr(corr), K, limit, _lib.ptr(table_offsets),
                                                 _lib.ptr(None if index_base is None else index_base.contiguous()),
@@ -407,8 +411,6 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
     if C < 1 or (lens < 0).any() or int(lens.sum()) != pts.shape[0]:
         raise ValueError("lengths do not add up to the rows of points")
     max_cloud = max(1, int(lens.max()))             # a level never has more rows per cloud than the one above it
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)       # noqa: E731
-    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)       # noqa: E731
 
     def launch(segs, n_pairs, r, limit, base, pad):
         """segs: [(level points, start, stop), ...], 2 per pair -> the tables of the launch."""
@@ -416,11 +418,11 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
         offs = np.concatenate([[0], np.cumsum(sizes)])
         rows = [P[a:b] for P, a, b in segs if b > a]
         buf = torch.cat(rows, 0) if rows else torch.zeros((1, 3), dtype=torch.float64, device=dev)
-        table, _, count = _neighbor_tables(buf, i64(offs), n_pairs, max_cloud, r, limit, i32(base), i32(pad),
-                                           query_rows=int(sizes[0::2].sum()))
+        table, _, count = _neighbor_tables(buf, _dev_i64(offs, dev), n_pairs, max_cloud, r, limit, _dev_i32(base, dev),
+                                           _dev_i32(pad, dev), query_rows=int(sizes[0::2].sum()))
         return table, count
 
-    out = {"points": [pts], "lengths": [i64(lens)], "neighbors": [], "subsampling": [], "upsampling": [],
+    out = {"points": [pts], "lengths": [_dev_i64(lens, dev)], "neighbors": [], "subsampling": [], "upsampling": [],
            "counts": {"neighbors": [], "subsampling": [], "upsampling": []}}
     P, o = pts, np.concatenate([[0], np.cumsum(lens)])                  # this level: points, host offsets
     for l in range(num_stages):
@@ -433,7 +435,7 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
             out["counts"]["neighbors"].append(count)
             break
         if N:
-            down, d_offs, status = voxel_grid_ragged(P, None, i64(o), float(voxel_size) * 2 ** (l + 1))
+            down, d_offs, status = voxel_grid_ragged(P, None, _dev_i64(o, dev), float(voxel_size) * 2 ** (l + 1))
             host = torch.cat([d_offs, status.to(torch.int64)]).cpu().numpy()
             on = host[:C + 1]
             check_voxel_status(host[C + 1:], ["cloud {} of level {}".format(c, l) for c in range(C)])
@@ -451,7 +453,7 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
         out["upsampling"].append(table)
         out["counts"]["upsampling"].append(count)
         out["points"].append(Pn)
-        out["lengths"].append(i64(np.diff(on)))
+        out["lengths"].append(_dev_i64(np.diff(on), dev))
         P, o = Pn, on
     return out
 
@@ -553,9 +555,8 @@ def patch_overlaps_ragged(pts: torch.Tensor, offsets, tables: torch.Tensor, tabl
     total = int(ho[-1])
     if total > 1 << 28:
         raise _lib.PrgError("patch_overlaps_ragged: more than 2^28 node pairs in one call")
-    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)       # noqa: E731
     hits = torch.empty((total, 2), dtype=torch.int32, device=dev)
-    d_o, d_to, d_ho, d_m = i64(o), i64(to), i64(ho), i64(m)     # named: a temporary's block could be handed out again at once
+    d_o, d_to, d_ho, d_m = (_dev_i64(a, dev) for a in (o, to, ho, m))   # named: a temporary's block could be handed out again
     if total:
         if pts.shape[0] == 0:                       # no rows: a tensor without elements has no address to pass
             pts = torch.zeros((1, 3), dtype=torch.float64, device=dev)
@@ -571,7 +572,7 @@ def patch_overlaps_ragged(pts: torch.Tensor, offsets, tables: torch.Tensor, tabl
     a, b = torch.div(local, mt, rounding_mode="floor"), torch.remainder(local, mt)
     listed = hits[g]
     # |patch| = the entries of a table row that are not the pad, i.e. not the row count of the row's cloud
-    rows_of = torch.repeat_interleave(i64(np.diff(o)), d_m, output_size=int(to[-1] - to[0]))
+    rows_of = torch.repeat_interleave(_dev_i64(np.diff(o), dev), d_m, output_size=int(to[-1] - to[0]))
     size = (tables[int(to[0]):int(to[-1])] != rows_of[:, None].to(torch.int32)).sum(1).to(torch.float64)
     size_a, size_b = size[d_to[2 * p] - int(to[0]) + a], size[d_to[2 * p + 1] - int(to[0]) + b]
     overlap = (listed[:, 0].to(torch.float64) / size_a + listed[:, 1].to(torch.float64) / size_b) / 2
@@ -599,17 +600,16 @@ def coarse_ground_truth(pyr: dict, *, fine_level: int, limit: int, radius: float
     if len(fl) % 2 or len(fl) < 2:
         raise ValueError("the stack must hold an even number of clouds: [src_0, tgt_0, src_1, tgt_1, ...]")
     fo, no = np.concatenate([[0], np.cumsum(fl)]), np.concatenate([[0], np.cumsum(nl)])
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)       # noqa: E731
     assign, local, sizes = node_patches_ragged(fine, fo, nodes, no, limit)
     corr, hits, overlap, corr_offsets = patch_overlaps_ragged(fine, fo, local, no, radius)
     # local rows -> rows of the level's stack, as the pyramid's tables are indexed
-    node_base = torch.repeat_interleave(i32(no[:-1]), torch.from_numpy(fl).to(dev), output_size=int(fo[-1]))
-    point_base = torch.repeat_interleave(i32(fo[:-1]), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
-    rows_of = torch.repeat_interleave(i32(fl), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
+    node_base = torch.repeat_interleave(_dev_i32(no[:-1], dev), torch.from_numpy(fl).to(dev), output_size=int(fo[-1]))
+    point_base = torch.repeat_interleave(_dev_i32(fo[:-1], dev), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
+    rows_of = torch.repeat_interleave(_dev_i32(fl, dev), torch.from_numpy(nl).to(dev), output_size=int(no[-1]))
     assign = torch.where(assign >= 0, assign + node_base, assign)
     table = torch.where(local != rows_of[:, None], local + point_base[:, None], torch.full_like(local, int(fo[-1])))
     item = torch.searchsorted(corr_offsets[1:].contiguous(), torch.arange(corr.shape[0], device=dev), right=True)
-    d_no = i32(no)
+    d_no = _dev_i32(no, dev)
     node_corr = corr + torch.stack([d_no[2 * item], d_no[2 * item + 1]], 1)
     return {"assign": assign, "table": table, "sizes": sizes, "node_corr": node_corr, "hits": hits, "overlap": overlap,
             "corr_offsets": corr_offsets}
@@ -714,7 +714,7 @@ def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.
     memory, xyz = memory.contiguous().view(-1, 3), xyz.contiguous()
     B, HW, _ = xyz.shape
     assert memory_offsets.numel() == B + 1 and memory_offsets.dtype == torch.int64
-    v8 = valid.contiguous().view(torch.uint8) if valid.dtype == torch.bool else valid.contiguous().to(torch.uint8)
+    v8 = _u8(valid)
     rows = memory.shape[0] + B * HW
     merged = torch.empty((rows, 3), dtype=torch.float64, device=xyz.device)
     merged_valid = torch.empty((rows,), dtype=torch.uint8, device=xyz.device)
@@ -723,13 +723,6 @@ def merge_memory(memory: torch.Tensor, memory_offsets: torch.Tensor, xyz: torch.
                                         _lib.ptr(xyz), _lib.ptr(v8), B, HW, _lib.ptr(merged), _lib.ptr(merged_valid),
                                         _lib.ptr(merged_offsets), _lib.stream_ptr()), "prg_merge_memory_f64")
     return merged, merged_valid, merged_offsets
-
-
-def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    t = t.contiguous()
-    return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).view(-1)
 
 
 def _transforms(T, B: int, device) -> Optional[torch.Tensor]:
@@ -758,12 +751,8 @@ def rigid_crop_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     crop = (lo, hi), valid_out = valid && lo <= p' <= hi.  `out` / `valid_out`: where to write (pts / valid themselves for
     in-place use); default: fresh tensors (valid_out only when there is a crop or a mask).  -> (out, valid_out uint8 | None)."""
     lib = _lib.load()
-    if not (pts.is_cuda and offsets.is_cuda):
-        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
-    assert pts.dtype == torch.float64 and offsets.dtype == torch.int64
-    pts = pts.contiguous().view(-1, 3)
-    offsets = offsets.contiguous()
-    total, B = pts.shape[0], offsets.numel() - 1
+    pts, offsets, total = _ragged_f64(pts, offsets)
+    B = offsets.numel() - 1
     v8 = _u8(valid)
     assert v8 is None or v8.numel() == total
     Td, hd = _transforms(T, B, pts.device), _flags(has_T, B, pts.device)
@@ -771,7 +760,7 @@ def rigid_crop_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     if crop is not None:
         lo, hi = (np.ascontiguousarray(c, dtype=np.float64).reshape(3) for c in crop)
     if out is None:
-        out = torch.empty_like(pts)
+        out = torch.empty((total, 3), dtype=torch.float64, device=pts.device)
     if valid_out is None and (crop is not None or v8 is not None):
         valid_out = torch.empty((total,), dtype=torch.uint8, device=pts.device)
     assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 3 * total
@@ -854,7 +843,7 @@ def apply_mask(prob: torch.Tensor, depth: torch.Tensor, hit: Optional[torch.Tens
     lib = _lib.load()
     prob, depth = _f32(prob), _f32(depth)
     B, _, H, W = depth.shape
-    h8 = None if hit is None else (hit.contiguous().view(torch.uint8) if hit.dtype == torch.bool else hit.contiguous().to(torch.uint8))
+    h8 = _u8(hit)
     d_out = torch.empty_like(depth)
     h_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=depth.device)
     cond = torch.empty((B, 2, H, W), dtype=torch.float32, device=depth.device) if want_cond else None
@@ -869,7 +858,7 @@ def occlusion_filter(depth_rpj: torch.Tensor, mask_rpj: torch.Tensor, threshold:
     lib = _lib.load()
     depth = _f32(depth_rpj)
     B, _, H, W = depth.shape
-    m8 = mask_rpj.contiguous().view(torch.uint8) if mask_rpj.dtype == torch.bool else mask_rpj.contiguous().to(torch.uint8)
+    m8 = _u8(mask_rpj)
     out = torch.empty_like(depth)
     _lib.check(lib.prg_occlusion_filter(_lib.ptr(depth), _lib.ptr(m8), _lib.ptr(out), B, H, W, float(threshold),
                                         _lib.stream_ptr()), "prg_occlusion_filter")

@@ -241,6 +241,14 @@ def nearest(a: np.ndarray, b: np.ndarray, chunk: int = 1024) -> Tuple[np.ndarray
     return d2, idx
 
 
+def _pair_clouds(pairs):
+    """[(a, b), ...] -> (clouds: the 2n float64 (rows,3) arrays in pair order, sizes (2n) int64, offs (2n+1) int64): the pair
+    layout of prg_overlap_counts, on the host."""
+    clouds = [_f64(c) for pair in pairs for c in pair]
+    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    return clouds, sizes, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
 def nearest_hip(pairs, device="cuda"):
     """[(a (n,3), b (m,3)), ...] -> [(d2_ab, idx_ab, d2_ba, idx_ba), ...] as `nearest(a, b)` and `nearest(b, a)` define them:
     all clouds uploaded once as one ragged float64 buffer, ONE prg_nearest_ragged_f64 launch for the whole list."""
@@ -250,10 +258,7 @@ def nearest_hip(pairs, device="cuda"):
     _lib.require_gpu()
     if not pairs:
         return []
-    clouds = [_f64(c) for pair in pairs for c in pair]
-    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
-    offs = np.zeros(len(clouds) + 1, dtype=np.int64)
-    offs[1:] = np.cumsum(sizes)
+    clouds, sizes, offs = _pair_clouds(pairs)
     if sizes.max() == 0:
         d2 = np.full(0, np.inf)
         idx = np.full(0, -1, dtype=np.int32)
@@ -300,8 +305,7 @@ def radius_pairs_hip(pairs, radius: float, device="cuda"):
     _lib.require_gpu()
     if not pairs:
         return []
-    clouds = [_f64(c) for pair in pairs for c in pair]
-    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    clouds, sizes, _ = _pair_clouds(pairs)
     if sizes.max() == 0:
         return [np.zeros((0, 2), dtype=np.int32) for _ in pairs]
     pts, d_offs = G.upload_clouds(clouds, device, dtype=np.float64)
@@ -357,8 +361,7 @@ def radius_neighbors_hip(pairs, radius: float, limit: int, device="cuda"):
     _lib.require_gpu()
     if not pairs:
         return []
-    clouds = [_f64(c) for pair in pairs for c in pair]
-    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
+    clouds, sizes, _ = _pair_clouds(pairs)
     pts, d_offs = G.upload_clouds(clouds, device, dtype=np.float64)
     table_d, to_d, count_d = G.radius_neighbors_ragged(pts, d_offs, len(pairs), max(1, int(sizes.max())), radius, int(limit))
     table, to, count = table_d.cpu().numpy(), to_d.cpu().numpy(), count_d.cpu().numpy()
@@ -912,14 +915,8 @@ def overlap_ratios_hip(pairs, voxel_size: float = 0.025, overlap_factor: float =
         with np.errstate(invalid="ignore", divide="ignore"):
             return [(float(cnt[i, 0] / np.float64(sizes[2 * i])), float(cnt[i, 1] / np.float64(sizes[2 * i + 1])))
                     for i in range(len(pairs))]
-    clouds = []
-    for a, b in pairs:
-        for c in (a, b):
-            clouds.append(native_voxel_down_sample(c, voxel_size) if is_down_sample else _f64(c))
-    sizes = np.array([len(c) for c in clouds], dtype=np.int64)
-    offs = np.zeros(len(clouds) + 1, dtype=np.int64)
-    offs[1:] = np.cumsum(sizes)
-    out = []
+    clouds, sizes, offs = _pair_clouds([tuple(native_voxel_down_sample(c, voxel_size) if is_down_sample else c for c in pair)
+                                        for pair in pairs])
     if offs[-1] == 0 or sizes.max() == 0:
         return [(float("nan"), float("nan"))] * len(pairs)
     pts = torch.from_numpy(np.concatenate([c for c in clouds if len(c)], axis=0)).to(device)
@@ -930,6 +927,5 @@ def overlap_ratios_hip(pairs, voxel_size: float = 0.025, overlap_factor: float =
                "prg_overlap_counts")
     cnt = counts.cpu().numpy().astype(np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
-        for i in range(len(pairs)):
-            out.append((float(cnt[i, 0] / np.float64(sizes[2 * i])), float(cnt[i, 1] / np.float64(sizes[2 * i + 1]))))
-    return out
+        return [(float(cnt[i, 0] / np.float64(sizes[2 * i])), float(cnt[i, 1] / np.float64(sizes[2 * i + 1])))
+                for i in range(len(pairs))]

@@ -134,10 +134,11 @@ def test_empty_clouds(L):
     assert total == 0 and rs.tolist() == [0] and np.all(corr == CORR_SENTINEL)
 
 
-@pytest.mark.parametrize("head,tail", [(5, 0), (0, 9), (301, 1777)])
+@pytest.mark.parametrize("head,tail", [(5, 0), (0, 9), (301, 1777), (1_048_877, 3)])
 def test_rows_outside_every_segment_are_left_alone(L, head, tail):
     """offsets[0] > 0, NaN-poisoned rows before and after: not read (they would poison nothing, but pts must stay as it is),
-    and row_start is flat over them."""
+    and row_start is flat over them.  The last case puts the pairs behind more than 1024 blocks of the row scan, where the
+    one-workgroup scan over the block sums is in the second round of its carry loop."""
     rng = np.random.default_rng(head + tail)
     got, _, _ = check(L, [(cloud(rng, 700), cloud(rng, 513)), (cloud(rng, 64), cloud(rng, 1))], head=head, tail=tail)
     assert len(got[0]) > 0

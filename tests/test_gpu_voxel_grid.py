@@ -184,6 +184,18 @@ def test_kernel_vs_numpy_specification(hip, name, v):
     check_against_numpy_spec(segs, valids, v, out, oo)
 
 
+def test_more_than_1024_scan_blocks(hip):
+    """1 100 000 rows are 1075 blocks of 1024 sorted rows: the one-workgroup scan over the block counts takes 1024 per round,
+    so its second round, which starts from the first round's carry, runs only here ("million" has 977 blocks).  Two segments,
+    no mask array; bit for bit against the host C++ grid.  At 0.025 the box has 1.7 million cells, so most rows are a voxel of
+    their own: every block has heads, and the slots of the last 51 blocks' voxels and the total depend on the carry."""
+    rng = np.random.default_rng(1075)
+    segs, v = [box(rng, 600_000), box(rng, 500_000)], 0.025
+    assert (len(segs[0]) + len(segs[1]) + 1023) // 1024 == 1075
+    out, oo, st = run_grid(hip, segs, v, None)
+    check_against_host(segs, None, v, out, oo, st, oracle=False)
+
+
 def test_total_zero(hip):
     for B in (1, 5):
         out, oo, st = hip.G.voxel_grid_ragged(torch.empty((0, 3), dtype=torch.float64, device="cuda"), None,
