@@ -11,6 +11,7 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "sampler.h"
@@ -43,31 +44,50 @@ int fail(int code, const std::string& m) {
 }
 const char* last_error() { return g_err.c_str(); }
 
-static bool head_fuse_enabled() {
-  static const int on = env_int("PRG_HEAD_FUSE", 1);
-  return on != 0;
-}
-static bool res_epilogue_enabled() {
-  static const int on = env_int("PRG_RES_EPILOGUE", 1);
-  return on != 0;
-}
+static bool head_fuse_enabled() { static const int on = env_int("PRG_HEAD_FUSE", 1); return on != 0; }
+static bool res_epilogue_enabled() { static const int on = env_int("PRG_RES_EPILOGUE", 1); return on != 0; }
 // PRG_GN_ACC=0: GroupNorm statistics as per-tile slabs + one gn_coeff_kernel launch per norm (rounds 1-2) instead of the
 // fixed-point accumulators folded by the consumers (common.h, GnFold).  bf16 / mxfp8 handles only; fp32 always uses slabs.
-static bool gn_acc_enabled() {
-  static const int on = env_int("PRG_GN_ACC", 1);
-  return on != 0;
-}
+static bool gn_acc_enabled() { static const int on = env_int("PRG_GN_ACC", 1); return on != 0; }
 
 struct ProfileSink {  // per-launch conv timing (bench roofline)
   bool on = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-  size_t used = 0;
+  // (start, stop) event pairs of the launches of one step: grown on demand, read and reused after every step
+  struct Events {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    size_t used = 0;
+    Events() = default;
+    Events(const Events&) = delete;   // (owns the events)
+    ~Events() { for (auto& ev : pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); } }
+    int start(hipStream_t s) {   // the next pair's start event
+      if (used == pool.size()) {
+        hipEvent_t a, b;
+        PRG_HIP(hipEventCreate(&a));
+        PRG_HIP(hipEventCreate(&b));
+        pool.push_back({a, b});
+      }
+      PRG_HIP(hipEventRecord(pool[used++].first, s));
+      return PRG_OK;
+    }
+    int stop(hipStream_t s) { PRG_HIP(hipEventRecord(pool[used - 1].second, s)); return PRG_OK; }   // ... and its stop event
+    template <typename Fn>
+    int harvest(Fn&& each) {     // each(i, ms) for the pairs recorded since the last harvest (the stream has drained)
+      for (size_t i = 0; i < used; ++i) {
+        float ms = 0;
+        PRG_HIP(hipEventElapsedTime(&ms, pool[i].first, pool[i].second));
+        each(i, ms);
+      }
+      used = 0;
+      return PRG_OK;
+    }
+  };
+  Events conv_ev;
   double conv_ms = 0, conv_flops = 0, conv_bytes = 0;   // conv_bytes: algorithmic input + output + weight bytes
   double conv_flops_exec = 0;                           // 2 * MACs the kernels executed (sub-pixel Upsample convs: 4 / 9 of the algorithmic count)
   int64_t launches = 0;
-  // per-SHAPE table (round 5, bench.py roofline.per_kernel): what pool[i] timed, and the totals per distinct conv shape
+  // per-SHAPE table (round 5, bench.py roofline.per_kernel): what conv_ev.pool[i] timed, and the totals per distinct conv shape
   struct Rec { prg_profile_shape key; double flops, flops_exec; };
-  std::vector<Rec> recs;                                       // recs[i] <-> pool[i] of the step being harvested
+  std::vector<Rec> recs;                                       // recs[i] <-> conv_ev.pool[i] of the step being harvested
   std::vector<prg_profile_shape> shapes;                       // accumulated (launches, ms, flops) per distinct key
   void add_shape(const Rec& r, double ms) {
     for (auto& sh : shapes)
@@ -81,26 +101,56 @@ struct ProfileSink {  // per-launch conv timing (bench roofline)
     sh.launches = 1; sh.ms = ms; sh.flops = r.flops; sh.flops_executed = r.flops_exec;
     shapes.push_back(sh);
   }
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> step_pool;   // the per-transition update kernel (HBM-bound)
-  size_t step_used = 0;
+  // the conv launch that conv_ev's last pair brackets (called right after launch_conv, on its thread)
+  void add_conv(const ConvDesc& d, bool prologue, size_t elem_bytes) {
+    Rec r{};
+    r.key.cin = d.C0 + d.C1; r.key.cout = d.Cout; r.key.k = d.KH; r.key.stride = d.stride; r.key.ups = d.ups;
+    r.key.hout = d.Hout; r.key.wout = d.Wout; r.key.two_source = d.C1 > 0; r.key.prologue = prologue;
+    r.key.mx = conv_last_was_mx();
+    r.flops = prg::conv_flops(d); r.flops_exec = prg::conv_flops(d) * conv_last_exec_scale();
+    conv_flops += r.flops;
+    conv_flops_exec += r.flops_exec;
+    if (recs.size() < conv_ev.used) recs.resize(conv_ev.used);
+    recs[conv_ev.used - 1] = r;
+    conv_bytes += ((double)d.B * d.Hin * d.Win * (d.C0 + d.C1) + (double)d.B * d.Hout * d.Wout * d.Cout +
+                   (double)d.Cout * (d.C0 + d.C1) * d.KH * d.KW) * elem_bytes;
+    launches += 1;
+  }
+  Events step_ev;                                              // the per-transition update kernel (HBM-bound)
   double step_ms = 0;
   int64_t step_launches = 0;
+  int harvest() {   // one step's events into the totals (keeps the pools small)
+    int rc = conv_ev.harvest([&](size_t i, float ms) { conv_ms += ms; if (i < recs.size()) add_shape(recs[i], ms); });
+    if (rc) return rc;
+    return step_ev.harvest([&](size_t, float ms) { step_ms += ms; });
+  }
+  void reset() {    // start of a run: totals to zero, the pools are kept
+    conv_ms = 0; conv_flops = 0; conv_flops_exec = 0; conv_bytes = 0; launches = 0; conv_ev.used = 0;
+    step_ms = 0; step_launches = 0; step_ev.used = 0;
+    shapes.clear(); recs.clear();
+  }
 };
 
 template <typename T>
 struct UnetImpl : prg_unet {
+  // -------- storage modes --------
+  // T = bf16_t: PRG_BF16 / PRG_MXFP8.  T = float: PRG_F32, or PRG_F16X3 (float storage, split-f16 weights for the MFMAs).
+  static constexpr bool kBf16 = std::is_same<T, bf16_t>::value;
+  bool f16x3() const { return !kBf16 && d_split != nullptr; }
+
   // -------- small helpers --------
   const float* F(int64_t off) const { return off < 0 ? nullptr : d_flat + off; }
   const T* W(const ConvP& p) const { return reinterpret_cast<const T*>(d_packed) + p.w_off; }
   template <typename U>
   U* alloc(size_t n) { return reinterpret_cast<U*>(arena.alloc(n * sizeof(U))); }
 
-  // set around the final block only: its fused tail also applies the head (launch_resblock_tail_fused)
-  const float* head_w = nullptr;
-  const float* head_b = nullptr;
-  float* head_out = nullptr;
-  int head_sigmoid = 0;
-  bool head_done = false;
+  // The one dry-run gate.  measure() walks forward() with arena.dry set: every allocation happens exactly as in a live
+  // evaluation and nothing is launched.  Every launch goes through run() (or conv(), which asks live() itself, as does the h16 probe).
+  bool live() const { return !arena.dry; }
+  template <typename Fn, typename... A>
+  int run(Fn&& launch, A&&... a) { return live() ? launch(std::forward<A>(a)...) : PRG_OK; }
+  struct Frame { Arena& a; size_t m; ~Frame() { a.reset(m); } };   // what a block allocates goes when the block returns
+  static int no_kernel(const char* what) { return fail(PRG_E_STATE, std::string(what) + ": no kernel for this storage type"); }
 
   struct ConvOpt {           // optional fusions of one conv launch
     const T* residual = nullptr;
@@ -162,40 +212,64 @@ struct UnetImpl : prg_unet {
     PRG_CHECK(C0 + C1 == p.Cin, "conv: channel mismatch");
     if (o.gn_nsplit) *o.gn_nsplit = 0;
     if (o.acc_done) *o.acc_done = 0;
-    if (arena.dry) return PRG_OK;
-    if (prof && prof->on) {
-      if (prof->used == prof->pool.size()) {
-        hipEvent_t a, b;
-        PRG_HIP(hipEventCreate(&a));
-        PRG_HIP(hipEventCreate(&b));
-        prof->pool.push_back({a, b});
-      }
-      auto& ev = prof->pool[prof->used++];
-      PRG_HIP(hipEventRecord(ev.first, s));
-      int rc = launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
-      PRG_HIP(hipEventRecord(ev.second, s));
-      prof->conv_flops += conv_flops(L.d);
-      prof->conv_flops_exec += conv_flops(L.d) * conv_last_exec_scale();
-      {
-        ProfileSink::Rec r{};
-        r.key.cin = L.d.C0 + L.d.C1; r.key.cout = L.d.Cout; r.key.k = L.d.KH; r.key.stride = L.d.stride; r.key.ups = L.d.ups;
-        r.key.hout = L.d.Hout; r.key.wout = L.d.Wout; r.key.two_source = L.d.C1 > 0; r.key.prologue = (L.pro_a != nullptr || L.pro_fold.acc != nullptr);
-        r.key.mx = conv_last_was_mx();
-        r.flops = conv_flops(L.d); r.flops_exec = conv_flops(L.d) * conv_last_exec_scale();
-        if (prof->recs.size() < prof->used) prof->recs.resize(prof->used);
-        prof->recs[prof->used - 1] = r;
-      }
-      prof->conv_bytes += ((double)L.d.B * L.d.Hin * L.d.Win * (L.d.C0 + L.d.C1) + (double)L.d.B * L.d.Hout * L.d.Wout * L.d.Cout +
-                           (double)L.d.Cout * (L.d.C0 + L.d.C1) * L.d.KH * L.d.KW) * sizeof(T);
-      prof->launches += 1;
-      return rc;
+    if (!live()) return PRG_OK;
+    if (!(prof && prof->on)) return launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
+    int rc, e;
+    if ((rc = prof->conv_ev.start(s))) return rc;
+    rc = launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
+    if ((e = prof->conv_ev.stop(s))) return e;
+    prof->add_conv(L.d, L.pro_a != nullptr || L.pro_fold.acc != nullptr, sizeof(T));
+    return rc;
+  }
+
+  // -------- launchers that exist for one storage type only --------
+  bool h16_probe(const ConvLaunch<T>& L1, const ConvLaunch<T>& L2) const {
+    if constexpr (kBf16) return conv_h16_pair_ok(L1, L2);
+    else return false;
+  }
+  int affine_silu_fold(const T* x, const GnFold& f, const T* skip, T* out, int B, int HW, int C, hipStream_t s) {
+    if constexpr (kBf16) return run(launch_affine_silu_fold, x, f, skip, out, B, HW, C, s);
+    else return no_kernel("affine_silu_fold");
+  }
+  // Residual(PreNorm(LinearAttention)) in one launch chain of its own: attn_fused.hip (bf16), attn_split.hip (f16x3)
+  bool linattn_fused_ok(const AttnP& a, int N) const {
+    return a.linear && (kBf16 ? a.fw_qkv >= 0 && d_attn : a.sp_qkv >= 0 && d_attn_split && linattn_split_supported(a.C, N));
+  }
+  int linattn_fused(const AttnP& a, const T* x, T* out, int B, int N, hipStream_t s) {
+    float* ws = alloc<float>(kBf16 ? linattn_fused_ws_floats(B, N) : linattn_split_ws_floats(B, N));
+    PRG_CHECK(arena.dry || ws, kBf16 ? "workspace exhausted (fused attention)" : "workspace exhausted (split attention)");
+    if constexpr (kBf16) {
+      return run([&] {
+        return launch_linear_attention_fused(x, d_attn + a.fw_qkv, d_attn + a.fw_out, F(a.out.b_off), F(a.out_g), out, ws, B, N, a.C,
+                                             a.kshift >= 0 ? d_kshift + a.kshift : nullptr, s);
+      });
+    } else {
+      const uint16_t* qh = d_attn_split + a.sp_qkv;
+      const uint16_t* oh = d_attn_split + a.sp_out;
+      return run(launch_linear_attention_split, x, qh, qh + (size_t)3 * kHidden * a.C, oh, oh + (size_t)a.C * kHidden, F(a.out.b_off),
+                 F(a.out_g), out, ws, B, N, a.C, s);
     }
-    return launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
+  }
+  int full_attention(const T* qkv, T* o, int B, int N, hipStream_t s) {   // MFMA core where one covers N, else the generic one
+    if constexpr (kBf16) { if (full_attention_mfma_supported(N)) return run(launch_full_attention_mfma, qkv, o, B, N, s); }
+    else { if (f16x3() && full_attention_split_supported(N)) return run(launch_full_attention_split, qkv, o, B, N, s); }
+    return run(launch_full_attention<T>, qkv, o, B, N, s);
+  }
+  int stem(const float* x_nchw, T* x0, int B, int S, hipStream_t s) {
+    const int cin = lay.cfg.in_channels, d0 = lay.cfg.dim;
+    if constexpr (kBf16) {
+      if (d_stem_frag && stem_conv_mfma_supported(cin, d0, S, S))
+        return run(launch_stem_conv_mfma, x_nchw, d_stem_frag, F(lay.stem_b), x0, B, cin, S, S, s);
+    } else {
+      if (d_stem_split && stem_conv_mfma_supported(cin, d0, S, S))
+        return run(launch_stem_conv_mfma_split, x_nchw, d_stem_split, F(lay.stem_b), d_stem_split_scale, x0, B, cin, S, S, s);
+    }
+    return run(launch_stem_conv<T>, x_nchw, d_stem, F(lay.stem_b), x0, B, cin, S, S, d0, s);
   }
 
   // ---- fixed-point GroupNorm statistics (bf16 path) ----
   const float* pq_dyn = nullptr;     // [B][ss_total] P | Q of the conditioned norms of THIS forward (cond_fold_kernel)
-  bool acc_on() const { return std::is_same<T, bf16_t>::value && d_gnacc && gn_acc_enabled(); }
+  bool acc_on() const { return kBf16 && d_gnacc && gn_acc_enabled(); }
   long long* next_acc(int B) {
     if (!acc_on() || gn_slot >= gn_slots) return nullptr;
     return d_gnacc + (size_t)(gn_slot++) * resB * lay.cfg.groups * 2;
@@ -228,12 +302,102 @@ struct UnetImpl : prg_unet {
     return p;
   }
 
+  // One GroupNorm of a ResnetBlock: the statistics of a conv's output and the coefficients y = x * A + Bc they turn into.
+  // The conv leaves the statistics in one of two forms and says which (nsplit / acc_done):
+  //   slabs (fp32 and f16x3 always; bf16 under PRG_GN_ACC=0 or from a kernel without accumulators): per-tile partial sums,
+  //     turned into the tables A / Bc by one gn_coeff launch;
+  //   accumulators (bf16): fixed-point sums in this norm's slot of d_gnacc, folded into coefficients by the kernel that
+  //     consumes them (GnFold); a consumer that cannot fold reads tables filled by one gn_coeff_acc launch.
+  struct NormStats {
+    UnetImpl* u;
+    int B, HW, C;
+    float* slabs;
+    long long* acc;         // null: slabs only
+    float *A, *Bc;          // [B][C] tables (scratch for a consumer that folds in-kernel)
+    GnApply apply;          // gamma, beta and conditioning of the slab path
+    GnFold f{};             // the same for the accumulator path (filled when acc is set)
+    int nsplit = 0, acc_done = 0;
+    bool tabled = false;
+    void ask(ConvOpt& o) { o.gn_partials = slabs; o.gn_nsplit = &nsplit; o.gn_acc = acc; o.acc_done = &acc_done; }   // of the conv this norm follows
+    int complete(const T* x, hipStream_t s) {   // the conv fused no statistics: one pass over its output
+      return nsplit == 0 ? u->run(launch_gn_stats<T>, x, slabs, B, HW, C, u->lay.cfg.groups, &nsplit, s) : PRG_OK;
+    }
+    const GnFold* fold() const { return acc_done ? &f : nullptr; }   // for a consumer that folds in-kernel; null on the slab path
+    int tables(hipStream_t s) {                 // A / Bc hold the coefficients from here on: at most one launch
+      if (std::exchange(tabled, true)) return PRG_OK;
+      if (acc_done) return u->run(launch_gn_coeff_acc, f, A, Bc, B, C, s);
+      return u->run(launch_gn_coeff, slabs, nsplit, apply, A, Bc, B, HW, C, u->lay.cfg.groups, s);
+    }
+    // x <- SiLU(GroupNorm(x)) + skip as a pass of its own
+    int pass(T* x, const T* skip, hipStream_t s) {
+      if (fold()) return u->affine_silu_fold(x, f, skip, x, B, HW, C, s);
+      int rc = tables(s);
+      return rc ? rc : u->run(launch_affine_silu<T>, x, A, Bc, skip, x, B, HW, C, s);
+    }
+  };
+  NormStats norm(float* slabs, float* A, float* Bc, const GnApply& apply, int B, int HW, int C, bool conditioned, int ss_off,
+                 int64_t pq_static) {
+    NormStats n{this, B, HW, C, slabs, next_acc(B), A, Bc, apply};
+    if (n.acc) n.f = make_fold(n.acc, C, HW, conditioned, ss_off, pq_static);
+    return n;
+  }
+
+  // The three forms of a block's tail, out <- SiLU(GroupNorm(out)) + res(cat[s0, s1]):
+  //   Fused (bf16): one kernel with the 1x1 res_conv inside (attn_fused.hip), which can also apply the network's head;
+  //   ResEpilogue (bf16, f16x3): a res_conv the fused kernel does not cover (up levels 0-1: 768 -> 512, 384 -> 256) takes the
+  //     tail into ITS epilogue, out = Wres . cat[s0, s1] + b + SiLU(GroupNorm(h)): one launch, `res` never materialised either;
+  //   Plain: `res` from its own conv (or the identity skip), then one elementwise pass (exact fp32 keeps these passes).
+  enum class Tail { Fused, ResEpilogue, Plain };
+  Tail pick_tail(const ResP& r, int C0, int C1) const {
+    if (!r.has_res) return Tail::Plain;
+    if (kBf16 && r.fw_res >= 0 && d_attn && resblock_tail_fused_supported(C0, C1, r.cout)) return Tail::Fused;
+    if ((kBf16 || f16x3()) && r.cout % 8 == 0 && res_epilogue_enabled()) return Tail::ResEpilogue;
+    return Tail::Plain;
+  }
+  struct Head { const float *w, *b; float* out; int sigmoid; };   // the network's final 1x1 conv, offered to the last block's tail
+  int tail_fused(const ResP& r, const NormStats& n, const T* s0, int C0, const T* s1, int C1, T* out, const Head* head, hipStream_t s) {
+    if constexpr (kBf16)
+      return run(launch_resblock_tail_fused, out, n.A, n.Bc, s0, C0, s1, C1, d_attn + r.fw_res, F(r.res.b_off), out, n.B, n.HW, n.C, s,
+                 head ? head->w : nullptr, head ? head->b : nullptr, head ? head->out : nullptr, head ? head->sigmoid : 0, n.fold());
+    else return no_kernel("resblock_tail_fused");
+  }
+  // `res`: room for the res_conv's output (Plain).  *head_applied: the fused tail wrote the network output instead of `out`.
+  int tail(const ResP& r, NormStats& n2, const T* s0, int C0, const T* s1, int C1, T* res, T* out, int B, int H, int Wd,
+           const Head* head, bool* head_applied, hipStream_t s) {
+    int rc;
+    switch (pick_tail(r, C0, C1)) {
+      case Tail::Fused:
+        if (!n2.fold() && (rc = n2.tables(s))) return rc;
+        if (head_applied) *head_applied = head != nullptr;
+        return tail_fused(r, n2, s0, C0, s1, C1, out, head, s);
+      case Tail::ResEpilogue: {
+        ConvOpt ro; ro.residual = out;
+        if (n2.fold() && n2.f.cpg % 8 == 0) {
+          ro.res_fold = n2.fold();                            // coefficients folded in the res_conv's epilogue
+        } else {
+          if ((rc = n2.tables(s))) return rc;
+          ro.res_a = n2.A; ro.res_b = n2.Bc;
+        }
+        return conv(r.res, s0, C0, s1, C1, B, H, Wd, 1, 0, 0, ro, out, s);
+      }
+      default: break;
+    }
+    const T* skip = s0;
+    if (r.has_res) {
+      if ((rc = conv(r.res, s0, C0, s1, C1, B, H, Wd, 1, 0, 0, ConvOpt(), res, s))) return rc;
+      skip = res;
+    } else {
+      PRG_CHECK(C1 == 0 && C0 == r.cout, "resblock: identity skip needs equal widths");
+    }
+    return n2.pass(out, skip, s);
+  }
+
   // ResnetBlock (sd:700-734 / dc:726-740): out <- block2(block1(cat[s0,s1])) + res(cat[s0,s1]).
-  //   conv1 (+ fused GN statistics) -> [GN + cond + SiLU folded into conv2's halo load] -> conv2 (+ statistics)
-  //   -> GN + SiLU + skip in one elementwise pass.
+  //   conv1 (+ statistics) -> norm 1 reaches conv2 (folded prologue, table prologue, or a pass over h1) -> conv2 (+ statistics)
+  //   -> tail.  head: the final block only.
   int resblock(const ResP& r, const T* s0, int C0, const T* s1, int C1, const CondSrc* cs, T* out, int B, int H, int Wd,
-               hipStream_t s) {
-    const size_t m = arena.mark();
+               hipStream_t s, const Head* head = nullptr, bool* head_applied = nullptr) {
+    const Frame frame{arena, arena.mark()};
     const size_t M = (size_t)B * H * Wd;
     const int G = lay.cfg.groups, HW = H * Wd;
     T* h1 = alloc<T>(M * r.cout);
@@ -247,193 +411,89 @@ struct UnetImpl : prg_unet {
     PRG_CHECK(arena.dry || (h1 && part1 && part2 && coefA && coefB && coefA2 && coefB2 && (!r.has_res || res)),
               "workspace exhausted (resblock)");
     const CondSrc* c1 = lay.cfg.conditional ? cs : nullptr;
-    int rc, ns1 = 0, ns2 = 0, ad1 = 0, ad2 = 0;
-    const GnApply g1 = gn_params(r.g1, r.b1, c1, r.ss_off);
-    const GnApply g2 = gn_params(r.g2, r.b2, nullptr, 0);
-    // bf16: statistics as fixed-point accumulators, coefficients folded by whoever consumes them (no gn_coeff launches)
-    long long* acc1 = next_acc(B);
-    long long* acc2 = next_acc(B);
-    ConvOpt o1;
-    o1.gn_partials = part1; o1.gn_nsplit = &ns1;
-    o1.gn_acc = acc1; o1.acc_done = &ad1;
-    // conv2's own statistics fold into a second coefficient pair (coefA / coefB are still being read by its prologue)
-    ConvOpt o2;
-    o2.gn_partials = part2; o2.gn_nsplit = &ns2;
-    o2.gn_acc = acc2; o2.acc_done = &ad2;
+    NormStats n1 = norm(part1, coefA, coefB, gn_params(r.g1, r.b1, c1, r.ss_off), B, HW, r.cout, c1 && c1->ss_a, r.ss_off, r.pq1);
+    // conv2's own statistics turn into a second coefficient pair (coefA / coefB are still being read by its prologue)
+    NormStats n2 = norm(part2, coefA2, coefB2, gn_params(r.g2, r.b2, nullptr, 0), B, HW, r.cout, false, 0, r.pq2);
+    ConvOpt o1, o2;
+    n1.ask(o1); n2.ask(o2);
     // conv2 applies GroupNorm + SiLU of h1 in its prologue wherever it supports one
     const bool fuse_pro = conv_supports_prologue<T>(make_desc(r.c2, r.cout, 0, B, H, Wd, 1, 1, 0));
-    GnFold f1{}, f2{};
     // h16 (conv.h): h1 only ever feeds conv2's fused prologue — stored as f16 when both launches land on kernels that implement it
     // (probed with the launches' own descriptors: PRG_H16=0, PRG_CONV_C64=0, ... and uncovered shapes fall back to bf16 h1)
     bool h16 = false;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!arena.dry && acc1 && fuse_pro && d_h16 && r.c2.h16_off >= 0) {
-        const GnFold fp = make_fold(acc1, r.cout, HW, c1 && c1->ss_a, r.ss_off, r.pq1);
-        ConvOpt p2 = o2;
-        p2.fold = &fp; p2.pro_a = coefA; p2.pro_b = coefB;
-        h16 = conv_h16_pair_ok(make_launch(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1),
-                               make_launch(r.c2, h1, r.cout, nullptr, 0, B, H, Wd, 1, 1, 0, p2, out));
-      }
+    if (live() && n1.acc && fuse_pro && d_h16 && r.c2.h16_off >= 0) {
+      ConvOpt p2 = o2;
+      p2.fold = &n1.f; p2.pro_a = n1.A; p2.pro_b = n1.Bc;
+      h16 = h16_probe(make_launch(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1),
+                      make_launch(r.c2, h1, r.cout, nullptr, 0, B, H, Wd, 1, 1, 0, p2, out));
     }
-    o1.out_f16 = h16;
-    o2.in_f16 = h16;
+    o1.out_f16 = o2.in_f16 = h16;
+    int rc;
     if ((rc = conv(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1, s))) return rc;
-    if (!arena.dry && ns1 == 0 && (rc = launch_gn_stats<T>(h1, part1, B, HW, r.cout, G, &ns1, s))) return rc;
-    PRG_CHECK(!h16 || ad1, "resblock: the h16 probe promised fixed-point statistics");
-    if (!arena.dry) {
-      if (ad1) {
-        f1 = make_fold(acc1, r.cout, HW, c1 && c1->ss_a, r.ss_off, r.pq1);
-        if (fuse_pro) {
-          o2.fold = &f1; o2.pro_a = coefA; o2.pro_b = coefB;    // (tables: scratch for kernels without the in-kernel fold)
-        } else {
-          if constexpr (std::is_same<T, bf16_t>::value) {
-            if ((rc = launch_affine_silu_fold(h1, f1, nullptr, h1, B, HW, r.cout, s))) return rc;
-          }
-        }
-      } else {
-        if ((rc = launch_gn_coeff(part1, ns1, g1, coefA, coefB, B, HW, r.cout, G, s))) return rc;
-        if (fuse_pro) {
-          o2.pro_a = coefA; o2.pro_b = coefB;
-        } else if ((rc = launch_affine_silu<T>(h1, coefA, coefB, nullptr, h1, B, HW, r.cout, s))) {
-          return rc;
-        }
-      }
+    if ((rc = n1.complete(h1, s))) return rc;
+    PRG_CHECK(!h16 || n1.acc_done, "resblock: the h16 probe promised fixed-point statistics");
+    if (!fuse_pro) {
+      if ((rc = n1.pass(h1, nullptr, s))) return rc;
+    } else {
+      o2.fold = n1.fold();              // (then the tables are scratch for kernels without the in-kernel fold: nothing fills them)
+      if (!o2.fold && (rc = n1.tables(s))) return rc;
+      o2.pro_a = n1.A; o2.pro_b = n1.Bc;
     }
     if ((rc = conv(r.c2, h1, r.cout, nullptr, 0, B, H, Wd, 1, 1, 0, o2, out, s))) return rc;
-    if (!arena.dry && ns2 == 0 && (rc = launch_gn_stats<T>(out, part2, B, HW, r.cout, G, &ns2, s))) return rc;
-    const T* skip = s0;
-    bool fused_tail = false;
-    if constexpr (std::is_same<T, bf16_t>::value)
-      fused_tail = r.has_res && r.fw_res >= 0 && d_attn && resblock_tail_fused_supported(C0, C1, r.cout);
-    // bf16: a res_conv the fused tail kernel does not cover (up levels 0-1: 768 -> 512, 384 -> 256) takes the tail into ITS
-    // epilogue instead: out = Wres . cat[s0, s1] + b + SiLU(GroupNorm(h)), one launch, `res` never materialised either
-    // (f16x3 too, round 4: the split-operand 1x1 kernel shares the transposing epilogue — `res` is not written and re-read, the
-    //  GroupNorm + SiLU + skip pass of these blocks is gone; the exact-f32 parity mode keeps its separate passes)
-    const bool epi_tail = (std::is_same<T, bf16_t>::value || (std::is_same<T, float>::value && d_split != nullptr)) && r.has_res && !fused_tail &&
-                          r.cout % 8 == 0 && res_epilogue_enabled();
-    if (fused_tail || epi_tail) {
-      // res_conv folded into the tail pass below: `res` is never materialised
-    } else if (r.has_res) {
-      if ((rc = conv(r.res, s0, C0, s1, C1, B, H, Wd, 1, 0, 0, ConvOpt(), res, s))) return rc;
-      skip = res;
-    } else {
-      PRG_CHECK(C1 == 0 && C0 == r.cout, "resblock: identity skip needs equal widths");
-    }
-    if (!arena.dry) {
-      // GroupNorm + SiLU + skip.  Accumulator path: the tail kernels fold the coefficients themselves (the 1x1 res_conv's
-      // epilogue reads tables: one gn_coeff_acc launch for those four blocks); slab path: gn_coeff launch, then the tables
-      if (ad2) f2 = make_fold(acc2, r.cout, HW, false, 0, r.pq2);
-      else if ((rc = launch_gn_coeff(part2, ns2, g2, coefA2, coefB2, B, HW, r.cout, G, s))) return rc;
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (fused_tail) {
-          rc = launch_resblock_tail_fused(out, coefA2, coefB2, s0, C0, s1, C1, d_attn + r.fw_res, F(r.res.b_off), out, B, HW,
-                                          r.cout, s, head_w, head_b, head_out, head_sigmoid, ad2 ? &f2 : nullptr);
-          head_done = head_out != nullptr;
-          arena.reset(m);
-          return rc;
-        }
-      }
-      if (epi_tail) {
-        ConvOpt ro;
-        ro.residual = out;
-        const bool fold_ok = ad2 && f2.cpg % 8 == 0;
-        if (fold_ok) {
-          ro.res_fold = &f2;                                  // coefficients folded in the res_conv's epilogue
-        } else {
-          if constexpr (std::is_same<T, bf16_t>::value) {
-            if (ad2 && (rc = launch_gn_coeff_acc(f2, coefA2, coefB2, B, r.cout, s))) return rc;
-          }
-          ro.res_a = coefA2; ro.res_b = coefB2;
-        }
-        rc = conv(r.res, s0, C0, s1, C1, B, H, Wd, 1, 0, 0, ro, out, s);
-        arena.reset(m);
-        return rc;
-      }
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (ad2) {
-          rc = launch_affine_silu_fold(out, f2, skip, out, B, HW, r.cout, s);
-          arena.reset(m);
-          return rc;
-        }
-      }
-      if ((rc = launch_affine_silu<T>(out, coefA2, coefB2, skip, out, B, HW, r.cout, s))) return rc;
-    } else if (epi_tail) {
-      ConvOpt ro;                                            // dry run (workspace sizing): the same conv call
-      if ((rc = conv(r.res, s0, C0, s1, C1, B, H, Wd, 1, 0, 0, ro, out, s))) return rc;
-    }
-    arena.reset(m);
-    return PRG_OK;
+    if ((rc = n2.complete(out, s))) return rc;
+    return tail(r, n2, s0, C0, s1, C1, res, out, B, H, Wd, head, head_applied, s);
   }
 
   // Residual(PreNorm(LinearAttention | Attention)) (sd:583-589, 631-639, 737-796)
   int attention(const AttnP& a, const T* x, T* out, int B, int H, int Wd, hipStream_t s) {
-    const size_t m = arena.mark();
+    const Frame frame{arena, arena.mark()};
     const int N = H * Wd;
     const size_t M = (size_t)B * N;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (a.linear && a.fw_qkv >= 0 && d_attn) {
-        float* ws = alloc<float>(linattn_fused_ws_floats(B, N));
-        PRG_CHECK(arena.dry || ws, "workspace exhausted (fused attention)");
-        int rc = PRG_OK;
-        if (!arena.dry)
-          rc = launch_linear_attention_fused(x, d_attn + a.fw_qkv, d_attn + a.fw_out, F(a.out.b_off), F(a.out_g), out, ws, B, N,
-                                             a.C, a.kshift >= 0 ? d_kshift + a.kshift : nullptr, s);
-        arena.reset(m);
-        return rc;
-      }
-    }
-    if constexpr (std::is_same<T, float>::value) {
-      if (a.linear && a.sp_qkv >= 0 && d_attn_split && linattn_split_supported(a.C, N)) {
-        float* ws = alloc<float>(linattn_split_ws_floats(B, N));
-        PRG_CHECK(arena.dry || ws, "workspace exhausted (split attention)");
-        int rc = PRG_OK;
-        if (!arena.dry) {
-          const uint16_t* qh = d_attn_split + a.sp_qkv;
-          const uint16_t* oh = d_attn_split + a.sp_out;
-          rc = launch_linear_attention_split(x, qh, qh + (size_t)3 * kHidden * a.C, oh, oh + (size_t)a.C * kHidden, F(a.out.b_off),
-                                             F(a.out_g), out, ws, B, N, a.C, s);
-        }
-        arena.reset(m);
-        return rc;
-      }
-    }
+    int rc;
+    if (linattn_fused_ok(a, N)) return linattn_fused(a, x, out, B, N, s);
     T* xn = alloc<T>(M * a.C);
     T* qkv = alloc<T>(M * 3 * kHidden);
     T* o = alloc<T>(M * kHidden);
     T* y = a.linear ? alloc<T>(M * a.C) : nullptr;
     float* ws = a.linear ? alloc<float>(linattn_ws_floats(B, N)) : nullptr;
     PRG_CHECK(arena.dry || (xn && qkv && o && (!a.linear || (y && ws))), "workspace exhausted (attention)");
-    int rc;
-    if (!arena.dry && (rc = launch_layernorm<T>(x, F(a.norm_g), nullptr, xn, (int64_t)M, a.C, s))) return rc;
+    if ((rc = run(launch_layernorm<T>, x, F(a.norm_g), nullptr, xn, (int64_t)M, a.C, s))) return rc;
     if ((rc = conv(a.qkv, xn, a.C, nullptr, 0, B, H, Wd, 1, 0, 0, ConvOpt(), qkv, s))) return rc;
     if (a.linear) {
-      if (!arena.dry && (rc = launch_linear_attention<T>(qkv, o, ws, B, N, s))) return rc;
+      if ((rc = run(launch_linear_attention<T>, qkv, o, ws, B, N, s))) return rc;
       if ((rc = conv(a.out, o, kHidden, nullptr, 0, B, H, Wd, 1, 0, 0, ConvOpt(), y, s))) return rc;
-      if (!arena.dry && (rc = launch_layernorm<T>(y, F(a.out_g), x, out, (int64_t)M, a.C, s))) return rc;
+      if ((rc = run(launch_layernorm<T>, y, F(a.out_g), x, out, (int64_t)M, a.C, s))) return rc;
     } else {
-      bool done = false;
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (!arena.dry && full_attention_mfma_supported(N)) {
-          if ((rc = launch_full_attention_mfma(qkv, o, B, N, s))) return rc;
-          done = true;
-        }
-      }
-      if constexpr (std::is_same<T, float>::value) {
-        if (!arena.dry && d_split && full_attention_split_supported(N)) {          // f16x3: split-f16 MFMAs (attn_split.hip)
-          if ((rc = launch_full_attention_split(qkv, o, B, N, s))) return rc;
-          done = true;
-        }
-      }
-      if (!arena.dry && !done && (rc = launch_full_attention<T>(qkv, o, B, N, s))) return rc;
-      { ConvOpt ro; ro.residual = x;
-        if ((rc = conv(a.out, o, kHidden, nullptr, 0, B, H, Wd, 1, 0, 0, ro, out, s))) return rc; }
+      if ((rc = full_attention(qkv, o, B, N, s))) return rc;
+      ConvOpt ro; ro.residual = x;
+      if ((rc = conv(a.out, o, kHidden, nullptr, 0, B, H, Wd, 1, 0, 0, ro, out, s))) return rc;
     }
-    arena.reset(m);
     return PRG_OK;
   }
 
   void tap(const char* name, const void* p, int B, int C, int H, int Wd, bool nchw = false) {
     if (taps_on && !arena.dry) taps[name] = Tap{p, C, H, Wd, B, nchw};
+  }
+
+  // Start of an evaluation on the fixed-point path (bf16): the accumulators of every norm are cleared by one memset, and one
+  // launch folds the conditioning (scale + 1, shift) of every ResnetBlock into P / Q — instead of one gn_coeff launch per norm.
+  int begin_norms(const CondSrc* cs, int B, hipStream_t s) {
+    gn_slot = 0; pq_dyn = nullptr;
+    if (!(kBf16 && gn_acc_enabled())) return PRG_OK;
+    const bool conditioned = lay.cfg.conditional && n_cond_entries > 0;
+    // (the conditioned network clears the accumulators inside its cond_fold launch below: one launch fewer per evaluation)
+    const bool fold = acc_on() && conditioned && cs && cs->ss_a;
+    int rc;
+    if (acc_on() && !fold && (rc = run([&] { PRG_HIP(hipMemsetAsync(d_gnacc, 0, gnacc_bytes, s)); return (int)PRG_OK; }))) return rc;
+    if (!conditioned) return PRG_OK;
+    float* pq = alloc<float>((size_t)B * lay.ss_total);
+    PRG_CHECK(arena.dry || pq, "workspace exhausted (conditioning fold)");
+    if (!fold) return PRG_OK;
+    const GnApply ss = gn_params(-1, -1, cs, 0);   // the conditioning rows alone: no gamma / beta
+    rc = run(launch_cond_fold, d_cond_entries, n_cond_entries, d_flat, ss, pq, lay.ss_total, B, s, d_gnacc,
+             (int64_t)(gnacc_bytes / sizeof(long long)));
+    if (!rc) pq_dyn = pq;
+    return rc;
   }
 
   int forward(const float* x_nchw, const CondSrc& cond, float* out, int B, int S, hipStream_t s) override {
@@ -446,44 +506,10 @@ struct UnetImpl : prg_unet {
     const CondSrc* cs = L.cfg.conditional ? &cond : nullptr;
     int rc;
     const int d0 = L.cfg.dim;
-    // fixed-point GroupNorm statistics (bf16 path): one memset for every norm of the evaluation, one launch that folds the
-    // conditioning (scale + 1, shift) of every ResnetBlock into P / Q — instead of one gn_coeff launch per norm
-    gn_slot = 0;
-    pq_dyn = nullptr;
-    if (std::is_same<T, bf16_t>::value && gn_acc_enabled()) {
-      // (the conditioned network clears the accumulators inside its cond_fold launch below: one launch fewer per evaluation)
-      const bool fold_clears = acc_on() && !arena.dry && L.cfg.conditional && n_cond_entries > 0 && cs && cs->ss_a;
-      if (acc_on() && !arena.dry && !fold_clears) PRG_HIP(hipMemsetAsync(d_gnacc, 0, gnacc_bytes, s));
-      if (L.cfg.conditional && n_cond_entries > 0) {
-        float* pq = alloc<float>((size_t)B * L.ss_total);
-        PRG_CHECK(arena.dry || pq, "workspace exhausted (conditioning fold)");
-        if (acc_on() && !arena.dry && cs && cs->ss_a) {
-          GnApply ss{};
-          ss.ss_a = cs->ss_a; ss.ss_a_stride = cs->ss_a_stride; ss.ss_b = cs->ss_b; ss.ss_b_stride = cs->ss_b_stride;
-          ss.ss_a_row = cs->row; ss.ss_a_row_stride = cs->row_stride;
-          if ((rc = launch_cond_fold(d_cond_entries, n_cond_entries, d_flat, ss, pq, L.ss_total, B, s, d_gnacc, (int64_t)(gnacc_bytes / sizeof(long long))))) return rc;
-          pq_dyn = pq;
-        }
-      }
-    }
+    if ((rc = begin_norms(cs, B, s))) return rc;
     T* x0 = alloc<T>((size_t)B * S * S * d0);
     PRG_CHECK(arena.dry || x0, "workspace exhausted (stem)");
-    bool stem_done = false;
-    if constexpr (std::is_same<T, bf16_t>::value) {
-      if (!arena.dry && d_stem_frag && stem_conv_mfma_supported(L.cfg.in_channels, d0, S, S)) {
-        if ((rc = launch_stem_conv_mfma(x_nchw, d_stem_frag, F(L.stem_b), x0, B, L.cfg.in_channels, S, S, s))) return rc;
-        stem_done = true;
-      }
-    }
-    if constexpr (std::is_same<T, float>::value) {
-      if (!arena.dry && d_stem_split && stem_conv_mfma_supported(L.cfg.in_channels, d0, S, S)) {
-        if ((rc = launch_stem_conv_mfma_split(x_nchw, d_stem_split, F(L.stem_b), d_stem_split_scale, x0, B, L.cfg.in_channels, S, S, s))) return rc;
-        stem_done = true;
-      }
-    }
-    if (!arena.dry && !stem_done &&
-        (rc = launch_stem_conv<T>(x_nchw, d_stem, F(L.stem_b), x0, B, L.cfg.in_channels, S, S, d0, s)))
-      return rc;
+    if ((rc = stem(x_nchw, x0, B, S, s))) return rc;
     tap("init_conv", x0, B, d0, S, S);
     std::vector<std::pair<const T*, int>> skips;
     const T* x = x0;
@@ -557,17 +583,12 @@ struct UnetImpl : prg_unet {
       PRG_CHECK(arena.dry || fr, "workspace exhausted (final)");
       // the final block's fused tail applies the 1x1 head to its LDS tile and writes only the network output (bf16 path,
       // no taps requested): `fr` is then never written
-      head_done = false;
-      if (!taps_on && !arena.dry && d0 == 64 && head_fuse_enabled()) {
-        head_w = F(L.head_w); head_b = F(L.head_b); head_out = out; head_sigmoid = L.cfg.sigmoid_out;
-      }
-      rc = resblock(L.fin, x, d0, x0, d0, cs, fr, B, H, H, s);
-      head_w = head_b = nullptr; head_out = nullptr;
-      if (rc) return rc;
+      const Head head{F(L.head_w), F(L.head_b), out, L.cfg.sigmoid_out};
+      const bool offer = !taps_on && d0 == 64 && head_fuse_enabled();
+      bool head_applied = false;
+      if ((rc = resblock(L.fin, x, d0, x0, d0, cs, fr, B, H, H, s, offer ? &head : nullptr, &head_applied))) return rc;
       tap("final_res", fr, B, d0, H, H);
-      if (!arena.dry && !head_done && (rc = launch_head_conv<T>(fr, F(L.head_w), F(L.head_b), out, (int64_t)M, d0,
-                                                                 L.cfg.sigmoid_out, s)))
-        return rc;
+      if (!head_applied && (rc = run(launch_head_conv<T>, fr, head.w, head.b, out, (int64_t)M, d0, head.sigmoid, s))) return rc;
     }
     return PRG_OK;
   }
@@ -700,8 +721,6 @@ struct prg_sampler {
   ProfileSink prof;
   double last_total_ms = 0;
   ~prg_sampler() {
-    for (auto& ev : prof.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    for (auto& ev : prof.step_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 };
@@ -731,22 +750,13 @@ static int sampler_one_step(prg_sampler* h, const float* cond, const float* nois
   a.ticket = h->d_step + 1;
   a.keep_p = h->keep.empty() ? nullptr : h->d_keep;
   a.keep_u = h->keep_u;
-  if (h->prof.on) {
-    ProfileSink& p = h->prof;
-    if (p.step_used == p.step_pool.size()) {
-      hipEvent_t e0, e1;
-      PRG_HIP(hipEventCreate(&e0));
-      PRG_HIP(hipEventCreate(&e1));
-      p.step_pool.push_back({e0, e1});
-    }
-    auto& ev = p.step_pool[p.step_used++];
-    PRG_HIP(hipEventRecord(ev.first, s));
-    rc = launch_sampler_step(a, s);
-    PRG_HIP(hipEventRecord(ev.second, s));
-    p.step_launches += 1;
-    return rc;
-  }
-  return launch_sampler_step(a, s);   // its last workgroup advances the step counter
+  ProfileSink& p = h->prof;
+  if (!p.on) return launch_sampler_step(a, s);   // its last workgroup advances the step counter
+  if ((rc = p.step_ev.start(s))) return rc;
+  rc = launch_sampler_step(a, s);
+  if (int e = p.step_ev.stop(s)) return e;
+  p.step_launches += 1;
+  return rc;
 }
 
 }  // namespace prg
@@ -1039,15 +1049,15 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
   if ((rc = launch_sampler_init(h->d_x, noise, h->d_seeds, B, h->S * h->S, s))) return rc;
 
   const bool profiling = h->prof.on;
+  h->prof.reset();
+  // the U-Net reports its conv launches to this sampler for the length of this call only, whichever way the call ends
+  struct ProfLink { prg_unet* u; ~ProfLink() { u->prof = nullptr; } } link{u};
   u->prof = profiling ? &h->prof : nullptr;
-  h->prof.conv_ms = 0; h->prof.conv_flops = 0; h->prof.conv_flops_exec = 0; h->prof.conv_bytes = 0; h->prof.launches = 0; h->prof.used = 0;
-  h->prof.step_ms = 0; h->prof.step_launches = 0; h->prof.step_used = 0;
-  h->prof.shapes.clear(); h->prof.recs.clear();
-  hipEvent_t t0 = nullptr, t1 = nullptr;
+  struct ScopedEvent { hipEvent_t e = nullptr; ~ScopedEvent() { if (e) (void)hipEventDestroy(e); } } t0, t1;
   if (profiling) {
-    PRG_HIP(hipEventCreate(&t0));
-    PRG_HIP(hipEventCreate(&t1));
-    PRG_HIP(hipEventRecord(t0, s));
+    PRG_HIP(hipEventCreate(&t0.e));
+    PRG_HIP(hipEventCreate(&t1.e));
+    PRG_HIP(hipEventRecord(t0.e, s));
   }
   if (h->use_graph && !profiling && !u->taps_on) {
     const float* keep_p = h->keep.empty() ? nullptr : h->d_keep;
@@ -1069,34 +1079,19 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
     for (int k = 0; k < h->n_steps; ++k) PRG_HIP(hipGraphLaunch(h->exec, s));
   } else {
     for (int k = 0; k < h->n_steps; ++k) {
-      if ((rc = sampler_one_step(h, img_cond, noise, out, s))) { u->prof = nullptr; return rc; }
-      if (profiling) {  // harvest this step's conv events (keeps the pool small)
+      if ((rc = sampler_one_step(h, img_cond, noise, out, s))) return rc;
+      if (profiling) {
         PRG_HIP(hipStreamSynchronize(s));
-        for (size_t i = 0; i < h->prof.used; ++i) {
-          float ms = 0;
-          PRG_HIP(hipEventElapsedTime(&ms, h->prof.pool[i].first, h->prof.pool[i].second));
-          h->prof.conv_ms += ms;
-          if (i < h->prof.recs.size()) h->prof.add_shape(h->prof.recs[i], ms);
-        }
-        h->prof.used = 0;
-        for (size_t i = 0; i < h->prof.step_used; ++i) {
-          float ms = 0;
-          PRG_HIP(hipEventElapsedTime(&ms, h->prof.step_pool[i].first, h->prof.step_pool[i].second));
-          h->prof.step_ms += ms;
-        }
-        h->prof.step_used = 0;
+        if ((rc = h->prof.harvest())) return rc;
       }
     }
   }
-  u->prof = nullptr;
   if (profiling) {
-    PRG_HIP(hipEventRecord(t1, s));
-    PRG_HIP(hipEventSynchronize(t1));
+    PRG_HIP(hipEventRecord(t1.e, s));
+    PRG_HIP(hipEventSynchronize(t1.e));
     float ms = 0;
-    PRG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    PRG_HIP(hipEventElapsedTime(&ms, t0.e, t1.e));
     h->last_total_ms = ms;
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
   }
   return PRG_OK;
 }

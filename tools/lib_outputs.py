@@ -7,23 +7,45 @@
 The cases cover every weight packing a handle can build (the kernels are deterministic, so two builds that pack the same bytes
 give the same bits): the conditional dim-64 U-Net at 128 x 128 with B = 2 and 16 in all four modes, the switches read during
 weight preparation, the MaskUnet's 3-channel stems, a dim-16 network on the generic paths and an 8-step sampler chain with and
-without graph capture.  The library reads its PRG_* switches once per process: every switch setting runs in a child of its own."""
+without graph capture.  They also cover every branch of the forward pass's host code (csrc/unet.hip): small shapes (B = 2 at
+64 x 64, and at 40 x 40 where tiles do not divide and the second conv of a block has no fused prologue) under each switch that
+moves a ResnetBlock onto another path, and the debug taps, which turn the fused head off.  The library reads its PRG_* switches
+once per process: every switch setting runs in a child of its own."""
 import json
 import os
 import subprocess
 import sys
 
 MODES = ("fp32", "bf16", "mxfp8", "f16x3")
+TAPS = ("init_conv", "down0_block0", "down0_attn", "down0_out", "mid_attn", "up0_out", "final_res")   # + "augment": MaskUnet
+
+
+def SMALL(mode):
+    return [("unet", 64, 2, S, mode) for S in (64, 40)]
+
 
 # (environment of the child process, [(kind, dim, B, S, mode), ...])
 GROUPS = [
     ({}, [("unet", 64, B, 128, m) for m in MODES for B in (2, 16)]
          + [("maskunet", 64, 2, 128, m) for m in ("bf16", "f16x3")]
          + [("unet", 16, 3, 32, m) for m in MODES]
-         + [("chain8_graph", 64, 2, 128, "bf16"), ("chain8_nograph", 64, 2, 128, "bf16")]),
+         + [("chain8_graph", 64, 2, 128, "bf16"), ("chain8_nograph", 64, 2, 128, "bf16")]
+         + [("unet", 64, 2, S, m) for m in MODES for S in (40, 64)]
+         + [("maskunet", 64, 2, 64, m) for m in ("fp32", "mxfp8")]
+         + [(k, 64, 2, 64, m) for k in ("unet_taps", "maskunet_taps") for m in ("bf16", "fp32")]),
     ({"PRG_SPLIT_UP2X2": "1"}, [("unet", 64, B, 128, "f16x3") for B in (2, 16)]),
     ({"PRG_LA_KSHIFT": "0"}, [("unet", 64, B, 128, "bf16") for B in (2, 16)]),
     ({"PRG_FUSED_ATTN": "0"}, [("unet", 64, B, 128, "bf16") for B in (2, 16)]),
+    # the branches of UnetImpl::resblock / attention / forward: slabs everywhere, no h16, no res_conv epilogue, no fused head, ...
+    ({"PRG_GN_ACC": "0"}, SMALL("bf16") + [("chain8_graph", 64, 2, 64, "bf16"), ("chain8_nograph", 64, 2, 64, "bf16")]),
+    ({"PRG_H16": "0"}, SMALL("bf16")),
+    ({"PRG_RES_EPILOGUE": "0"}, SMALL("bf16")),
+    ({"PRG_HEAD_FUSE": "0"}, SMALL("bf16")),
+    ({"PRG_CONV_C64": "0"}, SMALL("bf16")),
+    # a bf16 handle whose convs report no accumulators
+    ({"PRG_CONV_WS": "0", "PRG_CONV_C64": "0", "PRG_CONV_W256": "0", "PRG_CONV_DOWN_W256": "0"}, SMALL("bf16")),
+    ({"PRG_W256_MIN_TILES": "1"}, SMALL("bf16")),
+    ({"PRG_SPLIT_FULLATTN": "0", "PRG_SPLIT_LA_ONLINE": "0"}, SMALL("f16x3")),
 ]
 
 
@@ -45,13 +67,20 @@ def run_group(index, out):
     for case in cases:
         kind, dim, B, S, mode = case
         g = torch.Generator().manual_seed(1000 + dim + B + S)
-        if kind == "maskunet":
+        taps = ()
+        if kind in ("maskunet", "maskunet_taps"):
             net = MaskUnet(dim, dtype=mode).load_state_dict(W.synth_state_dict(W.maskunet_config(dim), 21))
+            if kind == "maskunet_taps":
+                net.set_taps(True)
+                taps = TAPS + ("augment",)
             y = net(torch.rand((B, 1, S, S), generator=g).cuda())
         else:
             net = Unet(dim, dtype=mode).load_state_dict(W.synth_state_dict(W.unet_config(dim), 20))
             pc = torch.rand((B, 4), generator=g)
-            if kind == "unet":
+            if kind in ("unet", "unet_taps"):
+                if kind == "unet_taps":
+                    net.set_taps(True)
+                    taps = TAPS
                 x = torch.randn((B, 1, S, S), generator=g)
                 t = torch.randint(0, 1000, (B,), generator=g)
                 y = net(x.cuda(), t.cuda(), pc.cuda())
@@ -62,6 +91,8 @@ def run_group(index, out):
                 y = d8.sample(param_cond=pc, img_cond=cond, noise=noise, use_graph=kind == "chain8_graph")
         torch.cuda.synchronize()
         res[case_name(env, case)] = y.cpu().numpy()
+        for k in taps:
+            res[f"{case_name(env, case)}:{k}"] = net.get_tap(k, B, max_floats=B * 512 * S * S).cpu().numpy()
         net.close()
     np.savez(out, **res)
 
