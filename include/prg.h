@@ -388,6 +388,17 @@ int prg_debug_layernorm(const float* x, const float* g, const float* residual, f
 int prg_debug_linear_attention_block(const float* x, const float* norm_g, const float* w_qkv, const float* w_out, const float* b_out,
                                      const float* out_g, float* out, int B, int C, int N, int dtype, int shift_mode, int psum,
                                      int* used_static, void* stream);
+/* Kernel unit-test hook: the fused ResnetBlock tail, out = SiLU(h * A[b] + Bc[b]) + w_res . cat[s0, s1] + b_res (sd:731-734 with
+ * the GroupNorm folded into A, Bc), through the bf16 kernel the forward pass launches.  h (B, N, Cout), s0 (B, N, C0),
+ * s1 (B, N, C1) float32 DEVICE, pixel-major, converted to bf16 first; A, Bc (B, Cout) float32 DEVICE; w_res (Cout, C0 + C1),
+ * b_res (Cout) float32 HOST, packed as a handle packs a res_conv.  head_w (Cout), head_b (1) float32 HOST or both NULL: with them
+ * (Cout = 64 only) the network's 1x1 head runs on the tile and out is (B, N) float32 DEVICE (head_sigmoid 1: sigmoid of it);
+ * without them out is (B, N, Cout).  in_place 1: the bf16 h buffer is also the kernel's output buffer, as in the forward pass.
+ * (C0 + C1, Cout) one of (128, 64), (192, 128), (256, 128), C0 and C1 multiples of 8.  Bad arguments fail with PRG_E_INVALID
+ * before any device call.  Synchronises.                                                                                        */
+int prg_debug_resblock_tail(const float* h, const float* s0, const float* s1, const float* A, const float* Bc, const float* w_res,
+                            const float* b_res, const float* head_w, const float* head_b, float* out, int B, int N, int C0, int C1,
+                            int Cout, int head_sigmoid, int in_place, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Sampler: GaussianDiffusion.sample / p_sample_loop / ddim_sample (sd:1283-1409), DDNM replacement included

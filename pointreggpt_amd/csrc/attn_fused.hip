@@ -705,21 +705,25 @@ int tail_slabs(int N) { return ceil_div(ceil_div(N, kTP), kTilesPerBlock); }
 // fused, res never exists in HBM: -268 MB per level-0 block.  64-pixel tiles; the source tile and the h tile go
 // through LDS (coalesced 16-byte global accesses on both sides), Wres lives in registers as MFMA fragments, the
 // accumulator has pixels as columns so a lane owns four consecutive channels of one pixel.
+// Reads in flight: two register sets per block (tiles t+1 and t+2 while tile t is worked on) and the per-channel
+// coefficients in LDS instead of 48 registers per lane: 148 / 210 / 250 VGPRs, 3 / 2 / 2 blocks per CU, 144 / 160 / 192 KB
+// of tile reads in flight per CU for <128,64> / <192,128> / <256,128> (one set and the coefficients in registers: 48 / 80 /
+// 96 KB).  Measured: the launches do not get faster for it; only the head launch does, by its weights in LDS.
 // =====================================================================================================
+constexpr int kTailDepth = 2;        // register sets of a tail block = tiles of reads in flight per block
 template <int CIN, int COUT>
-__global__ __launch_bounds__(256) void resblock_tail_fused_kernel(const bf16_t* __restrict__ h, const float* __restrict__ A,
-                                                                  const float* __restrict__ Bc, const bf16_t* __restrict__ s0,
-                                                                  int C0, const bf16_t* __restrict__ s1, int C1,
-                                                                  const bf16_t* __restrict__ wres, const float* __restrict__ bres,
-                                                                  bf16_t* __restrict__ out, int N, const float* __restrict__ head_w,
-                                                                  const float* __restrict__ head_b, float* __restrict__ head_out,
-                                                                  int head_sigmoid, const GnFold fold) {
+__global__ __launch_bounds__(256, COUT == 64 ? 3 : 2) void resblock_tail_fused_kernel(
+    const bf16_t* __restrict__ h, const float* __restrict__ A, const float* __restrict__ Bc, const bf16_t* __restrict__ s0, int C0,
+    const bf16_t* __restrict__ s1, int C1, const bf16_t* __restrict__ wres, const float* __restrict__ bres, bf16_t* __restrict__ out,
+    int N, const float* __restrict__ head_w, const float* __restrict__ head_b, float* __restrict__ head_out, int head_sigmoid,
+    const GnFold fold) {
   constexpr int LDX = CIN + 8, LDH = COUT + 8;
   constexpr int RT = COUT / 32, NA = RT / 2;          // row tiles of 32 channels; accumulators per wave
   constexpr int XV = CIN / 32, HV = COUT / 32;        // 16-byte vectors per thread of the source / h tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __bf16* xs = reinterpret_cast<__bf16*>(smem);       // [64][LDX]
   __bf16* hs = xs + kTP * LDX;                        // [64][LDH]
+  float* cf = reinterpret_cast<float*>(hs + kTP * LDH);   // [4][COUT]: A | Bc | bres of this image | head_w
   const int b = blockIdx.y, slab = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int row = threadIdx.x >> 2, part = threadIdx.x & 3;
@@ -731,72 +735,78 @@ __global__ __launch_bounds__(256) void resblock_tail_fused_kernel(const bf16_t* 
   for (int a = 0; a < NA; ++a) ypt[a] = RT == 2 ? (wave >> 1) : a;
   bf16x8 wr[CIN / 16];
   load_wfrags<CIN>(wr, wres, yrt * 32, l31, hi);
-  // this lane's 16 channels: yrt*32 + 8 g4 + 4 hi + {0..3}
-  float4 ca[4], cb[4], cr[4];
-#pragma unroll
-  for (int g4 = 0; g4 < 4; ++g4) {
-    const int c0 = yrt * 32 + 8 * g4 + 4 * hi;
+  // The image's coefficients, one channel per thread, once per block into LDS (48 registers per lane as quads: the
+  // third wave per SIMD); barrier (1) of the first tile publishes them.  Per channel the same operations as a handle's
+  // gn_coeff pass: the GroupNorm fold from the image's fixed-point statistics, or the A / Bc tables.
+  if (threadIdx.x < COUT) {
+    const int c = threadIdx.x;
+    float a, bb;
     if (fold.acc) {
-      // GroupNorm coefficients of this lane's channel quad (inside one group) from the image's fixed-point statistics
       float mean, rstd;
-      gn_fold_stats(fold, b, c0 / fold.cpg, mean, rstd);
-      const float4 p4 = *reinterpret_cast<const float4*>(fold.P + (size_t)b * fold.pq_stride + c0);
-      const float4 q4 = *reinterpret_cast<const float4*>(fold.Q + (size_t)b * fold.pq_stride + c0);
-      ca[g4] = make_float4(rstd * p4.x, rstd * p4.y, rstd * p4.z, rstd * p4.w);
-      cb[g4] = make_float4(fmaf(-mean, ca[g4].x, q4.x), fmaf(-mean, ca[g4].y, q4.y), fmaf(-mean, ca[g4].z, q4.z),
-                           fmaf(-mean, ca[g4].w, q4.w));
+      gn_fold_stats(fold, b, c / fold.cpg, mean, rstd);
+      a = rstd * fold.P[(size_t)b * fold.pq_stride + c];
+      bb = fmaf(-mean, a, fold.Q[(size_t)b * fold.pq_stride + c]);
     } else {
-      ca[g4] = *reinterpret_cast<const float4*>(A + (size_t)b * COUT + c0);
-      cb[g4] = *reinterpret_cast<const float4*>(Bc + (size_t)b * COUT + c0);
+      a = A[(size_t)b * COUT + c];
+      bb = Bc[(size_t)b * COUT + c];
     }
-    cr[g4] = *reinterpret_cast<const float4*>(bres + c0);
+    cf[c] = a;
+    cf[COUT + c] = bb;
+    cf[2 * COUT + c] = bres[c];
+    if (head_out) cf[3 * COUT + c] = head_w[c];        // (a global load inside the loop would wait for the tiles in flight)
   }
-  uint4 xv[XV], hv[HV];
-  auto load_tile = [&](int t) {
-    const int valid = min(kTP, N - t * kTP);
-    const int64_t pix = (int64_t)b * N + (int64_t)t * kTP + row;
+  const float hb = head_out ? head_b[0] : 0.0f;
+  // Two register sets: while tile t is worked on, tiles t+1 and t+2 are on their way (two tiles of reads in flight per
+  // block).  h of a later tile is never written before this block has read it: a block writes only its own tiles, after
+  // reading them, so `out` may be `h`.
+  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+  struct Tile { u32x4 x[XV], h[HV]; };
+  Tile ta, tb;
+  // Every load is issued for every lane, so that the waits on a register set stay counted (a load under a branch makes the
+  // compiler drain the whole queue): rows past the image's or the block's last pixel re-read that pixel (one line per
+  // wave; their columns of the MFMA and their LDS rows are never stored).
+  const int plast = min(t1 * kTP, N) - 1;
+  auto load_tile = [&](Tile& T, int t) {
+    const int64_t pix = (int64_t)b * N + min(t * kTP + row, plast);
 #pragma unroll
     for (int i = 0; i < XV; ++i) {
       const int c = (part + 4 * i) * 8;
-      xv[i] = row < valid ? (c < C0 ? *reinterpret_cast<const uint4*>(s0 + pix * C0 + c)
-                                    : *reinterpret_cast<const uint4*>(s1 + pix * C1 + (c - C0)))
-                          : make_uint4(0, 0, 0, 0);
+      const bf16_t* p = c < C0 ? s0 + pix * C0 + c : s1 + pix * C1 + (c - C0);
+      T.x[i] = *reinterpret_cast<const u32x4*>(p);
     }
 #pragma unroll
-    for (int i = 0; i < HV; ++i)
-      hv[i] = row < valid ? *reinterpret_cast<const uint4*>(h + pix * COUT + (part + 4 * i) * 8) : make_uint4(0, 0, 0, 0);
+    for (int i = 0; i < HV; ++i) T.h[i] = *reinterpret_cast<const u32x4*>(h + pix * COUT + (part + 4 * i) * 8);
   };
-  if (t0 < t1) load_tile(t0);
-  for (int t = t0; t < t1; ++t) {
-    const int valid = min(kTP, N - t * kTP);
+  auto do_tile = [&](Tile& T, int t) {
+    const int valid = t < t1 ? min(kTP, N - t * kTP) : 0;
 #pragma unroll
-    for (int i = 0; i < XV; ++i) *reinterpret_cast<uint4*>(xs + row * LDX + (part + 4 * i) * 8) = xv[i];
+    for (int i = 0; i < XV; ++i) *reinterpret_cast<u32x4*>(xs + row * LDX + (part + 4 * i) * 8) = T.x[i];
 #pragma unroll
-    for (int i = 0; i < HV; ++i) *reinterpret_cast<uint4*>(hs + row * LDH + (part + 4 * i) * 8) = hv[i];
+    for (int i = 0; i < HV; ++i) *reinterpret_cast<u32x4*>(hs + row * LDH + (part + 4 * i) * 8) = T.h[i];
     __syncthreads();                                                                            // (1) tiles staged
-    if (t + 1 < t1) load_tile(t + 1);
-    f32x16 ya[NA];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) ya[a] = zero16();
-#pragma unroll
-    for (int kk = 0; kk < CIN / 16; ++kk)
-#pragma unroll
-      for (int a = 0; a < NA; ++a)
-        ya[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[kk], frag(xs + ypt[a] * 32 * LDX, LDX, l31, hi, kk), ya[a], 0, 0, 0);
+    load_tile(T, t + kTailDepth);
+    // this lane's 16 channels: yrt*32 + 8 g4 + 4 hi + {0..3}; one 32-pixel half after the other (16 accumulators live)
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
-      const int px = ypt[a] * 32 + l31;
+      f32x16 ya = zero16();
+#pragma unroll
+      for (int kk = 0; kk < CIN / 16; ++kk)
+        ya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[kk], frag(xs + ypt[a] * 32 * LDX, LDX, l31, hi, kk), ya, 0, 0, 0);
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
-        __bf16* hp = hs + px * LDH + yrt * 32 + 8 * g4 + 4 * hi;
+        const int c0 = yrt * 32 + 8 * g4 + 4 * hi;
+        const float4 ca = *reinterpret_cast<const float4*>(cf + c0);
+        const float4 cb = *reinterpret_cast<const float4*>(cf + COUT + c0);
+        const float4 cr = *reinterpret_cast<const float4*>(cf + 2 * COUT + c0);
+        const float a4[4] = {ca.x, ca.y, ca.z, ca.w};
+        const float b4[4] = {cb.x, cb.y, cb.z, cb.w};
+        const float r4[4] = {cr.x, cr.y, cr.z, cr.w};
+        __bf16* hp = hs + (ypt[a] * 32 + l31) * LDH + c0;
         const uint2 hw = *reinterpret_cast<const uint2*>(hp);
-        const float a4[4] = {ca[g4].x, ca[g4].y, ca[g4].z, ca[g4].w};
-        const float b4[4] = {cb[g4].x, cb[g4].y, cb[g4].z, cb[g4].w};
-        const float r4[4] = {cr[g4].x, cr[g4].y, cr[g4].z, cr[g4].w};
         const float hx[4] = {bf_lo(hw.x), bf_hi(hw.x), bf_lo(hw.y), bf_hi(hw.y)};
         float y[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = Elem<bf16_t>::silu(fmaf(hx[j], a4[j], b4[j])) + (ya[a][4 * g4 + j] + r4[j]);
+        for (int j = 0; j < 4; ++j) y[j] = Elem<bf16_t>::silu(fmaf(hx[j], a4[j], b4[j])) + (ya[4 * g4 + j] + r4[j]);
         uint2 w;
         w.x = pack2(y[0], y[1]);
         w.y = pack2(y[2], y[3]);
@@ -810,7 +820,7 @@ __global__ __launch_bounds__(256) void resblock_tail_fused_kernel(const bf16_t* 
 #pragma unroll
       for (int i = 0; i < HV; ++i) {
         const uint4 v = *reinterpret_cast<const uint4*>(hs + row * LDH + (part + 4 * i) * 8);
-        const float* w = head_w + (part + 4 * i) * 8;
+        const float* w = cf + 3 * COUT + (part + 4 * i) * 8;
         const uint32_t q[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -821,7 +831,7 @@ __global__ __launch_bounds__(256) void resblock_tail_fused_kernel(const bf16_t* 
       acc += __shfl_xor(acc, 1, 64);
       acc += __shfl_xor(acc, 2, 64);
       if (part == 0 && row < valid) {
-        const float y = acc + head_b[0];
+        const float y = acc + hb;
         head_out[(int64_t)b * N + (int64_t)t * kTP + row] = head_sigmoid ? 1.0f / (1.0f + expf(-y)) : y;
       }
     } else if (row < valid) {
@@ -831,6 +841,14 @@ __global__ __launch_bounds__(256) void resblock_tail_fused_kernel(const bf16_t* 
             *reinterpret_cast<const uint4*>(hs + row * LDH + (part + 4 * i) * 8);
     }
     __syncthreads();                                                                            // (3) tiles free
+  };
+  load_tile(ta, t0);
+  load_tile(tb, t0 + 1);
+  // (one back edge and no exit between the two halves, so that the compiler's waits stay counted: with an odd number of
+  // tiles the second half runs once on a tile past the block's last one and stores nothing)
+  for (int t = t0; t < t1; t += kTailDepth) {
+    do_tile(ta, t);
+    do_tile(tb, t + 1);
   }
 }
 
@@ -838,7 +856,7 @@ template <int CIN, int COUT>
 int launch_tail(const bf16_t* h, const float* A, const float* Bc, const bf16_t* s0, int C0, const bf16_t* s1, int C1,
                 const bf16_t* wres, const float* bres, bf16_t* out, int B, int N, hipStream_t s, const GnFold& fold,
                 const float* head_w = nullptr, const float* head_b = nullptr, float* head_out = nullptr, int head_sigmoid = 0) {
-  const size_t lds = (size_t)kTP * (CIN + 8 + COUT + 8) * 2;
+  const size_t lds = (size_t)kTP * (CIN + 8 + COUT + 8) * 2 + (size_t)4 * COUT * 4;
   static DeviceOnce attr;   // one-time opt-in; atomic: lanes launch from several host threads (idempotent call)
   if (!attr.done()) {
     int rc = set_lds(&resblock_tail_fused_kernel<CIN, COUT>, lds);

@@ -1,7 +1,7 @@
 // unet_debug.hip — the prg_debug_* entries (prg.h): single convolutions and a ResnetBlock's Block pair through the library's own
 // packer (pack_conv_host: what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own;
-// the attention cores, the channel LayerNorm and the fused linear-attention blocks (pack_fused_attention / pack_split_attention)
-// through the launch functions the forward calls, with the kernel chosen by argument.
+// the attention cores, the channel LayerNorm, the fused linear-attention blocks (pack_fused_attention / pack_split_attention)
+// and the fused ResnetBlock tail through the launch functions the forward calls, with the kernel chosen by argument.
 #include <type_traits>
 
 #include "unet_layout.h"
@@ -198,6 +198,46 @@ int prg_debug_linear_attention_block(const float* x, const float* norm_g, const 
   if (rc == PRG_OK) rc = launch_linear_attention_fused(d_x, d_wqkv, d_wout, d_bias, d_outg, d_out, ws, B, N, C, stat ? d_shift : nullptr, s, psum);
   if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(d_out, out, B, N, C, s);
   if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, nosync);
+  return rc;
+}
+
+// The fused ResnetBlock tail on tensors of its own, with the res_conv weight packed as a handle packs it (prg.h).
+int prg_debug_resblock_tail(const float* h, const float* s0, const float* s1, const float* A, const float* Bc, const float* w_res,
+                            const float* b_res, const float* head_w, const float* head_b, float* out, int B, int N, int C0, int C1,
+                            int Cout, int head_sigmoid, int in_place, void* stream) {
+  PRG_CHECK(h && s0 && s1 && A && Bc && w_res && b_res && out, "prg_debug_resblock_tail: null pointer");
+  PRG_CHECK((head_w != nullptr) == (head_b != nullptr), "prg_debug_resblock_tail: head_w and head_b come together");
+  PRG_CHECK(B > 0 && B <= 65535 && N > 0 && (int64_t)B * N <= (int64_t)1 << 22, "prg_debug_resblock_tail: bad shape");
+  PRG_CHECK(C0 > 0 && C1 > 0 && Cout > 0 && resblock_tail_fused_supported(C0, C1, Cout),
+            "prg_debug_resblock_tail: the kernel does not take these channel counts");
+  PRG_CHECK(!head_w || Cout == 64, "prg_debug_resblock_tail: the head needs Cout = 64");
+  PRG_CHECK((head_sigmoid == 0 || head_sigmoid == 1) && (in_place == 0 || in_place == 1),
+            "prg_debug_resblock_tail: head_sigmoid and in_place are 0 or 1");
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_resblock_tail: hipMalloc failed";
+  const size_t M = (size_t)B * N;
+  const int cin = C0 + C1;
+  std::vector<bf16_t> wb((size_t)Cout * cin);
+  for (size_t i = 0; i < wb.size(); ++i) wb[i] = f32_to_bf16(w_res[i]);   // (upload_fused_attention: the raw weight as bf16)
+  DeviceBuffers own;
+  const bf16_t* d_w = own.upload(wb, nomem);
+  const float* d_b = own.upload(b_res, (size_t)Cout, nomem);
+  const float* d_hw = head_w ? own.upload(head_w, (size_t)Cout, nomem) : nullptr;
+  const float* d_hb = head_b ? own.upload(head_b, (size_t)1, nomem) : nullptr;
+  bf16_t* d_h = own.alloc<bf16_t>(M * Cout, nomem);
+  bf16_t* d_s0 = own.alloc<bf16_t>(M * C0, nomem);
+  bf16_t* d_s1 = own.alloc<bf16_t>(M * C1, nomem);
+  bf16_t* d_o = in_place ? d_h : own.alloc<bf16_t>(M * Cout, nomem);
+  if (own.rc) return own.rc;
+  // (pixel-major already: the layout kernels with one channel are plain conversions)
+  int rc = launch_nchw_f32_to_nhwc<bf16_t>(h, d_h, 1, (int)(M * Cout), 1, s);
+  if (rc == PRG_OK) rc = launch_nchw_f32_to_nhwc<bf16_t>(s0, d_s0, 1, (int)(M * C0), 1, s);
+  if (rc == PRG_OK) rc = launch_nchw_f32_to_nhwc<bf16_t>(s1, d_s1, 1, (int)(M * C1), 1, s);
+  if (rc == PRG_OK)
+    rc = launch_resblock_tail_fused(d_h, A, Bc, d_s0, C0, d_s1, C1, d_w, d_b, d_o, B, N, Cout, s, d_hw, d_hb, head_w ? out : nullptr,
+                                    head_sigmoid, nullptr);
+  if (rc == PRG_OK && !head_w) rc = launch_nhwc_to_nchw_f32<bf16_t>(d_o, out, 1, (int)(M * Cout), 1, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_resblock_tail: stream synchronise failed");
   return rc;
 }
 
