@@ -400,6 +400,53 @@ int prg_debug_resblock_tail(const float* h, const float* s0, const float* s1, co
                             const float* b_res, const float* head_w, const float* head_b, float* out, int B, int N, int C0, int C1,
                             int Cout, int head_sigmoid, int in_place, void* stream);
 
+/* Kernel unit-test hook: ONE bf16 convolution through the library's own packer and dispatch with the fused options the forward
+ * pass sets on it: two sources, statistics of the output, a prologue on the input, a residual in the epilogue.
+ *   Operands: x0 (B,C0,H,W), x1 (B,C1,H,W) float32 DEVICE (x1 NULL exactly when C1 = 0), converted to bf16; w (Cout,C0+C1,K,K),
+ *   bias (Cout) float32 HOST; a NULL bias reaches the launch as NULL.  K = 1 (pad 0) or 3 (pad 1), stride 1.  C0, C1, Cout are
+ *   multiples of 8; `groups` cuts Cout (and the folded tensor) into multiples of 8 channels.
+ *   prologue (K = 3, C1 = 0, a shape whose kernels have one): x <- SiLU(x * a[b][c] + b[b][c]) with PRG_CF_PRO_TABLES pro_a,
+ *   pro_b (B,C0) float32 DEVICE, or PRG_CF_PRO_FOLD coefficients folded from fold_acc (B,groups,2) int64 DEVICE fixed-point
+ *   (sum * 2^24, sum of squares * 2^20) and fold_p, fold_q (C0) float32 HOST (a = rstd * p, b = q - mean * a).
+ *   residual_mode (K = 1): residual (B,Cout,H,W) float32 DEVICE, converted to bf16; PRG_CF_RES_ADD out = conv + residual,
+ *   PRG_CF_RES_TABLES out = conv + SiLU(residual * res_a + res_b) with res_a, res_b (B,Cout) float32 DEVICE, PRG_CF_RES_FOLD the
+ *   same from fold_acc / fold_p / fold_q (Cout).  in_place 1: the bf16 residual buffer is also the output buffer.
+ *   stats (K = 3): PRG_CF_STATS_SLABS asks for per-tile slabs, PRG_CF_STATS_ACC also offers fixed-point accumulators.  A shape
+ *   that fuses nothing gets the separate statistics pass (stats_pass = 1).  sums (B,groups,2) float64 HOST: the slabs of an image
+ *   group added in slab order, or the accumulators scaled back; acc_raw (B,groups,2) int64 HOST (all zero when the kernel declined
+ *   the accumulators); coef_a, coef_b (B,Cout) float32 DEVICE: the GroupNorm coefficient tables the library's next step makes
+ *   of them with gamma, beta (Cout) float32 HOST.  nsplit and acc_done are what the conv launch reported.
+ * out (B,Cout,H,W) float32 DEVICE.  Bad arguments fail with PRG_E_INVALID before any device call.  Synchronises.                 */
+enum { PRG_CF_PRO_NONE = 0, PRG_CF_PRO_TABLES = 1, PRG_CF_PRO_FOLD = 2 };
+enum { PRG_CF_RES_NONE = 0, PRG_CF_RES_ADD = 1, PRG_CF_RES_TABLES = 2, PRG_CF_RES_FOLD = 3 };
+enum { PRG_CF_STATS_OFF = 0, PRG_CF_STATS_SLABS = 1, PRG_CF_STATS_ACC = 2 };
+typedef struct prg_conv_fused {
+  const float* x0;
+  const float* x1;
+  const float* w;
+  const float* bias;
+  const float* pro_a;
+  const float* pro_b;
+  const float* residual;
+  const float* res_a;
+  const float* res_b;
+  const int64_t* fold_acc;
+  const float* fold_p;
+  const float* fold_q;
+  const float* gamma;
+  const float* beta;
+  float* out;
+  double* sums;
+  int64_t* acc_raw;
+  float* coef_a;
+  float* coef_b;
+  int32_t B, C0, C1, Cout, H, W, K, groups;
+  int32_t prologue, residual_mode, in_place, stats;
+  int32_t nsplit, acc_done, stats_pass;   /* out */
+  int32_t reserved;
+} prg_conv_fused;
+int prg_debug_conv_fused(prg_conv_fused* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Sampler: GaussianDiffusion.sample / p_sample_loop / ddim_sample (sd:1283-1409), DDNM replacement included
  * ---------------------------------------------------------------------------------------------------- */

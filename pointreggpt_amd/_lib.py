@@ -28,6 +28,18 @@ class StepC(C.Structure):
                 ("sqrt_recipm1", C.c_float)]
 
 
+class ConvFusedC(C.Structure):
+    """prg_conv_fused (include/prg.h): the arguments of prg_debug_conv_fused."""
+    _fields_ = ([(n, C.c_void_p) for n in ("x0", "x1", "w", "bias", "pro_a", "pro_b", "residual", "res_a", "res_b", "fold_acc",
+                                           "fold_p", "fold_q", "gamma", "beta", "out", "sums", "acc_raw", "coef_a", "coef_b")] +
+                [(n, C.c_int32) for n in ("B", "C0", "C1", "Cout", "H", "W", "K", "groups", "prologue", "residual_mode",
+                                          "in_place", "stats", "nsplit", "acc_done", "stats_pass", "reserved")])
+
+
+CF_PRO_NONE, CF_PRO_TABLES, CF_PRO_FOLD = 0, 1, 2
+CF_RES_NONE, CF_RES_ADD, CF_RES_TABLES, CF_RES_FOLD = 0, 1, 2, 3
+CF_STATS_OFF, CF_STATS_SLABS, CF_STATS_ACC = 0, 1, 2
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> (restype, argtypes): every symbol include/prg.h declares
@@ -73,6 +85,7 @@ PROTOTYPES = {
     "prg_debug_layernorm": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P]),
     "prg_debug_linear_attention_block": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     "prg_debug_resblock_tail": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "prg_debug_conv_fused": (C.c_int, [C.POINTER(ConvFusedC), _P]),
     "prg_unet_set_taps": (C.c_int, [_P, _I]),
     "prg_unet_get_tap": (C.c_int, [_P, C.c_char_p, _P, _L, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
     "prg_sampler_create": (C.c_int, [_P, C.POINTER(StepC), _I, _I, _I, C.POINTER(_P)]),
