@@ -290,6 +290,31 @@ int prg_rigid_crop_ragged_f64(const double* pts, const uint8_t* valid, const int
                               const double* T, const uint8_t* has_T, const double* lo, const double* hi, double* out,
                               uint8_t* valid_out, void* stream);
 
+/* The registration loaders' augmentation of C ragged float64 clouds in one call: cut each cloud to a point limit by a keyed
+ * random permutation, move it by its rigid transform, add uniform per-point noise.  postprocess.augment_cloud is the numpy
+ * definition; the outputs are its bits.
+ * pts (total,3) float64, offsets (C+1) int64, both DEVICE: cloud c is rows [offsets[c], offsets[c+1]) (clamped into
+ *   [0, total]), n_c rows; rows outside the segments are not read.  1 <= C <= 65535, total and out_total < 2^31.
+ * T (C,16) float64 DEVICE or NULL, has_T (C) bytes DEVICE or NULL: exactly prg_rigid_crop_ragged_f64's, the same arithmetic;
+ *   a cloud that is not moved is copied, not multiplied.
+ * seeds (C) uint64 DEVICE: one Philox4x32-10 key per cloud (k0 = low word).  Row i (local index in its cloud) draws ONE
+ *   call, counter {i, draw, 0x6175676D ("augm"), 0}, giving w0..w3.  Its noise depends on (seed, draw, i) only.
+ * keys (total) uint32 DEVICE or NULL: the sort key of row i of cloud c is keys[offsets[c] + i], or w0 when keys is NULL.
+ * limit: rows kept per cloud, 0 = all.  m_c = min(n_c, limit (if > 0), out_offsets[c+1] - out_offsets[c]).  If m_c == n_c
+ *   the rows keep their order: slot i <- row i.  Otherwise rank(i) = #{u : (key_u, u) < (key_i, i)} and row i goes to slot
+ *   rank(i) iff rank(i) < m_c: the kept rows arrive in key order, a random permutation cut at m_c.
+ * Position of a kept row: the rigid move first, then, iff noise != 0, per axis a: + (u - 0.5) * noise with
+ *   u = ((double)w_{1+a} + 0.5) * 2^-32 — u and u - 0.5 are exact, the product is the one rounding; the noise lies strictly
+ *   inside (-noise/2, noise/2).  noise must be finite and >= 0.
+ * out_offsets (C+1) int64 DEVICE (clamped into [0, out_total]), out (out_total,3) float64 DEVICE, rows (out_total) int32
+ *   DEVICE: out[out_offsets[c] + slot] = the position, rows[...] = i.  Slots beyond m_c are not written.  out must not be
+ *   pts: the rows are permuted.
+ * Asynchronous on `stream`; reads no device data on the host; allocates nothing; no atomics.                              */
+int prg_augment_ragged_f64(const double* pts, const int64_t* offsets, int C, int64_t total, const double* T,
+                           const uint8_t* has_T, const uint64_t* seeds, uint32_t draw, const uint32_t* keys, int64_t limit,
+                           double noise, const int64_t* out_offsets, int64_t out_total, double* out, int32_t* rows,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * U-Nets (MFMA kernels)
  * ---------------------------------------------------------------------------------------------------- */

@@ -68,6 +68,7 @@ PROTOTYPES = {
     "prg_voxel_grid_ragged": (C.c_int, [_P, _P, _P, _I, _L, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
     "prg_merge_memory_f64": (C.c_int, [_P, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P]),
     "prg_rigid_crop_ragged_f64": (C.c_int, [_P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "prg_augment_ragged_f64": (C.c_int, [_P, _P, _I, _L, _P, _P, _P, C.c_uint32, _P, _L, C.c_double, _P, _L, _P, _P, _P]),
     "prg_unet_param_count": (_L, [C.POINTER(UnetConfigC)]),
     "prg_unet_create": (C.c_int, [C.POINTER(UnetConfigC), _P, _L, _I, C.POINTER(_P)]),
     "prg_unet_destroy": (C.c_int, [_P]),

@@ -12,12 +12,9 @@
 // (tools/micro/rows3_access.hip, 20 M rows): 5.5 TB/s for this one, 5.1-5.4 TB/s for the staged one — the simpler kernel stays.
 // Workgroups are dealt per segment (blockIdx.y, the way project_points_kernel and the voxel-grid kernels do), so a row's
 // segment — its matrix — is known without a search.
-#include "common.h"
+#include "cloudmove.h"
 
 namespace prg {
-
-static constexpr int kCfRows = 256;                 // threads per workgroup, one row each per pass
-static constexpr int kCfMaxSegments = 65535;        // gridDim.y
 
 struct CfBox {
   double lo[3], hi[3];
@@ -41,24 +38,12 @@ __global__ __launch_bounds__(256) void rigid_crop_kernel(const double* pts, cons
   for (int64_t i = beg + (int64_t)blockIdx.x * kCfRows + threadIdx.x; i < end; i += (int64_t)gridDim.x * kCfRows) {
     double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
     bool keep = valid == nullptr || valid[i] != 0;
-    if (moved) {
-      const double px = x, py = y, pz = z;
-      x = px * m[0] + py * m[1] + pz * m[2] + m[3];
-      y = px * m[4] + py * m[5] + pz * m[6] + m[7];
-      z = px * m[8] + py * m[9] + pz * m[10] + m[11];
-    }
+    if (moved) { const Row3 r = rigid_move_row(m, x, y, z); x = r.x; y = r.y; z = r.z; }
     if (kCrop)        // every comparison with NaN is false: a masked row of garbage stays masked and nothing else happens to it
       keep = keep && x >= box.lo[0] && x <= box.hi[0] && y >= box.lo[1] && y <= box.hi[1] && z >= box.lo[2] && z <= box.hi[2];
     if (moved || out != pts) { out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z; }
     if (valid_out) valid_out[i] = keep ? 1 : 0;
   }
-}
-
-static inline int cf_grid_x(int64_t total, int B) {
-  // enough workgroups for a segment four times the average, one row per thread; longer segments loop (grid-stride)
-  const int64_t avg = (total + B - 1) / B;
-  const int64_t gx = (4 * avg + kCfRows - 1) / kCfRows;
-  return (int)(gx < 1 ? 1 : gx > 4096 ? 4096 : gx);
 }
 
 }  // namespace prg

@@ -3,30 +3,13 @@
 // Built with -ffp-contract=off: the float ops are in the reference's order (sd:1158-1162, 1173-1180, 1210-1218,
 // 1250-1251, 1280, 1369-1373) so that, given identical network outputs and noise, the state is bit-identical.
 #include "sampler.h"
+#include "philox.h"
 
 #include <vector>
 
 namespace prg {
 
-// ---- Philox4x32-10 (counter-based; key = per-scene seed, counter = (pixel quad, draw index)) ----
-__device__ inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ inline void philox4x32_10(uint32_t (&c)[4], uint64_t key) {
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
+// ---- noise from Philox4x32-10 (philox.h): key = per-scene seed, counter = (pixel quad, draw index, stream tag) ----
 // four standard normals for (scene key, draw index, pixel quad): two Box-Muller pairs
 __device__ inline float4 philox_normal4(uint64_t key, uint32_t draw, uint32_t quad) {
   uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_NORMAL, 0u};

@@ -774,6 +774,61 @@ def rigid_crop_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     return out, valid_out
 
 
+def augment_clouds(points: torch.Tensor, lengths, *, seeds, draw: int = 0, noise: float = 0.0, limit: Optional[int] = None,
+                   T=None, has_T=None, keys=None):
+    """prg_augment_ragged_f64: the registration loaders' augmentation of a stack of C clouds on the device — each cloud cut to
+    `limit` rows by a keyed random permutation, moved by its 4x4, jittered by uniform noise inside (-noise/2, noise/2) — bit for
+    bit `postprocess.augment_cloud` per cloud (which states the definition).  points (N,3) float64 or float32 device tensor
+    (float32 is widened, which is exact), the clouds one after the other; lengths: their rows, a HOST list or array; seeds: C
+    64-bit Philox keys (host ints, e.g. `synthetic.augment_seed`); draw: the second counter word — the epoch, for a job that
+    re-augments cached pairs without regenerating them; T (C,4,4) float64 / has_T (C) as `rigid_crop_ragged` takes them; keys
+    (N,) uint32 sort keys (numpy or int32 / uint32 tensor) instead of Philox's.
+    -> {"points": (M,3) float64, "lengths": (C,) int64, "rows": (M,) int32 local input row of every output row}, all on the
+    device, M = sum of min(n_c, limit).  Host synchronisations: none — the output offsets follow from `lengths` on
+    the host, the small arrays are uploaded, one launch."""
+    lib = _lib.load()
+    if not points.is_cuda:
+        raise _lib.PrgError("expected a tensor on the HIP device (this package has no CPU path)")
+    if points.dtype not in (torch.float64, torch.float32):
+        raise _lib.PrgError("augment_clouds: points must be float64 or float32")
+    from .postprocess import _check_augment
+    lim = _check_augment(noise, limit)
+    if not 0 <= int(draw) < 2 ** 32:
+        raise ValueError("draw must fit 32 bits")
+    dev = points.device
+    pts = points.contiguous().view(-1, 3).to(torch.float64)
+    lens = np.asarray(lengths).astype(np.int64).reshape(-1)
+    C = len(lens)
+    if C < 1 or (lens < 0).any() or int(lens.sum()) != pts.shape[0]:
+        raise ValueError("lengths do not add up to the rows of points")
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+    if len(seeds) != C:
+        raise ValueError("one seed per cloud")
+    m = np.minimum(lens, lim) if lim else lens.copy()
+    offs, o_offs = np.concatenate([[0], np.cumsum(lens)]), np.concatenate([[0], np.cumsum(m)])
+    total, M = int(offs[-1]), int(o_offs[-1])
+    out = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    rows = torch.empty((M,), dtype=torch.int32, device=dev)
+    res = {"points": out, "lengths": _dev_i64(m, dev), "rows": rows}
+    if M == 0:                                      # no rows, and a tensor without elements has no address to pass
+        return res
+    kd = None
+    if keys is not None:
+        if not torch.is_tensor(keys):
+            keys = torch.from_numpy(np.ascontiguousarray(keys).astype(np.uint32).view(np.int32))
+        if keys.dtype == getattr(torch, "uint32", None):
+            keys = keys.view(torch.int32)
+        assert keys.dtype == torch.int32 and keys.numel() == total, "one 32-bit key per row"
+        kd = keys.to(dev).contiguous()
+    sd = torch.from_numpy(np.array(seeds, dtype=np.uint64).view(np.int64)).to(dev)
+    Td, hd = _transforms(T, C, dev), _flags(has_T, C, dev)
+    d_offs, d_o_offs = _dev_i64(offs, dev), _dev_i64(o_offs, dev)        # named: both must be alive when the call is made
+    _lib.check(lib.prg_augment_ragged_f64(_lib.ptr(pts), _lib.ptr(d_offs), C, total, _lib.ptr(Td), _lib.ptr(hd), _lib.ptr(sd),
+                                          int(draw), _lib.ptr(kd), lim, float(noise), _lib.ptr(d_o_offs), M, _lib.ptr(out),
+                                          _lib.ptr(rows), _lib.stream_ptr()), "prg_augment_ragged_f64")
+    return res
+
+
 def finish_clouds(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets: torch.Tensor, voxel: float, *, pre=None,
                   has_pre=None, crop=None, post=None, has_post=None):
     """`WriterPool.cloud`'s pipeline for B ragged clouds at once, on the device: pre-transform -> crop -> voxel mean ->

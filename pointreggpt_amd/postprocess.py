@@ -314,6 +314,83 @@ def radius_pairs_hip(pairs, radius: float, device="cuda"):
     return [corr[po[p]:po[p + 1]].copy() for p in range(len(pairs))]
 
 
+AUGMENT_TAG = 0x6175676D        # "augm": third Philox counter word of the augmentation stream, tag word of synthetic.augment_seed
+
+
+def _check_augment(noise, limit) -> int:
+    """-> limit as the entry point takes it (0 = all rows)."""
+    if not (np.isfinite(noise) and noise >= 0):
+        raise ValueError("noise must be finite and >= 0")
+    if limit is not None and (int(limit) != limit or limit < 1):
+        raise ValueError("limit must be a positive integer (or None for every row)")
+    return 0 if limit is None else int(limit)
+
+
+def augment_cloud(points: np.ndarray, *, seed: int, draw: int = 0, noise: float = 0.0, limit: Optional[int] = None,
+                  T: Optional[np.ndarray] = None, keys: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """What the registration loaders do to a cloud before they search its correspondences — cut it to `limit` points by a
+    random permutation, move it rigidly, add uniform noise — as a function of (seed, draw): the numpy specification of
+    prg_augment_ragged_f64, bit for bit.  -> (points_out (m,3) float64, rows (m,) int32: which input row each output row was).
+
+    Row i of the n input rows draws ONE Philox4x32-10 call, key `seed` (64 bits), counter {i, draw, 0x6175676D, 0} -> w0..w3.
+    Selection: key_i = keys[i] (uint32) if `keys` is given, else w0; m = min(n, limit).  If m == n the rows keep their order
+    (the loaders permute only when they cut).  Otherwise the rows are ordered by (key_i, i) and the first m are kept, in that
+    order: a random permutation cut at m, like `np.random.permutation(n)[:limit]`.
+    Position: `rigid_move(row, T)` if T is given (else the row's bits, -0.0 included), then, iff noise != 0, per axis a
+    + (u - 0.5) * noise with u = (float64(w_{1+a}) + 0.5) * 2^-32: u and u - 0.5 are exact in float64, the product is the one
+    rounding, and the noise lies strictly inside (-noise/2, noise/2) — the loaders' `(rand(n,3) - 0.5) * augment_noise`.  The
+    noise of a row depends on (seed, draw, i) only, not on what the cut keeps."""
+    from .philox import philox4x32_10
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(pts)
+    m = min(n, _check_augment(noise, limit) or n)
+    if not 0 <= int(draw) < 2 ** 32:
+        raise ValueError("draw must fit 32 bits")
+    w = philox4x32_10(np.arange(n, dtype=np.uint64), int(draw), AUGMENT_TAG, 0, seed)
+    if m == n:
+        rows = np.arange(n, dtype=np.int32)
+    else:
+        key = w[0] if keys is None else np.asarray(keys).reshape(-1).astype(np.uint32)
+        if len(key) != n:
+            raise ValueError("one key per row")
+        rows = np.lexsort((np.arange(n), key))[:m].astype(np.int32)          # by key, ties by row
+    out = pts[rows] if T is None else rigid_move(pts[rows], T)
+    if noise != 0.0:
+        u = (np.stack(w[1:], axis=1)[rows].astype(np.float64) + 0.5) * 2.0 ** -32
+        out = out + (u - 0.5) * np.float64(noise)
+    return np.ascontiguousarray(out, dtype=np.float64).reshape(-1, 3), rows
+
+
+def augment_clouds_hip(clouds, *, seeds, draw: int = 0, noise: float = 0.0, limit: Optional[int] = None, T=None, keys=None,
+                       device="cuda"):
+    """[cloud (n,3), ...] -> [(points_out, rows), ...] as `augment_cloud(cloud, seed=seeds[c], draw=, noise=, limit=, T=T[c],
+    keys=keys[c])` defines them, for clouds that are on the host: all clouds uploaded once as one ragged float64 buffer, ONE
+    prg_augment_ragged_f64 launch (`geometry.augment_clouds`), one copy back.  T: a list with a 4x4 or None per cloud, or None;
+    keys: a list with a uint32 array per cloud, or None (Philox keys)."""
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    clouds = [_f64(c) for c in clouds]
+    if not clouds:
+        return []
+    if sum(len(c) for c in clouds) == 0:
+        return [(np.zeros((0, 3)), np.zeros(0, dtype=np.int32)) for _ in clouds]
+    pts, _ = G.upload_clouds(clouds, device, dtype=np.float64)
+    has_T = Td = None
+    if T is not None:
+        has_T = np.array([t is not None for t in T], dtype=np.uint8)
+        Td = np.stack([np.eye(4) if t is None else np.asarray(t, dtype=np.float64).reshape(4, 4) for t in T])
+    kd = None
+    if keys is not None:
+        kd = np.concatenate([np.asarray(k).reshape(-1).astype(np.uint32) for k in keys])
+    res = G.augment_clouds(pts, [len(c) for c in clouds], seeds=seeds, draw=draw, noise=noise, limit=limit, T=Td, has_T=has_T,
+                           keys=kd)
+    out, rows = res["points"].cpu().numpy(), res["rows"].cpu().numpy()
+    o = np.concatenate([[0], np.cumsum([min(len(c), limit or len(c)) for c in clouds])])
+    return [(out[o[c]:o[c + 1]].copy(), rows[o[c]:o[c + 1]].copy()) for c in range(len(clouds))]
+
+
 def _check_radius_limit(radius, limit) -> None:
     if not (np.isfinite(radius) and radius > 0):
         raise ValueError("radius must be finite and > 0")

@@ -17,12 +17,18 @@ same `batch_size`, `start` and seeds.  `noise_seed` is required: besides the dif
 pose stream per (job seed, first scene of the batch) exactly as `generate(noise_seed=...)` does — the batches, and so the
 poses, are the same only for the same `start` and `batch_size`.  There is no unseeded mode here.
 
+Augmentation: `PairStream(..., augment=Augment(...), epoch=e)` applies the registration loaders' per-item augmentation on the
+device — a random pose, the cut to a point limit, uniform per-point noise — keyed per (noise_seed, scene, epoch), and searches
+`corr` on the augmented clouds under the ground-truth `transform` (see `Augment`).  With `augment=None` (the default) the
+items are exactly the ones described above.
+
 The stream runs on the calling thread's current HIP stream.  It uses no writer pool and no lanes, writes no file and creates
 nothing under the generator's `samples_folder` (the folder itself is `Generator.__init__`'s doing).
 """
 from __future__ import annotations
 
 import pickle
+from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -33,10 +39,69 @@ from . import synthetic
 from .sharding import num_to_groups
 
 
+@dataclass(frozen=True)
+class Augment:
+    """What the example loaders (Predator, CoFiNet, GeoTransformer) do to an item before they search its correspondences.
+
+    noise: both clouds get uniform per-point noise strictly inside (-noise/2, noise/2) per axis (the loaders' `augment_noise`);
+    point_limit: a cloud with more rows is cut to that many by a random permutation (None: never);
+    rotation: None — the clouds stay in their common frame, `transform` is the identity and nothing is drawn; "src" — the
+      source is moved by a uniform random pose, `src_aug = (src - t) @ R`; "both" — a second uniform rotation R2 moves the target
+      too, `tgt_aug = tgt @ R2.T`;
+    translation: the standard deviation of the Gaussian t, in metres."""
+    noise: float = 0.005
+    point_limit: Optional[int] = 30000
+    rotation: Optional[str] = "src"
+    translation: float = 1.0
+
+    def __post_init__(self):
+        if self.rotation not in (None, "src", "both"):
+            raise ValueError("rotation must be None, 'src' or 'both'")
+        if not (np.isfinite(self.translation) and self.translation >= 0):
+            raise ValueError("translation must be finite and >= 0")
+        PP._check_augment(self.noise, self.point_limit)
+
+
+def uniform_rotation(rng: np.random.Generator) -> np.ndarray:
+    """A rotation uniform on SO(3) (Haar measure) by the loaders' construction: the Q of the QR decomposition of a 3x3 Gaussian
+    matrix, its columns signed so that R's diagonal is positive, the whole negated if that leaves a reflection."""
+    z = rng.standard_normal((3, 3))
+    while np.linalg.matrix_rank(z) != 3:
+        z = rng.standard_normal((3, 3))
+    q, r = np.linalg.qr(z)
+    q = q * np.sign(np.diag(r))
+    return q if np.linalg.det(q) > 0 else -q
+
+
+def augment_poses(noise_seed: int, scene: int, epoch: int, augment: Augment):
+    """The poses of one scene's item -> (move_src, move_tgt, transform): float64 4x4 matrices built on the host, a move being
+    None for a cloud that stays where it is.  `src_aug = rigid_move(src, move_src)`, `tgt_aug = rigid_move(tgt, move_tgt)`, and
+    `transform` takes the augmented source into the augmented target's frame.
+
+    Drawn from `np.random.Generator(np.random.Philox(key=synthetic.augment_seed(noise_seed, scene, 2), counter=[0, 0, 0,
+    epoch]))` in this order: R (`uniform_rotation`), t = standard_normal(3) * translation, and for "both" R2.  "src":
+    move_src = [[R^T, -R^T t], [0, 1]] (the loaders' `(src - t) @ R`), transform = [R | t].  "both": move_tgt = [R2 | 0],
+    transform = R2 [R | t]."""
+    if augment.rotation is None:
+        return None, None, np.eye(4)
+    rng = np.random.Generator(np.random.Philox(key=synthetic.augment_seed(noise_seed, scene, 2), counter=[0, 0, 0, int(epoch)]))
+    R = uniform_rotation(rng)
+    t = rng.standard_normal(3) * float(augment.translation)
+    move_src, transform = np.eye(4), np.eye(4)
+    move_src[:3, :3], move_src[:3, 3] = R.T, -(R.T @ t)
+    transform[:3, :3], transform[:3, 3] = R, t
+    move_tgt = None
+    if augment.rotation == "both":
+        move_tgt = np.eye(4)
+        move_tgt[:3, :3] = uniform_rotation(rng)
+        transform = move_tgt @ transform
+    return move_src, move_tgt, transform
+
+
 class PairStream:
     def __init__(self, generator, depth_correction, *, start: int, stop: int, noise_seed: int,
                  matching_radius: Optional[float] = None, mask_threshold: float = 0.99, has_refine_step: bool = False,
-                 save_voxel_size: float = 0.025, to: str = "numpy"):
+                 save_voxel_size: float = 0.025, to: str = "numpy", augment: Optional[Augment] = None, epoch: int = 0):
         if to not in ("numpy", "torch"):
             raise ValueError("to must be 'numpy' or 'torch'")
         if generator.device.type == "cpu":
@@ -45,6 +110,11 @@ class PairStream:
             raise ValueError("PairStream needs a noise_seed (it also seeds the real-data pose stream per batch)")
         if matching_radius is not None and not (np.isfinite(matching_radius) and matching_radius > 0):
             raise ValueError("matching_radius must be finite and > 0 (or None for no correspondences)")
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError("augment must be a stream.Augment (or None)")
+        if not 0 <= int(epoch) < 2 ** 32:
+            raise ValueError("epoch must fit 32 bits")
+        self.augment, self.epoch = augment, int(epoch)
         self.generator = generator
         self.depth_correction = depth_correction
         self.start, self.stop = int(start), int(stop)
@@ -83,6 +153,28 @@ class PairStream:
         xyz, valid = G_.unproject_f64(images, K_dev, pose_dev)
         return gen._finish_pairs_launch(mem_pts, mem_offs, [len(m) for m in memory], [(xyz, valid)], pose, self.save_voxel_size)
 
+    # -- the loaders' augmentation of the surviving pairs of a batch: one launch for all of them -------------------------------
+    def _augment(self, pts, sizes, scenes):
+        """pts / sizes: the ragged buffer of the pairs (segments 2k, 2k+1 = src, tgt of scenes[k]) -> (augmented buffer, its
+        sizes, int32 rows, [transform per pair])."""
+        aug, G_ = self.augment, self.generator.G
+        n = len(scenes)
+        T = np.tile(np.eye(4), (2 * n, 1, 1))
+        has_T = np.zeros(2 * n, dtype=np.uint8)
+        seeds, transforms = [], []
+        for k, scene in enumerate(scenes):
+            moves = augment_poses(self.noise_seed, scene, self.epoch, aug)
+            for c in (0, 1):
+                if moves[c] is not None:
+                    T[2 * k + c], has_T[2 * k + c] = moves[c], 1
+                seeds.append(synthetic.augment_seed(self.noise_seed, scene, c))
+            transforms.append(moves[2])
+        res = G_.augment_clouds(pts, sizes, seeds=seeds, draw=self.epoch, noise=aug.noise, limit=aug.point_limit,
+                                T=T if has_T.any() else None, has_T=has_T if has_T.any() else None)
+        if aug.point_limit is not None:
+            sizes = np.minimum(sizes, int(aug.point_limit))
+        return res["points"], sizes, res["rows"], transforms
+
     def __iter__(self):
         gen = self.generator
         self.skipped = []
@@ -115,13 +207,23 @@ class PairStream:
                 pts = fin[int(offs[0]):int(offs[-1])]
             else:
                 pts = torch.cat([fin[int(offs[2 * j]):int(offs[2 * j + 2])] for j in keep], dim=0)
+            rows = transforms = None
+            if self.augment is not None:
+                pts, sizes, rows, transforms = self._augment(pts, sizes, [idxs[j] for j in keep])
+                k_offs[1:] = np.cumsum(sizes)
             corr = c_offs = None
             if self.matching_radius is not None:
-                corr, c_offs = gen.G.radius_pairs_ragged(pts.contiguous(), torch.from_numpy(k_offs).to(pts.device), len(keep),
-                                                         int(sizes.max()), self.matching_radius)
+                d_offs = torch.from_numpy(k_offs).to(pts.device)
+                search = pts.contiguous()
+                if transforms is not None:           # the correspondences hold under the ground truth: a moved copy of the sources
+                    T = np.tile(np.eye(4), (2 * len(keep), 1, 1))
+                    T[0::2] = transforms
+                    search, _ = gen.G.rigid_crop_ragged(search, None, d_offs, T=T, has_T=np.tile(np.array([1, 0], np.uint8), len(keep)))
+                corr, c_offs = gen.G.radius_pairs_ragged(search, d_offs, len(keep), int(sizes.max()), self.matching_radius)
                 c_offs = c_offs.cpu().numpy()
             if self.to == "numpy":
                 pts = pts.cpu().numpy()
+                rows = None if rows is None else rows.cpu().numpy()
                 corr = None if corr is None else corr.cpu().numpy()
                 own = np.copy
             else:
@@ -131,4 +233,8 @@ class PairStream:
                             overlap_src=ratios[k][0], overlap_tgt=ratios[k][1])
                 if corr is not None:
                     item["corr"] = own(corr[c_offs[k]:c_offs[k + 1]])
+                if rows is not None:
+                    item["transform"] = transforms[k] if self.to == "numpy" else torch.from_numpy(transforms[k]).to(pts.device)
+                    item["src_rows"] = own(rows[k_offs[2 * k]:k_offs[2 * k + 1]])
+                    item["tgt_rows"] = own(rows[k_offs[2 * k + 1]:k_offs[2 * k + 2]])
                 yield item

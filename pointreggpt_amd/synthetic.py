@@ -80,3 +80,15 @@ def noise_seed(base_seed: int, scene_index: int, sample_index: int = 0) -> int:
     if sample_index:
         words.append(int(sample_index))
     return int(np.random.SeedSequence(words).generate_state(1, np.uint64)[0])
+
+
+def augment_seed(base_seed: int, scene_index: int, cloud: int = 0) -> int:
+    """64-bit Philox key of a scene's augmentation streams, built the way `noise_seed` is, with the tag word 0x6175676D
+    ("augm"): cloud 0 = the source cloud's rows, 1 = the target cloud's rows (`postprocess.augment_cloud`'s seed), 2 = the pose
+    stream (`stream.augment_poses`).  Shard-invariant: it depends on the run's seed and the two indices only."""
+    if cloud not in (0, 1, 2):
+        raise ValueError("cloud is 0 (src), 1 (tgt) or 2 (the pose stream)")
+    words = [int(base_seed) & 0xFFFFFFFFFFFFFFFF, int(scene_index), 0x6175676D]
+    if cloud:
+        words.append(int(cloud))
+    return int(np.random.SeedSequence(words).generate_state(1, np.uint64)[0])
