@@ -40,6 +40,10 @@ def main():
     p.add_argument("--image_size", default=256, type=int)
     p.add_argument("--timesteps", default=1000, type=int)
     p.add_argument("--sampling_timesteps", default=250, type=int)
+    p.add_argument("--objective", default="pred_x0", choices=["pred_x0", "pred_noise", "pred_v"],
+                   help="what the checkpoint's network predicts (the reference Trainer's default is pred_noise)")
+    p.add_argument("--beta_schedule", default="sigmoid", choices=["sigmoid", "cosine", "linear"],
+                   help="noise schedule the checkpoint was trained with (the reference Trainer's default is cosine)")
     p.add_argument("--batch_size", default=4, type=int)
     p.add_argument("--dim", default=64, type=int)
     p.add_argument("--dtype", default="fp32", choices=["fp32", "f16x3", "bf16", "mxfp8"],
@@ -92,8 +96,8 @@ def main():
     model = Unet(dim=args.dim, param_cond_dim=4, dim_mults=(1, 2, 4, 8), channels=1, dtype=args.dtype)
     depth_correction = MaskUnet(dim=args.dim, dim_mults=(1, 2, 4, 8), dtype=args.dtype)
     diffusion = GaussianDiffusion(model, image_size=args.image_size, timesteps=args.timesteps,
-                                  sampling_timesteps=args.sampling_timesteps, loss_type="l1", objective="pred_x0",
-                                  beta_schedule="sigmoid", ddim_sampling_eta=1.0, is_ddnm_sampling=True)
+                                  sampling_timesteps=args.sampling_timesteps, loss_type="l1", objective=args.objective,
+                                  beta_schedule=args.beta_schedule, ddim_sampling_eta=1.0, is_ddnm_sampling=True)
     generator = Generator(diffusion, args.data_root, batch_size=args.batch_size,
                           results_folder="./successive_ddnm_diffusion_results",
                           samples_folder="./{}/data".format(args.dataset_name), synthetic_seed=args.synthetic,
@@ -117,8 +121,8 @@ def main():
         m2 = MaskUnet(dim=args.dim, dim_mults=(1, 2, 4, 8), dtype=args.dtype)
         load_weights(u2, m2)
         lanes.append((GaussianDiffusion(u2, image_size=args.image_size, timesteps=args.timesteps,
-                                        sampling_timesteps=args.sampling_timesteps, loss_type="l1", objective="pred_x0",
-                                        beta_schedule="sigmoid", ddim_sampling_eta=1.0, is_ddnm_sampling=True), m2))
+                                        sampling_timesteps=args.sampling_timesteps, loss_type="l1", objective=args.objective,
+                                        beta_schedule=args.beta_schedule, ddim_sampling_eta=1.0, is_ddnm_sampling=True), m2))
     if args.noise_seed is None:
         # ONE seed for the whole job: rank 0 draws it (secrets.randbits) and publishes it to every rank through a c10d store on
         # MASTER_ADDR:MASTER_PORT (sharding.job_seed), so a multi-rank run is reproducible from the one logged value (--noise_seed /

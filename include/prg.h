@@ -489,7 +489,17 @@ typedef struct prg_sampler prg_sampler;
  * Ancestral step t: c_x0 = posterior_mean_coef1[t], c_x = coef2[t], c_eps = 0, sigma = exp(0.5 logvar[t])
  * (0 at t = 0).  DDIM pair (t, t'): c_x0 = sqrt(ac[t']), c_x = 0, c_eps = c, sigma = sigma; last pair:
  * c_x0 = 1, everything else 0.  The host (pointreggpt_amd.diffusion) fills this table from the float64
- * schedule exactly as the reference computes it.                                                            */
+ * schedule exactly as the reference computes it.
+ *
+ * The above is objective 0 (pred_x0: u IS x0).  With prg_sampler_set_objective below (1 = pred_noise, 2 = pred_v) and the
+ * (p[k], q[k]) pair of transition k, only the first line changes:
+ *     x0r = objective ? p[k] * x - q[k] * u : u          two float32 products, each rounded, then one subtraction
+ *                                                        (sd:1153-1156 / sd:1169-1171)
+ *     x0p = (clip_pred & 1) ? clamp(x0r,-1,1) : x0r
+ *     eps = objective == 1 ? u : (sqrt_recip * x - x0p) / sqrt_recipm1      pred_noise: the network output itself, NEVER
+ *                                                        re-derived after the clamp or the replacement (sd:1195, 1372)
+ *     refine row: x' = known ? clamp(x0r,-1,1) : x
+ * The replacement, the second clamp, the update and the keep table are as above.                             */
 typedef struct prg_step {
   int32_t t;            /* timestep fed to the U-Net */
   int32_t clip_pred;    /* bit 0: clamp the network output before deriving eps (DDIM rows = 1);
@@ -536,6 +546,15 @@ int prg_sampler_set_keep(prg_sampler* h, const float* keep_p, int n);
  * slabs may hold anything); prg_sampler_run fails with PRG_E_INVALID if a drawing transition would read past `slabs`.          */
 int prg_sampler_set_keep_draws(prg_sampler* h, const float* u, int64_t slabs);
 
+/* What the network predicts (GaussianDiffusion's `objective`, sd:1194-1208); semantics at prg_step above.
+ * objective: 0 = pred_x0 (default; p, q ignored, may be NULL: clears the table), 1 = pred_noise, 2 = pred_v.
+ * p, q: HOST arrays of n floats, one pair per transition of the handle (n must equal its n_steps).  The handle owns
+ * the device copies.  pred_noise: (sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t]); pred_v:
+ * (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]).  Independent of the keep table.  May be called between two runs
+ * of one handle: the next run uploads the new table and, where the objective itself changed, captures its graph again.
+ * Wrong n, an unknown objective or a NULL table with objective != 0 fail with PRG_E_INVALID and leave the handle as it was. */
+int prg_sampler_set_objective(prg_sampler* h, int objective, const float* p, const float* q, int n);
+
 /* Kernel unit-test / bandwidth hook (round 6): the transition update above ALONE (sampler_step_kernel: what p_sample / ddim_sample
  * do after model_predictions, sd:1257-1281 / sd:1369-1373) on caller tensors, `reps` launches back to back on `stream`:
  * x (B,HW) DEVICE, updated in place by every launch; u (B,HW) DEVICE = the network output; img_cond (B,2,HW) DEVICE or NULL;
@@ -547,6 +566,11 @@ int prg_debug_sampler_step(float* x, const float* u, const float* img_cond, cons
  * (reps, B, HW) stored uniforms, launch i reads slab i, or NULL: launch i takes Philox keep draw i + 1 of seeds[b].           */
 int prg_debug_sampler_step_keep(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step,
                                 float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream);
+/* The same with an objective on every launch (prg_sampler_set_objective): the pair (p, q) for every launch, ignored with
+ * objective 0, which is prg_debug_sampler_step_keep.                                                                          */
+int prg_debug_sampler_step_objective(float* x, const float* u, const float* img_cond, const uint64_t* seeds,
+                                     const prg_step* step, int objective, float p, float q, float keep_p,
+                                     const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream);
 
 /* Wall-clock free timing hook for bench.py: average duration in milliseconds of the dominant kernel class
  * (implicit-GEMM convolution launches) measured with HIP events on the run's own stream during the last

@@ -62,6 +62,13 @@ int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, con
 int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* param_cond, const float* img_cond,
                              const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
                              const float* keep_u, int64_t keep_slabs, float* out, int B, int S);
+/* The same with the objective of prg_sampler_set_objective (prg.h): objective 0 = pred_x0 (p, q ignored, may be NULL), 1 =
+ * pred_noise, 2 = pred_v; p, q (n_steps) the per-transition pairs.  The two entries above are this one with objective 0.
+ * sd:1153-1171, 1194-1208.                                                                                                */
+int prg_cpu_sampler_run_objective(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* param_cond,
+                                  const float* img_cond, const float* noise, int64_t noise_slabs, const uint64_t* seeds,
+                                  const float* keep_p, const float* keep_u, int64_t keep_slabs, int objective, const float* p,
+                                  const float* q, float* out, int B, int S);
 
 /* ---- conv3x3_c64_kernel's step schedule (pointreggpt_amd/csrc/c64_schedule.h, shared with the kernel) as event rows ----
  * One role's instruction stream in program order: role 0 = producer waves, 1 = consumer waves; depth = halo register sets (2 or

@@ -101,7 +101,10 @@ PROTOTYPES = {
     "prg_sampler_get_profile_step": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(_L)]),
     "prg_debug_sampler_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
     "prg_debug_sampler_step_keep": (C.c_int, [_P, _P, _P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
+    "prg_debug_sampler_step_objective": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _F, _F, _F, _P, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_float), _P]),
     "prg_sampler_set_keep": (C.c_int, [_P, _P, _I]),
+    "prg_sampler_set_objective": (C.c_int, [_P, _I, _P, _P, _I]),
     "prg_sampler_set_keep_draws": (C.c_int, [_P, _P, _L]),
     "prg_sampler_get_profile_shapes": (C.c_int, [_P, _P, _I, C.POINTER(C.c_int32)]),
     "prg_host_crop_aabb": (C.c_int, [_P, _L, _P, _P, _P, C.POINTER(_L)]),

@@ -44,6 +44,7 @@ PROTOTYPES = {
     "prg_cpu_maskunet_forward": (C.c_int, [_P, _P, _P, _I, _I]),
     "prg_cpu_sampler_run": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _I, _I]),
     "prg_cpu_sampler_run_keep": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _I]),
+    "prg_cpu_sampler_run_objective": (C.c_int, [_P, C.POINTER(_hip.StepC), _I, _P, _P, _P, _L, _P, _P, _P, _L, _I, _P, _P, _P, _I, _I]),
     "prg_cpu_c64_schedule": (C.c_int, [_I, _I, _I, _P, _L, C.POINTER(_L)]),
 }
 
@@ -176,7 +177,8 @@ class MaskUnet(_CpuNet):
 
 class GaussianDiffusion(_diff.GaussianDiffusion):
     """The GPU front-end's schedule / transition table (computed with torch on the host exactly like the reference) driving
-    prg_cpu_sampler_run_keep (the keep table of stochastic DDNM included: never silently ignored here)."""
+    prg_cpu_sampler_run_objective (the keep table of stochastic DDNM and the objective's table included: never silently ignored
+    here).  Same constructor keywords as the GPU front-end: the three objectives, the three schedules."""
 
     def _sampler(self, batch, refine=False, mode="sample"):          # no device handle to keep
         raise _hip.PrgError("the CPU sampler has no persistent handle")
@@ -213,10 +215,13 @@ class GaussianDiffusion(_diff.GaussianDiffusion):
         if noise is None or (keep is not None and ku is None):
             seed_arr = (C.c_uint64 * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in (seeds if seeds is not None else range(B))])
         out = torch.empty((B, 1, S, S), dtype=torch.float32)
-        check(load().prg_cpu_sampler_run_keep(self.model.handle, arr, n, _p(pc), _p(cond), _p(nz), slabs,
-                                              C.cast(seed_arr, C.c_void_p) if seed_arr is not None else None,
-                                              C.cast(keep, C.c_void_p) if keep is not None else None, _p(ku), kslabs,
-                                              _p(out), B, S), "prg_cpu_sampler_run_keep")
+        code, op, oq = self._objective_c(refine)
+        check(load().prg_cpu_sampler_run_objective(self.model.handle, arr, n, _p(pc), _p(cond), _p(nz), slabs,
+                                                   C.cast(seed_arr, C.c_void_p) if seed_arr is not None else None,
+                                                   C.cast(keep, C.c_void_p) if keep is not None else None, _p(ku), kslabs,
+                                                   code, C.cast(op, C.c_void_p) if op is not None else None,
+                                                   C.cast(oq, C.c_void_p) if oq is not None else None,
+                                                   _p(out), B, S), "prg_cpu_sampler_run_objective")
         return out
 
 

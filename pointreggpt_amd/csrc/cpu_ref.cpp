@@ -762,6 +762,16 @@ int prg_cpu_sampler_run(prg_cpu_unet* h, const prg_step* steps, int n_steps, con
 int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* pc, const float* cond,
                              const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
                              const float* keep_u, int64_t keep_slabs, float* out, int B, int S) {
+  return prg_cpu_sampler_run_objective(h, steps, n_steps, pc, cond, noise, noise_slabs, seeds, keep_p, keep_u, keep_slabs, 0, nullptr,
+                                       nullptr, out, B, S);
+}
+
+int prg_cpu_sampler_run_objective(prg_cpu_unet* h, const prg_step* steps, int n_steps, const float* pc, const float* cond,
+                                  const float* noise, int64_t noise_slabs, const uint64_t* seeds, const float* keep_p,
+                                  const float* keep_u, int64_t keep_slabs, int objective, const float* obj_p, const float* obj_q,
+                                  float* out, int B, int S) {
+  CPU_CHECK(objective >= 0 && objective <= 2, "prg_cpu_sampler_run: unknown objective (0 = pred_x0, 1 = pred_noise, 2 = pred_v)");
+  CPU_CHECK(objective == 0 || (obj_p && obj_q), "prg_cpu_sampler_run: pred_noise and pred_v need their p and q tables");
   CPU_CHECK(h && steps && pc && out && n_steps > 0 && B > 0 && S > 0, "prg_cpu_sampler_run: bad arguments");
   CPU_CHECK(noise || seeds, "prg_cpu_sampler_run: need stored noise or per-scene seeds");
   CPU_CHECK((S * S) % 4 == 0, "prg_cpu_sampler_run: H*W must be a multiple of 4");
@@ -812,19 +822,20 @@ int prg_cpu_sampler_run_keep(prg_cpu_unet* h, const prg_step* steps, int n_steps
           const float cd = cond ? cond[(size_t)b * 2 * HW + (size_t)q * 4 + e] : 0.0f;
           const float cm = cond ? cond[(size_t)b * 2 * HW + HW + (size_t)q * 4 + e] : -1.0f;
           // arithmetic of sampler_step_kernel (sampler.hip) = the reference's order (sd:1158-1218, 1250-1280, 1369-1373)
-          const float x0p = (st.clip_pred & 1) ? clamp1(us) : us;
+          const float x0r = objective ? obj_p[k] * xs - obj_q[k] * us : us;   // two rounded products, one subtraction (sd:1153-1171)
+          const float x0p = (st.clip_pred & 1) ? clamp1(x0r) : x0r;
           const bool known = cond && ((cm + 1.0f) * 0.5f > 0.5f);
           const bool kept = !drop || ku[e] > keep_p[k];       // uniform_(0,1) > p in float32 (sd:1214-1216)
           float x0 = (known && kept) ? cd : x0p;
           if (st.clip_pred & 2) x0 = clamp1(x0);
           float v = st.c_x0 * x0;
           if (st.clip_pred & 4) {
-            x[o] = known ? clamp1(us) : xs;
+            x[o] = known ? clamp1(x0r) : xs;
             continue;
           }
           if (st.c_x != 0.0f) v = v + st.c_x * xs;
           if (st.c_eps != 0.0f) {
-            const float eps = (st.sqrt_recip * xs - x0p) / st.sqrt_recipm1;
+            const float eps = objective == 1 ? us : (st.sqrt_recip * xs - x0p) / st.sqrt_recipm1;   // pred_noise: u itself (sd:1195)
             v = v + st.c_eps * eps;
           }
           if (st.sigma != 0.0f) v = v + st.sigma * nz[e];

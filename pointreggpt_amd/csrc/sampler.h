@@ -8,7 +8,9 @@ namespace prg {
 constexpr uint32_t PHILOX_DOMAIN_NORMAL = 0x70726721u;
 constexpr uint32_t PHILOX_DOMAIN_KEEP = 0x6B656570u;
 
-struct SamplerStepArgs {
+// What every instantiation of sampler_step_kernel receives.  The objective-0 instantiations receive this part ALONE: their kernel
+// arguments, and with them their code, are what they were before the objectives existed.
+struct SamplerStepCore {
   float* x;                 // state (B, HW), updated in place
   const float* u;           // U-Net output (B, HW)
   const float* cond;        // (B, 2, HW) in [-1,1] or null
@@ -22,6 +24,13 @@ struct SamplerStepArgs {
                             // iff its uniform > keep_p[k]; < 0 (and null): every known pixel, nothing drawn
   const float* keep_u;      // stored uniforms (n_steps, B, HW), slab k feeds transition k, or null -> Philox (DOMAIN_KEEP)
   int B, HW, n_steps;
+};
+
+// The launch arguments: the core and what the network's output means.
+struct SamplerStepArgs : SamplerStepCore {
+  int objective;            // what u is: 0 = x0 (pred_x0), 1 = the noise (pred_noise), 2 = v (pred_v); prg_sampler_set_objective
+  const float* obj_p;       // device (n_steps,) coefficients of x0r = obj_p[k] * x - obj_q[k] * u; read iff objective != 0
+  const float* obj_q;
 };
 
 int launch_sampler_step(const SamplerStepArgs& a, hipStream_t s);

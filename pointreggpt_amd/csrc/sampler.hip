@@ -5,6 +5,8 @@
 #include "sampler.h"
 #include "philox.h"
 
+#include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace prg {
@@ -38,12 +40,24 @@ __device__ inline float4 philox_keep4(uint64_t key, uint32_t draw, uint32_t quad
 // torch.clamp: NaN stays NaN (fminf / fmaxf would return the bound and hide a non-finite network output as depth 0)
 __device__ inline float clamp1(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }
 
+// x0 before any clamp, from the network output u.  OBJ = 0: u itself; otherwise p * x - q * u with -ffp-contract=off: two rounded
+// products, one subtraction, like torch's three ops (sd:1153-1156, 1169-1171).  (A function named at every use, not a local
+// variable: with OBJ = 0 each use is then the plain us[e] it was, and hipcc emits the instruction stream it emitted before.)
+template <int OBJ>
+__device__ __forceinline__ float x0_raw(float p, float q, float x, float u) {
+  if constexpr (OBJ == 0) return u;
+  else return p * x - q * u;
+}
+
 // One transition on image b.  DROP (stochastic DDNM, sd:1213-1216 / 1223-1225): a known pixel is replaced iff its uniform > keep_p
 // (float32 comparison, like torch's of a float32 tensor with a 0-dim float64 one).  DROP = false is the kernel as it was before the
-// keep mask existed: same instructions, same data.
-template <bool DROP>
-__device__ inline void sampler_step_image(const SamplerStepArgs& a, const prg_step& st, int k, int b, bool last, float keep_p,
-                                          int q0, int q_stride) {
+// keep mask existed: same instructions, same data.  OBJ (prg_sampler_set_objective): what the network predicts.  0 = x0 itself, and
+// again the kernel as it was: obj_p / obj_q are dead there, no table is read and no branch is taken per pixel.  1 (pred_noise,
+// sd:1194-1197) and 2 (pred_v, sd:1204-1208): x0 before the clamp is x0_raw above; with OBJ = 1 the noise estimate is u itself,
+// never re-derived from the clamped x0 (sd:1195).
+template <bool DROP, int OBJ>
+__device__ inline void sampler_step_image(const SamplerStepCore& a, const prg_step& st, int k, int b, bool last, float keep_p,
+                                          float obj_p, float obj_q, int q0, int q_stride) {
   const size_t img = (size_t)b * a.HW;
   for (int q = q0; q * 4 < a.HW; q += q_stride) {
     const size_t o = img + (size_t)q * 4;
@@ -75,21 +89,21 @@ __device__ inline void sampler_step_image(const SamplerStepArgs& a, const prg_st
     float r[4], f[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float x0p = (st.clip_pred & 1) ? clamp1(us[e]) : us[e];
+      const float x0p = (st.clip_pred & 1) ? clamp1(x0_raw<OBJ>(obj_p, obj_q, xs[e], us[e])) : x0_raw<OBJ>(obj_p, obj_q, xs[e], us[e]);
       const bool known = a.cond && ((cms[e] + 1.0f) * 0.5f > 0.5f);  // get_mask_from_img_cond (sd:507-508)
       float x0 = (DROP ? known && kept[e] : known) ? cds[e] : x0p;   // keep_mask & mask_rpj (sd:1216): a dropped pixel stays in-painted
       if (st.clip_pred & 2) x0 = clamp1(x0);   // p_mean_variance clip_denoised (sd:1250); ddim_sample has no such clamp
       float v = st.c_x0 * x0;
       if (st.clip_pred & 4) {
         // refine row (has_refine_step, sd:1307-1314 / 1374-1388): evaluation without the replacement; only the KNOWN
-        // pixels take the clamped network output (posterior mean at t = 0 is exactly x0: coef1 = 1, coef2 = 0)
-        r[e] = known ? clamp1(us[e]) : xs[e];
+        // pixels take the clamped x0 of the network output (posterior mean at t = 0 is exactly x0: coef1 = 1, coef2 = 0)
+        r[e] = known ? clamp1(x0_raw<OBJ>(obj_p, obj_q, xs[e], us[e])) : xs[e];
         f[e] = (r[e] + 1.0f) * 0.5f;
         continue;
       }
       if (st.c_x != 0.0f) v = v + st.c_x * xs[e];
       if (st.c_eps != 0.0f) {
-        const float eps = (st.sqrt_recip * xs[e] - x0p) / st.sqrt_recipm1;
+        const float eps = OBJ == 1 ? us[e] : (st.sqrt_recip * xs[e] - x0p) / st.sqrt_recipm1;
         v = v + st.c_eps * eps;
       }
       if (st.sigma != 0.0f) v = v + st.sigma * nzs[e];
@@ -101,10 +115,15 @@ __device__ inline void sampler_step_image(const SamplerStepArgs& a, const prg_st
   }
 }
 
+// OBJ = 0 takes the core of the arguments alone (sampler.h): same kernel arguments, same instructions as before the objectives existed
+template <int OBJ>
+using StepKernelArgs = std::conditional_t<OBJ == 0, SamplerStepCore, SamplerStepArgs>;
+
 // grid (chunks, B); each thread handles 4 consecutive pixels.  KEEP = false (no keep table: the host chooses it, launch_sampler_step) is
-// the kernel as it was before the keep mask existed; KEEP = true reads the row's threshold.
-template <bool KEEP>
-__global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
+// the kernel as it was before the keep mask existed; KEEP = true reads the row's threshold.  OBJ != 0 reads the row's (p, q) the
+// same way: once per launch, uniform.
+template <bool KEEP, int OBJ>
+__global__ __launch_bounds__(256) void sampler_step_kernel(StepKernelArgs<OBJ> a) {
   const int k = *a.step_idx;
   const prg_step st = a.steps[k];
   const int b = blockIdx.y;
@@ -112,13 +131,15 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(SamplerStepArgs a) {
   // The row decides whether a keep mask is drawn, so the branch is uniform across the launch.  No table, a negative threshold,
   // no condition, or the refine row (which ignores the table): every known pixel is replaced and nothing is drawn.
   const float keep_p = KEEP ? a.keep_p[k] : -1.0f;
+  float obj_p = 0.0f, obj_q = 0.0f;
+  if constexpr (OBJ != 0) { obj_p = a.obj_p[k]; obj_q = a.obj_q[k]; }
   // (the grid-stride bounds are taken here: read in the kernel itself, blockDim folds to the launch bound's uniform group size;
   // read inside a device function it is the generic form, one more dependent load at the head of every launch)
   const int q0 = blockIdx.x * blockDim.x + threadIdx.x, q_stride = gridDim.x * blockDim.x;
   if (KEEP && keep_p >= 0.0f && a.cond && !(st.clip_pred & 4))
-    sampler_step_image<true>(a, st, k, b, last, keep_p, q0, q_stride);
+    sampler_step_image<true, OBJ>(a, st, k, b, last, keep_p, obj_p, obj_q, q0, q_stride);
   else
-    sampler_step_image<false>(a, st, k, b, last, keep_p, q0, q_stride);
+    sampler_step_image<false, OBJ>(a, st, k, b, last, keep_p, obj_p, obj_q, q0, q_stride);
   // Every workgroup read the step counter at its first instruction; the last one to arrive here advances it for the
   // next launch and re-arms the ticket (kernel boundaries order this against the neighbouring launches).
   __syncthreads();
@@ -155,12 +176,22 @@ static inline dim3 step_grid(int HW, int B) {
   return dim3(gx, B, 1);
 }
 
+template <int OBJ>
+static void launch_step_objective(const SamplerStepArgs& a, hipStream_t s) {
+  if (a.keep_p)
+    sampler_step_kernel<true, OBJ><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
+  else
+    sampler_step_kernel<false, OBJ><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
+}
+
 int launch_sampler_step(const SamplerStepArgs& a, hipStream_t s) {
   PRG_CHECK(a.HW % 4 == 0, "sampler: H*W must be a multiple of 4");
-  if (a.keep_p)
-    sampler_step_kernel<true><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
-  else
-    sampler_step_kernel<false><<<step_grid(a.HW, a.B), 256, 0, s>>>(a);
+  PRG_CHECK(a.objective >= 0 && a.objective <= 2, "sampler: unknown objective");
+  PRG_CHECK(a.objective == 0 || (a.obj_p && a.obj_q), "sampler: this objective needs its (p, q) table");
+  // the instantiation is the host's choice: one objective per launch, nothing for the kernel to branch on
+  if (a.objective == 1) launch_step_objective<1>(a, s);
+  else if (a.objective == 2) launch_step_objective<2>(a, s);
+  else launch_step_objective<0>(a, s);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }
@@ -175,23 +206,30 @@ int launch_sampler_init(float* x, const float* noise, const uint64_t* seeds, int
 
 using namespace prg;
 
-// has_keep: the launches also get a table of `reps` + 1 copies of keep_p (and keep_u); without it the table pointer is null
+// has_keep: the launches also get a table of `reps` + 1 copies of keep_p (and keep_u); without it the table pointer is null.
+// objective != 0: and tables of as many copies of (obj_p, obj_q).
 static int debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, bool has_keep,
-                              float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream) {
+                              float keep_p, const float* keep_u, int objective, float obj_p, float obj_q, int B, int HW, int reps,
+                              float* avg_us, void* stream) {
   PRG_CHECK(x && u && seeds && step && B > 0 && HW > 0 && HW % 4 == 0 && reps > 0, "prg_debug_sampler_step: bad argument");
+  PRG_CHECK(objective >= 0 && objective <= 2, "prg_debug_sampler_step: unknown objective");
   hipStream_t s = (hipStream_t)stream;
   // a table of `reps` copies of the transition (+1 row so that no launch is the chain's last), the device step counter and the ticket
   std::vector<prg_step> rows((size_t)reps + 1, *step);
   std::vector<float> keep(has_keep ? rows.size() : 0, keep_p);
+  std::vector<float> obj(objective ? 2 * rows.size() : 0, obj_p);   // [p copies | q copies], behind the keep table
+  std::fill(obj.begin() + obj.size() / 2, obj.end(), obj_q);
   char* scratch = nullptr;
   const size_t tab = sizeof(prg_step) * rows.size();
-  PRG_HIP(hipMalloc(&scratch, tab + 2 * sizeof(int) + sizeof(float) * keep.size()));
+  const size_t obj_off = tab + 2 * sizeof(int) + sizeof(float) * keep.size();
+  PRG_HIP(hipMalloc(&scratch, obj_off + sizeof(float) * obj.size()));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = PRG_OK;
   auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == PRG_OK) { set_error(std::string("prg_debug_sampler_step: ") + hipGetErrorString(e)); rc = PRG_E_HIP; } };
   fail(hipMemcpyAsync(scratch, rows.data(), tab, hipMemcpyHostToDevice, s));
   fail(hipMemsetAsync(scratch + tab, 0, 2 * sizeof(int), s));
   if (has_keep) fail(hipMemcpyAsync(scratch + tab + 2 * sizeof(int), keep.data(), sizeof(float) * keep.size(), hipMemcpyHostToDevice, s));
+  if (objective) fail(hipMemcpyAsync(scratch + obj_off, obj.data(), sizeof(float) * obj.size(), hipMemcpyHostToDevice, s));
   fail(hipEventCreate(&e0));
   fail(hipEventCreate(&e1));
   if (rc == PRG_OK) {
@@ -200,6 +238,11 @@ static int debug_sampler_step(float* x, const float* u, const float* img_cond, c
     a.step_idx = reinterpret_cast<int*>(scratch + tab); a.ticket = a.step_idx + 1; a.seeds = seeds; a.final_out = x;
     a.B = B; a.HW = HW; a.n_steps = reps + 1;
     if (has_keep) { a.keep_p = reinterpret_cast<const float*>(scratch + tab + 2 * sizeof(int)); a.keep_u = keep_u; }
+    if (objective) {
+      a.objective = objective;
+      a.obj_p = reinterpret_cast<const float*>(scratch + obj_off);
+      a.obj_q = a.obj_p + rows.size();
+    }
     fail(hipEventRecord(e0, s));
     for (int i = 0; i < reps && rc == PRG_OK; ++i) rc = launch_sampler_step(a, s);
     fail(hipEventRecord(e1, s));
@@ -216,10 +259,16 @@ static int debug_sampler_step(float* x, const float* u, const float* img_cond, c
 
 extern "C" int prg_debug_sampler_step(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step, int B,
                                       int HW, int reps, float* avg_us, void* stream) {
-  return debug_sampler_step(x, u, img_cond, seeds, step, false, -1.0f, nullptr, B, HW, reps, avg_us, stream);
+  return debug_sampler_step(x, u, img_cond, seeds, step, false, -1.0f, nullptr, 0, 0.0f, 0.0f, B, HW, reps, avg_us, stream);
 }
 
 extern "C" int prg_debug_sampler_step_keep(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step,
                                            float keep_p, const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream) {
-  return debug_sampler_step(x, u, img_cond, seeds, step, true, keep_p, keep_u, B, HW, reps, avg_us, stream);
+  return debug_sampler_step(x, u, img_cond, seeds, step, true, keep_p, keep_u, 0, 0.0f, 0.0f, B, HW, reps, avg_us, stream);
+}
+
+extern "C" int prg_debug_sampler_step_objective(float* x, const float* u, const float* img_cond, const uint64_t* seeds, const prg_step* step,
+                                                int objective, float p, float q, float keep_p, const float* keep_u, int B, int HW,
+                                                int reps, float* avg_us, void* stream) {
+  return debug_sampler_step(x, u, img_cond, seeds, step, true, keep_p, keep_u, objective, p, q, B, HW, reps, avg_us, stream);
 }

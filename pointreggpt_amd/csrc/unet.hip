@@ -707,6 +707,9 @@ struct prg_sampler {
   std::vector<float> keep;         // host copy; empty = no table: the kernel gets a null pointer
   const float* keep_u = nullptr;   // caller's stored keep-mask uniforms (keep_slabs, B, S, S), null = Philox
   int64_t keep_slabs = 0;
+  float* d_obj = nullptr;          // (2, n_steps) the objective's p row and q row: uploaded by every run whose objective != 0
+  std::vector<float> obj;          // host copy [p | q] (prg_sampler_set_objective); empty with objective 0
+  int objective = 0;
   hipStream_t own_stream = nullptr;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -714,6 +717,7 @@ struct prg_sampler {
   const float* g_noise = nullptr;
   const float* g_keep = nullptr;   // d_keep or null
   const float* g_keep_u = nullptr;
+  int g_objective = 0;             // the objective chooses the kernel instantiation the graph holds
   float* g_out = nullptr;
   hipStream_t g_stream = nullptr;
   uint64_t g_arena_gen = 0;        // workspace generation the graph was captured against
@@ -750,6 +754,9 @@ static int sampler_one_step(prg_sampler* h, const float* cond, const float* nois
   a.ticket = h->d_step + 1;
   a.keep_p = h->keep.empty() ? nullptr : h->d_keep;
   a.keep_u = h->keep_u;
+  a.objective = h->objective;
+  a.obj_p = h->objective ? h->d_obj : nullptr;
+  a.obj_q = h->objective ? h->d_obj + h->n_steps : nullptr;
   ProfileSink& p = h->prof;
   if (!p.on) return launch_sampler_step(a, s);   // its last workgroup advances the step counter
   if ((rc = p.step_ev.start(s))) return rc;
@@ -901,6 +908,7 @@ int prg_sampler_create(prg_unet* unet, const prg_step* steps, int n_steps, int B
   h->d_step = h->own.alloc<int>(2, nomem);
   h->d_seeds = h->own.alloc<uint64_t>((size_t)B, nomem);
   h->d_keep = h->own.alloc<float>((size_t)n_steps, nomem);
+  h->d_obj = h->own.alloc<float>(2 * (size_t)n_steps, nomem);
   if (h->own.rc) return h->own.rc;
   PRG_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamDefault));
   // time half of the conditioning for every transition: Tpart[k] = W_t . SiLU(time_mlp(t_k)) + bias
@@ -949,6 +957,20 @@ int prg_sampler_set_keep(prg_sampler* h, const float* keep_p, int n) {
   if (!keep_p) { h->keep.clear(); return PRG_OK; }
   PRG_CHECK(n == h->n_steps, "prg_sampler_set_keep: the table needs one threshold per transition");
   h->keep.assign(keep_p, keep_p + n);   // reaches d_keep on the stream of the next run, behind whatever still reads the old table
+  return PRG_OK;
+}
+
+int prg_sampler_set_objective(prg_sampler* h, int objective, const float* p, const float* q, int n) {
+  PRG_CHECK(h, "prg_sampler_set_objective: null handle");
+  PRG_CHECK(objective >= 0 && objective <= 2, "prg_sampler_set_objective: unknown objective (0 = pred_x0, 1 = pred_noise, 2 = pred_v)");
+  if (objective == 0) { h->objective = 0; h->obj.clear(); return PRG_OK; }
+  PRG_CHECK(p && q, "prg_sampler_set_objective: pred_noise and pred_v need their p and q tables");
+  PRG_CHECK(n == h->n_steps, "prg_sampler_set_objective: the table needs one (p, q) pair per transition");
+  // like the keep table: reaches d_obj on the stream of the next run, behind whatever still reads the old one.  A captured graph
+  // holds the instantiation of the objective it was captured with: prg_sampler_run captures again when the objective differs.
+  h->obj.assign(p, p + n);
+  h->obj.insert(h->obj.end(), q, q + n);
+  h->objective = objective;
   return PRG_OK;
 }
 
@@ -1030,6 +1052,7 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
   if (seeds) PRG_HIP(hipMemcpyAsync(h->d_seeds, seeds, sizeof(uint64_t) * B, hipMemcpyHostToDevice, s));
   PRG_HIP(hipMemsetAsync(h->d_step, 0, 2 * sizeof(int), s));   // [step counter, arrival ticket]
   if (!h->keep.empty()) PRG_HIP(hipMemcpyAsync(h->d_keep, h->keep.data(), sizeof(float) * h->n_steps, hipMemcpyHostToDevice, s));
+  if (h->objective) PRG_HIP(hipMemcpyAsync(h->d_obj, h->obj.data(), sizeof(float) * 2 * h->n_steps, hipMemcpyHostToDevice, s));
   // camera half of the conditioning: Ppart[b] = W_p . SiLU(param_mlp(K_b))
   {
     float* h2 = h->d_scratch;
@@ -1062,7 +1085,8 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
   if (h->use_graph && !profiling && !u->taps_on) {
     const float* keep_p = h->keep.empty() ? nullptr : h->d_keep;
     const bool stale = !h->exec || h->g_cond != img_cond || h->g_noise != noise || h->g_out != out || h->g_stream != s ||
-                       h->g_arena_gen != u->arena_gen || h->g_keep != keep_p || h->g_keep_u != h->keep_u;
+                       h->g_arena_gen != u->arena_gen || h->g_keep != keep_p || h->g_keep_u != h->keep_u ||
+                       h->g_objective != h->objective;
     if (stale) {
       sampler_free(h);
       PRG_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1074,7 +1098,7 @@ int prg_sampler_run(prg_sampler* h, const float* param_cond, const float* img_co
       h->graph = g;
       PRG_HIP(hipGraphInstantiate(&h->exec, h->graph, nullptr, nullptr, 0));
       h->g_cond = img_cond; h->g_noise = noise; h->g_out = out; h->g_stream = s; h->g_arena_gen = u->arena_gen;
-      h->g_keep = keep_p; h->g_keep_u = h->keep_u;
+      h->g_keep = keep_p; h->g_keep_u = h->keep_u; h->g_objective = h->objective;
     }
     for (int k = 0; k < h->n_steps; ++k) PRG_HIP(hipGraphLaunch(h->exec, s));
   } else {

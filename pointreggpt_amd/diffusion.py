@@ -8,6 +8,7 @@ sd = /root/reference/denoising_diffusion_pytorch/successive_ddnm_diffusion.py
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -27,9 +28,34 @@ def sigmoid_beta_schedule(timesteps: int, start=-3, end=3, tau=1) -> torch.Tenso
     return torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999)
 
 
-def make_schedule(timesteps: int) -> Dict[str, torch.Tensor]:
-    """The float32 buffers GaussianDiffusion registers (sd:1056-1134), from the float64 betas."""
-    betas = sigmoid_beta_schedule(timesteps)
+def linear_beta_schedule(timesteps: int) -> torch.Tensor:
+    """Linear betas scaled by 1000 / timesteps, float64, NOT clipped (sd:976-980): below 21 timesteps the last one exceeds 1."""
+    scale = 1000 / timesteps
+    return torch.linspace(scale * 0.0001, scale * 0.02, timesteps, dtype=torch.float64)
+
+
+def cosine_beta_schedule(timesteps: int, s=0.008) -> torch.Tensor:
+    """Cosine alpha-bar schedule, float64, betas clipped to [0, 0.999] (sd:983-994)."""
+    x = torch.linspace(0, timesteps, timesteps + 1, dtype=torch.float64)
+    ac = torch.cos(((x / timesteps) + s) / (1 + s) * math.pi * 0.5) ** 2
+    ac = ac / ac[0]
+    return torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999)
+
+
+BETA_SCHEDULES = {"linear": linear_beta_schedule, "cosine": cosine_beta_schedule, "sigmoid": sigmoid_beta_schedule}
+OBJECTIVES = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}     # the codes of prg_sampler_set_objective (include/prg.h)
+
+
+def make_schedule(timesteps: int, beta_schedule: str = "sigmoid") -> Dict[str, torch.Tensor]:
+    """The float32 buffers GaussianDiffusion registers (sd:1056-1134), from the float64 betas of the named schedule.
+    A beta >= 1 (the linear schedule below 21 timesteps) makes alphas_cumprod <= 0 and every chain NaN: the reference samples
+    on in silence, this raises."""
+    if beta_schedule not in BETA_SCHEDULES:
+        raise ValueError(f"unknown beta schedule {beta_schedule}")
+    betas = BETA_SCHEDULES[beta_schedule](timesteps)
+    if bool((betas >= 1).any()):
+        raise ValueError(f"beta_schedule='{beta_schedule}' with timesteps={timesteps} has a beta >= 1 "
+                         f"(max {float(betas.max()):.4g}): the chain would be NaN; the linear schedule needs timesteps >= 21")
     alphas = 1.0 - betas
     ac = torch.cumprod(alphas, dim=0)
     ac_prev = torch.nn.functional.pad(ac[:-1], (1, 0), value=1.0)
@@ -59,14 +85,27 @@ class _ProfileShape(C.Structure):     # include/prg.h: prg_profile_shape
                 ("mx", C.c_int32), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("flops_executed", C.c_double)]
 
 class GaussianDiffusion:
-    """Sampling half of the reference class: same constructor keywords, ``sample(param_cond=, img_cond=)``."""
+    """Sampling half of the reference class: same constructor keywords, ``sample(param_cond=, img_cond=)``.
+
+    ``objective`` and ``beta_schedule``: left out, they are the generator's ``pred_x0`` / ``sigmoid`` (generate_dataset.py:34-44).
+    Any other configuration names BOTH.  The reference class defaults to ``pred_noise`` / ``cosine``, so a call that names one
+    of them and leaves the other to a default means one model there and another here (``objective='pred_noise'`` alone: cosine
+    in the reference, sigmoid here); it is refused with ``ValueError`` instead of sampling from the wrong schedule in silence."""
 
     def __init__(self, model: Unet, *, image_size, timesteps=1000, sampling_timesteps=None, loss_type="l1",
-                 objective="pred_x0", beta_schedule="sigmoid", ddim_sampling_eta=1.0, is_ddnm_sampling=True,
+                 objective=None, beta_schedule=None, ddim_sampling_eta=1.0, is_ddnm_sampling=True,
                  ddnm_sampling_dropout=0.0, ddnm_dropout_schedule="none"):
-        if objective != "pred_x0" or beta_schedule != "sigmoid":
-            raise ValueError("this path implements the generator's configuration: objective='pred_x0', "
-                             "beta_schedule='sigmoid' (generate_dataset.py:34-44)")
+        given = (objective is not None, beta_schedule is not None)
+        objective = "pred_x0" if objective is None else objective
+        beta_schedule = "sigmoid" if beta_schedule is None else beta_schedule
+        if given != (True, True) and (objective, beta_schedule) != ("pred_x0", "sigmoid"):
+            raise ValueError(f"objective='{objective}', beta_schedule='{beta_schedule}': a configuration other than the generator's "
+                             "pred_x0 / sigmoid names both keywords (the reference class's defaults are pred_noise / cosine, "
+                             "not this project's: the one left out would not mean what it means there)")
+        if objective not in OBJECTIVES:
+            raise ValueError(f"unknown objective {objective}: one of {', '.join(OBJECTIVES)}")
+        if beta_schedule not in BETA_SCHEDULES:
+            raise ValueError(f"unknown beta schedule {beta_schedule}: one of {', '.join(BETA_SCHEDULES)}")
         if not 0.0 <= float(ddnm_sampling_dropout) <= 1.0:
             raise ValueError(f"ddnm_sampling_dropout must lie in [0, 1], got {ddnm_sampling_dropout}")
         if ddnm_dropout_schedule not in ("none", "linear"):
@@ -79,8 +118,13 @@ class GaussianDiffusion:
         assert self.sampling_timesteps <= self.num_timesteps
         self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
         self.ddim_sampling_eta = float(ddim_sampling_eta)
-        for k, v in make_schedule(self.num_timesteps).items():
+        self.beta_schedule = beta_schedule
+        for k, v in make_schedule(self.num_timesteps, beta_schedule).items():
             setattr(self, k, v)
+        # the refine row of the ancestral sampler is p_sample(t = 0) whose posterior mean the kernel takes to be x0 itself
+        # (sd:1173-1176, 1307-1314): true of the schedule built here, not assumed of every schedule
+        assert float(self.posterior_mean_coef1[0]) == 1.0 and float(self.posterior_mean_coef2[0]) == 0.0, \
+            f"beta_schedule='{beta_schedule}', timesteps={timesteps}: posterior_mean_coef1[0], coef2[0] are not 1, 0 in float32"
         # stochastic DDNM (sd:1075-1094): per-timestep probability of NOT replacing a known pixel, float64 like the reference's
         self.ddnm_sampling_dropout = float(ddnm_sampling_dropout)
         self.ddnm_dropout_schedule = ddnm_dropout_schedule
@@ -132,6 +176,25 @@ class GaussianDiffusion:
                                 r["sqrt_recipm1"])
         return arr, len(rows)
 
+    def objective_table(self, refine: bool = False):
+        """One (p, q) pair per row of ``_steps_c(refine)`` (prg_sampler_set_objective, include/prg.h): the row's x0 before the
+        clamp is ``p * x - q * u``.  ``pred_noise``: (sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t]) (sd:1153-1156);
+        ``pred_v``: (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) (sd:1169-1171); ``pred_x0``: None, u is x0."""
+        if self.objective == "pred_x0":
+            return None
+        p, q = ((self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod) if self.objective == "pred_noise" else
+                (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod))
+        ts = [r["t"] for r in self.step_table()] + ([0] if refine else [])
+        return [(float(p[t]), float(q[t])) for t in ts]
+
+    def _objective_c(self, refine: bool = False):
+        """(code, p, q) for the C entries; the arrays are None for pred_x0."""
+        tab = self.objective_table(refine)
+        if tab is None:
+            return 0, None, None
+        return (OBJECTIVES[self.objective], (C.c_float * len(tab))(*[p for p, _q in tab]),
+                (C.c_float * len(tab))(*[q for _p, q in tab]))
+
     def keep_table(self, mode: str = "sample", refine: bool = False) -> List[float]:
         """One keep threshold per row of ``_steps_c(refine)`` for a run WITH a condition (prg_sampler_set_keep, include/prg.h):
         >= 0: the row draws a uniform per pixel and replaces a known pixel iff ``u > threshold`` in float32; -1: it replaces
@@ -176,6 +239,9 @@ class GaussianDiffusion:
             keep = self._keep_c(mode, refine)
             if keep is not None:
                 _lib.check(lib.prg_sampler_set_keep(h, keep, n), "prg_sampler_set_keep")
+            code, op, oq = self._objective_c(refine)
+            if code:                    # independent of the keep table; pred_x0 sets nothing: the handle's default
+                _lib.check(lib.prg_sampler_set_objective(h, code, op, oq, n), "prg_sampler_set_objective")
             self._samplers[key] = (h, keep is not None)
         return self._samplers[key][0]
 

@@ -728,6 +728,109 @@ def g23_ddnm_dropout():
     save("G23_ddnm_dropout", **out)
 
 
+G24_OBJECTIVES = ("pred_x0", "pred_noise", "pred_v")
+G24_SCHEDULES = ("sigmoid", "cosine", "linear")
+G24_BUFFERS = ("betas", "alphas_cumprod", "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1",
+               "posterior_mean_coef2", "posterior_log_variance_clipped")
+# the pairs that get all four chains (ancestral / ddim5, each with and without the refine step); the other five new pairs get one
+G24_FULL = (("pred_noise", "cosine"), ("pred_v", "linear"), ("pred_x0", "cosine"))
+G24_ONE = {("pred_noise", "linear"): ("ddim5", False), ("pred_noise", "sigmoid"): ("anc", True), ("pred_v", "cosine"): ("ddim5", True),
+           ("pred_v", "sigmoid"): ("anc", False), ("pred_x0", "linear"): ("anc", False)}
+G24_SEED = 2400
+
+
+def g24_anc_T(schedule):
+    """Timesteps of the short ancestral chain: below 21 the linear schedule's last beta exceeds 1 and the reference samples NaN."""
+    return 40 if schedule == "linear" else 8
+
+
+def g24_objectives():
+    """pred_noise / pred_v and the linear / cosine schedules (sd:976-994, 1153-1171, 1194-1208) on the G9_G10 network, pc and
+    cond.  Per schedule the reference's float64 betas / alphas_cumprod (its schedule function's output and the cumprod its
+    constructor takes of it; the class itself keeps float32 copies, which are compared) and the float32 buffers the transition
+    table is made of, at T = 1000 and at the short chain's T; per chain the output
+    computed with 8 threads and with 1 thread; the normals per sampler (`anc_normals`: 40 slabs, the T = 8 chains drew the first
+    8; `ddim5_normals`); one pred_noise chain with ddnm_sampling_dropout = 0.3 and its uniforms; the DDIM rows of this host
+    (G0_host_tables' layout) per chain that needs them.  Every output has at least 60 % of its pixels strictly inside (0,1) and
+    moves by at most FP32_TOL / 4 = 2.5e-5 between 8 threads and 1."""
+    from pointreggpt_amd.diffusion import GaussianDiffusion
+
+    class _Net:
+        channels = out_dim = 1
+        random_or_learned_sinusoidal_cond = False
+
+    S, B, dim = 32, 2, 16
+    m = ref_unet(dim, 9)
+    pc = torch.tensor([[37.87, 38.02, 16.25, 16.0], [36.5, 36.7, 16.25, 16.0]])
+    cond = mixed_cond(B, S, 9)
+    out = {"pc": pc, "cond": cond, "p": np.float64(0.3)}
+
+    def ref(objective, schedule, T, steps=None, dropout=0.0):
+        return sd.GaussianDiffusion(m, image_size=S, timesteps=T, sampling_timesteps=steps, loss_type="l1", objective=objective,
+                                    beta_schedule=schedule, ddim_sampling_eta=1.0, is_ddnm_sampling=True,
+                                    ddnm_sampling_dropout=dropout, ddnm_dropout_schedule="none")
+
+    # ---- schedule arrays: they do not depend on the objective (asserted), so one set per (schedule, T) ----
+    fn = {"sigmoid": sd.sigmoid_beta_schedule, "cosine": sd.cosine_beta_schedule, "linear": sd.linear_beta_schedule}
+    for schedule in G24_SCHEDULES:
+        for T in (1000, g24_anc_T(schedule)):
+            betas64 = fn[schedule](T)
+            ds = [ref(o, schedule, T) for o in G24_OBJECTIVES]
+            assert betas64.dtype == torch.float64 and torch.equal(betas64.to(torch.float32), ds[0].betas)
+            for name in G24_BUFFERS:
+                assert all(torch.equal(getattr(d, name), getattr(ds[0], name)) for d in ds)
+                if name not in ("betas", "alphas_cumprod"):
+                    assert getattr(ds[0], name).dtype == torch.float32
+                    out[f"{schedule}_T{T}_{name}"] = getattr(ds[0], name)
+            # the class keeps float32 copies only; the float64 arrays are the schedule function's and their cumprod (sd:1048-1050)
+            out[f"{schedule}_T{T}_betas"] = betas64
+            out[f"{schedule}_T{T}_alphas_cumprod"] = torch.cumprod(1.0 - betas64, dim=0)
+            assert torch.equal(out[f"{schedule}_T{T}_alphas_cumprod"].to(torch.float32), ds[0].alphas_cumprod)
+
+    # ---- chains ----
+    chains = []     # (name, objective, schedule, sampler, refine, dropout)
+    for o, s_ in G24_FULL:
+        chains += [(f"{o}_{s_}_{smp}{'_refine' if r else ''}", o, s_, smp, r, 0.0) for smp in ("anc", "ddim5") for r in (False, True)]
+    chains += [(f"{o}_{s_}_{smp}{'_refine' if r else ''}", o, s_, smp, r, 0.0) for (o, s_), (smp, r) in G24_ONE.items()]
+    chains.append(("pred_noise_cosine_anc_dropout", "pred_noise", "cosine", "anc", False, 0.3))
+    shared = {}
+    for i, (name, o, s_, smp, refine, dropout) in enumerate(chains):
+        T, steps = (g24_anc_T(s_), None) if smp == "anc" else (1000, 5)
+        d = ref(o, s_, T, steps, dropout)
+        res = {}
+        for threads in (8, 1):
+            torch.set_num_threads(threads)
+            res[threads] = recorded_draws(lambda: d.sample(param_cond=pc, img_cond=cond, disable_tqdm=True, has_refine_step=refine),
+                                          d, G24_SEED + 1 + i, G24_SEED if smp == "anc" else G24_SEED + 50)
+        torch.set_num_threads(8)
+        (img, nz, un, kp), (img1, nz1, un1, kp1) = res[8], res[1]
+        assert torch.equal(nz, nz1) and torch.equal(un.nan_to_num(7.0), un1.nan_to_num(7.0)) and np.array_equal(kp, kp1)
+        inside = min(float(((x > 0) & (x < 1)).float().mean()) for x in (img, img1))
+        spread = float((img - img1).abs().max())
+        print(f"  {name}: T = {T}, {inside:.2f} of the output inside (0,1), |8 threads - 1 thread|max = {spread:.2e}")
+        assert torch.isfinite(img).all() and inside >= 0.6, "choose another seed: the chain's output is mostly clamped"
+        assert spread <= 2.5e-5, "choose another seed: the chain amplifies the summation order beyond FP32_TOL / 4"
+        assert len(kp) == (T if steps is None else steps) + int(refine) and bool((kp >= 0).any()) == (dropout > 0)
+        key = smp + "_normals"
+        if key in shared:                       # one stream per sampler: a shorter chain drew a prefix of a longer one's
+            n = min(len(nz), len(shared[key]))
+            assert torch.equal(shared[key][:n], nz[:n])
+        if key not in shared or len(nz) > len(shared[key]):
+            shared[key] = nz
+        out[name + "_out"], out[name + "_out_1thread"] = img, img1
+        if dropout > 0:
+            out[name + "_uniforms"], out[name + "_keep_p"] = un, kp
+        if steps is not None and f"{s_}_ddim5_rows" not in out:
+            rows = GaussianDiffusion(_Net(), image_size=S, timesteps=T, sampling_timesteps=steps, objective=o,
+                                     beta_schedule=s_).step_table()
+            out[f"{s_}_ddim5_rows"] = np.array([[r["c_x0"], r["c_x"], r["c_eps"], r["sigma"], r["sqrt_recip"], r["sqrt_recipm1"]]
+                                               for r in rows], dtype=np.float32)
+            out[f"{s_}_ddim5_t"] = np.array([r["t"] for r in rows], dtype=np.int32)
+    out["chains"] = np.array([c[0] for c in chains])
+    out.update(shared)
+    save("G24_objectives", **out)
+
+
 def spec_fixture():
     import json
     spec = {"unet64": [[k, list(v.shape)] for k, v in sd.Unet(dim=64, param_cond_dim=4).state_dict().items()],
@@ -746,7 +849,7 @@ if __name__ == "__main__":
             ("g12", g12_end_to_end), ("g12b", g12b_envelope), ("g13", g13_unet_128), ("g14", g14_chain_128),
             ("g15", g15_maskunet_128), ("g16", g16_unet_256), ("g17", g17_ddim_cond_gt1), ("g18", g18_refine_and_tester), ("g19", g19_chain1000_64),
             ("g20", g20_ddim250_128), ("g21", g21_ddim250_256), ("g21b", g21b_ddim250_256), ("g22", g22_chain1000_128), ("g23", g23_ddnm_dropout),
-            ("spec", spec_fixture)]
+            ("g24", g24_objectives), ("spec", spec_fixture)]
     for name, fn in jobs:
         if not only or name in only:
             fn()
