@@ -472,6 +472,63 @@ typedef struct prg_conv_fused {
 } prg_conv_fused;
 int prg_debug_conv_fused(prg_conv_fused* args, void* stream);
 
+/* Kernel unit-test hooks: the GroupNorm passes and the conditioning kernels of blocks.hip, each alone through the launch function
+ * the forward pass calls.  Every tensor is float32 DEVICE (int64 / int32 where said) and is copied or converted into buffers the
+ * hook owns; the few HOST arguments are named.  Bad arguments fail with PRG_E_INVALID before any device call.  All synchronise.
+ *
+ * prg_debug_gn_stats: launch_gn_stats<T> on x (B, C, HW), converted to T = float (PRG_F32) or bf16 (PRG_BF16) in NHWC.  slabs:
+ * room for (B, 1024, groups, 2) floats; the first B * nsplit * groups * 2 receive the raw slabs [B][nsplit][groups][2].  *nsplit
+ * (HOST) the slab count the launcher chose.  C / vec (vec = 4 / 8) a power of two <= 256, groups <= 64 divides C.              */
+int prg_debug_gn_stats(const float* x, float* slabs, int* nsplit, int B, int C, int HW, int groups, int dtype, void* stream);
+/* prg_debug_gn_coeff: launch_gn_coeff on the caller's slabs (B, nsplit, groups, 2), gamma, beta (C).  ss_a (ss_a_floats floats, or
+ * NULL) is read at b * ss_a_stride + *row * row_stride (+ C for the shift), ss_b (ss_b_floats floats, or NULL, only with ss_a) at
+ * b * ss_b_stride; row (HOST int, or NULL) is uploaded to a device int.  A, Bc (B, C).  C <= 1024, groups <= 64, nsplit <= 1024. */
+int prg_debug_gn_coeff(const float* slabs, int nsplit, const float* gamma, const float* beta, const float* ss_a, int64_t ss_a_stride,
+                       int64_t ss_a_floats, const float* ss_b, int64_t ss_b_stride, int64_t ss_b_floats, const int* row,
+                       int64_t row_stride, float* A, float* Bc, int B, int HW, int C, int groups, void* stream);
+/* prg_debug_gn_fold (bf16): the consumers of the fixed-point accumulators acc (B, groups, 2) int64 (sum * 2^24, sum of squares * 2^20).
+ *   P, Q directly: entries NULL; p, q (C), or (B, C) with pq_per_image 1.
+ *   P, Q from launch_cond_fold: entries (HOST, n_entries rows of four int64: ss_off, C, gamma offset, beta offset into flat), flat
+ *   (flat_floats), the conditioning rows ss_a / ss_b / row as in prg_debug_gn_coeff (each row ss_total floats wide), pq
+ *   (B, ss_total) in and out with pq_stride = ss_total.  The launch is also handed an accumulator array of zero_words + 64 int64
+ *   words of the hook's, every byte 0x5a, to clear zero_words of; zero_out (zero_words + 64 int64) receives that array.  P, Q of
+ *   the output are those of entry use_entry, whose C is `C`.
+ *   output PRG_GF_NONE (cond_fold alone), PRG_GF_TABLES: coef_a, coef_b (B, C) from launch_gn_coeff_acc, PRG_GF_APPLY: out (B, C, HW)
+ *   = launch_affine_silu_fold over x (B, C, HW) and an optional residual, converted to bf16; in_place 1: x's bf16 buffer is also
+ *   the output buffer.  C a multiple of 8 and <= 1024 for PRG_GF_APPLY.                                                           */
+enum { PRG_GF_NONE = 0, PRG_GF_TABLES = 1, PRG_GF_APPLY = 2 };
+typedef struct prg_gn_fold {
+  const int64_t* acc;
+  const float* p;
+  const float* q;
+  const int64_t* entries;
+  const float* flat;
+  const float* ss_a;
+  const float* ss_b;
+  const int32_t* row;
+  float* pq;
+  int64_t* zero_out;
+  const float* x;
+  const float* residual;
+  float* out;
+  float* coef_a;
+  float* coef_b;
+  int64_t ss_a_stride, ss_a_floats, ss_b_stride, ss_b_floats, row_stride, flat_floats, zero_words;
+  int32_t B, C, HW, groups, pq_per_image, n_entries, use_entry, ss_total, output, in_place;
+} prg_gn_fold;
+int prg_debug_gn_fold(prg_gn_fold* args, void* stream);
+/* prg_debug_affine_silu: out = SiLU(x * A[b][c] + Bc[b][c]) + residual through launch_affine_silu<T>; x, residual (or NULL), out
+ * (B, C, HW), A, Bc (B, C); dtype PRG_F32 (C a multiple of 4) or PRG_BF16 (of 8).  in_place 1: x's buffer of T is the output's. */
+int prg_debug_affine_silu(const float* x, const float* A, const float* Bc, const float* residual, float* out, int B, int C, int HW,
+                          int dtype, int in_place, void* stream);
+/* prg_debug_linear: launch_linear with every argument of it: x (R, ldx) read at column xoff, W (O, ldw) at column woff, bias (O) or
+ * NULL, act_in / act_out 0 none, 1 SiLU, 2 GELU.  y (R, ldy) is copied in, written at columns [ycol, ycol + O), and copied back. */
+int prg_debug_linear(const float* x, int ldx, int xoff, const float* W, int ldw, int woff, const float* bias, float* y, int ldy,
+                     int ycol, int R, int I, int O, int act_in, int act_out, void* stream);
+/* prg_debug_sinusoidal: the sinusoidal embedding of t (R) int64 (wide 1: launch_sinusoidal) or int32 (wide 0:
+ * launch_sinusoidal_i32) with the frequency table freqs (dim / 2): out (R, dim) = sin | cos.  dim even, >= 4.                   */
+int prg_debug_sinusoidal(const void* t, const float* freqs, float* out, int R, int dim, int wide, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Sampler: GaussianDiffusion.sample / p_sample_loop / ddim_sample (sd:1283-1409), DDNM replacement included
  * ---------------------------------------------------------------------------------------------------- */

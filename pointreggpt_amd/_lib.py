@@ -40,6 +40,19 @@ CF_PRO_NONE, CF_PRO_TABLES, CF_PRO_FOLD = 0, 1, 2
 CF_RES_NONE, CF_RES_ADD, CF_RES_TABLES, CF_RES_FOLD = 0, 1, 2, 3
 CF_STATS_OFF, CF_STATS_SLABS, CF_STATS_ACC = 0, 1, 2
 
+
+class GnFoldC(C.Structure):
+    """prg_gn_fold (include/prg.h): the arguments of prg_debug_gn_fold."""
+    _fields_ = ([(n, C.c_void_p) for n in ("acc", "p", "q", "entries", "flat", "ss_a", "ss_b", "row", "pq", "zero_out", "x", "residual",
+                                           "out", "coef_a", "coef_b")] +
+                [(n, C.c_int64) for n in ("ss_a_stride", "ss_a_floats", "ss_b_stride", "ss_b_floats", "row_stride", "flat_floats",
+                                          "zero_words")] +
+                [(n, C.c_int32) for n in ("B", "C", "HW", "groups", "pq_per_image", "n_entries", "use_entry", "ss_total", "output",
+                                          "in_place")])
+
+
+GF_NONE, GF_TABLES, GF_APPLY = 0, 1, 2
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> (restype, argtypes): every symbol include/prg.h declares
@@ -87,6 +100,12 @@ PROTOTYPES = {
     "prg_debug_linear_attention_block": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     "prg_debug_resblock_tail": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "prg_debug_conv_fused": (C.c_int, [C.POINTER(ConvFusedC), _P]),
+    "prg_debug_gn_stats": (C.c_int, [_P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _P]),
+    "prg_debug_gn_coeff": (C.c_int, [_P, _I, _P, _P, _P, _L, _L, _P, _L, _L, C.POINTER(_I), _L, _P, _P, _I, _I, _I, _I, _P]),
+    "prg_debug_gn_fold": (C.c_int, [C.POINTER(GnFoldC), _P]),
+    "prg_debug_affine_silu": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "prg_debug_linear": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "prg_debug_sinusoidal": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "prg_unet_set_taps": (C.c_int, [_P, _I]),
     "prg_unet_get_tap": (C.c_int, [_P, C.c_char_p, _P, _L, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
     "prg_sampler_create": (C.c_int, [_P, C.POINTER(StepC), _I, _I, _I, C.POINTER(_P)]),

@@ -1,4 +1,4 @@
-// blocks.h — launch interface of the non-conv U-Net kernels (all HBM-bound): GroupNorm statistics / apply,
+// blocks.h — launch interface of the non-conv U-Net kernels (all HBM-bound): GroupNorm statistics / coefficients / apply,
 // channel LayerNorm, linear attention, full attention, the small conditioning MLPs.
 #pragma once
 #include "common.h"
@@ -7,10 +7,10 @@ namespace prg {
 
 constexpr int kHeads = 4, kDimHead = 32, kHidden = 128;   // sd:738, sd:773
 
-// GroupNorm (sd:685, eps 1e-5) over NHWC x (B, HW, C).  Pass 1 writes per-slab (sum, sumsq) partials
-// [B][nsplit][G][2]; pass 2 reduces them in a fixed order (deterministic), normalises, applies the optional
-// conditioning (scale+1, shift) (sd:692-694), SiLU, and an optional residual add (sd:734).
-// Returns nsplit chosen by pass 1 through *nsplit.
+// GroupNorm (sd:685, eps 1e-5) over NHWC x (B, HW, C).  The statistics pass writes per-slab (sum, sumsq) partials
+// [B][nsplit][G][2]; launch_gn_coeff reduces them in a fixed order (deterministic) and folds the norm and the optional
+// conditioning (scale+1, shift) (sd:692-694) into coefficients; launch_affine_silu applies them with SiLU and an optional
+// residual add (sd:734).  Returns nsplit chosen by the statistics pass through *nsplit.
 template <typename T>
 int launch_gn_stats(const T* x, float* partials, int B, int HW, int C, int G, int* nsplit, hipStream_t s);
 
@@ -36,10 +36,6 @@ int launch_affine_silu_fold(const bf16_t* x, const GnFold& f, const bf16_t* resi
 template <typename T>
 int launch_affine_silu(const T* x, const float* A, const float* Bc, const T* residual, T* out, int B, int HW, int C,
                        hipStream_t s);
-
-template <typename T>
-int launch_gn_apply(const T* x, const float* partials, int nsplit, const GnApply& p, const T* residual, T* out, int B,
-                    int HW, int C, int G, hipStream_t s);
 
 // Channel LayerNorm with gain (sd:619-628) + optional residual add (sd:589).
 template <typename T>

@@ -1,5 +1,5 @@
 // blocks.hip — the HBM-bound kernels between the convolutions (NHWC activations of type T, fp32 math):
-// GroupNorm statistics + apply (+conditioning, SiLU, residual), channel LayerNorm (+residual), the linear-attention
+// GroupNorm statistics, coefficients (+conditioning) and the affine + SiLU (+residual) pass, channel LayerNorm (+residual), the linear-attention
 // core, the bottleneck attention core, and the tiny conditioning MLPs.  Reductions are wave-level (64 lanes) and
 // every cross-workgroup reduction is done in a fixed order, so results are run-to-run deterministic.
 //
@@ -101,95 +101,6 @@ int launch_gn_stats(const T* x, float* partials, int B, int HW, int C, int G, in
 }
 template int launch_gn_stats<float>(const float*, float*, int, int, int, int, int*, hipStream_t);
 template int launch_gn_stats<bf16_t>(const bf16_t*, float*, int, int, int, int, int*, hipStream_t);
-
-// grid (chunks, B).  y = silu( gn(x) * (scale + 1) + shift ) + residual
-template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, const float* __restrict__ partials,
-                                                       int nsplit, GnApply p, const T* __restrict__ residual,
-                                                       T* __restrict__ out, int HW, int C, int G, int slab) {
-  constexpr int VEC = Elem<T>::kVec;
-  __shared__ float s_mean[64], s_rstd[64];
-  const int b = blockIdx.y;
-  if (threadIdx.x < G) {
-    double ss = 0, qq = 0;
-    const float* pp = partials + ((size_t)b * nsplit * G + threadIdx.x) * 2;
-    for (int k = 0; k < nsplit; ++k) {
-      ss += (double)pp[(size_t)k * G * 2 + 0];
-      qq += (double)pp[(size_t)k * G * 2 + 1];
-    }
-    const double n = (double)HW * (C / G);
-    const double mean = ss / n;
-    double var = qq / n - mean * mean;
-    if (var < 0) var = 0;
-    s_mean[threadIdx.x] = (float)mean;
-    s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + 1e-5));
-  }
-  __syncthreads();
-  const int nvc = C / VEC, psub = 256 / nvc;
-  const int vc = threadIdx.x % nvc, ps = threadIdx.x / nvc;
-  const int cpg = C / G;
-  float a[VEC], bb[VEC], sc[VEC], sh[VEC];
-  const float* ssa = nullptr;
-  const float* ssb = nullptr;
-  if (p.ss_a) {
-    ssa = p.ss_a + (size_t)b * p.ss_a_stride;
-    if (p.ss_a_row) ssa += (size_t)(*p.ss_a_row) * p.ss_a_row_stride;
-    if (p.ss_b) ssb = p.ss_b + (size_t)b * p.ss_b_stride;
-  }
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) {
-    const int c = vc * VEC + u, g = c / cpg;
-    const float scale = s_rstd[g] * p.gamma[c];
-    a[u] = scale;
-    bb[u] = p.beta[c] - s_mean[g] * scale;
-    sc[u] = 1.0f;
-    sh[u] = 0.0f;
-    if (ssa) {
-      float s0 = ssa[c], s1 = ssa[C + c];
-      if (ssb) { s0 += ssb[c]; s1 += ssb[C + c]; }
-      sc[u] = s0 + 1.0f;
-      sh[u] = s1;
-    }
-  }
-  const int p0 = blockIdx.x * slab, p1 = min(HW, p0 + slab);
-  const size_t base = (size_t)b * HW * C;
-#pragma unroll 4
-  for (int px = p0 + ps; px < p1; px += psub) {
-    const size_t o = base + (size_t)px * C + vc * VEC;
-    Vec16<T> v = vec_load(x + o), r, w;
-    if (residual) r = vec_load(residual + o);
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) {
-      float y = fmaf(Elem<T>::load(v.e[u]), a[u], bb[u]);
-      if (ssa) y = fmaf(y, sc[u], sh[u]);
-      y = Elem<T>::silu(y);
-      if (residual) y += Elem<T>::load(r.e[u]);
-      w.e[u] = Elem<T>::store(y);
-    }
-    vec_store(out + o, w);
-  }
-}
-
-template <typename T>
-int launch_gn_apply(const T* x, const float* partials, int nsplit, const GnApply& p, const T* residual, T* out, int B,
-                    int HW, int C, int G, hipStream_t s) {
-  constexpr int VEC = Elem<T>::kVec;
-  const int nvc = C / VEC;
-  PRG_CHECK(C % VEC == 0 && is_pow2(nvc) && nvc <= 256, "groupnorm: C/VEC must be a power of two <= 256");
-  const int psub = 256 / nvc;
-  int chunks = ceil_div(HW, psub * 4);
-  if (chunks > 512) chunks = 512;
-  if (chunks < 1) chunks = 1;
-  const int slab = ceil_div(HW, chunks);
-  chunks = ceil_div(HW, slab);
-  gn_apply_kernel<T><<<dim3(chunks, B), 256, 0, s>>>(x, partials, nsplit, p, residual, out, HW, C, G, slab);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-template int launch_gn_apply<float>(const float*, const float*, int, const GnApply&, const float*, float*, int, int, int,
-                                    int, hipStream_t);
-template int launch_gn_apply<bf16_t>(const bf16_t*, const float*, int, const GnApply&, const bf16_t*, bf16_t*, int, int,
-                                     int, int, hipStream_t);
 
 // Flat elementwise pass: y = silu(x * A[b][c] + Bc[b][c]) + residual, with the coefficients precomputed by
 // gn_coeff_kernel (no per-workgroup statistics prologue: every workgroup streams from its first instruction).

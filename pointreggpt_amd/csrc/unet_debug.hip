@@ -2,7 +2,9 @@
 // (two sources, statistics, prologue, residual) and a ResnetBlock's Block pair through the library's own packer (pack_conv_host:
 // what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own;
 // the attention cores, the channel LayerNorm, the fused linear-attention blocks (pack_fused_attention / pack_split_attention)
-// and the fused ResnetBlock tail through the launch functions the forward calls, with the kernel chosen by argument.
+// and the fused ResnetBlock tail through the launch functions the forward calls, with the kernel chosen by argument;
+// the GroupNorm passes (statistics, coefficients, the fold from accumulators, the affine + SiLU pass) and the conditioning kernels
+// (cond_fold, linear, sinusoidal) of blocks.hip, each through its own launch function on buffers the hook owns.
 #include <type_traits>
 
 #include "unet_layout.h"
@@ -115,6 +117,65 @@ int debug_layernorm_t(const float* x, const float* g, const float* residual, flo
   if (rc == PRG_OK) rc = launch_layernorm<T>(d_x, d_g, d_r, d_o, M, C, s);
   if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(d_o, out, 1, (int)n, 1, s);
   if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_layernorm: stream synchronise failed");
+  return rc;
+}
+
+// device-to-device copy of `count` elements on the stream
+template <typename U>
+bool copy_dd(U* dst, const U* src, size_t count, hipStream_t s) {
+  return count == 0 || hipMemcpyAsync(dst, src, count * sizeof(U), hipMemcpyDeviceToDevice, s) == hipSuccess;
+}
+
+// what is wrong with a set of conditioning rows of `width` floats (GnApply's addressing), or null: every read stays inside its array
+const char* cond_rows_bad(const float* ss_a, int64_t ss_a_stride, int64_t ss_a_floats, const float* ss_b, int64_t ss_b_stride,
+                          int64_t ss_b_floats, const int* row, int64_t row_stride, int B, int64_t width) {
+  const int64_t lim = (int64_t)1 << 28;
+  if (!ss_a) return nullptr;
+  if (ss_a_stride < 0 || ss_a_stride > lim || row_stride < 0 || row_stride > lim || ss_a_floats <= 0 || ss_a_floats > lim)
+    return "ss_a strides and size out of range";
+  if (row && (*row < 0 || *row > 1 << 20)) return "row out of range";
+  if ((int64_t)(B - 1) * ss_a_stride + (row ? (int64_t)*row * row_stride : 0) + width > ss_a_floats) return "ss_a is read past its end";
+  if (!ss_b) return nullptr;
+  if (ss_b_stride < 0 || ss_b_stride > lim || ss_b_floats <= 0 || ss_b_floats > lim) return "ss_b stride and size out of range";
+  if ((int64_t)(B - 1) * ss_b_stride + width > ss_b_floats) return "ss_b is read past its end";
+  return nullptr;
+}
+
+int debug_gn_stats_t(const float* x, float* slabs, int* nsplit, int B, int C, int HW, int G, bool bf16, hipStream_t s) {
+  const char* nomem = "prg_debug_gn_stats: hipMalloc failed";
+  const size_t M = (size_t)B * HW * C;
+  DeviceBuffers own;
+  bf16_t* d_xb = bf16 ? own.alloc<bf16_t>(M, nomem) : nullptr;
+  float* d_xf = bf16 ? nullptr : own.alloc<float>(M, nomem);
+  float* d_slabs = own.alloc<float>((size_t)B * kGnMaxSplit * G * 2, nomem);
+  if (own.rc) return own.rc;
+  int ns = 0;
+  int rc = bf16 ? launch_nchw_f32_to_nhwc<bf16_t>(x, d_xb, B, HW, C, s) : launch_nchw_f32_to_nhwc<float>(x, d_xf, B, HW, C, s);
+  if (rc == PRG_OK) rc = bf16 ? launch_gn_stats<bf16_t>(d_xb, d_slabs, B, HW, C, G, &ns, s) : launch_gn_stats<float>(d_xf, d_slabs, B, HW, C, G, &ns, s);
+  if (rc == PRG_OK && (ns < 1 || ns > kGnMaxSplit)) rc = fail(PRG_E_INVALID, "prg_debug_gn_stats: slab count out of range");
+  if (rc == PRG_OK && !copy_dd(slabs, d_slabs, (size_t)B * ns * G * 2, s)) rc = fail(PRG_E_HIP, "prg_debug_gn_stats: copy failed");
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_gn_stats: stream synchronise failed");
+  if (rc == PRG_OK) *nsplit = ns;
+  return rc;
+}
+
+template <typename T>
+int debug_affine_silu_t(const float* x, const float* A, const float* Bc, const float* residual, float* out, int B, int C, int HW,
+                        int in_place, hipStream_t s) {
+  const char* nomem = "prg_debug_affine_silu: hipMalloc failed";
+  const size_t M = (size_t)B * HW * C, nc = (size_t)B * C;
+  DeviceBuffers own;
+  T* d_x = own.alloc<T>(M, nomem);
+  T* d_r = residual ? own.alloc<T>(M, nomem) : nullptr;
+  T* d_o = in_place ? d_x : own.alloc<T>(M, nomem);
+  float* d_ab = own.alloc<float>(2 * nc, nomem);
+  if (own.rc) return own.rc;
+  if (!copy_dd(d_ab, A, nc, s) || !copy_dd(d_ab + nc, Bc, nc, s)) return fail(PRG_E_HIP, "prg_debug_affine_silu: copy failed");
+  int rc = launch_nchw_f32_to_nhwc<T>(x, d_x, B, HW, C, s);
+  if (rc == PRG_OK && d_r) rc = launch_nchw_f32_to_nhwc<T>(residual, d_r, B, HW, C, s);
+  if (rc == PRG_OK) rc = launch_affine_silu<T>(d_x, d_ab, d_ab + nc, d_r, d_o, B, HW, C, s);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(d_o, out, B, HW, C, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_affine_silu: stream synchronise failed");
   return rc;
 }
 
@@ -428,6 +489,216 @@ int prg_debug_conv_fused(prg_conv_fused* a, void* stream) {
         a->sums[((size_t)b * G + g) * 2 + w] = t;
       }
   return PRG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the GroupNorm passes and the conditioning kernels of blocks.hip, alone (prg.h)
+// ---------------------------------------------------------------------------------------------
+int prg_debug_gn_stats(const float* x, float* slabs, int* nsplit, int B, int C, int HW, int groups, int dtype, void* stream) {
+  PRG_CHECK(x && slabs && nsplit, "prg_debug_gn_stats: null pointer");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16, "prg_debug_gn_stats: bad dtype");
+  const int vec = dtype == PRG_F32 ? 4 : 8;
+  PRG_CHECK(C > 0 && C % vec == 0 && C / vec <= 256 && ((C / vec) & (C / vec - 1)) == 0,
+            "prg_debug_gn_stats: C / vec must be a power of two <= 256");
+  PRG_CHECK(groups > 0 && groups <= 64 && C % groups == 0, "prg_debug_gn_stats: bad group count");
+  PRG_CHECK(B > 0 && B <= 65535 && HW > 0 && (int64_t)B * HW * C <= (int64_t)1 << 26, "prg_debug_gn_stats: bad shape");
+  *nsplit = 0;
+  hipStream_t s = (hipStream_t)stream;
+  return debug_gn_stats_t(x, slabs, nsplit, B, C, HW, groups, dtype == PRG_BF16, s);
+}
+
+int prg_debug_gn_coeff(const float* slabs, int nsplit, const float* gamma, const float* beta, const float* ss_a, int64_t ss_a_stride,
+                       int64_t ss_a_floats, const float* ss_b, int64_t ss_b_stride, int64_t ss_b_floats, const int* row,
+                       int64_t row_stride, float* A, float* Bc, int B, int HW, int C, int groups, void* stream) {
+  PRG_CHECK(slabs && gamma && beta && A && Bc, "prg_debug_gn_coeff: null pointer");
+  PRG_CHECK(B > 0 && B <= 65535 && HW > 0 && nsplit > 0 && nsplit <= kGnMaxSplit, "prg_debug_gn_coeff: bad shape");
+  PRG_CHECK(C > 0 && C <= 1024 && groups > 0 && groups <= 64 && C % groups == 0, "prg_debug_gn_coeff: at most 1024 channels in at most 64 groups");
+  PRG_CHECK(ss_a || (!ss_b && !row), "prg_debug_gn_coeff: ss_b and row come with ss_a");
+  const char* why = cond_rows_bad(ss_a, ss_a_stride, ss_a_floats, ss_b, ss_b_stride, ss_b_floats, row, row_stride, B, 2 * (int64_t)C);
+  PRG_CHECK(!why, std::string("prg_debug_gn_coeff: ") + (why ? why : ""));
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_gn_coeff: hipMalloc failed";
+  DeviceBuffers own;
+  const size_t nslab = (size_t)B * nsplit * groups * 2;
+  float* d_slabs = own.alloc<float>(nslab, nomem);
+  float* d_gb = own.alloc<float>(2 * (size_t)C, nomem);
+  float* d_ssa = own.alloc<float>(ss_a ? (size_t)ss_a_floats : 0, nomem);
+  float* d_ssb = own.alloc<float>(ss_b ? (size_t)ss_b_floats : 0, nomem);
+  int* d_row = row ? own.upload(row, (size_t)1, nomem) : nullptr;
+  float* d_ab = own.alloc<float>(2 * (size_t)B * C, nomem);
+  if (own.rc) return own.rc;
+  const char* nocopy = "prg_debug_gn_coeff: copy failed";
+  if (!copy_dd(d_slabs, slabs, nslab, s) || !copy_dd(d_gb, gamma, (size_t)C, s) || !copy_dd(d_gb + C, beta, (size_t)C, s) ||
+      (ss_a && !copy_dd(d_ssa, ss_a, (size_t)ss_a_floats, s)) || (ss_b && !copy_dd(d_ssb, ss_b, (size_t)ss_b_floats, s)))
+    return fail(PRG_E_HIP, nocopy);
+  GnApply p{};
+  p.gamma = d_gb; p.beta = d_gb + C;
+  p.ss_a = d_ssa; p.ss_a_stride = ss_a_stride; p.ss_b = d_ssb; p.ss_b_stride = ss_b_stride; p.ss_a_row = d_row; p.ss_a_row_stride = row_stride;
+  int rc = launch_gn_coeff(d_slabs, nsplit, p, d_ab, d_ab + (size_t)B * C, B, HW, C, groups, s);
+  if (rc == PRG_OK && (!copy_dd(A, d_ab, (size_t)B * C, s) || !copy_dd(Bc, d_ab + (size_t)B * C, (size_t)B * C, s))) rc = fail(PRG_E_HIP, nocopy);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_gn_coeff: stream synchronise failed");
+  return rc;
+}
+
+int prg_debug_gn_fold(prg_gn_fold* a, void* stream) {
+  PRG_CHECK(a != nullptr, "prg_debug_gn_fold: null argument struct");
+  const int B = a->B, C = a->C, HW = a->HW, G = a->groups, n = a->n_entries;
+  PRG_CHECK(a->output >= PRG_GF_NONE && a->output <= PRG_GF_APPLY, "prg_debug_gn_fold: bad output mode");
+  PRG_CHECK(a->in_place == 0 || a->in_place == 1, "prg_debug_gn_fold: in_place is 0 or 1");
+  PRG_CHECK(a->pq_per_image == 0 || a->pq_per_image == 1, "prg_debug_gn_fold: pq_per_image is 0 or 1");
+  PRG_CHECK(B > 0 && B <= 65535, "prg_debug_gn_fold: bad batch");
+  const bool cond = a->entries != nullptr;
+  PRG_CHECK(cond || a->output != PRG_GF_NONE, "prg_debug_gn_fold: nothing to do");
+  std::vector<CondFoldEntry> ent;
+  if (cond) {
+    PRG_CHECK(!a->p && !a->q && a->pq_per_image == 0, "prg_debug_gn_fold: p and q are given or folded from entries, not both");
+    PRG_CHECK(n > 0 && n <= 256 && a->ss_total > 0 && a->flat && a->flat_floats > 0 && a->ss_a && a->pq && a->zero_out,
+              "prg_debug_gn_fold: the conditioning fold needs entries, ss_total, flat, ss_a, pq and zero_out");
+    PRG_CHECK(a->zero_words >= 0 && a->zero_words <= (int64_t)1 << 24, "prg_debug_gn_fold: zero_words out of range");
+    const char* why = cond_rows_bad(a->ss_a, a->ss_a_stride, a->ss_a_floats, a->ss_b, a->ss_b_stride, a->ss_b_floats, a->row, a->row_stride,
+                                    B, a->ss_total);
+    PRG_CHECK(!why, std::string("prg_debug_gn_fold: ") + (why ? why : ""));
+    for (int k = 0; k < n; ++k) {
+      const int64_t* e = a->entries + 4 * (size_t)k;
+      PRG_CHECK(e[1] > 0 && e[1] <= 4096 && e[0] >= 0 && e[0] + 2 * e[1] <= a->ss_total, "prg_debug_gn_fold: an entry leaves its conditioning row");
+      PRG_CHECK(e[2] >= 0 && e[2] + e[1] <= a->flat_floats && e[3] >= 0 && e[3] + e[1] <= a->flat_floats, "prg_debug_gn_fold: an entry leaves flat");
+      ent.push_back(CondFoldEntry{(int)e[0], (int)e[1], (long long)e[2], (long long)e[3]});
+    }
+    PRG_CHECK(a->output == PRG_GF_NONE || (a->use_entry >= 0 && a->use_entry < n && ent[a->use_entry].C == C),
+              "prg_debug_gn_fold: use_entry names an entry of C channels");
+  } else {
+    PRG_CHECK(a->p && a->q, "prg_debug_gn_fold: p and q, or entries");
+  }
+  if (a->output != PRG_GF_NONE) {
+    PRG_CHECK(a->acc != nullptr, "prg_debug_gn_fold: null accumulators");
+    PRG_CHECK(C > 0 && C <= 4096 && G > 0 && C % G == 0 && HW > 0, "prg_debug_gn_fold: bad shape");
+  }
+  if (a->output == PRG_GF_TABLES) PRG_CHECK(a->coef_a && a->coef_b, "prg_debug_gn_fold: the tables need coef_a and coef_b");
+  if (a->output == PRG_GF_APPLY) {
+    PRG_CHECK(a->x && a->out, "prg_debug_gn_fold: the pass needs x and out");
+    PRG_CHECK(C % 8 == 0 && C <= 1024 && (int64_t)B * HW * C <= (int64_t)1 << 26, "prg_debug_gn_fold: the pass takes multiples of 8 channels, at most 1024");
+  } else {
+    PRG_CHECK(!a->residual && a->in_place == 0, "prg_debug_gn_fold: residual and in_place belong to the pass");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_gn_fold: hipMalloc failed";
+  const char* nocopy = "prg_debug_gn_fold: copy failed";
+  DeviceBuffers own;
+  GnFold f{};
+  int rc = PRG_OK;
+  const size_t nzero = cond ? (size_t)a->zero_words + 64 : 0;
+  long long* d_zero = nullptr;
+  if (cond) {
+    const CondFoldEntry* d_ent = own.upload(ent, nomem);
+    float* d_flat = own.alloc<float>((size_t)a->flat_floats, nomem);
+    float* d_ssa = own.alloc<float>((size_t)a->ss_a_floats, nomem);
+    float* d_ssb = own.alloc<float>(a->ss_b ? (size_t)a->ss_b_floats : 0, nomem);
+    int* d_row = a->row ? own.upload(reinterpret_cast<const int*>(a->row), (size_t)1, nomem) : nullptr;
+    float* d_pq = own.alloc<float>((size_t)B * a->ss_total, nomem);
+    d_zero = own.alloc<long long>(nzero, nomem);
+    if (own.rc) return own.rc;
+    if (!copy_dd(d_flat, a->flat, (size_t)a->flat_floats, s) || !copy_dd(d_ssa, a->ss_a, (size_t)a->ss_a_floats, s) ||
+        (a->ss_b && !copy_dd(d_ssb, a->ss_b, (size_t)a->ss_b_floats, s)) || !copy_dd(d_pq, a->pq, (size_t)B * a->ss_total, s) ||
+        hipMemsetAsync(d_zero, 0x5a, nzero * sizeof(long long), s) != hipSuccess)
+      return fail(PRG_E_HIP, nocopy);
+    GnApply ss{};
+    ss.ss_a = d_ssa; ss.ss_a_stride = a->ss_a_stride; ss.ss_b = d_ssb; ss.ss_b_stride = a->ss_b_stride; ss.ss_a_row = d_row; ss.ss_a_row_stride = a->row_stride;
+    rc = launch_cond_fold(d_ent, n, d_flat, ss, d_pq, a->ss_total, B, s, d_zero, a->zero_words);
+    if (rc == PRG_OK && (!copy_dd(a->pq, d_pq, (size_t)B * a->ss_total, s) || !copy_dd(reinterpret_cast<long long*>(a->zero_out), d_zero, nzero, s))) rc = fail(PRG_E_HIP, nocopy);
+    if (a->output != PRG_GF_NONE) { f.P = d_pq + ent[a->use_entry].ss_off; f.Q = f.P + C; f.pq_stride = a->ss_total; }
+  } else {
+    const size_t rows = a->pq_per_image ? (size_t)B : 1;
+    float* d_pq = own.alloc<float>(rows * 2 * C, nomem);   // image b: P at 2 C b, Q behind it
+    if (own.rc) return own.rc;
+    for (size_t b = 0; b < rows; ++b)
+      if (!copy_dd(d_pq + 2 * C * b, a->p + C * b, (size_t)C, s) || !copy_dd(d_pq + 2 * C * b + C, a->q + C * b, (size_t)C, s)) return fail(PRG_E_HIP, nocopy);
+    f.P = d_pq; f.Q = d_pq + C; f.pq_stride = a->pq_per_image ? 2 * (int64_t)C : 0;
+  }
+  if (rc == PRG_OK && a->output != PRG_GF_NONE) {
+    const size_t nacc = (size_t)B * G * 2, M = (size_t)B * HW * C;
+    long long* d_acc = own.alloc<long long>(nacc, nomem);
+    if (own.rc) return own.rc;
+    if (!copy_dd(d_acc, reinterpret_cast<const long long*>(a->acc), nacc, s)) return fail(PRG_E_HIP, nocopy);
+    f.acc = d_acc; f.G = G; f.cpg = C / G; f.inv_n = 1.0f / ((float)HW * (float)f.cpg);
+    if (a->output == PRG_GF_TABLES) {
+      float* d_ab = own.alloc<float>(2 * (size_t)B * C, nomem);
+      if (own.rc) return own.rc;
+      rc = launch_gn_coeff_acc(f, d_ab, d_ab + (size_t)B * C, B, C, s);
+      if (rc == PRG_OK && (!copy_dd(a->coef_a, d_ab, (size_t)B * C, s) || !copy_dd(a->coef_b, d_ab + (size_t)B * C, (size_t)B * C, s))) rc = fail(PRG_E_HIP, nocopy);
+    } else {
+      bf16_t* d_x = own.alloc<bf16_t>(M, nomem);
+      bf16_t* d_r = a->residual ? own.alloc<bf16_t>(M, nomem) : nullptr;
+      bf16_t* d_o = a->in_place ? d_x : own.alloc<bf16_t>(M, nomem);
+      if (own.rc) return own.rc;
+      rc = launch_nchw_f32_to_nhwc<bf16_t>(a->x, d_x, B, HW, C, s);
+      if (rc == PRG_OK && d_r) rc = launch_nchw_f32_to_nhwc<bf16_t>(a->residual, d_r, B, HW, C, s);
+      if (rc == PRG_OK) rc = launch_affine_silu_fold(d_x, f, d_r, d_o, B, HW, C, s);
+      if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(d_o, a->out, B, HW, C, s);
+    }
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_gn_fold: stream synchronise failed");
+  return rc;
+}
+
+int prg_debug_affine_silu(const float* x, const float* A, const float* Bc, const float* residual, float* out, int B, int C, int HW,
+                          int dtype, int in_place, void* stream) {
+  PRG_CHECK(x && A && Bc && out, "prg_debug_affine_silu: null pointer");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16, "prg_debug_affine_silu: bad dtype");
+  PRG_CHECK(in_place == 0 || in_place == 1, "prg_debug_affine_silu: in_place is 0 or 1");
+  PRG_CHECK(C > 0 && C % (dtype == PRG_F32 ? 4 : 8) == 0, "prg_debug_affine_silu: C must be a multiple of the vector width");
+  PRG_CHECK(B > 0 && HW > 0 && (int64_t)B * HW * C <= (int64_t)1 << 28, "prg_debug_affine_silu: bad shape");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == PRG_BF16) return debug_affine_silu_t<bf16_t>(x, A, Bc, residual, out, B, C, HW, in_place, s);
+  return debug_affine_silu_t<float>(x, A, Bc, residual, out, B, C, HW, in_place, s);
+}
+
+int prg_debug_linear(const float* x, int ldx, int xoff, const float* W, int ldw, int woff, const float* bias, float* y, int ldy,
+                     int ycol, int R, int I, int O, int act_in, int act_out, void* stream) {
+  PRG_CHECK(x && W && y, "prg_debug_linear: null pointer");
+  PRG_CHECK(R > 0 && R <= 1 << 20 && I > 0 && I <= 1 << 16 && O > 0 && O <= 1 << 16, "prg_debug_linear: bad shape");
+  PRG_CHECK(xoff >= 0 && ldx <= 1 << 20 && (int64_t)xoff + I <= ldx, "prg_debug_linear: x columns [xoff, xoff + I) leave the row");
+  PRG_CHECK(woff >= 0 && ldw <= 1 << 20 && (int64_t)woff + I <= ldw, "prg_debug_linear: W columns [woff, woff + I) leave the row");
+  PRG_CHECK(ycol >= 0 && ldy <= 1 << 20 && (int64_t)ycol + O <= ldy, "prg_debug_linear: y columns [ycol, ycol + O) leave the row");
+  PRG_CHECK((int64_t)R * ldx <= (int64_t)1 << 28 && (int64_t)O * ldw <= (int64_t)1 << 28 && (int64_t)R * ldy <= (int64_t)1 << 28,
+            "prg_debug_linear: operand too large");
+  PRG_CHECK(act_in >= ACT_NONE && act_in <= ACT_GELU && act_out >= ACT_NONE && act_out <= ACT_GELU, "prg_debug_linear: bad activation");
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_linear: hipMalloc failed";
+  const char* nocopy = "prg_debug_linear: copy failed";
+  DeviceBuffers own;
+  float* d_x = own.alloc<float>((size_t)R * ldx, nomem);
+  float* d_w = own.alloc<float>((size_t)O * ldw, nomem);
+  float* d_b = bias ? own.alloc<float>((size_t)O, nomem) : nullptr;
+  float* d_y = own.alloc<float>((size_t)R * ldy, nomem);
+  if (own.rc) return own.rc;
+  if (!copy_dd(d_x, x, (size_t)R * ldx, s) || !copy_dd(d_w, W, (size_t)O * ldw, s) || (bias && !copy_dd(d_b, bias, (size_t)O, s)) ||
+      !copy_dd(d_y, y, (size_t)R * ldy, s))
+    return fail(PRG_E_HIP, nocopy);
+  int rc = launch_linear(d_x, ldx, xoff, d_w, ldw, woff, d_b, d_y + ycol, ldy, R, I, O, act_in, act_out, s);
+  if (rc == PRG_OK && !copy_dd(y, d_y, (size_t)R * ldy, s)) rc = fail(PRG_E_HIP, nocopy);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_linear: stream synchronise failed");
+  return rc;
+}
+
+int prg_debug_sinusoidal(const void* t, const float* freqs, float* out, int R, int dim, int wide, void* stream) {
+  PRG_CHECK(t && freqs && out, "prg_debug_sinusoidal: null pointer");
+  PRG_CHECK(wide == 0 || wide == 1, "prg_debug_sinusoidal: wide is 0 (int32) or 1 (int64)");
+  PRG_CHECK(R > 0 && dim >= 4 && dim % 2 == 0 && (int64_t)R * dim <= (int64_t)1 << 24, "prg_debug_sinusoidal: bad shape");
+  hipStream_t s = (hipStream_t)stream;
+  const char* nomem = "prg_debug_sinusoidal: hipMalloc failed";
+  const char* nocopy = "prg_debug_sinusoidal: copy failed";
+  DeviceBuffers own;
+  const size_t tbytes = (size_t)R * (wide ? 8 : 4);
+  char* d_t = own.alloc<char>(tbytes, nomem);
+  float* d_f = own.alloc<float>((size_t)dim / 2, nomem);
+  float* d_o = own.alloc<float>((size_t)R * dim, nomem);
+  if (own.rc) return own.rc;
+  if (!copy_dd(d_t, static_cast<const char*>(t), tbytes, s) || !copy_dd(d_f, freqs, (size_t)dim / 2, s)) return fail(PRG_E_HIP, nocopy);
+  int rc = wide ? launch_sinusoidal(reinterpret_cast<const int64_t*>(d_t), d_f, d_o, R, dim, s)
+                : launch_sinusoidal_i32(reinterpret_cast<const int32_t*>(d_t), d_f, d_o, R, dim, s);
+  if (rc == PRG_OK && !copy_dd(out, d_o, (size_t)R * dim, s)) rc = fail(PRG_E_HIP, nocopy);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_sinusoidal: stream synchronise failed");
+  return rc;
 }
 
 int prg_debug_conv3x3(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,

@@ -286,7 +286,7 @@ def reference(d, images=None, dtype=torch.float64, kernel=None, partials=0, from
     if partials:      # gn_fold_stats_raw + gn_coeff_acc_kernel
         dA = gam.abs() * ch(drstd) + 4 * EPS * A.abs()
         dB = A.abs() * ch(dmean) + ch(mean.abs()) * gam.abs() * ch(drstd) + 5 * EPS * (ch(mean) * A).abs() + EPS * Bc.abs()
-    else:             # gn_coeff_kernel (blocks.hip:310-332): float64 to (float) mean, (float) rstd, then two float32 roundings each
+    else:             # gn_coeff_kernel (blocks.hip:221-243): float64 to (float) mean, (float) rstd, then two float32 roundings each
         dA = gam.abs() * (ch(drstd) + EPS * ch(rstd)) + EPS * A.abs()
         dB = A.abs() * (ch(dmean) + EPS * ch(mean.abs())) + ch(mean.abs()) * dA + EPS * (ch(mean) * A).abs() + EPS * Bc.abs()
     out.update(coef_a=A, coef_b=Bc, coef_a_tol=dA, coef_b_tol=dB)
