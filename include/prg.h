@@ -529,6 +529,35 @@ int prg_debug_linear(const float* x, int ldx, int xoff, const float* W, int ldw,
  * launch_sinusoidal_i32) with the frequency table freqs (dim / 2): out (R, dim) = sin | cos.  dim even, >= 4.                   */
 int prg_debug_sinusoidal(const void* t, const float* freqs, float* out, int R, int dim, int wide, void* stream);
 
+/* Host-only hooks into weight preparation (no GPU needed, HOST pointers throughout): what prg_unet_create would upload.
+ * Both copy at most capacity_bytes into `out` and write the size of the result to *bytes; out NULL only reports the size.
+ *
+ * prg_debug_weight_arena: one arena of a handle of `dtype` built from the flat state dict, under the switch settings `options`
+ * (PRG_WOPT_* bits, one per PRG_* environment switch read at load time; PRG_WOPT_DEFAULT = the library's defaults).
+ * PRG_ARENA_LAYOUT: every offset of the parameter layout as int64 — per conv in traversal order 23 values (Cout, Cin, KH, KW,
+ * CoutPad, kchunks, w_off, b_off, w_flat, ws, mx_off, mx_soff, s2d_off, s2d_kchunks, sp_off, sp_kchunks, h16_off, up_off,
+ * sp_scale_off, up_sp_scale_off, up_sp_off, conv2, upsample), then per ResnetBlock 7 (cin, cout, ss_off, fw_res, pq1, pq2, cpad),
+ * then per attention block 6 (C, fw_qkv, fw_out, kshift, sp_qkv, sp_out).                                                       */
+enum { PRG_WOPT_SPLIT_UP2X2 = 1, PRG_WOPT_FUSED_ATTN = 2, PRG_WOPT_LA_KSHIFT = 4, PRG_WOPT_SPLIT_STEM = 8, PRG_WOPT_DEFAULT = 14 };
+enum {
+  PRG_ARENA_LAYOUT = 0, PRG_ARENA_PACKED, PRG_ARENA_MX, PRG_ARENA_MX_SCALE, PRG_ARENA_H16, PRG_ARENA_SPLIT, PRG_ARENA_SPLIT_SCALE,
+  PRG_ARENA_STEM, PRG_ARENA_STEM_FRAG, PRG_ARENA_STEM_SPLIT, PRG_ARENA_STEM_SPLIT_SCALE, PRG_ARENA_FREQS, PRG_ARENA_ATTN_SPLIT,
+  PRG_ARENA_PQ_STATIC, PRG_ARENA_COND_ENTRIES, PRG_ARENA_ATTN, PRG_ARENA_KSHIFT, PRG_ARENA_COUNT,
+  PRG_ARENA_ALL = -1   /* every arena in this order, each behind its int64 byte count: one build for all of them */
+};
+int prg_debug_weight_arena(const prg_unet_config* cfg, const float* weights, int64_t n_floats, int dtype, int options, int arena,
+                           void* out, int64_t capacity_bytes, int64_t* bytes);
+/* prg_debug_pack_conv: one packing of one conv, w (Cout, Cin, K, K) used as it is, as a handle of `dtype` packs it for a conv in
+ * the role `role_bits`; empty where the conv has no such packing.  PRG_PACK_S2D_OIHW (K = 4) / PRG_PACK_UP_OIHW (K = 3): the
+ * float32 OIHW tensors of the equivalent convolutions, (Cout, 4 Cin, 3, 3) and (4, Cout, Cin, 2, 2).                              */
+enum { PRG_ROLE_CONV2 = 1, PRG_ROLE_UPSAMPLE = 2 };
+enum {
+  PRG_PACK_MAIN = 0, PRG_PACK_S2D, PRG_PACK_UP, PRG_PACK_MX, PRG_PACK_MX_SCALE, PRG_PACK_H16, PRG_PACK_SPLIT, PRG_PACK_SPLIT_SCALE,
+  PRG_PACK_UP_SPLIT, PRG_PACK_UP_SPLIT_SCALE, PRG_PACK_S2D_OIHW, PRG_PACK_UP_OIHW
+};
+int prg_debug_pack_conv(const float* w, int Cout, int Cin, int K, int dtype, int role_bits, int packing, void* out,
+                        int64_t capacity_bytes, int64_t* bytes);
+
 /* ------------------------------------------------------------------------------------------------------
  * Sampler: GaussianDiffusion.sample / p_sample_loop / ddim_sample (sd:1283-1409), DDNM replacement included
  * ---------------------------------------------------------------------------------------------------- */

@@ -106,6 +106,8 @@ PROTOTYPES = {
     "prg_debug_affine_silu": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "prg_debug_linear": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "prg_debug_sinusoidal": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    "prg_debug_weight_arena": (C.c_int, [C.POINTER(UnetConfigC), _P, _L, _I, _I, _I, _P, _L, C.POINTER(_L)]),
+    "prg_debug_pack_conv": (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _L, C.POINTER(_L)]),
     "prg_unet_set_taps": (C.c_int, [_P, _I]),
     "prg_unet_get_tap": (C.c_int, [_P, C.c_char_p, _P, _L, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
     "prg_sampler_create": (C.c_int, [_P, C.POINTER(StepC), _I, _I, _I, C.POINTER(_P)]),

@@ -2,10 +2,9 @@
 // channel LayerNorm, linear attention, full attention, the small conditioning MLPs.
 #pragma once
 #include "common.h"
+#include "weights_host.h"   // kHeads, kDimHead, kHidden, CondFoldEntry
 
 namespace prg {
-
-constexpr int kHeads = 4, kDimHead = 32, kHidden = 128;   // sd:738, sd:773
 
 // GroupNorm (sd:685, eps 1e-5) over NHWC x (B, HW, C).  The statistics pass writes per-slab (sum, sumsq) partials
 // [B][nsplit][G][2]; launch_gn_coeff reduces them in a fixed order (deterministic) and folds the norm and the optional
@@ -24,8 +23,7 @@ int launch_gn_coeff(const float* partials, int nsplit, const GnApply& p, float* 
 // for consumers that cannot fold in-kernel (the wave-specialised conv's prologue, the 1x1 res_conv epilogue).
 int launch_gn_coeff_acc(const GnFold& f, float* A, float* Bc, int B, int C, hipStream_t s);
 // P = gamma * (scale + 1), Q = beta * (scale + 1) + shift for every conditioned GroupNorm of a forward, ONE launch:
-// entries [n] of (ss_off, C, gamma offset, beta offset into `flat`); pq [B][ss_total]: P at ss_off, Q at ss_off + C.
-struct CondFoldEntry { int ss_off, C; long long gamma_off, beta_off; };
+// entries [n] of (ss_off, C, gamma offset, beta offset into `flat`: CondFoldEntry); pq [B][ss_total]: P at ss_off, Q at ss_off + C.
 int launch_cond_fold(const CondFoldEntry* entries, int n, const float* flat, const GnApply& ss, float* pq, int64_t pq_stride,
                      int B, hipStream_t s, long long* zero = nullptr, int64_t zero_words = 0);
 // y = silu(x * A + B) + residual with the coefficients folded per block from the accumulators (one image per block row)

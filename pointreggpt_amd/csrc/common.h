@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/prg.h"
+#include "bf16.h"   // bf16_t, bf16_to_f32, f32_to_bf16 (shared with the host-only weight preparation)
 
 namespace prg {
 
@@ -57,46 +58,6 @@ struct DeviceOnce {
   void mark() { mask.fetch_or(bit(), std::memory_order_release); }
 };
 int device_cu_count();   // multiProcessorCount of the CURRENT device (cached per device ordinal); 0 on failure
-
-// ---------------------------------------------------------------------------------------------
-// bf16 storage type (raw 16 bits; conversions round-to-nearest-even, NaN preserved)
-// ---------------------------------------------------------------------------------------------
-struct bf16_t {
-  uint16_t v;
-};
-
-__host__ __device__ inline float bf16_to_f32(bf16_t b) {
-  union {
-    uint32_t u;
-    float f;
-  } x;
-  x.u = ((uint32_t)b.v) << 16;
-  return x.f;
-}
-
-__host__ __device__ inline bf16_t f32_to_bf16(float f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  // gfx950 has a native round-to-nearest-even conversion (v_cvt_pk_bf16_f32)
-  bf16_t r;
-  r.v = __builtin_bit_cast(uint16_t, (__bf16)f);
-  return r;
-#else
-  union {
-    uint32_t u;
-    float f;
-  } x;
-  x.f = f;
-  bf16_t r;
-  if ((x.u & 0x7fffffffu) > 0x7f800000u) {  // NaN
-    r.v = (uint16_t)((x.u >> 16) | 0x40);
-    return r;
-  }
-  uint32_t lsb = (x.u >> 16) & 1u;
-  x.u += 0x7fffu + lsb;
-  r.v = (uint16_t)(x.u >> 16);
-  return r;
-#endif
-}
 
 template <typename T>
 struct Elem;

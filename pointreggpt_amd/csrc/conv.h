@@ -23,17 +23,13 @@ struct ConvDesc {
   int kchunks;              // ceil((C0+C1) / BK)
 };
 
-// Packed weights: [tap = kh*KW+kw][chunk][CoutPad][BK] of T, zero padded in both Cout and channel.
-template <typename T>
-void pack_conv_weight(const float* w_oihw, int Cout, int Cin, int KH, int KW, std::vector<T>& out, int* CoutPad,
-                      int* kchunks);
-
+// Every weight pointer below is a packing that weights_host.cpp builds (pack_conv_host).
 template <typename T>
 struct ConvLaunch {
   ConvDesc d;
   const T* src0;
   const T* src1;
-  const T* w;            // packed
+  const T* w;            // packed: [tap = kh*KW+kw][chunk][CoutPad][BK] of T, zero padded in both Cout and channel
   const float* bias;     // [Cout] or null
   const T* residual;     // NHWC (M, Cout) added in the epilogue, or null
   // Activated residual (1x1 convs on the implicit-GEMM kernel, bf16 mode): out = conv + bias + SiLU(residual * res_a[b][c]
@@ -101,7 +97,7 @@ struct ConvLaunch {
   //   w_f16 is the f16 twin of `w`, same layout (conv2).  Only the kernels that conv_h16_pair_ok() probes implement them.
   //   probe: try_launch_* return 1 where they would launch, without launching.
   int out_f16 = 0, in_f16 = 0, probe = 0;
-  const uint16_t* w_f16 = nullptr;
+  const uint16_t* w_f16 = nullptr;   // [tap][32-channel chunk][CoutPad][32] IEEE f16 bits, round to nearest even
 };
 
 #if defined(__HIPCC__)
@@ -152,34 +148,12 @@ __device__ inline h16_u32x4 h16_silu8(h16_u32x4 x, const h16x2 (&a)[4], const h1
 #undef PRG_H16_TRANS4
 #endif
 
-// f16 twin of pack_conv_weight<bf16_t> (same [tap][32-channel chunk][CoutPad][32] layout, IEEE f16 bits, round to nearest even)
-void pack_conv_weight_f16(const float* w_oihw, int Cout, int Cin, int KH, int KW, std::vector<uint16_t>& out);
 // true when conv1 (L1, asked to store f16) and conv2 (L2, asked to read f16 through its folded prologue) of a ResnetBlock would both
 // run on kernels that implement the h16 format, L1 with fixed-point statistics; nothing is launched
 bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1, const ConvLaunch<bf16_t>& L2);
 
-// hi / lo f16 split of a conv weight for the f16x3 mode (layout at ConvLaunch::w_split)
-// oscale (may be null = no scaling): receives [CoutPad] exact powers of two the kernels multiply the float32 totals by — the
-// inverse of the per-output-channel scale the packer applied so that the lo halves stay normal f16 (ConvLaunch::split_scale)
-void pack_conv_weight_split(const float* w_oihw, int Cout, int Cin, int KH, int KW, std::vector<uint16_t>& out, int* CoutPad,
-                            int* kchunks32, std::vector<float>* oscale = nullptr);
 // f16x3 kernels: 1 = launched, 0 = shape not covered (the exact-f32 kernels run), < 0 = error
 int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsplit_out);
-
-// OIHW weights of the equivalent convolution described at ConvLaunch::w_s2d, from Conv2d(Cin, Cout, 4, 2, 1) weights
-void s2d_equivalent_weights(const float* w_oihw, int Cout, int Cin, std::vector<float>& out);
-// The four [Cout][Cin][2][2] tensors (phase-major) of ConvLaunch::w_up from Conv2d(Cin, Cout, 3, 1, 1) weights: for output sub-pixel
-// dy the kernel rows {0 | 1, 2} (dy = 0) or {0, 1 | 2} (dy = 1) fall on the two source rows of its window (summed in float64)
-void up_equivalent_weights(const float* w_oihw, int Cout, int Cin, std::vector<float>& out);
-
-// MX (OCP microscaling) fp8 packing of a conv weight: per (tap, output channel) the input channels are cut into blocks of
-// 32; block scale = 2^(floor(log2 max|w|) - 8) as an E8M0 byte (bias 127), elements = e4m3fn(w / scale), round to
-// nearest even, saturating at 448.  data: [tap][ceil(Cin/64)][CoutPad][64], scales: [tap][ceil(Cin/64)][CoutPad][2].
-void pack_conv_weight_mxfp8(const float* w_oihw, int Cout, int Cin, int KH, int KW, std::vector<uint8_t>& data,
-                            std::vector<uint8_t>& scales, int* CoutPad, int* chunks64);
-// host-side e4m3fn conversion used by the packer (and, through the debug entry, checked against the device's)
-uint8_t f32_to_e4m3(float v);
-float e4m3_to_f32(uint8_t b);
 
 // Returns PRG_OK; *gn_nsplit_out (may be null) receives the number of statistic slabs per image written, or 0
 // when statistics were requested but this shape cannot fuse them.  `allow_prologue` must be checked by the
@@ -205,11 +179,9 @@ inline double conv_flops(const ConvDesc& d) {
 // stem on MFMA (bf16 path, Cin 1 or 3 -> 64): fragments packed once by pack_stem_mfma_weights
 bool stem_conv_mfma_supported(int Cin, int Cout, int H, int W);
 int launch_stem_conv_mfma(const float* x, const bf16_t* wf, const float* bias, bf16_t* out, int B, int Cin, int H, int W, hipStream_t s);
-void pack_stem_mfma_weights(const float* w, int Cin, std::vector<bf16_t>& out);
 // f16x3 (round 5): the same kernel on f16 hi / lo halves with a float32 output; scale[64] = the inverse of the packer's per-channel power of two
 int launch_stem_conv_mfma_split(const float* x, const uint16_t* wf, const float* bias, const float* wscale, float* out, int B, int Cin,
                                 int H, int W, hipStream_t s);
-void pack_stem_mfma_weights_split(const float* w, int Cin, std::vector<uint16_t>& out, std::vector<float>& scale);
 template <typename T>
 int launch_stem_conv(const float* x, const float* wk, const float* bias, T* out, int B, int Cin, int H, int W,
                      int Cout, hipStream_t s);

@@ -959,141 +959,8 @@ int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int
   return launch_igemm<T, 128, 64>(L, M, s, want_stats, gn_nsplit_out);
 }
 
-void up_equivalent_weights(const float* w, int Cout, int Cin, std::vector<float>& out) {
-  out.assign((size_t)4 * Cout * Cin * 4, 0.0f);
-  // tap a of phase dy collects kernel rows ky with source row offset (dy + ky - 1 floor-div 2) - (dy - 1) == a
-  auto slot = [](int dphase, int k) { const int r = dphase + k - 1; return (r >= 0 ? r / 2 : -1) - (dphase - 1); };
-  for (int dy = 0; dy < 2; ++dy)
-    for (int dx = 0; dx < 2; ++dx)
-      for (int o = 0; o < Cout; ++o)
-        for (int c = 0; c < Cin; ++c) {
-          double acc[2][2] = {{0, 0}, {0, 0}};
-          for (int ky = 0; ky < 3; ++ky)
-            for (int kx = 0; kx < 3; ++kx) acc[slot(dy, ky)][slot(dx, kx)] += (double)w[(((size_t)o * Cin + c) * 3 + ky) * 3 + kx];
-          float* dst = out.data() + ((((size_t)(2 * dy + dx) * Cout + o) * Cin + c) * 4);
-          dst[0] = (float)acc[0][0]; dst[1] = (float)acc[0][1]; dst[2] = (float)acc[1][0]; dst[3] = (float)acc[1][1];
-        }
-}
-
-void s2d_equivalent_weights(const float* w, int Cout, int Cin, std::vector<float>& out) {
-  out.assign((size_t)Cout * 4 * Cin * 9, 0.0f);
-  for (int o = 0; o < Cout; ++o)
-    for (int c = 0; c < Cin; ++c)
-      for (int ky = 0; ky < 4; ++ky)
-        for (int kx = 0; kx < 4; ++kx) {
-          const int by = ky >> 1, dy = ky & 1, bx = kx >> 1, dx = kx & 1;
-          const int cv = (2 * dy + dx) * Cin + c;
-          out[(((size_t)o * 4 * Cin + cv) * 3 + 1 + by) * 3 + 1 + bx] = w[(((size_t)o * Cin + c) * 4 + ky) * 4 + kx];
-        }
-}
-
 template int launch_conv<float>(const ConvLaunch<float>&, hipStream_t, int*, int*);
 template int launch_conv<bf16_t>(const ConvLaunch<bf16_t>&, hipStream_t, int*, int*);
-
-// ---------------------------------------------------------------------------------------------
-// weight packing (host)
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-void pack_conv_weight(const float* w, int Cout, int Cin, int KH, int KW, std::vector<T>& out, int* CoutPad,
-                      int* kchunks) {
-  constexpr int BK = ConvTile<T>::BK;
-  const int cp = (Cout + 63) / 64 * 64;
-  const int kcn = (Cin + BK - 1) / BK;
-  out.assign((size_t)KH * KW * kcn * cp * BK, Elem<T>::store(0.0f));
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw)
-      for (int kc = 0; kc < kcn; ++kc)
-        for (int n = 0; n < Cout; ++n)
-          for (int k = 0; k < BK; ++k) {
-            int c = kc * BK + k;
-            if (c >= Cin) break;
-            float v = w[(((size_t)n * Cin + c) * KH + kh) * KW + kw];
-            out[((((size_t)(kh * KW + kw)) * kcn + kc) * cp + n) * BK + k] = Elem<T>::store(v);
-          }
-  *CoutPad = cp;
-  *kchunks = kcn;
-}
-template void pack_conv_weight<float>(const float*, int, int, int, int, std::vector<float>&, int*, int*);
-template void pack_conv_weight<bf16_t>(const float*, int, int, int, int, std::vector<bf16_t>&, int*, int*);
-
-void pack_conv_weight_f16(const float* w, int Cout, int Cin, int KH, int KW, std::vector<uint16_t>& out) {
-  constexpr int BK = 32;
-  const int cp = (Cout + 63) / 64 * 64;
-  const int kcn = (Cin + BK - 1) / BK;
-  out.assign((size_t)KH * KW * kcn * cp * BK, 0);
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw)
-      for (int kc = 0; kc < kcn; ++kc)
-        for (int n = 0; n < Cout; ++n)
-          for (int k = 0; k < BK; ++k) {
-            const int c = kc * BK + k;
-            if (c >= Cin) break;
-            const _Float16 h = (_Float16)w[(((size_t)n * Cin + c) * KH + kh) * KW + kw];   // round to nearest even
-            uint16_t bits;
-            std::memcpy(&bits, &h, 2);
-            out[((((size_t)(kh * KW + kw)) * kcn + kc) * cp + n) * BK + k] = bits;
-          }
-}
-
-// e4m3fn (OCP): 1-4-3, bias 7, max 448, no infinities; round to nearest even, saturating
-uint8_t f32_to_e4m3(float v) {
-  const uint8_t sign = std::signbit(v) ? 0x80 : 0;
-  float a = std::fabs(v);
-  if (!(a == a)) return sign | 0x7f;
-  if (a >= 448.0f) return sign | 0x7e;
-  if (a < 0.0009765625f) return sign;                       // < 2^-10: rounds to 0 (half of the smallest subnormal 2^-9, ties to even)
-  int e;
-  std::frexp(a, &e);                                         // a = m 2^e, m in [0.5, 1)
-  int E = e - 1;                                             // floor(log2 a)
-  if (E < -6) E = -6;                                        // subnormal range: fixed exponent, step 2^-9
-  const float step = std::ldexp(1.0f, E - 3);
-  float q = std::nearbyint(a / step);                        // round-half-even in the default rounding mode
-  float r = q * step;
-  if (r >= 448.0f) return sign | 0x7e;
-  if (r < 0.015625f) return sign | (uint8_t)q;               // subnormal: q in 0..7
-  int e2;
-  const float m2 = std::frexp(r, &e2);                       // r may have carried into the next binade
-  const int Eb = e2 - 1 + 7;
-  const int man = (int)std::nearbyint((m2 * 2.0f - 1.0f) * 8.0f);
-  return sign | (uint8_t)((Eb << 3) | man);
-}
-float e4m3_to_f32(uint8_t b) {
-  const int s = b >> 7, e = (b >> 3) & 15, m = b & 7;
-  const float x = e == 0 ? std::ldexp((float)m, -9) : std::ldexp(1.0f + m / 8.0f, e - 7);
-  return s ? -x : x;
-}
-
-void pack_conv_weight_mxfp8(const float* w, int Cout, int Cin, int KH, int KW, std::vector<uint8_t>& data,
-                            std::vector<uint8_t>& scales, int* CoutPad, int* chunks64) {
-  const int cp = (Cout + 63) / 64 * 64, kc = (Cin + 63) / 64;
-  data.assign((size_t)KH * KW * kc * cp * 64, 0);
-  scales.assign((size_t)KH * KW * kc * cp * 2, 0);
-  for (int tap = 0; tap < KH * KW; ++tap)
-    for (int c64 = 0; c64 < kc; ++c64)
-      for (int n = 0; n < Cout; ++n)
-        for (int blk = 0; blk < 2; ++blk) {
-          float v[32], am = 0.0f;
-          for (int k = 0; k < 32; ++k) {
-            const int c = c64 * 64 + blk * 32 + k;
-            v[k] = c < Cin ? w[((size_t)n * Cin + c) * KH * KW + tap] : 0.0f;
-            am = std::fmax(am, std::fabs(v[k]));
-          }
-          uint32_t bits;
-          std::memcpy(&bits, &am, 4);
-          const int E = (int)((bits >> 23) & 0xff);
-          const int S = E > 8 ? E - 8 : 0;
-          const float mult = std::ldexp(1.0f, 127 - S);
-          const size_t row = ((size_t)(tap * kc + c64) * cp + n);
-          scales[row * 2 + blk] = (uint8_t)S;
-          for (int k = 0; k < 32; ++k) {
-            float g = v[k] * mult;
-            g = g > 448.0f ? 448.0f : (g < -448.0f ? -448.0f : g);
-            data[row * 64 + blk * 32 + k] = f32_to_e4m3(g);
-          }
-        }
-  *CoutPad = cp;
-  *chunks64 = kc;
-}
 
 // ---------------------------------------------------------------------------------------------
 // stem: 7x7 pad 3 direct conv, float32 NCHW in (Cin 1 or 3) -> T NHWC out (sd:824 / dc:822)
@@ -1312,56 +1179,6 @@ int launch_stem_conv_mfma_split(const float* x, const uint16_t* wf, const float*
   else stem_mfma_kernel<3, true><<<dim3(W / 32, H / 8, B), 256, 0, s>>>(x, wf, bias, wscale, out, H, W);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
-}
-
-void pack_stem_mfma_weights(const float* w /* [64][Cin][7][7] */, int Cin, std::vector<bf16_t>& outv) {
-  outv.assign((size_t)Cin * 2 * 2 * 4 * 64 * 8, f32_to_bf16(0.0f));
-  for (int c = 0; c < Cin; ++c)
-    for (int rt = 0; rt < 2; ++rt)
-      for (int kk = 0; kk < 4; ++kk)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int co = rt * 32 + (lane & 31), kh = 2 * kk + (lane >> 5);
-          for (int j = 0; j < 7 && kh < 7; ++j) {
-            const float v = w[((size_t)co * Cin + c) * 49 + kh * 7 + j];
-            const bf16_t h16 = f32_to_bf16(v);
-            const bf16_t l16 = f32_to_bf16(v - bf16_to_f32(h16));
-            outv[(((((size_t)c * 2 + rt) * 2 + 0) * 4 + kk) * 64 + lane) * 8 + j] = h16;
-            outv[(((((size_t)c * 2 + rt) * 2 + 1) * 4 + kk) * 64 + lane) * 8 + j] = l16;
-          }
-        }
-}
-
-// f16 hi / lo halves of the same fragment layout; every output channel scaled by an exact power of two so that max|w| lands in
-// [2^9, 2^10) (the lo halves of ~1/7-sized weights would be subnormal f16 otherwise: conv_split.hip, pack_conv_weight_split);
-// scale[co] = the inverse
-void pack_stem_mfma_weights_split(const float* w /* [64][Cin][7][7] */, int Cin, std::vector<uint16_t>& outv, std::vector<float>& scale) {
-  outv.assign((size_t)Cin * 2 * 2 * 4 * 64 * 8, 0);
-  scale.assign(64, 1.0f);
-  std::vector<float> mul(64, 1.0f);
-  for (int co = 0; co < 64; ++co) {
-    float m = 0.0f;
-    for (int i = 0; i < Cin * 49; ++i) m = std::fmax(m, std::fabs(w[(size_t)co * Cin * 49 + i]));
-    if (m >= 0x1p-100f && std::isfinite(m)) {   // (a dead / denormal channel stays unscaled: 2^k would overflow, pack_conv_weight_split)
-      int e = 0;
-      (void)std::frexp(m, &e);
-      mul[co] = std::ldexp(1.0f, 10 - e);
-      scale[co] = std::ldexp(1.0f, e - 10);
-    }
-  }
-  auto bits = [](_Float16 h) { uint16_t u; std::memcpy(&u, &h, 2); return u; };
-  for (int c = 0; c < Cin; ++c)
-    for (int rt = 0; rt < 2; ++rt)
-      for (int kk = 0; kk < 4; ++kk)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int co = rt * 32 + (lane & 31), kh = 2 * kk + (lane >> 5);
-          for (int j = 0; j < 7 && kh < 7; ++j) {
-            const float v = w[((size_t)co * Cin + c) * 49 + kh * 7 + j] * mul[co];
-            const _Float16 h = (_Float16)v;
-            const _Float16 l = (_Float16)(v - (float)h);
-            outv[(((((size_t)c * 2 + rt) * 2 + 0) * 4 + kk) * 64 + lane) * 8 + j] = bits(h);
-            outv[(((((size_t)c * 2 + rt) * 2 + 1) * 4 + kk) * 64 + lane) * 8 + j] = bits(l);
-          }
-        }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1555,60 +1555,5 @@ int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsp
   return rc ? rc : 1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// weight packing (host): [tap][32-channel chunk][CoutPad][32 hi | 32 lo] as f16 bit patterns, zero padded
-// ---------------------------------------------------------------------------------------------
-static inline uint16_t f16_bits(_Float16 h) {
-  uint16_t u;
-  std::memcpy(&u, &h, 2);
-  return u;
-}
-void pack_conv_weight_split(const float* w, int Cout, int Cin, int KH, int KW, std::vector<uint16_t>& out, int* CoutPad, int* kchunks32,
-                            std::vector<float>* oscale) {
-  const int cp = (Cout + 63) / 64 * 64;
-  const int kcn = (Cin + 31) / 32;
-  out.assign((size_t)KH * KW * kcn * cp * 64, 0);
-  if (oscale) oscale->assign((size_t)cp, 1.0f);
-  // Round 5: |a - hi - lo| <= 2^-22 |a| only holds while the lo half is a NORMAL f16; below |a| ~ 2^-3 it is
-  // subnormal with an absolute floor of 2^-25, so unstandardised weights of ~1 / sqrt(fan_in) (res_conv, Downsample, Upsample:
-  // 0.02-0.1) kept 18-20 bits.  Each output channel's weights are therefore multiplied by an exact power of two that brings
-  // max|w| into [2^9, 2^10) (hi exact to 2^-2, lo's 2^-25 floor = 2^-35 of the maximum; |w| < 2^10 stays far from f16's 65504
-  // with O(100) activations in the other operand being a float32-accumulated product), and the kernels multiply the float32
-  // total by the inverse (exact) before the bias: split_scale.
-  std::vector<float> mul((size_t)Cout, 1.0f);
-  if (oscale) {
-    const size_t per = (size_t)Cin * KH * KW;
-    for (int n = 0; n < Cout; ++n) {
-      float m = 0.0f;
-      for (size_t i = 0; i < per; ++i) m = std::fmax(m, std::fabs(w[(size_t)n * per + i]));
-      // (m < 2^-100: a dead / denormal channel — 2^k would overflow to +inf and 0 * inf = NaN: left unscaled,
-      //  its halves flush to zero like the products they stand for)
-      if (m >= 0x1p-100f && std::isfinite(m)) {
-        int e = 0;
-        (void)std::frexp(m, &e);                 // m = f * 2^e, f in [0.5, 1)
-        const int k = 10 - e;                    // m * 2^k in [2^9, 2^10); |k| <= 110
-        mul[n] = std::ldexp(1.0f, k);
-        (*oscale)[n] = std::ldexp(1.0f, -k);
-      }
-    }
-  }
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw)
-      for (int kc = 0; kc < kcn; ++kc)
-        for (int n = 0; n < Cout; ++n)
-          for (int k = 0; k < 32; ++k) {
-            const int c = kc * 32 + k;
-            if (c >= Cin) break;
-            const float v = w[(((size_t)n * Cin + c) * KH + kh) * KW + kw] * mul[n];
-            const _Float16 h = (_Float16)v;                       // round to nearest even (compiler-rt / F16C)
-            const _Float16 l = (_Float16)(v - (float)h);
-            const size_t row = ((((size_t)(kh * KW + kw)) * kcn + kc) * cp + n) * 64;
-            out[row + k] = f16_bits(h);
-            out[row + 32 + k] = f16_bits(l);
-          }
-  *CoutPad = cp;
-  *kchunks32 = kcn;
-}
-
 }  // namespace prg
 

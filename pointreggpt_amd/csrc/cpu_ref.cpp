@@ -17,6 +17,12 @@
 
 #include "../../include/prg_cpu.h"
 #include "c64_schedule.h"
+#include "weights_host.h"   // the parameter layout and its walk, weight standardisation: shared with libprg_hip.so
+
+using prg::AttnP;
+using prg::ConvP;
+using prg::LevelP;
+using prg::ResP;
 
 namespace {
 
@@ -121,22 +127,6 @@ void conv2d(const float* in, int B, int Cin, int H, int W, const float* w, const
   }
 }
 
-// weight standardisation per output channel, biased variance, eps 1e-5 (sd:601-616)
-Vec standardize(const float* w, int Cout, int K) {
-  Vec o((size_t)Cout * K);
-  for (int c = 0; c < Cout; ++c) {
-    double m = 0;
-    for (int k = 0; k < K; ++k) m += w[(size_t)c * K + k];
-    m /= K;
-    double v = 0;
-    for (int k = 0; k < K; ++k) { const double d = w[(size_t)c * K + k] - m; v += d * d; }
-    v /= K;
-    const double rs = 1.0 / std::sqrt(v + 1e-5);
-    for (int k = 0; k < K; ++k) o[(size_t)c * K + k] = (float)((w[(size_t)c * K + k] - m) * rs);
-  }
-  return o;
-}
-
 inline float silu(float x) { return x / (1.0f + std::exp(-x)); }
 inline float gelu(float x) { return 0.5f * x * (1.0f + std::erf(x * 0.70710678118654752440f)); }
 
@@ -199,58 +189,16 @@ void linear(const float* x, int R, int I, const float* W, const float* b, int O,
 
 constexpr int kHeads = 4, kDh = 32, kHid = 128;
 
-// ------------------------------------------------------------------------------------------------------------------
-// parameter walk over the flat state dict (order of weights.param_spec / the reference's state_dict)
-// ------------------------------------------------------------------------------------------------------------------
-struct ConvP { int64_t w = -1, b = -1; int Cout = 0, Cin = 0, K = 0; };
-struct ResP { int cin = 0, cout = 0; int64_t mlp_w = -1, mlp_b = -1; ConvP c1, c2, res; int64_t g1 = 0, b1 = 0, g2 = 0, b2 = 0; bool has_res = false; };
-struct AttnP { int C = 0; bool linear = true; ConvP qkv, out; int64_t out_g = -1, norm_g = -1; };
-struct LevelP { ResP r0, r1; AttnP at; ConvP resample; bool strided = false; };
-struct Cursor {
-  int64_t pos = 0;
-  int64_t take(int64_t n) { const int64_t p = pos; pos += n; return p; }
-};
-void walk_conv(Cursor& c, ConvP& p, int Cout, int Cin, int K, bool bias) {
-  p.Cout = Cout; p.Cin = Cin; p.K = K;
-  p.w = c.take((int64_t)Cout * Cin * K * K);
-  p.b = bias ? c.take(Cout) : -1;
-}
-void walk_res(Cursor& c, ResP& r, int cin, int cout, bool cond, int emb) {
-  r.cin = cin; r.cout = cout;
-  if (cond) { r.mlp_w = c.take((int64_t)2 * cout * 2 * emb); r.mlp_b = c.take(2 * cout); }
-  walk_conv(c, r.c1, cout, cin, 3, true);
-  r.g1 = c.take(cout); r.b1 = c.take(cout);
-  walk_conv(c, r.c2, cout, cout, 3, true);
-  r.g2 = c.take(cout); r.b2 = c.take(cout);
-  r.has_res = cin != cout;
-  if (r.has_res) walk_conv(c, r.res, cout, cin, 1, true);
-}
-void walk_attn(Cursor& c, AttnP& a, int C, bool lin) {
-  a.C = C; a.linear = lin;
-  walk_conv(c, a.qkv, 3 * kHid, C, 1, false);
-  walk_conv(c, a.out, C, kHid, 1, true);
-  if (lin) a.out_g = c.take(C);
-  a.norm_g = c.take(C);
-}
-
 }  // namespace
 
-struct prg_cpu_unet {
-  prg_unet_config cfg;
-  int L = 0, emb = 0;
-  std::vector<int> dims;
-  int64_t stem_w = 0, stem_b = 0, tm1_w = 0, tm1_b = 0, tm3_w = 0, tm3_b = 0, pm0_w = 0, pm0_b = 0, pm2_w = 0, pm2_b = 0;
-  std::vector<LevelP> downs, ups;
-  ResP mid1, mid2, fin;
-  AttnP mid_at;
-  int64_t head_w = 0, head_b = 0, total = 0;
+struct prg_cpu_unet : prg::Layout {   // the parameter layout (prg::build_layout), plus:
   Vec flat;               // the state dict; the Block conv weights are standardised in place at create
   Vec freqs;              // SinusoidalPosEmb frequencies
 
   const float* F(int64_t o) const { return o < 0 ? nullptr : flat.data() + o; }
 
   void conv(const ConvP& p, const Vec& in, int B, int H, int W, int stride, int pad, int ups, Vec& out, int& Ho, int& Wo) const {
-    conv2d(in.data(), B, p.Cin, H, W, F(p.w), F(p.b), p.Cout, p.K, stride, pad, ups, out, Ho, Wo);
+    conv2d(in.data(), B, p.Cin, H, W, F(p.w_flat), F(p.b_off), p.Cout, p.KH, stride, pad, ups, out, Ho, Wo);
   }
 
   // ResnetBlock (sd:700-734 / dc:726-740): x (B,cin,H,W) -> (B,cout,H,W); cond (B, 2 emb) or null
@@ -360,7 +308,7 @@ struct prg_cpu_unet {
     Vec xin(x_in, x_in + (size_t)B * cfg.in_channels * S * S), x0, x;
     int H = S, ho, wo;
     ConvP stem;
-    stem.w = stem_w; stem.b = stem_b; stem.Cout = d0; stem.Cin = cfg.in_channels; stem.K = 7;
+    stem.w_flat = stem_w; stem.b_off = stem_b; stem.Cout = d0; stem.Cin = cfg.in_channels; stem.KH = 7;
     conv(stem, xin, B, S, S, 1, 3, 0, x0, ho, wo);
     x = x0;
     std::vector<std::pair<Vec, int>> skips;
@@ -411,7 +359,7 @@ struct prg_cpu_unet {
     Vec fr, y;
     resblock(fin, cat(x, d0, x0, d0, H * H), cond, B, H, H, fr);
     ConvP head;
-    head.w = head_w; head.b = head_b; head.Cout = 1; head.Cin = d0; head.K = 1;
+    head.w_flat = head_w; head.b_off = head_b; head.Cout = 1; head.Cin = d0; head.KH = 1;
     conv(head, fr, B, H, H, 1, 0, 0, y, ho, wo);
     for (size_t i = 0; i < y.size(); ++i) out[i] = cfg.sigmoid_out ? 1.0f / (1.0f + std::exp(-y[i])) : y[i];
     return PRG_OK;
@@ -442,59 +390,6 @@ struct prg_cpu_unet {
 };
 
 namespace {
-
-int build(prg_cpu_unet& u, const prg_unet_config& cfg) {
-  CPU_CHECK(cfg.dim >= 8 && cfg.dim % 8 == 0, "config: dim must be a multiple of 8");
-  CPU_CHECK(cfg.n_levels >= 1 && cfg.n_levels <= 8, "config: n_levels out of range");
-  CPU_CHECK(cfg.in_channels == 1 || cfg.in_channels == 3, "config: in_channels must be 1 or 3");
-  CPU_CHECK(cfg.groups >= 1 && cfg.groups <= 64, "config: groups out of range");
-  u.cfg = cfg;
-  u.L = cfg.n_levels;
-  u.emb = cfg.dim * 4;
-  u.dims.assign(1, cfg.dim);
-  for (int i = 0; i < cfg.n_levels; ++i) u.dims.push_back(cfg.dim * cfg.dim_mults[i]);
-  for (int d : u.dims) CPU_CHECK(d % cfg.groups == 0, "config: width not divisible by groups");
-  const bool cond = cfg.conditional != 0;
-  Cursor c;
-  const int d0 = cfg.dim, e = u.emb;
-  u.stem_w = c.take((int64_t)d0 * cfg.in_channels * 49);
-  u.stem_b = c.take(d0);
-  if (cond) {
-    u.tm1_w = c.take((int64_t)e * d0); u.tm1_b = c.take(e);
-    u.tm3_w = c.take((int64_t)e * e); u.tm3_b = c.take(e);
-    u.pm0_w = c.take((int64_t)e * cfg.param_cond_dim); u.pm0_b = c.take(e);
-    u.pm2_w = c.take((int64_t)e * e); u.pm2_b = c.take(e);
-  }
-  u.downs.resize(u.L);
-  u.ups.resize(u.L);
-  for (int i = 0; i < u.L; ++i) {
-    const int ci = u.dims[i], co = u.dims[i + 1];
-    LevelP& lv = u.downs[i];
-    walk_res(c, lv.r0, ci, ci, cond, e);
-    walk_res(c, lv.r1, ci, ci, cond, e);
-    walk_attn(c, lv.at, ci, true);
-    lv.strided = i != u.L - 1;
-    walk_conv(c, lv.resample, co, ci, lv.strided ? 4 : 3, true);
-  }
-  for (int i = 0; i < u.L; ++i) {
-    const int ci = u.dims[u.L - 1 - i], co = u.dims[u.L - i];
-    LevelP& lv = u.ups[i];
-    walk_res(c, lv.r0, co + ci, co, cond, e);
-    walk_res(c, lv.r1, co + ci, co, cond, e);
-    walk_attn(c, lv.at, co, true);
-    lv.strided = i != u.L - 1;
-    walk_conv(c, lv.resample, ci, co, 3, true);
-  }
-  const int mid = u.dims.back();
-  walk_res(c, u.mid1, mid, mid, cond, e);
-  walk_attn(c, u.mid_at, mid, false);
-  walk_res(c, u.mid2, mid, mid, cond, e);
-  walk_res(c, u.fin, 2 * d0, d0, cond, e);
-  u.head_w = c.take(d0);
-  u.head_b = c.take(1);
-  u.total = c.pos;
-  return PRG_OK;
-}
 
 // ---- Philox4x32-10, the device generator's counter layout (sampler.hip) ----
 // third counter word: the stream's name (sampler.h)
@@ -705,19 +600,19 @@ int prg_cpu_apply_mask(const float* prob, const float* depth, const uint8_t* hit
 int prg_cpu_unet_create(const prg_unet_config* cfg, const float* weights, int64_t n, prg_cpu_unet** out) {
   CPU_CHECK(cfg && weights && out, "prg_cpu_unet_create: null pointer");
   prg_cpu_unet* u = new prg_cpu_unet();
-  int rc = build(*u, *cfg);
+  std::string err;
+  int rc = prg::build_layout(*cfg, *u, err);
+  if (rc) rc = fail(rc, err);
   if (rc == PRG_OK && u->total != n)
     rc = fail(PRG_E_INVALID, "prg_cpu_unet_create: expected " + std::to_string(u->total) + " floats, got " + std::to_string(n));
   if (rc) { delete u; return rc; }
   u->flat.assign(weights, weights + n);
-  auto ws = [&](const ConvP& p) {       // Block.proj: standardised once (the reference does it every forward, sd:601-616)
-    Vec s = standardize(u->flat.data() + p.w, p.Cout, p.Cin * p.K * p.K);
-    std::memcpy(u->flat.data() + p.w, s.data(), sizeof(float) * s.size());
-  };
-  auto res = [&](const ResP& r) { ws(r.c1); ws(r.c2); };
-  for (auto& lv : u->downs) { res(lv.r0); res(lv.r1); }
-  for (auto& lv : u->ups) { res(lv.r0); res(lv.r1); }
-  res(u->mid1); res(u->mid2); res(u->fin);
+  Vec s;
+  prg::for_each_conv(*u, [&](const ConvP& p, prg::ConvRole) {   // Block.proj: standardised once (the reference does it every forward, sd:601-616)
+    if (!p.ws) return;
+    prg::standardize(u->flat.data() + p.w_flat, p.Cout, p.Cin * p.KH * p.KW, s);
+    std::memcpy(u->flat.data() + p.w_flat, s.data(), sizeof(float) * s.size());
+  });
   const int half = cfg->dim / 2;
   u->freqs.resize(half);
   const float stepf = -(float)(9.210340371976184 / (double)(half - 1));

@@ -792,7 +792,7 @@ int prg_device_info(char* name, size_t name_len, int* compute_units) {
 int64_t prg_unet_param_count(const prg_unet_config* cfg) {
   if (!cfg) return PRG_E_INVALID;
   Layout L;
-  if (build_layout(*cfg, L)) return PRG_E_INVALID;
+  if (build_layout_checked(*cfg, L)) return PRG_E_INVALID;
   return L.total;
 }
 

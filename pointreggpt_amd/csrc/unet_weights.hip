@@ -1,415 +1,189 @@
-// unet_weights.hip — host side of the U-Nets, load time: the state-dict walk (build_layout), the per-conv packer and the weight
-// arenas of a handle.  Weight standardisation is folded into the packed weights here, once per conv; every arena is appended in
-// the order of the one traversal (unet_layout.h) and uploaded into buffers the handle owns.
-#include <algorithm>
-#include <cmath>
-#include <type_traits>
-#include <utility>
-
+// unet_weights.hip — load time of a U-Net handle: read the switches, let weights_host.cpp build every arena as a host value,
+// upload each into a buffer the handle owns.  Also the two host-only hooks that expose that value to the tests.
 #include "unet_layout.h"
 
 namespace prg {
 
-// ---------------------------------------------------------------------------------------------
-// parameter walk
-// ---------------------------------------------------------------------------------------------
-struct Cursor {
-  int64_t pos = 0;
-  int64_t take(int64_t n) {
-    int64_t p = pos;
-    pos += n;
-    return p;
-  }
-};
+// the packer's row length (weights_host.h) is the kernels' K-chunk (conv.h): this unit sees both
+static_assert(kPackBK<float> == ConvTile<float>::BK && kPackBK<bf16_t> == ConvTile<bf16_t>::BK, "packer rows != kernel K-chunk");
 
-static void walk_conv(Cursor& c, ConvP& p, int Cout, int Cin, int K, bool bias, bool ws) {
-  p.Cout = Cout; p.Cin = Cin; p.KH = K; p.KW = K; p.ws = ws;
-  p.w_flat = c.take((int64_t)Cout * Cin * K * K);
-  p.b_off = bias ? c.take(Cout) : -1;
+// The switches weight preparation depends on.  PRG_SPLIT_UP2X2: the Upsample convs' sub-pixel packings of the f16x3 mode are off by
+// default (conv_split.hip: try_launch_conv_split); PRG_SPLIT_STEM=0: the direct fmaf stem kernel of the parity mode;
+// PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every fused attention block.
+static WeightOptions weight_options(bool split_up2x2, bool fused_attn, bool split_stem, bool la_kshift) {
+  WeightOptions o;
+  o.split_up2x2 = split_up2x2; o.fused_attn = fused_attn; o.split_stem = split_stem; o.la_kshift = la_kshift;
+  o.linattn_fused_supported = linattn_fused_supported;
+  o.resblock_tail_fused_supported = resblock_tail_fused_supported;
+  return o;
 }
-static void walk_res(Cursor& c, ResP& r, int cin, int cout, bool cond, int emb, int& ss_total) {
-  r.cin = cin; r.cout = cout;
-  if (cond) {
-    r.mlp_w = c.take((int64_t)2 * cout * 2 * emb);
-    r.mlp_b = c.take(2 * cout);
-    r.ss_off = ss_total;
-    ss_total += 2 * cout;
-  }
-  walk_conv(c, r.c1, cout, cin, 3, true, true);
-  r.g1 = c.take(cout); r.b1 = c.take(cout);
-  walk_conv(c, r.c2, cout, cout, 3, true, true);
-  r.g2 = c.take(cout); r.b2 = c.take(cout);
-  r.has_res = cin != cout;
-  if (r.has_res) walk_conv(c, r.res, cout, cin, 1, true, false);
-}
-static void walk_attn(Cursor& c, AttnP& a, int C, bool linear) {
-  a.C = C; a.linear = linear;
-  walk_conv(c, a.qkv, 3 * kHidden, C, 1, false, false);
-  walk_conv(c, a.out, C, kHidden, 1, true, false);
-  if (linear) a.out_g = c.take(C);
-  a.norm_g = c.take(C);
-}
-
-int build_layout(const prg_unet_config& cfg, Layout& L) {
-  PRG_CHECK(cfg.dim >= 8 && cfg.dim % 8 == 0, "config: dim must be a multiple of 8");
-  PRG_CHECK(cfg.n_levels >= 1 && cfg.n_levels <= 8, "config: n_levels out of range");
-  PRG_CHECK(cfg.in_channels == 1 || cfg.in_channels == 3, "config: in_channels must be 1 or 3");
-  PRG_CHECK(cfg.groups >= 1 && cfg.groups <= 64, "config: groups out of range");
-  L.cfg = cfg;
-  L.L = cfg.n_levels;
-  L.emb = cfg.dim * 4;
-  L.dims.assign(1, cfg.dim);
-  for (int i = 0; i < cfg.n_levels; ++i) {
-    PRG_CHECK(cfg.dim_mults[i] >= 1, "config: bad dim_mult");
-    L.dims.push_back(cfg.dim * cfg.dim_mults[i]);
-  }
-  for (size_t i = 0; i < L.dims.size(); ++i) PRG_CHECK(L.dims[i] % cfg.groups == 0, "config: width not divisible by groups");
-  for (size_t i = 0; i < L.dims.size(); ++i)
-    if (L.dims[i] > 1024)
-      return fail(PRG_E_INVALID, "config: dim * dim_mult = " + std::to_string(L.dims[i]) + " exceeds 1024 channels, the widest "
-                  "GroupNorm the coefficient kernels handle (gn_coeff_kernel / affine_silu_fold_kernel: four channels per thread)");
-  const bool cond = cfg.conditional != 0;
-  Cursor c;
-  const int d0 = cfg.dim, e = L.emb;
-  L.stem_w = c.take((int64_t)d0 * cfg.in_channels * 49);
-  L.stem_b = c.take(d0);
-  if (cond) {
-    L.tm1_w = c.take((int64_t)e * d0); L.tm1_b = c.take(e);
-    L.tm3_w = c.take((int64_t)e * e);  L.tm3_b = c.take(e);
-    L.pm0_w = c.take((int64_t)e * cfg.param_cond_dim); L.pm0_b = c.take(e);
-    L.pm2_w = c.take((int64_t)e * e);  L.pm2_b = c.take(e);
-  }
-  L.downs.resize(L.L);
-  L.ups.resize(L.L);
-  for (int i = 0; i < L.L; ++i) {
-    const int ci = L.dims[i], co = L.dims[i + 1];
-    LevelP& lv = L.downs[i];
-    walk_res(c, lv.r0, ci, ci, cond, e, L.ss_total);
-    walk_res(c, lv.r1, ci, ci, cond, e, L.ss_total);
-    walk_attn(c, lv.at, ci, true);
-    lv.strided = i != L.L - 1;
-    walk_conv(c, lv.resample, co, ci, lv.strided ? 4 : 3, true, false);
-  }
-  for (int i = 0; i < L.L; ++i) {
-    const int ci = L.dims[L.L - 1 - i], co = L.dims[L.L - i];
-    LevelP& lv = L.ups[i];
-    walk_res(c, lv.r0, co + ci, co, cond, e, L.ss_total);
-    walk_res(c, lv.r1, co + ci, co, cond, e, L.ss_total);
-    walk_attn(c, lv.at, co, true);
-    lv.strided = i != L.L - 1;  // here: "followed by x2 upsample"
-    walk_conv(c, lv.resample, ci, co, 3, true, false);
-  }
-  const int mid = L.dims.back();
-  walk_res(c, L.mid1, mid, mid, cond, e, L.ss_total);
-  walk_attn(c, L.mid_at, mid, false);
-  walk_res(c, L.mid2, mid, mid, cond, e, L.ss_total);
-  walk_res(c, L.fin, 2 * d0, d0, cond, e, L.ss_total);
-  L.head_w = c.take(d0);
-  L.head_b = c.take(1);
-  L.total = c.pos;
-  return PRG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// per-conv packing
-// ---------------------------------------------------------------------------------------------
-static void standardize(const float* w, int Cout, int K, std::vector<float>& out) {
-  out.resize((size_t)Cout * K);
-  for (int o = 0; o < Cout; ++o) {
-    double m = 0;
-    for (int k = 0; k < K; ++k) m += w[(size_t)o * K + k];
-    m /= K;
-    double v = 0;
-    for (int k = 0; k < K; ++k) { double d = w[(size_t)o * K + k] - m; v += d * d; }
-    v /= K;
-    const double rs = 1.0 / std::sqrt(v + 1e-5);
-    for (int k = 0; k < K; ++k) out[(size_t)o * K + k] = (float)((w[(size_t)o * K + k] - m) * rs);
-  }
-}
-
-template <typename T>
-PackedConv<T> pack_conv_host(const float* w, int Cout, int Cin, int K, int dtype, ConvRole role) {
-  constexpr bool bf16 = std::is_same<T, bf16_t>::value;
-  PackedConv<T> pk;
-  int cp = 0, kc = 0;
-  pack_conv_weight<T>(w, Cout, Cin, K, K, pk.main, &pk.CoutPad, &pk.kchunks);
-  if (bf16 && s2d_eligible(Cout, Cin, K)) {
-    std::vector<float> eq;
-    s2d_equivalent_weights(w, Cout, Cin, eq);
-    pack_conv_weight<T>(eq.data(), Cout, 4 * Cin, 3, 3, pk.s2d, &cp, &pk.s2d_kchunks);
-  }
-  if (dtype == PRG_MXFP8 && mx_eligible(Cout, Cin, K)) pack_conv_weight_mxfp8(w, Cout, Cin, 3, 3, pk.mx, pk.mx_scale, &cp, &kc);
-  if (bf16 && role.conv2 && h16_eligible(Cout, Cin, K)) pack_conv_weight_f16(w, Cout, Cin, 3, 3, pk.h16);
-  if (dtype == PRG_F16X3) pack_conv_weight_split(w, Cout, Cin, K, K, pk.split, &cp, &pk.split_kchunks, &pk.split_scale);
-  // Upsample convs: the four [Cout][Cin][2][2] tensors of the sub-pixel decomposition, packed phase after phase
-  const bool up = bf16 && role.upsample && up_eligible(Cout, Cin, K);
-  const bool up_split = dtype == PRG_F16X3 && role.upsample && up_split_eligible(Cout, Cin, K);
-  if (up || up_split) {
-    std::vector<float> eq, sc1;
-    std::vector<T> one;
-    std::vector<uint16_t> one_split;
-    up_equivalent_weights(w, Cout, Cin, eq);
-    for (int ph = 0; ph < 4; ++ph) {
-      const float* wp = eq.data() + (size_t)ph * Cout * Cin * 4;
-      if (up) {
-        pack_conv_weight<T>(wp, Cout, Cin, 2, 2, one, &cp, &kc);
-        pk.up.insert(pk.up.end(), one.begin(), one.end());
-      } else {
-        pack_conv_weight_split(wp, Cout, Cin, 2, 2, one_split, &cp, &kc, &sc1);
-        pk.up_split.insert(pk.up_split.end(), one_split.begin(), one_split.end());
-        pk.up_split_scale.insert(pk.up_split_scale.end(), sc1.begin(), sc1.end());     // [phase][CoutPad]
-      }
-    }
-  }
-  return pk;
-}
-template PackedConv<float> pack_conv_host<float>(const float*, int, int, int, int, ConvRole);
-template PackedConv<bf16_t> pack_conv_host<bf16_t>(const float*, int, int, int, int, ConvRole);
-
-// ---------------------------------------------------------------------------------------------
-// the weight arenas of a handle
-// ---------------------------------------------------------------------------------------------
-static bool fused_attention_enabled() {
-  static const int on = env_int("PRG_FUSED_ATTN", 1);
-  return on != 0;
-}
-// f16x3: the Upsample convs' sub-pixel packings are built only when the option is on — it is off by default
-// (conv_split.hip: try_launch_conv_split)
-static bool split_up2x2_enabled() {
-  static const int on = env_int("PRG_SPLIT_UP2X2", 0);
-  return on != 0;
-}
-
-// Every conv of the network through the packer.  Alignments: 128 elements (256-byte tiles of bf16) in the packed, h16 and split
-// arenas, 256 bytes for the MX data and scales.  The Upsample packings follow all the other packings of their arena.
-template <typename T>
-static int upload_convs(prg_unet& u, const float* weights, int dtype) {
-  std::vector<T> packed;
-  std::vector<uint8_t> mx, mx_scale;
-  std::vector<uint16_t> h16, split;
-  std::vector<float> split_scale, tmp;
-  std::vector<std::pair<ConvP*, PackedConv<T>>> upsample;
-  for_each_conv(u.lay, [&](ConvP& p, ConvRole role) {
-    const float* w = weights + p.w_flat;
-    if (p.ws) { standardize(w, p.Cout, p.Cin * p.KH * p.KW, tmp); w = tmp.data(); }
-    if (dtype == PRG_F16X3 && !split_up2x2_enabled()) role.upsample = false;
-    PackedConv<T> pk = pack_conv_host<T>(w, p.Cout, p.Cin, p.KH, dtype, role);
-    p.CoutPad = pk.CoutPad; p.kchunks = pk.kchunks;
-    p.w_off = append_aligned(packed, pk.main, 128);
-    if (!pk.s2d.empty()) { p.s2d_off = (int64_t)append_aligned(packed, pk.s2d, 128); p.s2d_kchunks = pk.s2d_kchunks; }
-    if (!pk.mx.empty()) {
-      p.mx_off = (int64_t)append_aligned(mx, pk.mx, 256);
-      p.mx_soff = (int64_t)append_aligned(mx_scale, pk.mx_scale, 256);
-    }
-    if (!pk.h16.empty()) p.h16_off = (int64_t)append_aligned(h16, pk.h16, 128);
-    if (!pk.split.empty()) {
-      p.sp_off = (int64_t)append_aligned(split, pk.split, 128);
-      p.sp_kchunks = pk.split_kchunks;
-      p.sp_scale_off = (int64_t)append_aligned(split_scale, pk.split_scale, 1);
-    }
-    if (!pk.up.empty() || !pk.up_split.empty()) upsample.emplace_back(&p, std::move(pk));
-  });
-  for (auto& pu : upsample) {
-    ConvP& p = *pu.first;
-    const PackedConv<T>& pk = pu.second;
-    if (!pk.up.empty()) p.up_off = (int64_t)append_aligned(packed, pk.up, 128);
-    if (!pk.up_split.empty()) {
-      p.up_sp_off = (int64_t)append_aligned(split, pk.up_split, 128);
-      p.up_sp_scale_off = (int64_t)append_aligned(split_scale, pk.up_split_scale, 1);
-    }
-  }
-  u.d_packed = u.own.upload(packed, "hipMalloc(packed weights)");
-  u.d_mx = u.own.upload(mx, "hipMalloc(MX-fp8 weights)");
-  u.d_mx_scale = u.own.upload(mx_scale, "hipMalloc(MX-fp8 weights)");
-  u.d_h16 = u.own.upload(h16, "hipMalloc(h16 weights)");
-  u.d_split_scale = u.own.upload(split_scale, "hipMalloc(split scales)");
-  u.d_split = u.own.upload(split, "hipMalloc(split weights)");
-  return u.own.rc;
-}
-
-// the direct stem kernel's [49 * Cin][dim] weights, and the fragments of the MFMA stem (bf16: Cin 1 / 3 -> 64; f16x3: the same as
-// f16 hi / lo halves — PRG_SPLIT_STEM=0: the direct fmaf kernel of the parity mode)
-static int upload_stems(prg_unet& u, const float* weights, int dtype) {
-  const Layout& L = u.lay;
-  std::vector<float> stem((size_t)49 * L.cfg.in_channels * L.cfg.dim);
-  for (int o = 0; o < L.cfg.dim; ++o)
-    for (int c = 0; c < L.cfg.in_channels; ++c)
-      for (int t = 0; t < 49; ++t)
-        stem[((size_t)t * L.cfg.in_channels + c) * L.cfg.dim + o] = weights[L.stem_w + ((size_t)o * L.cfg.in_channels + c) * 49 + t];
-  u.d_stem = u.own.upload(stem, "hipMalloc(stem weights)");
-  static const int split_stem_on = env_int("PRG_SPLIT_STEM", 1);
-  const bool mfma_shape = (L.cfg.in_channels == 1 || L.cfg.in_channels == 3) && L.cfg.dim == 64;
-  if ((dtype == PRG_BF16 || dtype == PRG_MXFP8) && mfma_shape) {
-    std::vector<bf16_t> sf;
-    pack_stem_mfma_weights(weights + L.stem_w, L.cfg.in_channels, sf);
-    u.d_stem_frag = u.own.upload(sf, "hipMalloc(stem fragments)");
-  }
-  if (dtype == PRG_F16X3 && split_stem_on && mfma_shape) {
-    std::vector<uint16_t> sf;
-    std::vector<float> sc;
-    pack_stem_mfma_weights_split(weights + L.stem_w, L.cfg.in_channels, sf, sc);
-    u.d_stem_split = u.own.upload(sf, "hipMalloc(split stem fragments)");
-    u.d_stem_split_scale = u.own.upload(sc, "hipMalloc(split stem scales)");
-  }
-  return u.own.rc;
-}
-
-// default frequency table: the reference's expression in float32 with this host's libm (the Python front-end
-// replaces it with torch's own evaluation, which is what the reference would compute on the same host)
-static int upload_time_freqs(prg_unet& u) {
-  const int half = u.lay.cfg.dim / 2;
-  std::vector<float> fr(half);
-  const float stepf = -(float)(9.210340371976184 / (double)(half - 1));
-  for (int i = 0; i < half; ++i) fr[i] = std::exp((float)i * stepf);
-  u.d_freqs = u.own.upload(fr, "hipMalloc(time frequencies)");
-  return u.own.rc;
-}
-
-// f16x3: fused linear attention (attn_split.hip): to_qkv with the PreNorm gain folded in (q and k rows times log2 e: both only ever
-// enter a softmax, evaluated with exp2) and to_out, each as f16 hi halves followed by the lo halves
-void pack_split_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, SplitAttnPack& p) {
-  auto f16bits = [](float v, uint16_t& h, uint16_t& l) {
-    const _Float16 a = (_Float16)v, b = (_Float16)(v - (float)a);
-    std::memcpy(&h, &a, 2);
-    std::memcpy(&l, &b, 2);
-  };
-  const size_t nq = (size_t)3 * kHidden * C;
-  p.qkv.assign(2 * nq, 0);
-  for (int o = 0; o < 3 * kHidden; ++o)
-    for (int c = 0; c < C; ++c) {
-      const float v = w_qkv[(size_t)o * C + c] * norm_g[c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f);
-      f16bits(v, p.qkv[(size_t)o * C + c], p.qkv[nq + (size_t)o * C + c]);
-    }
-  const size_t no = (size_t)C * kHidden;
-  p.out.assign(2 * no, 0);
-  for (size_t i = 0; i < no; ++i) f16bits(w_out[i], p.out[i], p.out[no + i]);
-}
-
-static int upload_split_attention(prg_unet& u, const float* weights) {
-  std::vector<uint16_t> aw;
-  SplitAttnPack one;
-  for_each_attn(u.lay, [&](AttnP& a) {
-    // mid_at is not linear; linattn_split_supported: C = 64 / 128 (the token count is checked per call)
-    if (!a.linear || (a.C != 64 && a.C != 128)) return;
-    pack_split_attention(weights + a.qkv.w_flat, weights + a.norm_g, weights + a.out.w_flat, a.C, one);
-    a.sp_qkv = (int64_t)append_aligned(aw, one.qkv, 64);
-    a.sp_out = (int64_t)append_aligned(aw, one.out, 64);
-  });
-  u.d_attn_split = u.own.upload(aw, "hipMalloc(split attention weights)");
-  return u.own.rc;
-}
-
-// bf16: fixed-point GroupNorm statistics (common.h, GnFold): P = gamma, Q = beta of every norm in 16-byte aligned rows (what
-// the unconditioned norms use directly) and the table cond_fold_kernel walks for the conditioned ones
-static int upload_norm_rows(prg_unet& u, const float* weights) {
-  std::vector<float> pq, row;
-  std::vector<CondFoldEntry> ent;
-  const bool conditional = u.lay.cfg.conditional != 0;
-  for_each_res(u.lay, [&](ResP& r) {
-    r.cpad = (r.cout + 3) & ~3;
-    auto put = [&](int64_t g_off, int64_t b_off) {
-      row.assign(2 * (size_t)r.cpad, 0.0f);
-      std::memcpy(row.data(), weights + g_off, sizeof(float) * r.cout);
-      std::memcpy(row.data() + r.cpad, weights + b_off, sizeof(float) * r.cout);
-      return (int64_t)append_aligned(pq, row, 1);
-    };
-    r.pq1 = put(r.g1, r.b1);
-    r.pq2 = put(r.g2, r.b2);
-    if (conditional) ent.push_back(CondFoldEntry{r.ss_off, r.cout, (long long)r.g1, (long long)r.b1});
-  });
-  u.d_pq_static = u.own.upload(pq, "hipMalloc(norm gains)");
-  u.d_cond_entries = u.own.upload(ent, "hipMalloc(cond entries)");
-  u.n_cond_entries = (int)ent.size();
-  return u.own.rc;
-}
-
-// bf16: fused linear attention (attn_fused.hip): to_qkv with the PreNorm gain folded in, to_out as is, both [out][in] bf16, and the
-// static softmax shifts
-void pack_fused_attention(const float* w_qkv, const float* norm_g, const float* w_out, int C, FusedAttnPack& p) {
-  p.qkv.clear();
-  for (int o = 0; o < 3 * kHidden; ++o)
-    for (int c = 0; c < C; ++c)
-      // q and k only ever enter a softmax: their rows carry log2(e), so the kernels exponentiate with a bare v_exp_f32
-      p.qkv.push_back(f32_to_bf16(w_qkv[(size_t)o * C + c] * norm_g[c] * (o < 2 * kHidden ? 1.4426950408889634f : 1.0f)));
-  // Softmax over pixels of k[n][d] = w_d . LN(x_n): a LayerNorm output has norm <= sqrt(C), so |k| <= ||w_d|| sqrt(C)
-  // (Cauchy-Schwarz; w_d = the bf16 weights the kernel multiplies with, 2 % slack for the bf16 rounding of LN(x)).
-  // exp(k - bound) >= exp(-2 bound): with bound <= 40 nothing underflows and the column maxima need not be measured.
-  // (k, hence the bound, in units of 1 / log2(e): the rows above are pre-scaled.)
-  p.ok = true;
-  for (int d = 0; d < kHidden; ++d) {
-    double n2 = 0;
-    for (int c = 0; c < C; ++c) {
-      const double w = bf16_to_f32(p.qkv[(size_t)(kHidden + d) * C + c]);
-      n2 += w * w;
-    }
-    p.shifts[d] = (float)(1.02 * std::sqrt(n2 * C));
-    p.ok = p.ok && p.shifts[d] <= 40.0f * 1.4426950408889634f;
-  }
-  // the same bound for the q rows (softmax over the 32 d of a head, per pixel): one shift per head
-  for (int h = 0; h < kHeads; ++h) {
-    double worst = 0;
-    for (int d = 0; d < kDimHead; ++d) {
-      double n2 = 0;
-      for (int c = 0; c < C; ++c) {
-        const double w = bf16_to_f32(p.qkv[(size_t)(h * kDimHead + d) * C + c]);
-        n2 += w * w;
-      }
-      worst = std::max(worst, 1.02 * std::sqrt(n2 * C));
-    }
-    p.shifts[kHidden + h] = (float)worst;
-    p.ok = p.ok && p.shifts[kHidden + h] <= 40.0f * 1.4426950408889634f;
-  }
-  p.out.clear();
-  for (int c = 0; c < C; ++c)
-    for (int j = 0; j < kHidden; ++j) p.out.push_back(f32_to_bf16(w_out[(size_t)c * kHidden + j]));
-}
-
-// bf16: the fused linear-attention blocks and the raw res_conv weights of the fused ResnetBlock tail.  64-element alignment, shifts
-// padded to 4 floats.
-static int upload_fused_attention(prg_unet& u, const float* weights) {
-  std::vector<bf16_t> aw, one;
-  std::vector<float> ks;
-  FusedAttnPack pk;
-  // PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every block
-  static const int kshift_on = env_int("PRG_LA_KSHIFT", 1);
-  for_each_attn(u.lay, [&](AttnP& a) {
-    if (!a.linear || !linattn_fused_supported(a.C)) return;   // (mid_at is not linear)
-    pack_fused_attention(weights + a.qkv.w_flat, weights + a.norm_g, weights + a.out.w_flat, a.C, pk);
-    a.fw_qkv = (int64_t)append_aligned(aw, pk.qkv, 64);
-    if (kshift_on != 0 && pk.ok) {
-      a.kshift = (int64_t)ks.size();
-      ks.insert(ks.end(), pk.shifts, pk.shifts + kHidden + kHeads);
-      ks.resize((ks.size() + 3) & ~(size_t)3);
-    }
-    a.fw_out = (int64_t)append_aligned(aw, pk.out, 1);
-  });
-  // fused ResnetBlock tail: raw res_conv weights [Cout][Cin] as bf16.  (has_res: the blocks of the up levels and the final one)
-  for_each_res(u.lay, [&](ResP& r) {
-    if (!r.has_res || r.res.b_off < 0 || !resblock_tail_fused_supported(r.cin / 2, r.cin - r.cin / 2, r.cout)) return;
-    one.clear();
-    for (size_t i = 0; i < (size_t)r.cout * r.cin; ++i) one.push_back(f32_to_bf16(weights[r.res.w_flat + i]));
-    r.fw_res = (int64_t)append_aligned(aw, one, 64);
-  });
-  u.d_attn = u.own.upload(aw, "hipMalloc(attention weights)");
-  u.d_kshift = u.own.upload(ks, "hipMalloc(softmax shifts)");
-  return u.own.rc;
+static const WeightOptions& env_weight_options() {
+  static const WeightOptions o = weight_options(env_int("PRG_SPLIT_UP2X2", 0) != 0, env_int("PRG_FUSED_ATTN", 1) != 0,
+                                                env_int("PRG_SPLIT_STEM", 1) != 0, env_int("PRG_LA_KSHIFT", 1) != 0);
+  return o;
 }
 
 int prepare_unet_weights(prg_unet& u, const prg_unet_config& cfg, const float* weights, int64_t n, int dtype) {
-  int rc = build_layout(cfg, u.lay);
+  // the kernels' limits first (the walk costs microseconds): a config they cannot run is refused before anything is packed
+  int rc = build_layout_checked(cfg, u.lay);
   if (rc) return rc;
   if (u.lay.total != n)
     return fail(PRG_E_INVALID, "prg_unet_create: expected " + std::to_string(u.lay.total) + " floats, got " + std::to_string(n));
-  const bool bf16 = dtype == PRG_BF16 || dtype == PRG_MXFP8;
-  u.d_flat = u.own.upload(weights, (size_t)n, "hipMalloc(flat weights)");
-  if ((rc = bf16 ? upload_convs<bf16_t>(u, weights, dtype) : upload_convs<float>(u, weights, dtype))) return rc;
-  if ((rc = upload_stems(u, weights, dtype))) return rc;
-  if ((rc = upload_time_freqs(u))) return rc;
-  if (dtype == PRG_F16X3 && (rc = upload_split_attention(u, weights))) return rc;
-  if (bf16 && (rc = upload_norm_rows(u, weights))) return rc;
-  if (bf16 && fused_attention_enabled() && (rc = upload_fused_attention(u, weights))) return rc;
+  DeviceBuffers& own = u.own;
+  u.d_flat = own.upload(weights, (size_t)n, "hipMalloc(flat weights)");   // (before the build, as ever: measured 2-5 ms faster than after)
+  UnetWeights w;
+  std::string err;
+  if ((rc = build_unet_weights(cfg, weights, n, dtype, env_weight_options(), w, err))) return fail(rc, err);
+  u.lay = w.lay;
+  // each host arena is given back as soon as it is on the device: held together they cost a few hundred MB of peak host memory
+  // and, measured, 10-20 ms of prg_unet_create
+  auto up = [&own](auto& v, const char* nomem) {
+    auto* p = own.upload(v, nomem);
+    std::decay_t<decltype(v)>().swap(v);
+    return p;
+  };
+  u.n_cond_entries = (int)w.cond_entries.size();
+  u.d_packed = w.packed_bf16.empty() ? (void*)up(w.packed_f32, "hipMalloc(packed weights)") : (void*)up(w.packed_bf16, "hipMalloc(packed weights)");
+  u.d_mx = up(w.mx, "hipMalloc(MX-fp8 weights)");
+  u.d_mx_scale = up(w.mx_scale, "hipMalloc(MX-fp8 weights)");
+  u.d_h16 = up(w.h16, "hipMalloc(h16 weights)");
+  u.d_split_scale = up(w.split_scale, "hipMalloc(split scales)");
+  u.d_split = up(w.split, "hipMalloc(split weights)");
+  u.d_stem = up(w.stem, "hipMalloc(stem weights)");
+  u.d_stem_frag = up(w.stem_frag, "hipMalloc(stem fragments)");
+  u.d_stem_split = up(w.stem_split, "hipMalloc(split stem fragments)");
+  u.d_stem_split_scale = up(w.stem_split_scale, "hipMalloc(split stem scales)");
+  u.d_freqs = up(w.freqs, "hipMalloc(time frequencies)");
+  u.d_attn_split = up(w.attn_split, "hipMalloc(split attention weights)");
+  u.d_pq_static = up(w.pq_static, "hipMalloc(norm gains)");
+  u.d_cond_entries = up(w.cond_entries, "hipMalloc(cond entries)");
+  u.d_attn = up(w.attn, "hipMalloc(attention weights)");
+  u.d_kshift = up(w.kshift, "hipMalloc(softmax shifts)");
+  if (own.rc) return own.rc;
   u.dtype = dtype;
   return PRG_OK;
 }
 
+// copies `bytes` of `src` behind a hook's (out, capacity, written) triple; out == null only reports the size
+static int hook_copy(const void* src, size_t bytes, void* out, int64_t capacity, int64_t* written, const char* who) {
+  if (written) *written = (int64_t)bytes;
+  if (!out) return PRG_OK;
+  if ((int64_t)bytes > capacity) return fail(PRG_E_INVALID, std::string(who) + ": output buffer too small");
+  if (bytes) std::memcpy(out, src, bytes);
+  return PRG_OK;
+}
+template <typename U>
+static int hook_copy(const std::vector<U>& v, void* out, int64_t capacity, int64_t* written, const char* who) {
+  return hook_copy(v.data(), v.size() * sizeof(U), out, capacity, written, who);
+}
+
+// every offset of the layout as int64: one row per conv, then per ResnetBlock, then per attention block, in traversal order
+static std::vector<int64_t> layout_rows(const Layout& L) {
+  std::vector<int64_t> r;
+  for_each_conv(L, [&](const ConvP& p, ConvRole role) {
+    r.insert(r.end(), {p.Cout, p.Cin, p.KH, p.KW, p.CoutPad, p.kchunks, (int64_t)p.w_off, p.b_off, p.w_flat, p.ws, p.mx_off, p.mx_soff,
+                       p.s2d_off, p.s2d_kchunks, p.sp_off, p.sp_kchunks, p.h16_off, p.up_off, p.sp_scale_off, p.up_sp_scale_off,
+                       p.up_sp_off, role.conv2, role.upsample});
+  });
+  for_each_res(L, [&](const ResP& p) { r.insert(r.end(), {p.cin, p.cout, p.ss_off, p.fw_res, p.pq1, p.pq2, p.cpad}); });
+  for_each_attn(L, [&](const AttnP& a) { r.insert(r.end(), {a.C, a.fw_qkv, a.fw_out, a.kshift, a.sp_qkv, a.sp_out}); });
+  return r;
+}
+
 }  // namespace prg
+
+using namespace prg;
+
+extern "C" {
+
+int prg_debug_weight_arena(const prg_unet_config* cfg, const float* weights, int64_t n_floats, int dtype, int options, int arena,
+                           void* out, int64_t capacity_bytes, int64_t* bytes) {
+  const char* who = "prg_debug_weight_arena";
+  PRG_CHECK(cfg && weights, "prg_debug_weight_arena: null pointer");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16 || dtype == PRG_MXFP8 || dtype == PRG_F16X3, "prg_debug_weight_arena: bad dtype");
+  UnetWeights w;
+  std::string err;
+  const WeightOptions opt = weight_options(options & PRG_WOPT_SPLIT_UP2X2, options & PRG_WOPT_FUSED_ATTN, options & PRG_WOPT_SPLIT_STEM,
+                                           options & PRG_WOPT_LA_KSHIFT);
+  const int rc = build_unet_weights(*cfg, weights, n_floats, dtype, opt, w, err);
+  if (rc) return fail(rc, err);
+  const std::vector<int64_t> rows = layout_rows(w.lay);
+  auto view = [&](int id) -> std::pair<const void*, size_t> {
+    auto of = [](const auto& v) { return std::pair<const void*, size_t>(v.data(), v.size() * sizeof(v[0])); };
+    switch (id) {
+      case PRG_ARENA_LAYOUT: return of(rows);
+      case PRG_ARENA_PACKED: return w.packed_bf16.empty() ? of(w.packed_f32) : of(w.packed_bf16);
+      case PRG_ARENA_MX: return of(w.mx);
+      case PRG_ARENA_MX_SCALE: return of(w.mx_scale);
+      case PRG_ARENA_H16: return of(w.h16);
+      case PRG_ARENA_SPLIT: return of(w.split);
+      case PRG_ARENA_SPLIT_SCALE: return of(w.split_scale);
+      case PRG_ARENA_STEM: return of(w.stem);
+      case PRG_ARENA_STEM_FRAG: return of(w.stem_frag);
+      case PRG_ARENA_STEM_SPLIT: return of(w.stem_split);
+      case PRG_ARENA_STEM_SPLIT_SCALE: return of(w.stem_split_scale);
+      case PRG_ARENA_FREQS: return of(w.freqs);
+      case PRG_ARENA_ATTN_SPLIT: return of(w.attn_split);
+      case PRG_ARENA_PQ_STATIC: return of(w.pq_static);
+      case PRG_ARENA_COND_ENTRIES: return of(w.cond_entries);
+      case PRG_ARENA_ATTN: return of(w.attn);
+      case PRG_ARENA_KSHIFT: return of(w.kshift);
+    }
+    return {nullptr, 0};
+  };
+  if (arena == PRG_ARENA_ALL) {   // every arena in id order, each behind its int64 byte count
+    std::vector<uint8_t> all;
+    for (int id = 0; id < PRG_ARENA_COUNT; ++id) {
+      const auto v = view(id);
+      const int64_t nb = (int64_t)v.second;
+      all.insert(all.end(), (const uint8_t*)&nb, (const uint8_t*)(&nb + 1));
+      all.insert(all.end(), (const uint8_t*)v.first, (const uint8_t*)v.first + v.second);
+    }
+    return hook_copy(all, out, capacity_bytes, bytes, who);
+  }
+  if (arena >= 0 && arena < PRG_ARENA_COUNT) {
+    const auto v = view(arena);
+    return hook_copy(v.first, v.second, out, capacity_bytes, bytes, who);
+  }
+  return fail(PRG_E_INVALID, "prg_debug_weight_arena: no such arena");
+}
+
+int prg_debug_pack_conv(const float* w, int Cout, int Cin, int K, int dtype, int role_bits, int packing, void* out,
+                        int64_t capacity_bytes, int64_t* bytes) {
+  const char* who = "prg_debug_pack_conv";
+  PRG_CHECK(w && Cout > 0 && Cin > 0 && K > 0, "prg_debug_pack_conv: bad arguments");
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16 || dtype == PRG_MXFP8 || dtype == PRG_F16X3, "prg_debug_pack_conv: bad dtype");
+  std::vector<float> eq;
+  if (packing == PRG_PACK_S2D_OIHW) {
+    PRG_CHECK(K == 4, "prg_debug_pack_conv: the space-to-depth form belongs to 4 x 4 convs");
+    s2d_equivalent_weights(w, Cout, Cin, eq);
+    return hook_copy(eq, out, capacity_bytes, bytes, who);
+  }
+  if (packing == PRG_PACK_UP_OIHW) {
+    PRG_CHECK(K == 3, "prg_debug_pack_conv: the sub-pixel form belongs to 3 x 3 convs");
+    up_equivalent_weights(w, Cout, Cin, eq);
+    return hook_copy(eq, out, capacity_bytes, bytes, who);
+  }
+  ConvRole role;
+  role.conv2 = (role_bits & PRG_ROLE_CONV2) != 0;
+  role.upsample = (role_bits & PRG_ROLE_UPSAMPLE) != 0;
+  auto pick = [&](const auto& pk) {
+    switch (packing) {
+      case PRG_PACK_MAIN: return hook_copy(pk.main, out, capacity_bytes, bytes, who);
+      case PRG_PACK_S2D: return hook_copy(pk.s2d, out, capacity_bytes, bytes, who);
+      case PRG_PACK_UP: return hook_copy(pk.up, out, capacity_bytes, bytes, who);
+      case PRG_PACK_MX: return hook_copy(pk.mx, out, capacity_bytes, bytes, who);
+      case PRG_PACK_MX_SCALE: return hook_copy(pk.mx_scale, out, capacity_bytes, bytes, who);
+      case PRG_PACK_H16: return hook_copy(pk.h16, out, capacity_bytes, bytes, who);
+      case PRG_PACK_SPLIT: return hook_copy(pk.split, out, capacity_bytes, bytes, who);
+      case PRG_PACK_SPLIT_SCALE: return hook_copy(pk.split_scale, out, capacity_bytes, bytes, who);
+      case PRG_PACK_UP_SPLIT: return hook_copy(pk.up_split, out, capacity_bytes, bytes, who);
+      case PRG_PACK_UP_SPLIT_SCALE: return hook_copy(pk.up_split_scale, out, capacity_bytes, bytes, who);
+    }
+    return fail(PRG_E_INVALID, "prg_debug_pack_conv: no such packing");
+  };
+  if (dtype == PRG_F32 || dtype == PRG_F16X3) return pick(pack_conv_host<float>(w, Cout, Cin, K, dtype, role));
+  return pick(pack_conv_host<bf16_t>(w, Cout, Cin, K, dtype, role));
+}
+
+}  // extern "C"

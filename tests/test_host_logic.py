@@ -258,7 +258,7 @@ def test_real_data_input_side(tmp_path, monkeypatch):
 
 
 def test_downsample_equals_two_by_two_taps_over_space_to_depth():
-    """The identity conv_w256.hip's Downsample mode rests on (csrc/conv.hip: s2d_equivalent_weights): Conv2d(C, Co, 4, 2, 1)
+    """The identity conv_w256.hip's Downsample mode rests on (csrc/weights_host.cpp: s2d_equivalent_weights): Conv2d(C, Co, 4, 2, 1)
     (sd:596-597) of x equals a 3x3 / pad 1 convolution, with only taps (1..2, 1..2) non-zero, of the space-to-depth view
     [4C, H/2, W/2] of x shifted by (1, 1) — virtual channel (2 dy + dx) C + c of block (y', x') is x[c, 2y'+dy-1, 2x'+dx-1]
     (zero outside), weight [co][(2 dy + dx) C + c][1 + by][1 + bx] = W[co][c][2 by + dy][2 bx + dx]."""
