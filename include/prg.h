@@ -472,6 +472,35 @@ typedef struct prg_conv_fused {
 } prg_conv_fused;
 int prg_debug_conv_fused(prg_conv_fused* args, void* stream);
 
+/* prg_debug_conv_choice: which kernel launch_conv would run for a convolution, and with what launch geometry: the library's own
+ * selection function on plain values.  HOST only, no device call: the CU count and the PRG_* switches are arguments.
+ *   query: PRG_CQ_COUNT int32 in the order of the enum below.  dtype = the handle's (PRG_F32 / PRG_F16X3: float storage, PRG_BF16 /
+ *   PRG_MXFP8: bf16 storage); then the conv descriptor; `present` = the PRG_CP_* bits of the launch's non-null pointers
+ *   (MX = w_mx and w_mx_scale; FOLD_ACC / FOLD_PQ = pro_fold.acc / pro_fold.P and Q); gn_groups; pro_fold's G and cpg; in_f16,
+ *   out_f16, mx_pure; num_cus; the twelve switches as PRG_CONV_WS, PRG_CONV_C64, PRG_CONV_W256, PRG_CONV_DOWN_W256,
+ *   PRG_CONV_W256MX, PRG_W256_MIN_TILES, PRG_UP2X2, PRG_H16, PRG_MX_PURE, PRG_SPLIT_UP2X2, PRG_SPLIT_P64, PRG_SPLIT_W512.
+ *   query2: NULL, or conv2 of a ResnetBlock whose conv1 is `query`: choice[PRG_CC_H16_PAIR] then answers whether the pair runs with
+ *   an f16 tensor between them (num_cus and the switches are read from `query`).
+ *   choice: PRG_CC_COUNT int32 (family 0 = no kernel takes the request); exec_scale: executed / algorithmic MACs (1 or 4 / 9).
+ * Descriptors launch_conv rejects (sizes <= 0, B Hout Wout >= 2^31, C0 / C1 not multiples of the 16-byte vector, CoutPad not a
+ * multiple of 64 or below Cout) fail with PRG_E_INVALID.                                                                         */
+enum {
+  PRG_CQ_DTYPE = 0, PRG_CQ_B, PRG_CQ_HIN, PRG_CQ_WIN, PRG_CQ_C0, PRG_CQ_C1, PRG_CQ_UPS, PRG_CQ_KH, PRG_CQ_KW, PRG_CQ_STRIDE, PRG_CQ_PAD,
+  PRG_CQ_HOUT, PRG_CQ_WOUT, PRG_CQ_COUT, PRG_CQ_COUTPAD, PRG_CQ_KCHUNKS, PRG_CQ_PRESENT, PRG_CQ_GN_GROUPS, PRG_CQ_FOLD_G,
+  PRG_CQ_FOLD_CPG, PRG_CQ_IN_F16, PRG_CQ_OUT_F16, PRG_CQ_MX_PURE, PRG_CQ_NUM_CUS, PRG_CQ_SWITCHES, PRG_CQ_COUNT = PRG_CQ_SWITCHES + 12
+};
+enum {
+  PRG_CP_BIAS = 1, PRG_CP_RESIDUAL = 2, PRG_CP_RES_A = 4, PRG_CP_PRO_A = 8, PRG_CP_GN_PARTIALS = 16, PRG_CP_GN_ACC = 32, PRG_CP_MX = 64,
+  PRG_CP_S2D = 128, PRG_CP_UP = 256, PRG_CP_SPLIT = 512, PRG_CP_UP_SPLIT = 1024, PRG_CP_F16 = 2048, PRG_CP_RES_FOLD_ACC = 4096,
+  PRG_CP_FOLD_ACC = 8192, PRG_CP_FOLD_PQ = 16384
+};
+enum {
+  PRG_CC_FAMILY = 0, PRG_CC_TH, PRG_CC_TW, PRG_CC_BM, PRG_CC_BN, PRG_CC_PRO, PRG_CC_MODE, PRG_CC_TILES_X, PRG_CC_TILES_Y, PRG_CC_TILES_N,
+  PRG_CC_GRID, PRG_CC_FUSE_STATS, PRG_CC_NSPLIT, PRG_CC_ACC_DONE, PRG_CC_FILL_TABLES, PRG_CC_IS_MX, PRG_CC_SUPPORTS_PROLOGUE,
+  PRG_CC_H16_PAIR, PRG_CC_COUNT
+};
+int prg_debug_conv_choice(const int32_t* query, const int32_t* query2, int32_t* choice, float* exec_scale);
+
 /* Kernel unit-test hooks: the GroupNorm passes and the conditioning kernels of blocks.hip, each alone through the launch function
  * the forward pass calls.  Every tensor is float32 DEVICE (int64 / int32 where said) and is copied or converted into buffers the
  * hook owns; the few HOST arguments are named.  Bad arguments fail with PRG_E_INVALID before any device call.  All synchronise.

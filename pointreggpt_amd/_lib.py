@@ -100,6 +100,7 @@ PROTOTYPES = {
     "prg_debug_linear_attention_block": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(_I), _P]),
     "prg_debug_resblock_tail": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "prg_debug_conv_fused": (C.c_int, [C.POINTER(ConvFusedC), _P]),
+    "prg_debug_conv_choice": (C.c_int, [_P, _P, _P, _P]),
     "prg_debug_gn_stats": (C.c_int, [_P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _P]),
     "prg_debug_gn_coeff": (C.c_int, [_P, _I, _P, _P, _P, _L, _L, _P, _L, _L, C.POINTER(_I), _L, _P, _P, _I, _I, _I, _I, _P]),
     "prg_debug_gn_fold": (C.c_int, [C.POINTER(GnFoldC), _P]),

@@ -9,6 +9,7 @@
 
 #include "../../include/prg.h"
 #include "bf16.h"   // bf16_t, bf16_to_f32, f32_to_bf16 (shared with the host-only weight preparation)
+#include "conv_choose.h"   // kGnMaxSplit (shared with the host-only conv selection)
 
 namespace prg {
 
@@ -132,7 +133,7 @@ inline int env_int(const char* name, int dflt) {
   return e ? std::atoi(e) : dflt;
 }
 
-constexpr int kGnMaxSplit = 1024;  // max GroupNorm (sum, sumsq) partial slabs per image (256x256: 8x32 tiles x 4 wave rows)
+// kGnMaxSplit (max GroupNorm partial slabs per image) lives in conv_choose.h, which the host-only conv selection compiles without HIP
 
 // GroupNorm parameters of one Block (+ the ResnetBlock conditioning): what folds the statistics into y = x * A + B
 struct GnApply {

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "conv_choose.h"   // ConvDesc, ConvFacts, ConvChoice: the host-only selection
 
 namespace prg {
 
@@ -11,16 +12,6 @@ namespace prg {
 template <typename T>
 struct ConvTile {
   static constexpr int BK = 64 / (int)sizeof(T);  // bf16: 32, f32: 16
-};
-
-struct ConvDesc {
-  int B, Hin, Win;          // source tensors' spatial size (before the optional x2 nearest upsample)
-  int C0, C1;               // channels of src0 / src1 (virtual concat [src0, src1]); C1 = 0 when unused
-  int ups;                  // 1: conv runs on the 2x nearest-upsampled image (Upsample, sd:592-594)
-  int KH, KW, stride, pad;
-  int Hout, Wout;
-  int Cout, CoutPad;        // CoutPad = Cout rounded up to 64: packed weight rows (zeros beyond Cout)
-  int kchunks;              // ceil((C0+C1) / BK)
 };
 
 // Every weight pointer below is a packing that weights_host.cpp builds (pack_conv_host).
@@ -94,9 +85,9 @@ struct ConvLaunch {
   // v_rcp_f16: two channels per instruction, no unpack / repack) and conv2 contracts f16 operands
   // (v_mfma_f32_32x32x16_f16, the bf16 instruction's rate) against an f16 packing of its weights.
   //   out_f16: this launch stores f16 bit patterns into `out` (conv1);  in_f16: src0 holds f16, the prologue is pro_fold's and
-  //   w_f16 is the f16 twin of `w`, same layout (conv2).  Only the kernels that conv_h16_pair_ok() probes implement them.
-  //   probe: try_launch_* return 1 where they would launch, without launching.
-  int out_f16 = 0, in_f16 = 0, probe = 0;
+  //   w_f16 is the f16 twin of `w`, same layout (conv2).  Only the kernels that conv_h16_pair_ok() accepts implement them.
+  int out_f16 = 0, in_f16 = 0;
+  int reserved = 0;      // unused (was a host-side probe flag): the struct is a kernel argument, its size and offsets are kept
   const uint16_t* w_f16 = nullptr;   // [tap][32-channel chunk][CoutPad][32] IEEE f16 bits, round to nearest even
 };
 
@@ -148,28 +139,94 @@ __device__ inline h16_u32x4 h16_silu8(h16_u32x4 x, const h16x2 (&a)[4], const h1
 #undef PRG_H16_TRANS4
 #endif
 
+// what the selection (conv_choose.h) reads of a launch
+template <typename T>
+inline ConvFacts conv_facts(const ConvLaunch<T>& L) {
+  ConvFacts f{};
+  f.d = L.d;
+  f.f32 = sizeof(T) == 4;
+  f.bias = L.bias != nullptr; f.residual = L.residual != nullptr; f.res_a = L.res_a != nullptr; f.pro_a = L.pro_a != nullptr;
+  f.gn_partials = L.gn_partials != nullptr; f.gn_acc = L.gn_acc != nullptr; f.w_mx = L.w_mx && L.w_mx_scale;
+  f.w_s2d = L.w_s2d != nullptr; f.w_up = L.w_up != nullptr; f.w_split = L.w_split != nullptr;
+  f.w_up_split = L.w_up_split != nullptr; f.w_f16 = L.w_f16 != nullptr;
+  f.res_fold_acc = L.res_fold.acc != nullptr;
+  f.gn_groups = L.gn_groups;
+  f.pro_fold_acc = L.pro_fold.acc != nullptr; f.pro_fold_pq = L.pro_fold.P && L.pro_fold.Q;
+  f.pro_fold_G = L.pro_fold.G; f.pro_fold_cpg = L.pro_fold.cpg;
+  f.in_f16 = L.in_f16; f.out_f16 = L.out_f16; f.mx_pure = L.mx_pure;
+  return f;
+}
+
+// the PRG_* switches of the selection, read from the environment once
+const ConvSwitches& conv_switches();
+
 // true when conv1 (L1, asked to store f16) and conv2 (L2, asked to read f16 through its folded prologue) of a ResnetBlock would both
 // run on kernels that implement the h16 format, L1 with fixed-point statistics; nothing is launched
 bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1, const ConvLaunch<bf16_t>& L2);
 
-// f16x3 kernels: 1 = launched, 0 = shape not covered (the exact-f32 kernels run), < 0 = error
-int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsplit_out);
-
 // Returns PRG_OK; *gn_nsplit_out (may be null) receives the number of statistic slabs per image written, or 0
-// when statistics were requested but this shape cannot fuse them.  `allow_prologue` must be checked by the
-// caller with conv_supports_prologue() before setting pro_a / pro_b.
+// when statistics were requested but this shape cannot fuse them; *acc_done (may be null) 1 when they went to gn_acc instead;
+// *chosen (may be null) what ran.  `allow_prologue` must be checked by the caller with conv_supports_prologue() before setting
+// pro_a / pro_b.
 template <typename T>
-int launch_conv(const ConvLaunch<T>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done = nullptr);
+int launch_conv(const ConvLaunch<T>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done = nullptr, ConvChoice* chosen = nullptr);
 
-// true when the 3x3 halo kernel will run this conv (so a fused input prologue is available)
+// The families' launchers: each owns the table of its instantiations (kernel, dynamic LDS bytes) and launches the one `c` names,
+// with the geometry `c` holds.  launch_conv is their only caller.
+int launch_conv_c64(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s);          // conv_c64.hip
+int launch_conv_ws(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s);           // conv_ws.hip
+int launch_conv_w256(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s);         // conv_w256.hip (kConvW256, kConvW256Mx)
+int launch_conv_split(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s);         // conv_split.hip (the kConvSplit* families)
+int launch_conv_split_w512(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s);    // conv_split512.hip
+
+#if defined(__HIPCC__)
+// One instantiation in a family's table: the template parameters as a key, the kernel, its workgroup size and dynamic LDS bytes, and
+// the MaxDynamicSharedMemorySize opt-in it needs (0 = none).  The same row serves the one-time hipFuncSetAttribute (per device:
+// DeviceOnce is atomic, lanes launch from several host threads) and the launch.
+template <typename Fn>
+struct ConvKernel {
+  int key;
+  Fn fn;
+  int block;
+  size_t lds;
+  int lds_attr;
+  DeviceOnce attr;
+};
+constexpr int conv_key(int a, int b = 0, int c = 0, int d = 0) { return ((a * 512 + b) * 512 + c) * 8 + d; }
+// the kernels that take (L, tiles_x, tiles_y, tiles_n, fuse_stats)
 template <typename T>
-bool conv_supports_prologue(const ConvDesc& d);
+using ConvTileKernel = void (*)(const ConvLaunch<T>, int, int, int, int);
 
-// executed / algorithmic MAC ratio of the calling thread's last launch_conv: 1, or 4 / 9 when an Upsample conv ran as four
-// 2 x 2-tap sub-pixel convolutions (conv_w256.hip MODE 2) — conv_flops() below is the ALGORITHMIC count (the reference's op)
-double conv_last_exec_scale();
-int conv_last_was_mx();
+template <typename Fn, size_t N>
+inline int conv_kernel_find(ConvKernel<Fn> (&tab)[N], int key, const char* family, ConvKernel<Fn>** out) {
+  for (ConvKernel<Fn>& e : tab) {
+    if (e.key != key) continue;
+    if (e.lds_attr && !e.attr.done()) {
+      hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(e.fn), hipFuncAttributeMaxDynamicSharedMemorySize, e.lds_attr);
+      if (err != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(") + family + "): " + hipGetErrorString(err));
+      e.attr.mark();
+    }
+    *out = &e;
+    return PRG_OK;
+  }
+  return fail(PRG_E_STATE, std::string(family) + ": the selection named an instantiation this family does not have");
+}
+template <typename T, size_t N>
+inline int launch_conv_tiles(ConvKernel<ConvTileKernel<T>> (&tab)[N], int key, const char* family, const ConvChoice& c,
+                             const ConvLaunch<T>& L, hipStream_t s) {
+  ConvKernel<ConvTileKernel<T>>* e = nullptr;
+  if (int rc = conv_kernel_find(tab, key, family, &e)) return rc;
+  e->fn<<<dim3(c.grid), e->block, e->lds, s>>>(L, c.tiles_x, c.tiles_y, c.tiles_n, c.fuse_stats);
+  PRG_LAUNCH_CHECK();
+  return PRG_OK;
+}
+#endif
 
+// true when a single-source conv of this shape takes a fused input prologue (asked of the selection)
+template <typename T>
+inline bool conv_supports_prologue(const ConvDesc& d) { return choose_supports_prologue(d, sizeof(T) == 4); }
+
+// conv_flops() is the ALGORITHMIC count (the reference's op); ConvChoice::exec_scale of the launch gives the executed share
 inline double conv_flops(const ConvDesc& d) {
   return 2.0 * (double)d.B * d.Hout * d.Wout * d.Cout * (double)(d.C0 + d.C1) * d.KH * d.KW;
 }

@@ -711,256 +711,139 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 1 : 2) void conv_igemm_kernel
 // launch
 // ---------------------------------------------------------------------------------------------
 
+// dynamic LDS of the generic kernels: their staging buffers, at least the shared epilogue's scratch
+constexpr size_t staging_lds(size_t bytes) { return bytes < kEpilogueLds ? kEpilogueLds : bytes; }
+
+// conv3x3_halo_kernel<T, TH, TW, BN>: the four tiles pick_halo (conv_choose.cpp) hands out
 template <typename T>
-struct HaloPick {
-  int TH, TW, BN;
-};
-template <typename T>
-static bool pick_halo(const ConvDesc& d, HaloPick<T>* p) {
-  constexpr int CH = 8 * Elem<T>::kVec;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return false;
-  if (d.C0 % CH || d.C1 % CH || d.Cout % 64) return false;
-  const int H = d.Hout, W = d.Wout;
-  if (d.Cout % 128 == 0) {
-    if (W % 32 == 0 && H % 4 == 0) { *p = {4, 32, 128}; return true; }
-    if (W % 16 == 0 && H % 8 == 0) { *p = {8, 16, 128}; return true; }
-    return false;
-  }
-  if (W % 32 == 0 && H % 8 == 0) { *p = {8, 32, 64}; return true; }
-  if (W % 16 == 0 && H % 8 == 0) { *p = {8, 16, 64}; return true; }
-  return false;
+static int launch_conv_halo(const ConvChoice& c, const ConvLaunch<T>& L, hipStream_t s) {
+#define PRG_HALO(TH, TW, BN) \
+  {conv_key(TH, TW, BN), &conv3x3_halo_kernel<T, TH, TW, BN>, 256, staging_lds((size_t)((TH + 2) * (TW + 2) * 8 + 2 * BN * 8) * 16), 0}
+  static ConvKernel<ConvTileKernel<T>> tab[] = {PRG_HALO(8, 32, 64), PRG_HALO(4, 32, 128), PRG_HALO(8, 16, 128), PRG_HALO(8, 16, 64)};
+#undef PRG_HALO
+  return launch_conv_tiles(tab, conv_key(c.th, c.tw, c.bn), "halo conv", c, L, s);
+}
+// conv3x3_mx_kernel<TH, TW, BN>: MX-fp8 operands on the same tiles (PRG_MX_PURE)
+static int launch_conv_mx_halo(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s) {
+#define PRG_MX(TH, TW, BN)                                                                                                              \
+  {conv_key(TH, TW, BN), &conv3x3_mx_kernel<TH, TW, BN>, 256,                                                                           \
+   staging_lds((size_t)(TH + 2) * (TW + 2) * 80 + (size_t)2 * BN * 80 + (((TH + 2) * (TW + 2) * 2 + 15) & ~15) + 2 * BN * 2 + 16), 0}
+  static ConvKernel<ConvTileKernel<bf16_t>> tab[] = {PRG_MX(8, 32, 64), PRG_MX(4, 32, 128), PRG_MX(8, 16, 128), PRG_MX(8, 16, 64)};
+#undef PRG_MX
+  return launch_conv_tiles(tab, conv_key(c.th, c.tw, c.bn), "mx halo conv", c, L, s);
 }
 
+// conv_igemm_kernel<T, BM, BN, ONE>; mode = ONE (1x1, stride 1, no padding: the gather is a plain row read)
 template <typename T>
-bool conv_supports_prologue(const ConvDesc& d) {
-  HaloPick<T> p;
-  return d.C1 == 0 && pick_halo<T>(d, &p);
-}
-template bool conv_supports_prologue<float>(const ConvDesc&);
-template bool conv_supports_prologue<bf16_t>(const ConvDesc&);
-
-template <typename T, int TH, int TW, int BN>
-static int launch_halo(const ConvLaunch<T>& L, hipStream_t s, int fuse_stats, int* nsplit) {
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / TW, tiles_y = d.Hout / TH, tiles_n = d.Cout / BN;
-  constexpr int HALO = (TH + 2) * (TW + 2);
-  size_t lds = (size_t)(HALO * 8 + 2 * BN * 8) * 16;
-  if (lds < kEpilogueLds) lds = kEpilogueLds;
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y : 0;
-  conv3x3_halo_kernel<T, TH, TW, BN><<<dim3(tiles_x * tiles_y * tiles_n * d.B), 256, lds, s>>>(L, tiles_x, tiles_y,
-                                                                                            tiles_n, fuse_stats);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-template <typename T, int BM, int BN>
-static int launch_igemm(const ConvLaunch<T>& L, int M, hipStream_t s, int want_stats, int* nsplit) {
+static int launch_conv_igemm(const ConvChoice& c, const ConvLaunch<T>& L, hipStream_t s) {
+  using Fn = void (*)(const ConvLaunch<T>, int, int, int, int, int);   // (L, M, tiles_m, tiles_n, fuse_stats, wide)
   constexpr int UPR = ConvTile<T>::BK / Elem<T>::kVec;
-  const ConvDesc& d = L.d;
-  const int tiles_m = ceil_div(M, BM), tiles_n = d.CoutPad / BN;
-  const int HWo = d.Hout * d.Wout;
-  const int wide = d.Cout % 8 == 0;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int fuse = want_stats && wide && cpg % 8 == 0 && cpg <= BN && HWo % BM == 0 && HWo / BM <= kGnMaxSplit;
-  if (nsplit) *nsplit = fuse ? HWo / BM : 0;
-  size_t lds = (size_t)2 * (BM + BN) * UPR * 16;
-  if (lds < kEpilogueLds) lds = kEpilogueLds;
-  const bool one = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ups;
-  if (one) conv_igemm_kernel<T, BM, BN, true><<<dim3(tiles_m * tiles_n), 256, lds, s>>>(L, M, tiles_m, tiles_n, fuse, wide);
-  else conv_igemm_kernel<T, BM, BN, false><<<dim3(tiles_m * tiles_n), 256, lds, s>>>(L, M, tiles_m, tiles_n, fuse, wide);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-template <int TH, int TW, int BN>
-static int launch_mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int fuse_stats, int* nsplit) {
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / TW, tiles_y = d.Hout / TH, tiles_n = d.Cout / BN;
-  constexpr int HALO = (TH + 2) * (TW + 2);
-  size_t lds = (size_t)HALO * 80 + (size_t)2 * BN * 80 + ((HALO * 2 + 15) & ~15) + 2 * BN * 2 + 16;
-  if (lds < kEpilogueLds) lds = kEpilogueLds;
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y : 0;
-  conv3x3_mx_kernel<TH, TW, BN><<<dim3(tiles_x * tiles_y * tiles_n * d.B), 256, lds, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-// MX-fp8 operands: 1 = launched, 0 = shape not covered (bf16 kernels run instead)
-int try_launch_conv3x3_w256mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);   // conv_w256.hip
-// executed / algorithmic MAC ratio of this thread's last launch_conv (1 except for the sub-pixel Upsample form: 4 / 9)
-static thread_local double g_last_exec_scale = 1.0;
-double conv_last_exec_scale() { return g_last_exec_scale; }
-// 1 when this thread's last launch_conv ran on MX-fp8 operands (v_mfma_scale_f32_32x32x64_f8f6f4); bench.py configs4.mx_flop_fraction
-static thread_local int g_last_mx = 0;
-int conv_last_was_mx() { return g_last_mx; }
-
-// Consumers without the in-kernel GroupNorm fold (common.h, GnFold): fill the pro_a / pro_b tables from the accumulators
-// with one small launch, then run on the tables as before.
-int materialize_prologue(ConvLaunch<bf16_t>& L, hipStream_t s) {
-  if (!L.pro_fold.acc) return PRG_OK;
-  PRG_CHECK(L.pro_a && L.pro_b, "conv: pro_fold needs scratch coefficient tables in pro_a / pro_b");
-  const int rc = launch_gn_coeff_acc(L.pro_fold, const_cast<float*>(L.pro_a), const_cast<float*>(L.pro_b), L.d.B, L.d.C0, s);
-  L.pro_fold.acc = nullptr;
-  return rc;
-}
-static int materialize_prologue(ConvLaunch<float>&, hipStream_t) { return PRG_OK; }
-
-static int mx_pure_env() {
-  static const int pure = env_int("PRG_MX_PURE", 0);
-  return pure;
-}
-int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                     // conv_w256.hip
-static int try_mx(ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  if (!L.w_mx || !L.w_mx_scale) return 0;
-  // Round 5: the wide Upsample convs of an mxfp8 handle run the bf16 SUB-PIXEL form (four 2 x 2-tap convolutions, 4 / 9 of the MACs:
-  // 64-67 us at the configs[4] shape) — the nine-tap MX launch took 77-81 us (same box, same positions:
-  // profiles/r05_configs4_conv_per_launch_bf16_vs_mxfp8.txt); mx_pure keeps them on MX operands
-  if (L.d.ups && !L.gn_partials && !L.mx_pure && !mx_pure_env()) {
-    const int r = try_launch_conv3x3_up_w256(L, s);
-    if (r == 1) g_last_exec_scale = 4.0 / 9.0;
-    if (r != 0) return r;
-  }
-  {
-    const int r = try_launch_conv3x3_w256mx(L, s, gn_nsplit_out, acc_done);   // 256-pixel x 128-channel tiles with MX operands
-    if (r == 1) g_last_mx = 1;
-    if (r != 0) return r;
-  }
-  // Shapes the 256-pixel MX kernel does not cover (the 64-channel convs, launches with few tiles): by default the bf16
-  // kernels run them (those shapes are HBM- / VALU-bound: fp8 operands buy nothing there); PRG_MX_PURE=1 keeps every 3x3
-  // conv on MX operands through the simple halo-tile kernel below.
-  if (!mx_pure_env() && !L.mx_pure) return 0;
-  const ConvDesc& d = L.d;
-  HaloPick<bf16_t> hp;
-  if (!pick_halo<bf16_t>(d, &hp) || L.residual) return 0;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int tiles = (d.Wout / hp.TW) * (d.Hout / hp.TH);
-  const int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= hp.BN && tiles <= kGnMaxSplit;
+#define PRG_IGEMM(BM, BN)                                                                                                 \
+  {conv_key(BM, BN, 1), &conv_igemm_kernel<T, BM, BN, true>, 256, staging_lds((size_t)2 * (BM + BN) * UPR * 16), 0},      \
+  {conv_key(BM, BN, 0), &conv_igemm_kernel<T, BM, BN, false>, 256, staging_lds((size_t)2 * (BM + BN) * UPR * 16), 0}
+  ConvKernel<Fn>* e = nullptr;
   int rc;
-  if ((rc = materialize_prologue(L, s))) return rc;
-  if (hp.TH == 8 && hp.TW == 32 && hp.BN == 64) rc = launch_mx<8, 32, 64>(L, s, fuse, gn_nsplit_out);
-  else if (hp.TH == 4 && hp.TW == 32 && hp.BN == 128) rc = launch_mx<4, 32, 128>(L, s, fuse, gn_nsplit_out);
-  else if (hp.TH == 8 && hp.TW == 16 && hp.BN == 128) rc = launch_mx<8, 16, 128>(L, s, fuse, gn_nsplit_out);
-  else if (hp.TH == 8 && hp.TW == 16 && hp.BN == 64) rc = launch_mx<8, 16, 64>(L, s, fuse, gn_nsplit_out);
-  else return 0;
-  if (rc == PRG_OK) g_last_mx = 1;
-  return rc == PRG_OK ? 1 : rc;
-}
-static int try_mx(ConvLaunch<float>&, hipStream_t, int*, int*) { return 0; }
-
-int try_launch_conv3x3_ws(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);   // conv_ws.hip
-int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);  // conv_c64.hip
-int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done);   // conv_w256.hip
-int try_launch_conv4x4s2_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                       // conv_w256.hip
-int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s);                     // conv_w256.hip
-static inline int try_down(const ConvLaunch<bf16_t>& L, hipStream_t s) { return try_launch_conv4x4s2_w256(L, s); }
-static inline int try_down(const ConvLaunch<float>&, hipStream_t) { return 0; }
-static inline int try_ws(ConvLaunch<bf16_t>& L, hipStream_t s, int* n, int* acc_done) {
-  int r = try_launch_conv3x3_c64(L, s, n, acc_done);   // weights-stationary kernel for the 64 -> 64 convs
-  if (r == 0 && L.d.ups && !L.gn_partials) {
-    r = try_launch_conv3x3_up_w256(L, s);                    // Upsample convs as four 2 x 2-tap sub-pixel convs
-    if (r == 1) g_last_exec_scale = 4.0 / 9.0;               // (what the profile reports as EXECUTED work)
+  if constexpr (std::is_same<T, bf16_t>::value) {            // (the 256 x 128 tile exists in bf16 only)
+    static ConvKernel<Fn> tab[] = {PRG_IGEMM(256, 128), PRG_IGEMM(128, 128), PRG_IGEMM(256, 64), PRG_IGEMM(128, 64)};
+    rc = conv_kernel_find(tab, conv_key(c.bm, c.bn, c.mode), "implicit-GEMM conv", &e);
+  } else {
+    static ConvKernel<Fn> tab[] = {PRG_IGEMM(128, 128), PRG_IGEMM(256, 64), PRG_IGEMM(128, 64)};
+    rc = conv_kernel_find(tab, conv_key(c.bm, c.bn, c.mode), "implicit-GEMM conv", &e);
   }
-  if (r == 0) r = try_launch_conv3x3_w256(L, s, n, acc_done);     // 256-pixel x 128-channel tiles where the launch fills the chip
-  if (r != 0) return r;
-  // the wave-specialised kernel reads coefficient tables (hand-counted loads): fold the accumulators into them first when
-  // it is going to run (its shape test is repeated here so that a conv it does not cover launches nothing)
-  const ConvDesc& d = L.d;
-  if (L.pro_fold.acc && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C0 % 64 == 0 && d.C1 % 64 == 0 && d.Cout % 64 == 0)
-    if (int rc = materialize_prologue(L, s)) return rc;
-  return try_launch_conv3x3_ws(L, s, n, acc_done);
-}
-static inline int try_ws(ConvLaunch<float>&, hipStream_t, int*, int*) { return 0; }
-static inline int try_split(const ConvLaunch<float>& L, hipStream_t s, int* n) { return try_launch_conv_split(L, s, n); }
-static inline int try_split(const ConvLaunch<bf16_t>&, hipStream_t, int*) { return 0; }
-
-// h16 (conv.h): would both convs of a ResnetBlock take kernels that implement the f16 format?  The same try_launch_* functions
-// the dispatch below calls, in the same order, in probe mode (they stop where they would launch).
-bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1in, const ConvLaunch<bf16_t>& L2in) {
-  // PRG_H16=0: off (every ResnetBlock keeps its bf16 h1)
-  static const int on = env_int("PRG_H16", 1);
-  if (!on) return false;
-  ConvLaunch<bf16_t> L1 = L1in, L2 = L2in;
-  // mxfp8 handles: a conv whose MX copy would run (the 256-pixel MX kernel takes Cout % 128 == 0; PRG_MX_PURE / mx_pure take every
-  // 3x3 conv) never carries the f16 format — the 64-channel pairs, which the bf16 kernels run in that mode too, do
-  auto mx_takes = [](const ConvLaunch<bf16_t>& L) { return L.w_mx && (L.d.Cout % 128 == 0 || mx_pure_env() || L.mx_pure); };
-  if (mx_takes(L1) || mx_takes(L2) || !L2.w_f16 || !L1.gn_acc || !L2.pro_fold.acc) return false;
-  L1.probe = L2.probe = 1;
-  L1.out_f16 = 1;
-  L2.in_f16 = 1;
-  int ns = 0, ad = 0;
-  int r1 = try_launch_conv3x3_c64(L1, nullptr, &ns, &ad);
-  if (r1 == 0) r1 = try_launch_conv3x3_w256(L1, nullptr, &ns, &ad);
-  if (r1 == 0) r1 = try_launch_conv3x3_ws(L1, nullptr, &ns, &ad);
-  if (r1 != 1 || !ad) return false;
-  int r2 = try_launch_conv3x3_c64(L2, nullptr, &ns, &ad);
-  if (r2 == 0) r2 = try_launch_conv3x3_w256(L2, nullptr, &ns, &ad);
-  return r2 == 1;
+#undef PRG_IGEMM
+  if (rc) return rc;
+  e->fn<<<dim3(c.grid), e->block, e->lds, s>>>(L, L.d.B * L.d.Hout * L.d.Wout, c.tiles_x, c.tiles_n, c.fuse_stats, L.d.Cout % 8 == 0);
+  PRG_LAUNCH_CHECK();
+  return PRG_OK;
 }
 
+static int launch_family(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s) {
+  switch (c.family) {
+    case kConvSplitW512: return launch_conv_split_w512(c, L, s);
+    case kConvSplitHalo: case kConvSplitWs: case kConvSplitP64: case kConvSplitIgemm: return launch_conv_split(c, L, s);
+    case kConvHalo: return launch_conv_halo(c, L, s);
+    case kConvIgemm: return launch_conv_igemm(c, L, s);
+    default: return fail(PRG_E_STATE, "conv: the selection named a family that has no float kernels");
+  }
+}
+
+static int launch_family(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s) {
+  switch (c.family) {
+    case kConvC64: return launch_conv_c64(c, L, s);
+    case kConvWs: return launch_conv_ws(c, L, s);
+    case kConvW256: case kConvW256Mx: return launch_conv_w256(c, L, s);
+    case kConvMxHalo: return launch_conv_mx_halo(c, L, s);
+    case kConvHalo: return launch_conv_halo(c, L, s);
+    case kConvIgemm: return launch_conv_igemm(c, L, s);
+    default: return fail(PRG_E_STATE, "conv: the selection named a family that has no bf16 kernels");
+  }
+}
+// The one place that reads the selection's switches (each pins an alternative schedule that a test compares against the default).
+const ConvSwitches& conv_switches() {
+  static const ConvSwitches sw = [] {
+    ConvSwitches v;
+    v.conv_ws = env_int("PRG_CONV_WS", 1);
+    v.conv_c64 = env_int("PRG_CONV_C64", 1);
+    v.conv_w256 = env_int("PRG_CONV_W256", 1);
+    v.conv_down_w256 = env_int("PRG_CONV_DOWN_W256", 1);
+    v.conv_w256mx = env_int("PRG_CONV_W256MX", 1);
+    v.w256_min_tiles = env_int("PRG_W256_MIN_TILES", 0);
+    v.up2x2 = env_int("PRG_UP2X2", 1);
+    v.h16 = env_int("PRG_H16", 1);
+    v.mx_pure = env_int("PRG_MX_PURE", 0);
+    v.split_up2x2 = env_int("PRG_SPLIT_UP2X2", 0);
+    v.split_p64 = env_int("PRG_SPLIT_P64", 256);
+    v.split_w512 = env_int("PRG_SPLIT_W512", 1);
+    return v;
+  }();
+  return sw;
+}
+
+bool conv_h16_pair_ok(const ConvLaunch<bf16_t>& L1, const ConvLaunch<bf16_t>& L2) {
+  return choose_h16_pair(conv_facts(L1), conv_facts(L2), device_cu_count(), conv_switches());
+}
+
+// validate, choose, fill the coefficient tables if the chosen kernel reads them, launch
 template <typename T>
-int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  g_last_exec_scale = 1.0;
-  g_last_mx = 0;
+int launch_conv(const ConvLaunch<T>& Lin, hipStream_t s, int* gn_nsplit_out, int* acc_done, ConvChoice* chosen) {
   if (acc_done) *acc_done = 0;
-  ConvLaunch<T> L = Lin;          // (materialize_prologue clears pro_fold once the coefficient tables are filled)
-  const ConvDesc& d = L.d;
+  if (gn_nsplit_out) *gn_nsplit_out = 0;
+  const ConvDesc& d = Lin.d;
   constexpr int VEC = Elem<T>::kVec;
-  PRG_CHECK(L.src0 && L.w && L.out, "conv: null pointer");
+  PRG_CHECK(Lin.src0 && Lin.w && Lin.out, "conv: null pointer");
   PRG_CHECK(d.C0 % VEC == 0 && d.C1 % VEC == 0, "conv: channel counts must be multiples of the 16-byte vector");
-  PRG_CHECK(d.C1 == 0 || L.src1, "conv: second source missing");
-  PRG_CHECK(!L.res_a || (L.residual && L.res_b && d.KH == 1 && d.KW == 1 && d.Cout % 8 == 0),
+  PRG_CHECK(d.C1 == 0 || Lin.src1, "conv: second source missing");
+  PRG_CHECK(!Lin.res_a || (Lin.residual && Lin.res_b && d.KH == 1 && d.KW == 1 && d.Cout % 8 == 0),
             "conv: the activated residual is a 1x1 (implicit-GEMM, wide epilogue) feature");
-  PRG_CHECK(!L.res_fold.acc || (L.residual && d.KH == 1 && d.KW == 1 && d.Cout % 8 == 0 && L.res_fold.cpg % 8 == 0 &&
-                                L.res_fold.G * L.res_fold.cpg == d.Cout && L.res_fold.P && L.res_fold.Q),
+  PRG_CHECK(!Lin.res_fold.acc || (Lin.residual && d.KH == 1 && d.KW == 1 && d.Cout % 8 == 0 && Lin.res_fold.cpg % 8 == 0 &&
+                                  Lin.res_fold.G * Lin.res_fold.cpg == d.Cout && Lin.res_fold.P && Lin.res_fold.Q),
             "conv: the folded activated residual needs a 1x1 conv whose 8-channel vectors lie inside one GroupNorm group");
   PRG_CHECK(d.CoutPad % 64 == 0 && d.CoutPad >= d.Cout, "conv: bad CoutPad");
   const int64_t M64 = (int64_t)d.B * d.Hout * d.Wout;
   PRG_CHECK(M64 > 0 && M64 < (int64_t)1 << 31, "conv: M out of range");
-  const int M = (int)M64;
-  const int want_stats = L.gn_partials != nullptr;
-  if (gn_nsplit_out) *gn_nsplit_out = 0;
-  {
-    const int r = try_mx(L, s, gn_nsplit_out, acc_done);    // MX-fp8 operands when the handle carries them
-    if (r < 0) return r;
-    if (r == 1) return PRG_OK;
-  }
-  {
-    int r = try_ws(L, s, gn_nsplit_out, acc_done);   // persistent kernels of the bf16 throughput path
-    if (r == 0 && !L.gn_partials) r = try_down(L, s);       // Downsample (4 x 4, stride 2) as a 2 x 2-tap conv of the same kernel
-    if (r < 0) return r;
-    if (r == 1) return PRG_OK;
-  }
-  PRG_CHECK(!L.out_f16 && !L.in_f16, "conv: an h16 launch reached a kernel without the f16 format (conv_h16_pair_ok disagrees with the dispatch)");
-  if (int rc = materialize_prologue(L, s)) return rc;       // the generic kernels below read coefficient tables
-  {
-    const int r = try_split(L, s, gn_nsplit_out);           // f16x3 mode: split-operand kernels (conv_split.hip)
-    if (r < 0) return r;
-    if (r == 1) return PRG_OK;
-  }
-  HaloPick<T> hp;
-  if (pick_halo<T>(d, &hp)) {
-    const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-    const int tiles = (d.Wout / hp.TW) * (d.Hout / hp.TH);
-    const int fuse = want_stats && cpg % 8 == 0 && cpg <= hp.BN && tiles <= kGnMaxSplit;
-    if (hp.TH == 8 && hp.TW == 32 && hp.BN == 64) return launch_halo<T, 8, 32, 64>(L, s, fuse, gn_nsplit_out);
-    if (hp.TH == 4 && hp.TW == 32 && hp.BN == 128) return launch_halo<T, 4, 32, 128>(L, s, fuse, gn_nsplit_out);
-    if (hp.TH == 8 && hp.TW == 16 && hp.BN == 128) return launch_halo<T, 8, 16, 128>(L, s, fuse, gn_nsplit_out);
-    if (hp.TH == 8 && hp.TW == 16 && hp.BN == 64) return launch_halo<T, 8, 16, 64>(L, s, fuse, gn_nsplit_out);
-  }
-  PRG_CHECK(!L.pro_a, "conv: fused prologue requested on a shape the halo kernel does not cover");
+
+  const ConvChoice c = choose_conv(conv_facts(Lin), device_cu_count(), conv_switches());
+  if (c.family == kConvNone) return fail(PRG_E_INVALID, c.why);
+
+  ConvLaunch<T> L = Lin;
   if constexpr (std::is_same<T, bf16_t>::value) {
-    // 256 x 128 tiles (round 5): the 1x1 res_convs / projections of the coarse levels are bound by L2 -> LDS operand traffic
-    // (M N K (1 / BM + 1 / BN) elements: 0.75x of the 128 x 128 tile's) and meet one barrier per 16 instead of 8 MFMAs per wave;
-    // taken when the launch still has two workgroups per CU.
-    if (d.CoutPad % 128 == 0 && M % 256 == 0 && (int64_t)(M / 256) * (d.CoutPad / 128) >= (int64_t)2 * 256)
-      return launch_igemm<T, 256, 128>(L, M, s, want_stats, gn_nsplit_out);
+    if (c.fill_tables) {
+      // Consumers without the in-kernel GroupNorm fold (common.h, GnFold): fill the pro_a / pro_b tables from the accumulators
+      // with one small launch, then run on the tables as before.
+      PRG_CHECK(L.pro_a && L.pro_b, "conv: pro_fold needs scratch coefficient tables in pro_a / pro_b");
+      if (int rc = launch_gn_coeff_acc(L.pro_fold, const_cast<float*>(L.pro_a), const_cast<float*>(L.pro_b), d.B, d.C0, s)) return rc;
+      L.pro_fold.acc = nullptr;
+    }
   }
-  if (d.CoutPad % 128 == 0) return launch_igemm<T, 128, 128>(L, M, s, want_stats, gn_nsplit_out);
-  if (M >= 256 * 64) return launch_igemm<T, 256, 64>(L, M, s, want_stats, gn_nsplit_out);
-  return launch_igemm<T, 128, 64>(L, M, s, want_stats, gn_nsplit_out);
+  if (int rc = launch_family(c, L, s)) return rc;
+  if (gn_nsplit_out) *gn_nsplit_out = c.nsplit;
+  if (acc_done) *acc_done = c.acc_done;
+  if (chosen) *chosen = c;
+  return PRG_OK;
 }
 
-template int launch_conv<float>(const ConvLaunch<float>&, hipStream_t, int*, int*);
-template int launch_conv<bf16_t>(const ConvLaunch<bf16_t>&, hipStream_t, int*, int*);
+template int launch_conv<float>(const ConvLaunch<float>&, hipStream_t, int*, int*, ConvChoice*);
+template int launch_conv<bf16_t>(const ConvLaunch<bf16_t>&, hipStream_t, int*, int*, ConvChoice*);
 
 // ---------------------------------------------------------------------------------------------
 // stem: 7x7 pad 3 direct conv, float32 NCHW in (Cin 1 or 3) -> T NHWC out (sd:824 / dc:822)

@@ -91,7 +91,7 @@ __device__ __forceinline__ void c64_barrier() {
 }
 
 // The per-image ticket fold below (c64_fold_coefficients, the `ticket` lambda, flags bit 1 = 0: contiguous tile runs) is retired:
-// try_launch_conv3x3_c64 never passes tickets and always asks for interleaved runs.  Its device code stays as it was because deleting
+// launch_conv_c64 never passes tickets and always asks for interleaved runs.  Its device code stays as it was because deleting
 // it changes the producers' register allocation (conv3x3_c64_kernel<1 | 2> then spill to scratch) and measured 0.4 % slower end to end.
 //
 // What gn_coeff_kernel does in a launch of its own, for ONE image, by one wave (lane = channel of the 64): the image's
@@ -510,62 +510,22 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 
 }  // namespace
 
-// Returns 1 when it launched, 0 when the shape is not covered (caller falls back), negative on error.
-int try_launch_conv3x3_c64(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = env_int("PRG_CONV_C64", 1);
-  if (!enabled) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
-  if (d.C0 != 64 || d.C1 != 0 || d.Cout != 64 || d.CoutPad != 64 || d.kchunks != 2) return 0;
-  if (L.residual || !L.bias) return 0;
-  if (d.ups) return 0;                                       // (no 64 -> 64 Upsample conv exists in the networks: not a tested shape)
-  if (d.Wout % TW || d.Hout % TH) return 0;
-  // the producers address the input through ONE buffer descriptor with 32-bit byte offsets (pixel index * 128 in an SGPR,
-  // num_records as an int): beyond 2 GiB of input the generic kernel (64-bit addressing) runs instead — B = 256 at 256x256
-  if ((size_t)d.B * d.Hin * d.Win * 128 + 4096 >= ((size_t)1 << 31)) return 0;
-  const int tiles_x = d.Wout / TW, tiles_y = d.Hout / TH;
-  const int total = tiles_x * tiles_y * d.B;
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  int grid = (total < num_cus ? total : num_cus) & ~7;       // multiple of 8: XCD-contiguous tile runs
-  if (grid < 8) return 0;                                    // tiny launches stay on the generic kernels
-  const int cpg = L.gn_groups > 0 ? 64 / L.gn_groups : 0;
-  const int split_n = cpg > 32 ? 2 : 1;
-  int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 &&
-             tiles_x * tiles_y * 2 * split_n <= kGnMaxSplit;
-  if (L.gn_partials && !fuse) return 0;
-  static DeviceOnce attr_done[5];     // zero-initialised; atomic: lanes launch from several host threads
-  const GnFold& pf = L.pro_fold;
-  const bool fold_ok = pf.acc && pf.P && pf.Q && pf.G * pf.cpg == 64 && pf.cpg % 8 == 0;
-  if (pf.acc && !fold_ok) return 0;
-  if (L.in_f16 && !(fold_ok && L.w_f16)) return 0;           // h16 input: only through the folded prologue, with f16 weights
-  const int pro = L.in_f16 ? 3 : fold_ok ? 2 : (L.pro_a ? 1 : 0);
-  if (L.out_f16 && pro != 0) return 0;                       // h16 output: conv1 of a ResnetBlock (no prologue)
-  const int variant = L.out_f16 ? 4 : pro;
-  const void* const fns[5] = {reinterpret_cast<const void*>(&conv3x3_c64_kernel<0, false>), reinterpret_cast<const void*>(&conv3x3_c64_kernel<1, false>),
-                              reinterpret_cast<const void*>(&conv3x3_c64_kernel<2, false>), reinterpret_cast<const void*>(&conv3x3_c64_kernel<3, false>),
-                              reinterpret_cast<const void*>(&conv3x3_c64_kernel<0, true>)};
-  if (!attr_done[variant].done()) {
-    hipError_t e = hipFuncSetAttribute(fns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, (int)C64_LDS);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(c64 conv): ") + hipGetErrorString(e));
-    attr_done[variant].mark();
-  }
-  if (gn_nsplit_out) *gn_nsplit_out = fuse ? tiles_x * tiles_y * 2 * split_n : 0;
-  const bool use_acc = fuse && L.gn_acc != nullptr;          // fixed-point accumulators instead of slabs
+// conv3x3_c64_kernel<PRO, OUT_F16>: pro 0-3, mode 1 = f16 output (conv1 of an h16 pair, no prologue)
+int launch_conv_c64(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s) {
+  using Fn = void (*)(const ConvLaunch<bf16_t>, int, int, int);
+#define PRG_C64(PRO, F16) {conv_key(PRO, F16), &conv3x3_c64_kernel<PRO, F16>, 512, C64_LDS, (int)C64_LDS}
+  static ConvKernel<Fn> tab[] = {PRG_C64(0, false), PRG_C64(1, false), PRG_C64(2, false), PRG_C64(3, false), PRG_C64(0, true)};
+#undef PRG_C64
+  ConvKernel<Fn>* e = nullptr;
+  if (int rc = conv_kernel_find(tab, conv_key(c.pro, c.mode), "c64 conv", &e)) return rc;
   ConvLaunch<bf16_t> Lk = L;
   Lk.gn_tickets = nullptr;                                   // (the in-kernel ticket fold is retired: never launched)
-  if (!use_acc) Lk.gn_acc = nullptr;
-  if (acc_done) *acc_done = use_acc ? 1 : 0;
+  if (!c.acc_done) Lk.gn_acc = nullptr;                      // slabs: the kernel takes a non-null gn_acc as "accumulate"
   // interleaved tile runs are ~2 % faster (neighbouring tiles run at the same time on neighbouring CUs of the XCD)
-  const int flags = (fuse ? 1 : 0) | 2;
-  if (L.probe) return 1;
-  if (variant == 4) conv3x3_c64_kernel<0, true><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
-  else if (pro == 3) conv3x3_c64_kernel<3, false><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
-  else if (pro == 2) conv3x3_c64_kernel<2, false><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
-  else if (pro == 1) conv3x3_c64_kernel<1, false><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
-  else conv3x3_c64_kernel<0, false><<<dim3(grid), 512, C64_LDS, s>>>(Lk, tiles_x, tiles_y, flags);
+  const int flags = (c.fuse_stats ? 1 : 0) | 2;
+  e->fn<<<dim3(c.grid), e->block, e->lds, s>>>(Lk, c.tiles_x, c.tiles_y, flags);
   PRG_LAUNCH_CHECK();
-  return 1;
+  return PRG_OK;
 }
 
 }  // namespace prg

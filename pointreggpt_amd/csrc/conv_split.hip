@@ -1390,169 +1390,45 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const ConvLaun
 // ---------------------------------------------------------------------------------------------
 // launch
 // ---------------------------------------------------------------------------------------------
+// conv3x3_split_kernel<TH, TW, NS> (weight ring slots NS: two workgroups must fit a CU)
 template <int TH, int TW>
-static int launch_split_halo(const ConvLaunch<float>& L, hipStream_t s, int fuse_stats, int* nsplit) {
-  [[maybe_unused]] constexpr int HALO = (TH + 2) * (TW + 2);
-  constexpr int RSTRIDE = ((TW + 2) * 144 + 255) / 256 * 256, HB = (TH + 2) * RSTRIDE;
-  constexpr int NS = (2 * HB + 3 * 8192) * 2 <= 160 * 1024 ? 3 : 2;   // weight ring slots: two workgroups must fit a CU
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / TW, tiles_y = d.Hout / TH, tiles_n = d.Cout / 64;
-  size_t lds = (size_t)2 * HB + NS * 8192 + 512;      // (+ the statistics scratch of the direct epilogue)
-  if (lds < kEpilogueLds) lds = kEpilogueLds;
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y : 0;
-  static DeviceOnce attr_done;   // > 64 KB of dynamic LDS needs the opt-in (idempotent: a race between lanes is benign)
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<TH, TW, NS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    attr_done.mark();
+struct SplitHalo {
+  static constexpr int RSTRIDE = ((TW + 2) * 144 + 255) / 256 * 256, HB = (TH + 2) * RSTRIDE;
+  static constexpr int NS = (2 * HB + 3 * 8192) * 2 <= 160 * 1024 ? 3 : 2;
+  static constexpr size_t lds0 = (size_t)2 * HB + NS * 8192 + 512;      // (+ the statistics scratch of the direct epilogue)
+  static constexpr size_t lds = lds0 < kEpilogueLds ? kEpilogueLds : lds0;
+};
+
+// The f16x3 families of this file; when each is chosen: conv_choose.cpp, choose_split.  > 64 KB of dynamic LDS needs the opt-in.
+int launch_conv_split(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s) {
+  constexpr int HB10 = 10 * ((18 * 144 + 255) / 256 * 256), HB18 = 18 * ((18 * 144 + 255) / 256 * 256);
+  constexpr size_t ig128 = (size_t)2 * (128 + 128) * 8 * 16, ig64 = (size_t)2 * (128 + 64) * 8 * 16;
+  static_assert(ig128 >= kEpilogueLds && ig64 >= kEpilogueLds, "the gather kernel's staging covers the epilogue scratch");
+  static ConvKernel<ConvTileKernel<float>> tab[] = {
+      {conv_key(kConvSplitWs, 1), &conv3x3_split_ws_kernel<4, true>, 512, (size_t)2 * HB10 + 4 * 128 * 128, 128 * 1024},   // sub-pixel Upsample
+      {conv_key(kConvSplitWs, 0), &conv3x3_split_ws_kernel<4, false>, 512, (size_t)2 * HB10 + 4 * 128 * 128, 128 * 1024},
+      // the persistent Cout = 64 kernel: 16 x 16-pixel tiles, one 512-thread workgroup per CU (tiles_n = all its tiles)
+      {conv_key(kConvSplitP64), &conv3x3_split_p64_kernel<4>, 512, (size_t)2 * HB18 + 4 * 64 * 128, 136 * 1024},
+      {conv_key(kConvSplitHalo, 8, 16), &conv3x3_split_kernel<8, 16, SplitHalo<8, 16>::NS>, 256, SplitHalo<8, 16>::lds, 80 * 1024},
+      {conv_key(kConvSplitHalo, 4, 32), &conv3x3_split_kernel<4, 32, SplitHalo<4, 32>::NS>, 256, SplitHalo<4, 32>::lds, 80 * 1024}};
+  using Ig = void (*)(const ConvLaunch<float>, int, int, int, int);   // (L, M, tiles_m, tiles_n, fuse_stats)
+  static ConvKernel<Ig> igemm[] = {{conv_key(128, 128, 1), &conv_igemm_split_kernel<128, 128, true>, 256, ig128, 80 * 1024},
+                                   {conv_key(128, 128, 0), &conv_igemm_split_kernel<128, 128, false>, 256, ig128, 80 * 1024},
+                                   {conv_key(128, 64, 1), &conv_igemm_split_kernel<128, 64, true>, 256, ig64, 80 * 1024},
+                                   {conv_key(128, 64, 0), &conv_igemm_split_kernel<128, 64, false>, 256, ig64, 80 * 1024}};
+  switch (c.family) {
+    case kConvSplitHalo: return launch_conv_tiles(tab, conv_key(c.family, c.th, c.tw), "split halo conv", c, L, s);
+    case kConvSplitWs: return launch_conv_tiles(tab, conv_key(c.family, c.mode), "split ws conv", c, L, s);
+    case kConvSplitP64:
+      PRG_CHECK(c.grid > 0, "conv3x3_split_p64: no device properties");
+      return launch_conv_tiles(tab, conv_key(c.family), "split p64 conv", c, L, s);
+    default: break;
   }
-  conv3x3_split_kernel<TH, TW, NS><<<dim3(tiles_x * tiles_y * tiles_n * d.B), 256, lds, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
+  ConvKernel<Ig>* e = nullptr;
+  if (int rc = conv_kernel_find(igemm, conv_key(c.bm, c.bn, c.mode), "split implicit-GEMM conv", &e)) return rc;
+  e->fn<<<dim3(c.grid), e->block, e->lds, s>>>(L, L.d.B * L.d.Hout * L.d.Wout, c.tiles_x, c.tiles_n, c.fuse_stats);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
-}
-
-// Upsample conv as four 2 x 2-tap sub-pixel convolutions of the source image (the UP form of the wave-specialised kernel)
-static int launch_split_ws_up(const ConvLaunch<float>& L, hipStream_t s) {
-  constexpr int NS = 4, HB = 10 * ((18 * 144 + 255) / 256 * 256);
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Win / 16, tiles_y = d.Hin / 8, tiles_n = d.Cout / 128;
-  const size_t lds = (size_t)2 * HB + NS * 128 * 128;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_ws_kernel<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_done.mark();
-  }
-  conv3x3_split_ws_kernel<NS, true><<<dim3(tiles_x * tiles_y * tiles_n * d.B * 4), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, 0);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-static int launch_split_ws(const ConvLaunch<float>& L, hipStream_t s, int fuse_stats, int* nsplit) {
-  constexpr int NS = 4, HB = 10 * ((18 * 144 + 255) / 256 * 256);
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / 16, tiles_y = d.Hout / 8, tiles_n = d.Cout / 128;
-  const size_t lds = (size_t)2 * HB + NS * 128 * 128;
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y * 2 : 0;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_ws_kernel<NS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_done.mark();
-  }
-  conv3x3_split_ws_kernel<NS, false><<<dim3(tiles_x * tiles_y * tiles_n * d.B), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-// the persistent Cout = 64 kernel: 16 x 16-pixel tiles, one 512-thread workgroup per CU
-static int launch_split_p64(const ConvLaunch<float>& L, hipStream_t s, int fuse_stats, int* nsplit) {
-  constexpr int NS = 4, HB = 18 * ((18 * 144 + 255) / 256 * 256);
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / 16, tiles_y = d.Hout / 16;
-  const int ntiles = tiles_x * tiles_y * d.B;
-  const size_t lds = (size_t)2 * HB + NS * 64 * 128;
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y * 4 : 0;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_p64_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024));
-    attr_done.mark();
-  }
-  const int num_cus = device_cu_count();
-  PRG_CHECK(num_cus > 0, "conv3x3_split_p64: no device properties");
-  int grid = ntiles < num_cus ? ntiles : num_cus;
-  if (grid >= 8) grid &= ~7;                             // multiple of 8: XCD-contiguous tile runs
-  conv3x3_split_p64_kernel<NS><<<dim3(grid), 512, lds, s>>>(L, tiles_x, tiles_y, ntiles, fuse_stats);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-template <int BM, int BN>
-static int launch_split_igemm(const ConvLaunch<float>& L, int M, hipStream_t s, int want_stats, int* nsplit) {
-  const ConvDesc& d = L.d;
-  const int tiles_m = ceil_div(M, BM), tiles_n = d.CoutPad / BN;
-  const int HWo = d.Hout * d.Wout;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int fuse = want_stats && cpg % 8 == 0 && cpg <= BN && HWo % BM == 0 && HWo / BM <= kGnMaxSplit;
-  if (nsplit) *nsplit = fuse ? HWo / BM : 0;
-  size_t lds = (size_t)2 * (BM + BN) * 8 * 16;
-  if (lds < kEpilogueLds) lds = kEpilogueLds;
-  const bool one = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && !d.ups;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_split_kernel<BM, BN, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_split_kernel<BM, BN, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    attr_done.mark();
-  }
-  if (one) conv_igemm_split_kernel<BM, BN, true><<<dim3(tiles_m * tiles_n), 256, lds, s>>>(L, M, tiles_m, tiles_n, fuse);
-  else conv_igemm_split_kernel<BM, BN, false><<<dim3(tiles_m * tiles_n), 256, lds, s>>>(L, M, tiles_m, tiles_n, fuse);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-int try_launch_conv3x3_split_w512(const ConvLaunch<float>& L, hipStream_t s, int want_stats, int* gn_nsplit_out);   // conv_split512.hip
-
-// 1 = launched, 0 = shape not covered (the exact-f32 kernels of conv.hip run it), < 0 = error
-int try_launch_conv_split(const ConvLaunch<float>& L, hipStream_t s, int* gn_nsplit_out) {
-  if (!L.w_split) return 0;
-  const ConvDesc& d = L.d;
-  if (d.Cout % 8 || d.C0 % 8 || d.C1 % 8 || L.res_fold.acc || L.pro_fold.acc) return 0;
-  // the activated residual (ConvLaunch::res_a: the ResnetBlock tail in a 1x1 res_conv's epilogue) is the shared transposing
-  // epilogue's feature: the gather kernel below has it, the 3x3 kernels do not
-  if (L.res_a && !(d.KH == 1 && d.KW == 1)) return 0;
-  const int64_t M64 = (int64_t)d.B * d.Hout * d.Wout;
-  if ((int64_t)d.B * d.Hin * d.Win >= ((int64_t)1 << 31) || M64 >= ((int64_t)1 << 31)) return 0;
-  const int M = (int)M64;
-  const int want_stats = L.gn_partials != nullptr;
-  int rc = PRG_OK;
-  const bool halo = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.C0 % 32 == 0 && d.C1 % 32 == 0 && d.Cout % 64 == 0;
-  if (halo) {
-    const int H = d.Hout, W = d.Wout;
-    const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-    auto fuse = [&](int TH, int TW, int BN) {
-      return want_stats && cpg % 8 == 0 && cpg <= BN && (W / TW) * (H / TH) <= kGnMaxSplit;
-    };
-    // The Upsample convs as four 2 x 2-tap sub-pixel convolutions (4 / 9 of their MFMAs: 0.3 ms = 2.5 % of an f16x3 evaluation): OFF by
-    // default.  Per evaluation it is as accurate as the nine-tap form (test_split_upsample_conv_against_float64: rms 2.0e-7 against
-    // torch-CPU's 2.9e-7), but every change of the rounding pattern RE-DRAWS the long chains' distance from the reference — over nine
-    // equal-precision variants of the mode's arithmetic the 250-step 256 x 256 chain G21b sits anywhere in 3.7e-5 .. 8.8e-5 m at B = 1
-    // (profiles/r05_chain_metric_spread_f16x3.txt; the reference's own 1-vs-8-thread spread is 4.7e-5 m) — and round 5 tried it as the
-    // default: G21b drew 5.9e-5 m at B = 1 and 1.001e-4 m at B = 8 (the batch that selects the persistent 64-channel kernel).  The
-    // mode's claim is the LITERAL 1e-4 m on that chain at the tested batches, so the nine-tap form stays.  PRG_SPLIT_UP2X2=1: on.
-    static const int up_on = env_int("PRG_SPLIT_UP2X2", 0);
-    if (up_on && d.ups && L.w_up_split && d.C1 == 0 && d.Cout % 128 == 0 && d.Win % 16 == 0 && d.Hin % 8 == 0 && d.Hout == 2 * d.Hin &&
-        d.Wout == 2 * d.Win && !L.residual && !L.pro_a && !want_stats) {
-      rc = launch_split_ws_up(L, s);
-      return rc ? rc : 1;
-    }
-    {
-      // conv_split512.hip (round 6): one wave per SIMD, 128 x 64 wave tiles, for launches with a 256-pixel tile per CU; bit-identical to
-      // the kernel below (PRG_SPLIT_W512=0: off)
-      const int r = try_launch_conv3x3_split_w512(L, s, want_stats, gn_nsplit_out);
-      if (r != 0) return r;
-    }
-    // Cout % 128 == 0: the wave-specialised kernel (128-pixel x 128-channel tiles, one workgroup per CU)
-    if (d.Cout % 128 == 0 && W % 16 == 0 && H % 8 == 0 && !L.residual) {
-      const int tiles = (W / 16) * (H / 8) * 2;
-      const int f = want_stats && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && tiles <= kGnMaxSplit;
-      if (f || !want_stats) { rc = launch_split_ws(L, s, f, gn_nsplit_out); return rc ? rc : 1; }
-    }
-    // Cout = 64 and a launch that fills the chip (>= one 16 x 16 tile per CU): the persistent kernel; PRG_SPLIT_P64=0: never,
-    // PRG_SPLIT_P64=<n>: from n tiles (tests force it at small shapes)
-    static const int p64_min = env_int("PRG_SPLIT_P64", 256);
-    if (p64_min > 0 && d.Cout == 64 && W % 16 == 0 && H % 16 == 0 && !L.residual && !L.res_a && d.B * (W / 16) * (H / 16) >= p64_min &&
-        (d.C0 + d.C1) >= 64) {
-      const int tiles = (W / 16) * (H / 16) * 4;
-      const int f = want_stats && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && tiles <= kGnMaxSplit;
-      if (f || !want_stats) { rc = launch_split_p64(L, s, f, gn_nsplit_out); return rc ? rc : 1; }
-    }
-    if (W % 16 == 0 && H % 8 == 0) { rc = launch_split_halo<8, 16>(L, s, fuse(8, 16, 64), gn_nsplit_out); return rc ? rc : 1; }
-    if (W % 32 == 0 && H % 4 == 0) { rc = launch_split_halo<4, 32>(L, s, fuse(4, 32, 64), gn_nsplit_out); return rc ? rc : 1; }
-  }
-  if (L.pro_a) return 0;                       // (a fused prologue is only requested where pick_halo<float> = the test above holds)
-  if (d.CoutPad % 128 == 0) rc = launch_split_igemm<128, 128>(L, M, s, want_stats, gn_nsplit_out);
-  else rc = launch_split_igemm<128, 64>(L, M, s, want_stats, gn_nsplit_out);
-  return rc ? rc : 1;
 }
 
 }  // namespace prg

@@ -13,7 +13,7 @@
 //     stream — one s_barrier per tap for four waves.
 // The arithmetic is conv3x3_split_ws_kernel's term for term (same MFMA sequence per accumulator, 288-term partials, same epilogue
 // expression, same GroupNorm slab partition: a wave's 128 pixels are one 8 x 16 tile of that kernel), so the two are bit-identical
-// (tests/test_gpu_f16x3.py::test_f16x3_one_wave_per_simd_kernel).  Dispatch: try_launch_conv3x3_split_w512 below; the same-box A/B is
+// (tests/test_gpu_f16x3.py::test_f16x3_one_wave_per_simd_kernel).  Dispatch: choose_split (conv_choose.cpp); the same-box A/B is
 // profiles/r06_ab_split_w512.txt.
 #include <atomic>
 #include <cstdlib>
@@ -337,37 +337,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   }
 }
 
-// 1 = launched, 0 = not this kernel's shape / switched off, < 0 = error.  Default ON for launches with at least one 256-pixel x
-// 128-channel tile per CU (same-box A/B, profiles/r06_ab_split_w512.txt: -3 ... -5 % per launch against conv3x3_split_ws_kernel, the
-// whole f16x3 pipeline +2.4 %; with half as many workgroups as the 128-pixel kernel a launch below that size leaves CUs idle:
-// 256 -> 256 @16x16 at B = 64 ran 83 us against 52).  PRG_SPLIT_W512=0: never; =2: every shape it covers (tests).
-int try_launch_conv3x3_split_w512(const ConvLaunch<float>& L, hipStream_t s, int want_stats, int* gn_nsplit_out) {
-  static const int on = env_int("PRG_SPLIT_W512", 1);
-  if (!on) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Cout % 128 == 0 && d.Wout % 16 == 0 && d.Hout % 16 == 0 && !L.residual &&
-        d.C0 % 32 == 0 && d.C1 % 32 == 0))
-    return 0;
+// conv3x3_split_w512_kernel<NS, PRO>; when it is chosen: conv_choose.cpp, choose_split
+int launch_conv_split_w512(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s) {
   constexpr int NS = 3, HB = 18 * ((18 * 144 + 255) / 256 * 256);
-  const int tiles_x = d.Wout / 16, tiles_y = d.Hout / 16, tiles_n = d.Cout / 128;
-  if (on != 2 && tiles_x * tiles_y * tiles_n * d.B < device_cu_count()) return 0;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int slabs = tiles_x * tiles_y * 4;
-  const int f = want_stats && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && slabs <= kGnMaxSplit;
-  if (want_stats && !f) return 0;
-  const size_t lds = (size_t)2 * HB + NS * 128 * 128;
-  if (gn_nsplit_out) *gn_nsplit_out = f ? slabs : 0;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_w512_kernel<NS, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_w512_kernel<NS, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-    attr_done.mark();
-  }
-  const dim3 grid(tiles_x * tiles_y * tiles_n * d.B);
-  if (L.pro_a) conv3x3_split_w512_kernel<NS, true><<<grid, 256, lds, s>>>(L, tiles_x, tiles_y, tiles_n, f);
-  else conv3x3_split_w512_kernel<NS, false><<<grid, 256, lds, s>>>(L, tiles_x, tiles_y, tiles_n, f);
-  PRG_LAUNCH_CHECK();
-  return 1;
+  constexpr size_t lds = (size_t)2 * HB + NS * 128 * 128;
+  static ConvKernel<ConvTileKernel<float>> tab[] = {{conv_key(0), &conv3x3_split_w512_kernel<NS, false>, 256, lds, 152 * 1024},
+                                                    {conv_key(1), &conv3x3_split_w512_kernel<NS, true>, 256, lds, 152 * 1024}};
+  return launch_conv_tiles(tab, conv_key(c.pro), "split w512 conv", c, L, s);
 }
 
 }  // namespace prg

@@ -1056,222 +1056,18 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
 
 }  // namespace
 
-// Returns 1 when it launched, 0 when the shape is not covered (caller falls back), negative on error.
-int materialize_prologue(ConvLaunch<bf16_t>& L, hipStream_t s);   // conv.hip
-
-// in-kernel GroupNorm fold of the prologue (common.h, GnFold): valid when an 8-channel unit lies inside one group
-static int w256_prepare_fold(ConvLaunch<bf16_t>& Lk, hipStream_t s) {
-  if (!Lk.pro_fold.acc) return PRG_OK;
-  const GnFold& f = Lk.pro_fold;
-  if (f.P && f.Q && f.cpg % 8 == 0 && f.G * f.cpg == Lk.d.C0 && Lk.d.C1 == 0) return PRG_OK;
-  return materialize_prologue(Lk, s);
-}
-
-// whether a launch of `total` tiles is large enough for these kernels (at least `dflt` tiles); PRG_W256_MIN_TILES=<n> > 0 replaces
-// the threshold (tests force small shapes onto them)
-static bool w256_fills(long total, int dflt) {
-  static const int min_tiles = env_int("PRG_W256_MIN_TILES", 0);
-  return total >= (min_tiles > 0 ? min_tiles : dflt);
-}
-
-int try_launch_conv3x3_w256(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = env_int("PRG_CONV_W256", 1);
-  if (!enabled) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
-  if (d.C0 % kCH || d.C1 % kCH || d.C0 == 0 || d.Cout % BN || d.CoutPad != d.Cout) return 0;
-  if (L.residual || !L.bias) return 0;
-  if (L.pro_a && d.C1) return 0;                            // the fused prologue is defined for a single source
-  const int tiles_n = d.Cout / BN;
-  if (tiles_n != 1 && tiles_n != 2 && tiles_n != 4 && tiles_n != 8) return 0;   // an XCD is pinned to one channel tile
-  const int H = d.Hout, W = d.Wout;
-  int tw = 0;
-  if (W % 32 == 0 && H % 8 == 0) tw = 32;
-  else if (W % 16 == 0 && H % 16 == 0) tw = 16;
-  else return 0;
-  if (d.ups && ((H | W) & 1)) return 0;
-  const int th = 256 / tw, tiles_x = W / tw, tiles_y = H / th;
-  const long total = (long)tiles_x * tiles_y * tiles_n * d.B;
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  // fewer tiles than CUs: the 128-pixel tiles of conv_ws.hip fill the chip better
-  const int grid = num_cus & ~7;
-  if (grid < 8 || !w256_fills(total, grid)) return 0;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 &&
-                   tiles_x * tiles_y * 2 <= kGnMaxSplit;
-  if (L.gn_partials && !fuse) return 0;
-  ConvLaunch<bf16_t> Lk = L;
-  if (L.in_f16) {                                            // h16 input: only through the in-kernel fold, with f16 weights
-    const GnFold& f = L.pro_fold;
-    if (!(f.acc && f.P && f.Q && f.cpg % 8 == 0 && f.G * f.cpg == d.C0 && d.C1 == 0 && L.w_f16)) return 0;
-  }
-  if (L.out_f16 && (L.pro_a || L.pro_fold.acc)) return 0;   // h16 output: conv1 of a ResnetBlock (no prologue)
-  if (!L.probe)
-    if (int rc = w256_prepare_fold(Lk, s)) return rc;
-  const int pro = L.in_f16 ? 3 : Lk.pro_fold.acc ? 2 : (L.pro_a ? 1 : 0);
-  const void* fns[2][4] = {{reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 0, 0>), reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 1, 0>),
-                            reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 2, 0>), reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 3, 0>)},
-                           {reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 0, 0>), reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 1, 0>),
-                            reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 2, 0>), reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 3, 0>)}};
-  const size_t lds = tw == 32 ? W2Geom<32>::LDS : W2Geom<16>::LDS;
-  static DeviceOnce attr_done[2][4];   // zero-initialised; atomic: lanes launch from several host threads
-  if (!attr_done[tw == 32][pro].done()) {
-    hipError_t e = hipFuncSetAttribute(fns[tw == 32][pro], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(w256 conv): ") + hipGetErrorString(e));
-    attr_done[tw == 32][pro].mark();
-  }
-  if (gn_nsplit_out) *gn_nsplit_out = fuse ? tiles_x * tiles_y * 2 : 0;
-  if (acc_done) *acc_done = (fuse && L.gn_acc) ? 1 : 0;
-  if (L.probe) return 1;
-  if (tw == 32) {
-    if (pro == 3) conv3x3_w256_kernel<32, 3, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 2) conv3x3_w256_kernel<32, 2, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 1) conv3x3_w256_kernel<32, 1, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else conv3x3_w256_kernel<32, 0, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-  } else {
-    if (pro == 3) conv3x3_w256_kernel<16, 3, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 2) conv3x3_w256_kernel<16, 2, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 1) conv3x3_w256_kernel<16, 1, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else conv3x3_w256_kernel<16, 0, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-  }
-  PRG_LAUNCH_CHECK();
-  return 1;
-}
-
-// Upsample (nearest x2) + 3x3 conv as four 2 x 2-tap sub-pixel convolutions of the source image (MODE 2).  Returns 1 / 0 / negative.
-int try_launch_conv3x3_up_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
-  static const int enabled = env_int("PRG_UP2X2", 1);
-  if (!enabled || !L.w_up) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.ups == 1 && d.C1 == 0)) return 0;
-  if (d.C0 % kCH || d.C0 == 0 || (d.Cout != 64 && d.Cout % BN) || d.CoutPad != d.Cout) return 0;
-  if (L.residual || !L.bias || L.pro_a || L.pro_fold.acc || L.gn_partials || L.out_f16 || L.in_f16) return 0;
-  if (d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win) return 0;
-  const int tiles_n = d.Cout == 64 ? 1 : d.Cout / BN;
-  if (tiles_n != 1 && tiles_n != 2 && tiles_n != 4 && tiles_n != 8) return 0;
-  const int H = d.Hin, W = d.Win;                            // tiles of 256 SOURCE pixels, four phases each
-  int tw = 0;
-  if (W % 32 == 0 && H % 8 == 0) tw = 32;
-  else if (W % 16 == 0 && H % 16 == 0) tw = 16;
-  else return 0;
-  if ((size_t)d.B * d.Hin * d.Win * d.C0 * 2 >= ((size_t)1 << 31)) return 0;   // (32-bit halo offsets, as the other modes)
-  const int th = 256 / tw, tiles_x = W / tw, tiles_y = H / th;
-  const long total = (long)tiles_x * tiles_y * tiles_n * d.B * (d.Cout == 64 ? 2 : 4);   // (Cout = 64: two x-phases per tile)
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  const int grid = num_cus & ~7;
-  if (grid < 8 || !w256_fills(total, grid / 2)) return 0;
-  const void* fn = tw == 32 ? reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 0, 2>)
-                            : reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 0, 2>);
-  const size_t lds = tw == 32 ? W2Geom<32>::LDS : W2Geom<16>::LDS;
-  static DeviceOnce attr_done[2];
-  if (!attr_done[tw == 32].done()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(w256 upsample): ") + hipGetErrorString(e));
-    attr_done[tw == 32].mark();
-  }
-  if (L.probe) return 1;
-  if (tw == 32) conv3x3_w256_kernel<32, 0, 2><<<dim3(grid), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, 0);
-  else conv3x3_w256_kernel<16, 0, 2><<<dim3(grid), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, 0);
-  PRG_LAUNCH_CHECK();
-  return 1;
-}
-
-// MX-fp8 operands (handles of dtype PRG_MXFP8): same shapes as the bf16 entry.  Returns 1 / 0 / negative.
-int try_launch_conv3x3_w256mx(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = env_int("PRG_CONV_W256MX", 1);
-  if (!enabled || !L.w_mx || !L.w_mx_scale) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
-  if (d.C0 % kCH || d.C1 % kCH || d.C0 == 0 || d.Cout % BN || d.CoutPad != d.Cout) return 0;
-  if (L.residual || !L.bias) return 0;
-  if (L.pro_a && d.C1) return 0;
-  const int tiles_n = d.Cout / BN;
-  if (tiles_n != 1 && tiles_n != 2 && tiles_n != 4 && tiles_n != 8) return 0;
-  const int H = d.Hout, W = d.Wout;
-  int tw = 0;
-  if (W % 32 == 0 && H % 8 == 0) tw = 32;
-  else if (W % 16 == 0 && H % 16 == 0) tw = 16;
-  else return 0;
-  if (d.ups && ((H | W) & 1)) return 0;
-  const int th = 256 / tw, tiles_x = W / tw, tiles_y = H / th;
-  const long total = (long)tiles_x * tiles_y * tiles_n * d.B;
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  const int grid = num_cus & ~7;
-  // Round 5: a launch with fewer tiles than CUs stays on the bf16 kernels (the network's level-3 convs: 128 tiles on 256 CUs — measured
-  // at the configs[4] shape, same box, same positions: 25 / 29 us on conv3x3_ws_kernel against 28-29 / 38-40 us here,
-  // profiles/r05_configs4_conv_per_launch_bf16_vs_mxfp8.txt); mx_pure (the conv-level tests) keeps the old half-a-wave threshold
-  if (grid < 8 || !w256_fills(total, L.mx_pure ? grid / 2 : grid)) return 0;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const int fuse = L.gn_partials != nullptr && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 &&
-                   tiles_x * tiles_y * 2 <= kGnMaxSplit;
-  if (L.gn_partials && !fuse) return 0;
-  ConvLaunch<bf16_t> Lk = L;
-  if (int rc = w256_prepare_fold(Lk, s)) return rc;
-  const int pro = Lk.pro_fold.acc ? 2 : (L.pro_a ? 1 : 0);
-  const void* fns[2][3] = {{reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<16, 0>), reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<16, 1>),
-                            reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<16, 2>)},
-                           {reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<32, 0>), reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<32, 1>),
-                            reinterpret_cast<const void*>(&conv3x3_w256mx_kernel<32, 2>)}};
-  const size_t lds = tw == 32 ? W2MxGeom<32>::LDS : W2MxGeom<16>::LDS;
-  static DeviceOnce attr_done[2][3];   // zero-initialised; atomic: lanes launch from several host threads
-  if (!attr_done[tw == 32][pro].done()) {
-    hipError_t e = hipFuncSetAttribute(fns[tw == 32][pro], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(w256 mx conv): ") + hipGetErrorString(e));
-    attr_done[tw == 32][pro].mark();
-  }
-  if (gn_nsplit_out) *gn_nsplit_out = fuse ? tiles_x * tiles_y * 2 : 0;
-  if (acc_done) *acc_done = (fuse && L.gn_acc) ? 1 : 0;
-  if (tw == 32) {
-    if (pro == 2) conv3x3_w256mx_kernel<32, 2><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 1) conv3x3_w256mx_kernel<32, 1><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else conv3x3_w256mx_kernel<32, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-  } else {
-    if (pro == 2) conv3x3_w256mx_kernel<16, 2><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else if (pro == 1) conv3x3_w256mx_kernel<16, 1><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-    else conv3x3_w256mx_kernel<16, 0><<<dim3(grid), 512, lds, s>>>(Lk, tiles_x, tiles_y, tiles_n, fuse);
-  }
-  PRG_LAUNCH_CHECK();
-  return 1;
-}
-
-// Conv2d(C, Cout, 4, stride 2, pad 1) through the same kernel (MODE 1).  Returns 1 / 0 / negative like the entry above.
-int try_launch_conv4x4s2_w256(const ConvLaunch<bf16_t>& L, hipStream_t s) {
-  static const int enabled = env_int("PRG_CONV_DOWN_W256", 1);
-  if (!enabled || !L.w_s2d) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad == 1 && d.ups == 0 && d.C1 == 0)) return 0;
-  if (d.C0 % kCH || d.C0 == 0 || d.C0 > 128 || (d.Cout != 64 && d.Cout % BN) || d.CoutPad != d.Cout) return 0;
-  if (L.residual || !L.bias || L.pro_a || L.gn_partials) return 0;
-  if (d.Hin != 2 * d.Hout || d.Win != 2 * d.Wout) return 0;
-  const int tiles_n = d.Cout == 64 ? 1 : d.Cout / BN;
-  if (tiles_n != 1 && tiles_n != 2 && tiles_n != 4 && tiles_n != 8) return 0;
-  const int H = d.Hout, W = d.Wout;
-  int tw = 0;
-  if (W % 32 == 0 && H % 8 == 0) tw = 32;
-  else if (W % 16 == 0 && H % 16 == 0) tw = 16;
-  else return 0;
-  const int th = 256 / tw, tiles_x = W / tw, tiles_y = H / th;
-  const long total = (long)tiles_x * tiles_y * tiles_n * d.B;
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  const int grid = num_cus & ~7;
-  if (grid < 8 || !w256_fills(total, grid / 2)) return 0;   // the generic kernel for tiny launches
-  const void* fn = tw == 32 ? reinterpret_cast<const void*>(&conv3x3_w256_kernel<32, 0, 1>)
-                            : reinterpret_cast<const void*>(&conv3x3_w256_kernel<16, 0, 1>);
-  const size_t lds = tw == 32 ? W2Geom<32>::LDS : W2Geom<16>::LDS;
-  static DeviceOnce attr_done[2];
-  if (!attr_done[tw == 32].done()) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(w256 downsample): ") + hipGetErrorString(e));
-    attr_done[tw == 32].mark();
-  }
-  if (tw == 32) conv3x3_w256_kernel<32, 0, 1><<<dim3(grid), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, 0);
-  else conv3x3_w256_kernel<16, 0, 1><<<dim3(grid), 512, lds, s>>>(L, tiles_x, tiles_y, tiles_n, 0);
-  PRG_LAUNCH_CHECK();
-  return 1;
+// conv3x3_w256_kernel<TW, PRO, MODE> (mode 0: 3x3 with prologue 0-3, 1: Downsample, 2: sub-pixel Upsample) and
+// conv3x3_w256mx_kernel<TW, PRO> (MX-fp8 operands, prologue 0-2)
+int launch_conv_w256(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s) {
+#define PRG_W256(TW, PRO, MODE) {conv_key(kConvW256, TW, PRO, MODE), &conv3x3_w256_kernel<TW, PRO, MODE>, 512, W2Geom<TW>::LDS, (int)W2Geom<TW>::LDS}
+#define PRG_W256MX(TW, PRO) {conv_key(kConvW256Mx, TW, PRO, 0), &conv3x3_w256mx_kernel<TW, PRO>, 512, W2MxGeom<TW>::LDS, (int)W2MxGeom<TW>::LDS}
+  static ConvKernel<ConvTileKernel<bf16_t>> tab[] = {
+      PRG_W256(16, 0, 0), PRG_W256(16, 1, 0), PRG_W256(16, 2, 0), PRG_W256(16, 3, 0), PRG_W256(32, 0, 0), PRG_W256(32, 1, 0),
+      PRG_W256(32, 2, 0), PRG_W256(32, 3, 0), PRG_W256(32, 0, 2), PRG_W256(16, 0, 2), PRG_W256MX(16, 0),  PRG_W256MX(16, 1),
+      PRG_W256MX(16, 2),  PRG_W256MX(32, 0),  PRG_W256MX(32, 1),  PRG_W256MX(32, 2),  PRG_W256(32, 0, 1), PRG_W256(16, 0, 1)};
+#undef PRG_W256
+#undef PRG_W256MX
+  return launch_conv_tiles(tab, conv_key(c.family, c.tw, c.pro, c.mode), "w256 conv", c, L, s);
 }
 
 }  // namespace prg

@@ -798,74 +798,15 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
   }
 }
 
-constexpr int kWsUnsupported = 100;   // launch_ws_cfg: shape not covered, caller falls back
-
-template <int TH, int TW, int BN, bool PRO>
-int launch_ws_cfg2(const ConvLaunch<bf16_t>& L, hipStream_t s, int fuse_stats, int* nsplit, int num_cus) {
-  using G = WsGeom<TH, TW, BN>;
-  const ConvDesc& d = L.d;
-  const int tiles_x = d.Wout / TW, tiles_y = d.Hout / TH, tiles_n = d.Cout / BN;
-  const int total = tiles_x * tiles_y * tiles_n * d.B;
-  int grid = num_cus;
-  if (grid > total) grid = total;
-  if (grid >= 8) grid &= ~7;                     // multiple of 8: XCD-contiguous runs inside a round
-  if (tiles_n > 1 && (grid & 7) != 0) return kWsUnsupported;   // a workgroup must own one channel tile (bias in LDS)
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_ws_kernel<TH, TW, BN, PRO>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
-    if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(ws conv): ") + hipGetErrorString(e));
-    attr_done.mark();
-  }
-  if (nsplit) *nsplit = fuse_stats ? tiles_x * tiles_y * G::WAVES_M : 0;
-  if (L.probe) return PRG_OK;
-  conv3x3_ws_kernel<TH, TW, BN, PRO><<<dim3(grid), 768, G::LDS, s>>>(L, tiles_x, tiles_y, tiles_n, fuse_stats);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
-template <int TH, int TW, int BN>
-int launch_ws_cfg(const ConvLaunch<bf16_t>& L, hipStream_t s, int fuse_stats, int* nsplit, int num_cus) {
-  return L.pro_a ? launch_ws_cfg2<TH, TW, BN, true>(L, s, fuse_stats, nsplit, num_cus)
-                 : launch_ws_cfg2<TH, TW, BN, false>(L, s, fuse_stats, nsplit, num_cus);
-}
-
 }  // namespace
 
-// Returns 1 when it launched, 0 when the shape is not covered (caller falls back), negative on error.
-int try_launch_conv3x3_ws(const ConvLaunch<bf16_t>& L, hipStream_t s, int* gn_nsplit_out, int* acc_done) {
-  static const int enabled = env_int("PRG_CONV_WS", 1);
-  if (!enabled) return 0;
-  const ConvDesc& d = L.d;
-  if (!(d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1)) return 0;
-  if (d.C0 % kCH || d.C1 % kCH || d.Cout % 64) return 0;
-  if (L.residual || !L.bias) return 0;
-  if (L.in_f16 || (L.out_f16 && L.pro_a)) return 0;          // h16 (conv.h): f16 OUTPUT only, from a launch without prologue
-  {
-    const int tn128 = d.Cout % 128 == 0 ? d.Cout / 128 : d.Cout / 64;   // Cout tiles of the configuration chosen below
-    if (tn128 != 1 && tn128 != 2 && tn128 != 4 && tn128 != 8) return 0;  // every workgroup must own ONE channel tile
-  }
-  const int num_cus = device_cu_count();
-  if (num_cus <= 0) return 0;
-  const int H = d.Hout, W = d.Wout;
-  const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 0;
-  const bool want = L.gn_partials != nullptr;
-  auto fuse_for = [&](int TH, int TW, int BN) {
-    // one partial per (tile, consumer wave row): a group must lie inside one wave's 64 channels
-    return want && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && (W / TW) * (H / TH) * (4 / (BN / 64)) <= kGnMaxSplit ? 1 : 0;
-  };
-  int rc = 0;
-  if (d.Cout % 128 == 0) {
-    if (W % 32 == 0 && H % 4 == 0) rc = launch_ws_cfg<4, 32, 128>(L, s, fuse_for(4, 32, 128), gn_nsplit_out, num_cus);
-    else if (W % 16 == 0 && H % 8 == 0) rc = launch_ws_cfg<8, 16, 128>(L, s, fuse_for(8, 16, 128), gn_nsplit_out, num_cus);
-    else return 0;
-  } else {
-    if (W % 32 == 0 && H % 8 == 0) rc = launch_ws_cfg<8, 32, 64>(L, s, fuse_for(8, 32, 64), gn_nsplit_out, num_cus);
-    else return 0;
-  }
-  if (rc == kWsUnsupported) return 0;
-  if (rc == PRG_OK && acc_done) *acc_done = (L.gn_acc && gn_nsplit_out && *gn_nsplit_out > 0) ? 1 : 0;
-  return rc == PRG_OK ? 1 : rc;
+// conv3x3_ws_kernel<TH, TW, BN, PRO>: three tiles, with and without the table prologue
+int launch_conv_ws(const ConvChoice& c, const ConvLaunch<bf16_t>& L, hipStream_t s) {
+#define PRG_WS(TH, TW, BN, PRO) {conv_key(TH, TW, BN, PRO), &conv3x3_ws_kernel<TH, TW, BN, PRO>, 768, WsGeom<TH, TW, BN>::LDS, (int)WsGeom<TH, TW, BN>::LDS}
+  static ConvKernel<ConvTileKernel<bf16_t>> tab[] = {PRG_WS(4, 32, 128, true), PRG_WS(4, 32, 128, false), PRG_WS(8, 16, 128, true),
+                                                     PRG_WS(8, 16, 128, false), PRG_WS(8, 32, 64, true),   PRG_WS(8, 32, 64, false)};
+#undef PRG_WS
+  return launch_conv_tiles(tab, conv_key(c.th, c.tw, c.bn, c.pro), "ws conv", c, L, s);
 }
 
 }  // namespace prg

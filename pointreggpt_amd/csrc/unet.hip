@@ -101,13 +101,13 @@ struct ProfileSink {  // per-launch conv timing (bench roofline)
     sh.launches = 1; sh.ms = ms; sh.flops = r.flops; sh.flops_executed = r.flops_exec;
     shapes.push_back(sh);
   }
-  // the conv launch that conv_ev's last pair brackets (called right after launch_conv, on its thread)
-  void add_conv(const ConvDesc& d, bool prologue, size_t elem_bytes) {
+  // the conv launch that conv_ev's last pair brackets; `c`: what launch_conv chose for it
+  void add_conv(const ConvDesc& d, const ConvChoice& c, bool prologue, size_t elem_bytes) {
     Rec r{};
     r.key.cin = d.C0 + d.C1; r.key.cout = d.Cout; r.key.k = d.KH; r.key.stride = d.stride; r.key.ups = d.ups;
     r.key.hout = d.Hout; r.key.wout = d.Wout; r.key.two_source = d.C1 > 0; r.key.prologue = prologue;
-    r.key.mx = conv_last_was_mx();
-    r.flops = prg::conv_flops(d); r.flops_exec = prg::conv_flops(d) * conv_last_exec_scale();
+    r.key.mx = c.is_mx;
+    r.flops = prg::conv_flops(d); r.flops_exec = prg::conv_flops(d) * c.exec_scale;
     conv_flops += r.flops;
     conv_flops_exec += r.flops_exec;
     if (recs.size() < conv_ev.used) recs.resize(conv_ev.used);
@@ -145,7 +145,7 @@ struct UnetImpl : prg_unet {
   U* alloc(size_t n) { return reinterpret_cast<U*>(arena.alloc(n * sizeof(U))); }
 
   // The one dry-run gate.  measure() walks forward() with arena.dry set: every allocation happens exactly as in a live
-  // evaluation and nothing is launched.  Every launch goes through run() (or conv(), which asks live() itself, as does the h16 probe).
+  // evaluation and nothing is launched.  Every launch goes through run() (or conv(), which asks live() itself, as does the h16 pair query).
   bool live() const { return !arena.dry; }
   template <typename Fn, typename... A>
   int run(Fn&& launch, A&&... a) { return live() ? launch(std::forward<A>(a)...) : PRG_OK; }
@@ -216,14 +216,15 @@ struct UnetImpl : prg_unet {
     if (!(prof && prof->on)) return launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
     int rc, e;
     if ((rc = prof->conv_ev.start(s))) return rc;
-    rc = launch_conv<T>(L, s, o.gn_nsplit, o.acc_done);
+    ConvChoice chosen;
+    rc = launch_conv<T>(L, s, o.gn_nsplit, o.acc_done, &chosen);
     if ((e = prof->conv_ev.stop(s))) return e;
-    prof->add_conv(L.d, L.pro_a != nullptr || L.pro_fold.acc != nullptr, sizeof(T));
+    prof->add_conv(L.d, chosen, L.pro_a != nullptr || L.pro_fold.acc != nullptr, sizeof(T));
     return rc;
   }
 
   // -------- launchers that exist for one storage type only --------
-  bool h16_probe(const ConvLaunch<T>& L1, const ConvLaunch<T>& L2) const {
+  bool h16_pair(const ConvLaunch<T>& L1, const ConvLaunch<T>& L2) const {
     if constexpr (kBf16) return conv_h16_pair_ok(L1, L2);
     else return false;
   }
@@ -419,19 +420,19 @@ struct UnetImpl : prg_unet {
     // conv2 applies GroupNorm + SiLU of h1 in its prologue wherever it supports one
     const bool fuse_pro = conv_supports_prologue<T>(make_desc(r.c2, r.cout, 0, B, H, Wd, 1, 1, 0));
     // h16 (conv.h): h1 only ever feeds conv2's fused prologue — stored as f16 when both launches land on kernels that implement it
-    // (probed with the launches' own descriptors: PRG_H16=0, PRG_CONV_C64=0, ... and uncovered shapes fall back to bf16 h1)
+    // (asked of the selection with the launches' own descriptors: PRG_H16=0, PRG_CONV_C64=0, ... and uncovered shapes fall back to bf16 h1)
     bool h16 = false;
     if (live() && n1.acc && fuse_pro && d_h16 && r.c2.h16_off >= 0) {
       ConvOpt p2 = o2;
       p2.fold = &n1.f; p2.pro_a = n1.A; p2.pro_b = n1.Bc;
-      h16 = h16_probe(make_launch(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1),
+      h16 = h16_pair(make_launch(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1),
                       make_launch(r.c2, h1, r.cout, nullptr, 0, B, H, Wd, 1, 1, 0, p2, out));
     }
     o1.out_f16 = o2.in_f16 = h16;
     int rc;
     if ((rc = conv(r.c1, s0, C0, s1, C1, B, H, Wd, 1, 1, 0, o1, h1, s))) return rc;
     if ((rc = n1.complete(h1, s))) return rc;
-    PRG_CHECK(!h16 || n1.acc_done, "resblock: the h16 probe promised fixed-point statistics");
+    PRG_CHECK(!h16 || n1.acc_done, "resblock: the h16 pair query promised fixed-point statistics");
     if (!fuse_pro) {
       if ((rc = n1.pass(h1, nullptr, s))) return rc;
     } else {

@@ -730,4 +730,53 @@ int prg_debug_conv4x4s2(const float* x, const float* w, const float* bias, float
   return debug_conv(x, w, bias, out, B, Cin, Cout, H, W, PRG_BF16, 4, 2, stream);
 }
 
+// prg_debug_conv_choice: the selection of conv_choose.h on plain values (no device)
+static int conv_choice_facts(const int32_t* q, ConvFacts* f) {
+  const int dtype = q[PRG_CQ_DTYPE];
+  PRG_CHECK(dtype == PRG_F32 || dtype == PRG_BF16 || dtype == PRG_MXFP8 || dtype == PRG_F16X3, "prg_debug_conv_choice: bad dtype");
+  *f = ConvFacts{};
+  ConvDesc& d = f->d;
+  d.B = q[PRG_CQ_B]; d.Hin = q[PRG_CQ_HIN]; d.Win = q[PRG_CQ_WIN]; d.C0 = q[PRG_CQ_C0]; d.C1 = q[PRG_CQ_C1]; d.ups = q[PRG_CQ_UPS];
+  d.KH = q[PRG_CQ_KH]; d.KW = q[PRG_CQ_KW]; d.stride = q[PRG_CQ_STRIDE]; d.pad = q[PRG_CQ_PAD]; d.Hout = q[PRG_CQ_HOUT];
+  d.Wout = q[PRG_CQ_WOUT]; d.Cout = q[PRG_CQ_COUT]; d.CoutPad = q[PRG_CQ_COUTPAD]; d.kchunks = q[PRG_CQ_KCHUNKS];
+  f->f32 = dtype == PRG_F32 || dtype == PRG_F16X3;
+  const int vec = f->f32 ? 4 : 8;
+  PRG_CHECK(d.B > 0 && d.Hin > 0 && d.Win > 0 && d.Hout > 0 && d.Wout > 0 && d.C0 > 0 && d.C1 >= 0 && d.Cout > 0 && d.KH > 0 && d.KW > 0 &&
+                d.stride > 0 && d.pad >= 0 && d.kchunks > 0 && (d.ups == 0 || d.ups == 1),
+            "prg_debug_conv_choice: bad descriptor");
+  PRG_CHECK((int64_t)d.B * d.Hout * d.Wout < (int64_t)1 << 31 && (int64_t)d.B * d.Hin * d.Win < (int64_t)1 << 31, "prg_debug_conv_choice: M out of range");
+  PRG_CHECK(d.C0 % vec == 0 && d.C1 % vec == 0, "prg_debug_conv_choice: channel counts must be multiples of the 16-byte vector");
+  PRG_CHECK(d.CoutPad % 64 == 0 && d.CoutPad >= d.Cout, "prg_debug_conv_choice: bad CoutPad");
+  const int p = q[PRG_CQ_PRESENT];
+  PRG_CHECK(p >= 0 && p < 2 * PRG_CP_FOLD_PQ, "prg_debug_conv_choice: bad present bits");
+  f->bias = (p & PRG_CP_BIAS) != 0; f->residual = (p & PRG_CP_RESIDUAL) != 0; f->res_a = (p & PRG_CP_RES_A) != 0;
+  f->pro_a = (p & PRG_CP_PRO_A) != 0; f->gn_partials = (p & PRG_CP_GN_PARTIALS) != 0; f->gn_acc = (p & PRG_CP_GN_ACC) != 0;
+  f->w_mx = (p & PRG_CP_MX) != 0; f->w_s2d = (p & PRG_CP_S2D) != 0; f->w_up = (p & PRG_CP_UP) != 0; f->w_split = (p & PRG_CP_SPLIT) != 0;
+  f->w_up_split = (p & PRG_CP_UP_SPLIT) != 0; f->w_f16 = (p & PRG_CP_F16) != 0; f->res_fold_acc = (p & PRG_CP_RES_FOLD_ACC) != 0;
+  f->pro_fold_acc = (p & PRG_CP_FOLD_ACC) != 0; f->pro_fold_pq = (p & PRG_CP_FOLD_PQ) != 0;
+  f->gn_groups = q[PRG_CQ_GN_GROUPS]; f->pro_fold_G = q[PRG_CQ_FOLD_G]; f->pro_fold_cpg = q[PRG_CQ_FOLD_CPG];
+  f->in_f16 = q[PRG_CQ_IN_F16] != 0; f->out_f16 = q[PRG_CQ_OUT_F16] != 0; f->mx_pure = q[PRG_CQ_MX_PURE] != 0;
+  return PRG_OK;
+}
+
+int prg_debug_conv_choice(const int32_t* query, const int32_t* query2, int32_t* choice, float* exec_scale) {
+  PRG_CHECK(query && choice && exec_scale, "prg_debug_conv_choice: null pointer");
+  ConvFacts f1, f2;
+  if (int rc = conv_choice_facts(query, &f1)) return rc;
+  if (query2)
+    if (int rc = conv_choice_facts(query2, &f2)) return rc;
+  const int32_t* w = query + PRG_CQ_SWITCHES;
+  ConvSwitches sw;
+  sw.conv_ws = w[0]; sw.conv_c64 = w[1]; sw.conv_w256 = w[2]; sw.conv_down_w256 = w[3]; sw.conv_w256mx = w[4]; sw.w256_min_tiles = w[5];
+  sw.up2x2 = w[6]; sw.h16 = w[7]; sw.mx_pure = w[8]; sw.split_up2x2 = w[9]; sw.split_p64 = w[10]; sw.split_w512 = w[11];
+  const int num_cus = query[PRG_CQ_NUM_CUS];
+  const ConvChoice c = choose_conv(f1, num_cus, sw);
+  const int32_t out[PRG_CC_COUNT] = {c.family, c.th, c.tw, c.bm, c.bn, c.pro, c.mode, c.tiles_x, c.tiles_y, c.tiles_n, c.grid, c.fuse_stats,
+                                     c.nsplit, c.acc_done, c.fill_tables, c.is_mx, choose_supports_prologue(f1.d, f1.f32),
+                                     query2 && !f1.f32 && !f2.f32 && choose_h16_pair(f1, f2, num_cus, sw)};
+  for (int i = 0; i < PRG_CC_COUNT; ++i) choice[i] = out[i];
+  *exec_scale = (float)c.exec_scale;
+  return PRG_OK;
+}
+
 }  // extern "C"

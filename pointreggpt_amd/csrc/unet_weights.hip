@@ -8,7 +8,7 @@ namespace prg {
 static_assert(kPackBK<float> == ConvTile<float>::BK && kPackBK<bf16_t> == ConvTile<bf16_t>::BK, "packer rows != kernel K-chunk");
 
 // The switches weight preparation depends on.  PRG_SPLIT_UP2X2: the Upsample convs' sub-pixel packings of the f16x3 mode are off by
-// default (conv_split.hip: try_launch_conv_split); PRG_SPLIT_STEM=0: the direct fmaf stem kernel of the parity mode;
+// default (conv_choose.cpp: choose_split); PRG_SPLIT_STEM=0: the direct fmaf stem kernel of the parity mode;
 // PRG_LA_KSHIFT=0 forces the measured column maxima (the la_kmax pass) for every fused attention block.
 static WeightOptions weight_options(bool split_up2x2, bool fused_attn, bool split_stem, bool la_kshift) {
   WeightOptions o;

@@ -216,7 +216,7 @@ def test_conv3x3_sources_and_statistics(name, cus):
 
 
 # single-source shapes with a prologue: (shape, groups, kernel, tile, bias); the fold on conv_ws and the halo kernel goes through
-# launch_gn_coeff_acc (materialize_prologue), on conv_c64 and conv_w256 it is folded in the kernel
+# launch_gn_coeff_acc (ConvChoice::fill_tables), on conv_c64 and conv_w256 it is folded in the kernel
 def cases_pro(cus):
     q = cus // 8
     return {

@@ -45,6 +45,11 @@ GROUPS = [
     # a bf16 handle whose convs report no accumulators
     ({"PRG_CONV_WS": "0", "PRG_CONV_C64": "0", "PRG_CONV_W256": "0", "PRG_CONV_DOWN_W256": "0"}, SMALL("bf16")),
     ({"PRG_W256_MIN_TILES": "1"}, SMALL("bf16")),
+    # switches of the conv selection (tests/golden/conv_dispatch.json) that change a kernel at these shapes
+    ({"PRG_CONV_W256": "0"}, SMALL("bf16") + [("unet", 64, 2, 128, "bf16")]),
+    ({"PRG_UP2X2": "0"}, SMALL("bf16") + [("unet", 64, 2, 128, "bf16")]),
+    ({"PRG_SPLIT_P64": "1"}, SMALL("f16x3")),
+    ({"PRG_SPLIT_W512": "2"}, SMALL("f16x3")),
     ({"PRG_SPLIT_FULLATTN": "0", "PRG_SPLIT_LA_ONLINE": "0"}, SMALL("f16x3")),
 ]
 
