@@ -22,12 +22,9 @@
 #include <type_traits>
 
 #include "blocks.h"
+#include "wave_ops.h"
 
 namespace prg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 namespace {
 
@@ -50,13 +47,6 @@ __host__ __device__ inline int la_out_tpb(int ntiles) {         // la_out (pixel
 constexpr int kLdO = kHid + 8;       // LDS row stride of 128-wide rows (bf16 elements)
 constexpr float kLnEps = 1e-5f;
 
-__device__ inline uint32_t pack2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ inline float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ inline float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 __device__ inline float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
 template <int C>
@@ -114,10 +104,10 @@ struct XTile {
 #pragma unroll
     for (int i = 0; i < Geo<C>::VPT; ++i) {
       uint4 o;
-      o.x = pack2(f[i][0] * rstd, f[i][1] * rstd);
-      o.y = pack2(f[i][2] * rstd, f[i][3] * rstd);
-      o.z = pack2(f[i][4] * rstd, f[i][5] * rstd);
-      o.w = pack2(f[i][6] * rstd, f[i][7] * rstd);
+      o.x = pack_bf16(f[i][0] * rstd, f[i][1] * rstd);
+      o.y = pack_bf16(f[i][2] * rstd, f[i][3] * rstd);
+      o.z = pack_bf16(f[i][4] * rstd, f[i][5] * rstd);
+      o.w = pack_bf16(f[i][6] * rstd, f[i][7] * rstd);
       *reinterpret_cast<uint4*>(xn + row * Geo<C>::LDW + (part + 4 * i) * 8) = o;
     }
   }
@@ -455,8 +445,8 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         uint2 w;
-        w.x = pack2(oa[4 * g4], oa[4 * g4 + 1]);
-        w.y = pack2(oa[4 * g4 + 2], oa[4 * g4 + 3]);
+        w.x = pack_bf16(oa[4 * g4], oa[4 * g4 + 1]);
+        w.y = pack_bf16(oa[4 * g4 + 2], oa[4 * g4 + 3]);
         *reinterpret_cast<uint2*>(ot + px * kLdO + 32 * wave + 8 * g4 + 4 * hi) = w;
       }
     }
@@ -505,8 +495,8 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
         const int c0 = yrt[a] * 32 + 8 * g4 + 4 * hi;
         const float4 gg = *reinterpret_cast<const float4*>(outg_l + c0);
         uint2 w;
-        w.x = pack2((ya[a][4 * g4] - mean) * rstd * gg.x, (ya[a][4 * g4 + 1] - mean) * rstd * gg.y);
-        w.y = pack2((ya[a][4 * g4 + 2] - mean) * rstd * gg.z, (ya[a][4 * g4 + 3] - mean) * rstd * gg.w);
+        w.x = pack_bf16((ya[a][4 * g4] - mean) * rstd * gg.x, (ya[a][4 * g4 + 1] - mean) * rstd * gg.y);
+        w.y = pack_bf16((ya[a][4 * g4 + 2] - mean) * rstd * gg.z, (ya[a][4 * g4 + 3] - mean) * rstd * gg.w);
         *reinterpret_cast<uint2*>(yt + px * G::LDW + c0) = w;
       }
     }
@@ -519,10 +509,10 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
           const uint4 yv = *reinterpret_cast<const uint4*>(yt + row * G::LDW + (part + 4 * i) * 8);
           const uint4 xv = xraw.v[i];
           uint4 o;
-          o.x = pack2(bf_lo(yv.x) + bf_lo(xv.x), bf_hi(yv.x) + bf_hi(xv.x));
-          o.y = pack2(bf_lo(yv.y) + bf_lo(xv.y), bf_hi(yv.y) + bf_hi(xv.y));
-          o.z = pack2(bf_lo(yv.z) + bf_lo(xv.z), bf_hi(yv.z) + bf_hi(xv.z));
-          o.w = pack2(bf_lo(yv.w) + bf_lo(xv.w), bf_hi(yv.w) + bf_hi(xv.w));
+          o.x = pack_bf16(bf_lo(yv.x) + bf_lo(xv.x), bf_hi(yv.x) + bf_hi(xv.x));
+          o.y = pack_bf16(bf_lo(yv.y) + bf_lo(xv.y), bf_hi(yv.y) + bf_hi(xv.y));
+          o.z = pack_bf16(bf_lo(yv.z) + bf_lo(xv.z), bf_hi(yv.z) + bf_hi(xv.z));
+          o.w = pack_bf16(bf_lo(yv.w) + bf_lo(xv.w), bf_hi(yv.w) + bf_hi(xv.w));
           *reinterpret_cast<uint4*>(out + ((int64_t)b * N + (int64_t)t * kTP + row) * C + (part + 4 * i) * 8) = o;
         }
       }
@@ -600,8 +590,8 @@ __global__ __launch_bounds__(256) void full_attn_mfma_kernel(const bf16_t* __res
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
       uint2 w;
-      w.x = pack2(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
-      w.y = pack2(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
+      w.x = pack_bf16(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
+      w.y = pack_bf16(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
       *reinterpret_cast<uint2*>(op + 8 * g4) = w;
     }
   }
@@ -676,8 +666,8 @@ __global__ __launch_bounds__(256) void full_attn_mfma_big_kernel(const bf16_t* _
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
       uint2 w;
-      w.x = pack2(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
-      w.y = pack2(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
+      w.x = pack_bf16(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
+      w.y = pack_bf16(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
       *reinterpret_cast<uint2*>(op + 8 * g4) = w;
     }
   }
@@ -759,7 +749,6 @@ __global__ __launch_bounds__(256, COUT == 64 ? 3 : 2) void resblock_tail_fused_k
   // Two register sets: while tile t is worked on, tiles t+1 and t+2 are on their way (two tiles of reads in flight per
   // block).  h of a later tile is never written before this block has read it: a block writes only its own tiles, after
   // reading them, so `out` may be `h`.
-  typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
   struct Tile { u32x4 x[XV], h[HV]; };
   Tile ta, tb;
   // Every load is issued for every lane, so that the waits on a register set stay counted (a load under a branch makes the
@@ -808,8 +797,8 @@ __global__ __launch_bounds__(256, COUT == 64 ? 3 : 2) void resblock_tail_fused_k
 #pragma unroll
         for (int j = 0; j < 4; ++j) y[j] = Elem<bf16_t>::silu(fmaf(hx[j], a4[j], b4[j])) + (ya[4 * g4 + j] + r4[j]);
         uint2 w;
-        w.x = pack2(y[0], y[1]);
-        w.y = pack2(y[2], y[3]);
+        w.x = pack_bf16(y[0], y[1]);
+        w.y = pack_bf16(y[2], y[3]);
         *reinterpret_cast<uint2*>(hp) = w;            // each (pixel, channel quad) is owned by exactly one lane
       }
     }

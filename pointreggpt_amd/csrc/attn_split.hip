@@ -20,14 +20,14 @@
 #include <cstdlib>
 
 #include "blocks.h"
+#include "wave_ops.h"
 
 namespace prg {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) _Float16 h8;
+typedef f16x8 h8;
 typedef __attribute__((ext_vector_type(4))) _Float16 h4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kTP = 64;              // pixels per tile
 constexpr int kHid = 128;            // heads x dim_head

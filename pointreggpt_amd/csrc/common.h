@@ -60,6 +60,12 @@ struct DeviceOnce {
 };
 int device_cu_count();   // multiProcessorCount of the CURRENT device (cached per device ordinal); 0 on failure
 
+// throughput-mode SiLU: v_exp_f32 + v_rcp_f32 (1 ulp-class, far below bf16 resolution).  The one definition: the bf16 kernels,
+// the f16x3 prologues and wave_ops.h all call it.
+__device__ inline float fast_silu(float x) {
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
+}
+
 template <typename T>
 struct Elem;
 template <>
@@ -75,10 +81,7 @@ struct Elem<bf16_t> {
   static constexpr int kVec = 8;
   __host__ __device__ static inline float load(bf16_t v) { return bf16_to_f32(v); }
   __host__ __device__ static inline bf16_t store(float v) { return f32_to_bf16(v); }
-  // throughput mode: v_exp_f32 + v_rcp_f32 (1 ulp-class, far below bf16 resolution)
-  __device__ static inline float silu(float x) {
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
-  }
+  __device__ static inline float silu(float x) { return fast_silu(x); }   // throughput mode
 };
 
 // 16-byte vector of T with element access as float

@@ -917,13 +917,6 @@ template int launch_stem_conv<bf16_t>(const float*, const float*, const float*, 
 // window goes to LDS once, is expanded to P[row][px] = the 8 consecutive columns px-3 .. px+4 as one 16-byte
 // fragment (hi and lo), and each wave runs 12 MFMAs per 32-pixel row against register-resident weight fragments.
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 stem_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float stem_f32x16;
-__device__ inline uint32_t pack_bf16x2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 // CIN = 1: the denoiser's stem; CIN = 3 (round 5): MaskUnet's stem over the three DepthAugment planes (dc:822) — the same GEMM per
 // input plane, one plane after the other through the same LDS images, the accumulators of the block's eight rows kept in registers
@@ -931,13 +924,12 @@ __device__ inline uint32_t pack_bf16x2(float a, float b) {
 // SPLIT (round 5, dtype f16x3): the same kernel on f16 hi + lo halves (22 significant bits, v_mfma_f32_32x32x16_f16) with a float32
 // NHWC output — the f16x3 mode's stem ran on the direct fmaf kernel (194 us per evaluation at B = 64, 128 x 128: VALU-bound); the
 // weights carry the split packer's per-output-channel power-of-two scale (conv_split.hip), undone on the float32 total (`wscale`).
-typedef __attribute__((ext_vector_type(8))) _Float16 stem_f16x8;
 template <int CIN, bool SPLIT>
 __global__ __launch_bounds__(256) void stem_mfma_kernel(const float* __restrict__ x, const uint16_t* __restrict__ wf,
                                                         const float* __restrict__ bias, const float* __restrict__ wscale,
                                                         void* __restrict__ outv, int H, int W) {
   using E = typename std::conditional<SPLIT, _Float16, __bf16>::type;
-  using EV = typename std::conditional<SPLIT, stem_f16x8, stem_bf16x8>::type;
+  using EV = typename std::conditional<SPLIT, f16x8, bf16x8>::type;
   using OT = typename std::conditional<SPLIT, float, uint16_t>::type;
   constexpr int ROWS = 8, PR = ROWS + 7, RC = 40, LDS_ST = SPLIT ? 68 : 72;
   __shared__ float raw[(ROWS + 6) * RC];
@@ -948,7 +940,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const float* __restrict_
   const int b = blockIdx.z, y0 = blockIdx.y * ROWS, x0 = blockIdx.x * 32, tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int rt = wave & 1, prow = wave >> 1;     // 32-channel row tile; which row of the row pair
-  stem_f32x16 acc[ROWS / 2];
+  f32x16 acc[ROWS / 2];
 #pragma unroll
   for (int ti = 0; ti < ROWS / 2; ++ti)
 #pragma unroll
@@ -1022,8 +1014,8 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const float* __restrict_
         *reinterpret_cast<float4*>(stage + (prow * 32 + l31) * LDS_ST + rt * 32 + 8 * g4 + 4 * hi) = w;
       } else {
         uint2 w;
-        w.x = pack_bf16x2(acc[ti][4 * g4] + bv[4 * g4], acc[ti][4 * g4 + 1] + bv[4 * g4 + 1]);
-        w.y = pack_bf16x2(acc[ti][4 * g4 + 2] + bv[4 * g4 + 2], acc[ti][4 * g4 + 3] + bv[4 * g4 + 3]);
+        w.x = pack_bf16(acc[ti][4 * g4] + bv[4 * g4], acc[ti][4 * g4 + 1] + bv[4 * g4 + 1]);
+        w.y = pack_bf16(acc[ti][4 * g4 + 2] + bv[4 * g4 + 2], acc[ti][4 * g4 + 3] + bv[4 * g4 + 3]);
         *reinterpret_cast<uint2*>(stage + (prow * 32 + l31) * LDS_ST + rt * 32 + 8 * g4 + 4 * hi) = w;
       }
     }

@@ -12,8 +12,8 @@
 // 72 ds_read_b128 per 144 MFMAs; no weight reads, no weight ring, no per-tap barrier).  The workgroup (512 threads, 256 registers per lane) is
 //
 //   waves 0-3  CONSUMERS (2 pixel halves x 2 channel halves of a 8 x 32 pixel x 64 channel tile): 144 MFMAs per tile,
-//              fragments prefetched three reads ahead; epilogue = bias, GroupNorm partial sums (the deterministic butterfly
-//              of conv_ws.hip), bf16 and DIRECT stores: a v_permlane32_swap pairs the two lane halves' channel quads, so
+//              fragments prefetched three reads ahead; epilogue = bias, GroupNorm partial sums (wave_sums<8>, wave_ops.h:
+//              the deterministic butterfly), bf16 and DIRECT stores: pair_chunks pairs the two lane halves' channel quads, so
 //              every lane stores 16 contiguous bytes (no LDS stage, nothing for the producers to drain).  The four pixel
 //              rows' accumulators finish one halo row apart (the row-reuse skew): rows 0-2 are packed, summed and stored
 //              INSIDE the MFMA stream, in the shadows of the next halo row's MFMAs; only row 3, the butterfly and the
@@ -35,42 +35,16 @@
 
 #include "c64_schedule.h"
 #include "conv.h"
+#include "wave_ops.h"
 
 namespace prg {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 c64_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float c64_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int c64_u32x4;
-typedef __attribute__((ext_vector_type(8))) _Float16 c64_f16x8;
-
 namespace {
 
-constexpr int TH = 8, TW = 32, HP = TW + 2, HALO = (TH + 2) * HP;   // 340 halo rows
-constexpr int ROWB = 144;                                              // padded LDS row (64 bf16 = 128 B + 16)
-constexpr int NPT = 256;                                               // producer threads
-constexpr int RPP = NPT / 8;                                           // halo rows per pass
-constexpr int KU = (HALO + RPP - 1) / RPP;                             // 11 units per producer thread
-constexpr size_t AH_BYTES = (size_t)KU * RPP * ROWB;                   // 352 rows: the units past the halo end land in spare rows
+using G = HaloGeom<8, 32, 256>;                                       // 8 x 32 pixel tiles, 256 producer threads: 340 halo rows, 11 units
+constexpr int TH = G::TH, TW = G::TW, HP = G::HP, HALO = G::HALO, ROWB = G::ROWB, RPP = G::RPP, KU = G::KU;
+constexpr size_t AH_BYTES = (size_t)G::HROWS * ROWB;                   // 352 rows: the units past the halo end land in spare rows
 constexpr size_t C64_LDS = 2 * AH_BYTES + 64 * sizeof(float);          // + the bias
-
-__device__ inline float c64_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ inline float c64_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ inline uint32_t c64_pack(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ inline float c64_silu(float x) {
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
-}
-template <int CTRL>
-__device__ inline float c64_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-template <int XOR>
-__device__ inline float c64_swz(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (XOR << 10) | 0x1F));
-}
 
 // tile t of this workgroup: XCD-contiguous runs (workgroup b runs on XCD b % 8; speed only), image-major
 __device__ inline void c64_tile(int t, int tiles_x, int tiles_y, int& b, int& y0, int& x0) {
@@ -80,14 +54,6 @@ __device__ inline void c64_tile(int t, int tiles_x, int tiles_y, int& b, int& y0
   b = t / tiles_y;
   y0 = ty * TH;
   x0 = tx * TW;
-}
-
-// one LDS-visibility point: this wave's LDS operations are done, then the workgroup barrier.  Never waits for VMEM: the
-// producers' halo loads and drain stores stay in flight across it.
-__device__ __forceinline__ void c64_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // The per-image ticket fold below (c64_fold_coefficients, the `ticket` lambda, flags bit 1 = 0: contiguous tile runs) is retired:
@@ -152,7 +118,7 @@ __device__ inline void c64_fold_coefficients(const ConvLaunch<bf16_t>& L, int im
 }
 
 // PRO 0: no prologue; 1: GroupNorm coefficient tables (pro_a / pro_b); 2: coefficients folded here from pro_fold; 3: as 2 on an
-// f16 input with f16 weights (the h16 format, conv.h: packed-f16 prologue, v_mfma_f32_32x32x16_f16).  O16: f16 output.
+// f16 input with f16 weights (the h16 format, conv.h; h16_silu8: packed-f16 prologue, v_mfma_f32_32x32x16_f16).  O16: f16 output.
 template <int PRO, bool O16>
 __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_t> L, const int tiles_x, const int tiles_y,
                                                           const int flags) {
@@ -184,14 +150,14 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     const int wm = wave >> 1, wn = wave & 1;              // pixel half (tile rows 4 wm .. 4 wm + 3), channel half
     const int l31 = lane & 31, hi = lane >> 5;
     // weights of channel wn*32 + l31: 9 taps x 4 k-steps; lane half hi takes k = 16 c + 8 hi .. + 7
-    c64_bf16x8 wf[9][4];
+    bf16x8 wf[9][4];
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const bf16_t* const wsrc = PRO == 3 ? reinterpret_cast<const bf16_t*>(L.w_f16) : L.w;
         const bf16_t* p = wsrc + ((size_t)(tap * d.kchunks + (c >> 1)) * d.CoutPad + wn * 32 + l31) * 32 + (c & 1) * 16 + hi * 8;
-        wf[tap][c] = *reinterpret_cast<const c64_bf16x8*>(p);
+        wf[tap][c] = *reinterpret_cast<const bf16x8*>(p);
       }
     float* const bias_lds = reinterpret_cast<float*>(smem + 2 * AH_BYTES);
     if (tid < 64) bias_lds[tid] = L.bias[tid];             // visible after the prologue barrier
@@ -199,19 +165,19 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     const int gn_per = fuse_stats ? (64 / L.gn_groups) >> 3 : 1;   // 8-channel chunks per group (1, 2, 4 or 8)
     // LDS byte offset of pixel (row 4 wm + pt, column l31), tap (0,0), k-step 0: rows are HP * ROWB apart
     const unsigned x0off = (unsigned)(((wm * 4) * HP + l31) * ROWB + hi * 16);
-    auto mma = [](const c64_bf16x8& a, const c64_bf16x8& b, const c64_f32x16& c) -> c64_f32x16 {
+    auto mma = [](const bf16x8& a, const bf16x8& b, const f32x16& c) -> f32x16 {
       if constexpr (PRO == 3)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(c64_f16x8, a), __builtin_bit_cast(c64_f16x8, b), c, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
       else
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     };
-    c64_barrier();                                         // halo 0 is in LDS (producers' prologue)
+    lds_barrier();                                         // halo 0 is in LDS (producers' prologue)
     for (int s = 0; s < nsteps; ++s) {
       const char* const xb = smem + (size_t)c64_lds_buf(s) * AH_BYTES + x0off;
       // Round 5: the accumulators START at the bias (16 values per lane, re-read from LDS per tile: they are dead again before the
       // fragment sets fill up) instead of at zero — the epilogue's 64 bias additions per tile and wave are gone; the sum's rounding
       // order changes (bias first), far below the bf16 / f16 output rounding.
-      c64_f32x16 acc[4];
+      f32x16 acc[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float4 b4 = *reinterpret_cast<const float4*>(biasp + 8 * q);
@@ -242,18 +208,13 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
           V[q] += v[r];
           V[4 + q] = fmaf(v[r], v[r], V[4 + q]);
         }
-        pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : c64_pack(v[0], v[1]);
-        pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : c64_pack(v[2], v[3]);
+        pk[2 * q] = O16 ? h16_pack(v[0], v[1]) : pack_bf16(v[0], v[1]);
+        pk[2 * q + 1] = O16 ? h16_pack(v[2], v[3]) : pack_bf16(v[2], v[3]);
         if (pin) asm volatile("" : "+v"(V[q]), "+v"(V[4 + q]), "+v"(pk[2 * q]), "+v"(pk[2 * q + 1]));
       };
-      // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper half
-      // of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m, half 1 with
-      // those of chunk 2m+1: one 16-byte store each
+      // chunks 2m and 2m + 1 of pixel row pt: one 16-byte store per lane (pair_chunks)
       auto store_half = [&](const int pt, const int m) __attribute__((always_inline)) {
-        const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-        const c64_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-        *reinterpret_cast<c64_u32x4*>(obase + pt * orow + m * 32) = o;
+        *reinterpret_cast<u32x4*>(obase + pt * orow + m * 32) = pair_chunks(pk[4 * m], pk[4 * m + 1], pk[4 * m + 2], pk[4 * m + 3]);
       };
       // Round 6: ROW REUSE.  Tap (dy, dx) of pixel row pt reads halo row pt + dy: the twelve (pt, dy) pairs of one (dx, k-step) touch
       // only SIX halo rows.  The four accumulators are independent chains, so they are skewed by one tap row: fragment (halo row r,
@@ -266,14 +227,14 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       // epilogue (no LDS in it, so it needs no barrier) is issued in the MFMA shadows of halo row pt + 3: chunk q at fragments 1, 3,
       // 5, 7 of that row, the two stores at fragments 9 and 10.  Only acc[3] is finished behind the barrier.
       constexpr int FD = 3, FR = 4, NF = 72;
-      c64_bf16x8 fr[FR];
+      bf16x8 fr[FR];
       auto foff = [](int n) { return ((n / 12) * HP + (n / 4) % 3) * ROWB + (n & 3) * 32; };   // n = (r * 3 + dx) * 4 + c
 #pragma unroll
-      for (int j = 0; j < FD && j < NF; ++j) fr[j] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(j));
+      for (int j = 0; j < FD && j < NF; ++j) fr[j] = *reinterpret_cast<const bf16x8*>(xb + foff(j));
 #pragma unroll
       for (int n = 0; n < NF; ++n) {
         const int r = n / 12, dx = (n / 4) % 3, c = n & 3;
-        if (n + FD < NF) fr[(n + FD) % FR] = *reinterpret_cast<const c64_bf16x8*>(xb + foff(n + FD));
+        if (n + FD < NF) fr[(n + FD) % FR] = *reinterpret_cast<const bf16x8*>(xb + foff(n + FD));
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
           const int pt = r - dy;
@@ -289,29 +250,18 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       }
       // the partial sums of the previous tile have left this CU before the barrier its ticket is taken behind
       if (fuse_stats && L.gn_tickets) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      c64_barrier();                                       // halo s+1 is written; nobody reads buffer s & 1 any more
+      lds_barrier();                                       // halo s+1 is written; nobody reads buffer s & 1 any more
 #pragma unroll
       for (int q = 0; q < 4; ++q) pack_chunk(3, q, false);
 #pragma unroll
       for (int m = 0; m < 2; ++m) store_half(3, m);
       if (fuse_stats) {
-        // 8 full-wave sums with a halving butterfly (conv_ws.hip's, one level shorter): fixed order, deterministic
-        const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
-        float A4[4], B2[2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) A4[j] = (b0 ? V[4 + j] : V[j]) + c64_dpp<0xB1>(b0 ? V[j] : V[4 + j]);        // lane ^ 1
-#pragma unroll
-        for (int j = 0; j < 2; ++j) B2[j] = (b1 ? A4[2 + j] : A4[j]) + c64_dpp<0x4E>(b1 ? A4[j] : A4[2 + j]);    // lane ^ 2
-        float D = (b2 ? B2[1] : B2[0]) + c64_swz<4>(b2 ? B2[0] : B2[1]);
-        D += c64_swz<8>(D);
-        D += c64_swz<16>(D);
-        D += __shfl_xor(D, 32, 64);
-        // lane (< 8) holds the wave total of value i = 4 b0 + 2 b1 + b2 = [sq][q]: 8-channel chunk q of this wave's 32
-        // channels.  Fold the chunks of one group (per = cpg / 8 <= 4 inside a wave; 8 = both channel halves: two slabs).
+        // lane (< 8) gets the wave total of value i = [sq][q]: 8-channel chunk q of this wave's 32 channels; then the chunks of
+        // one group are folded (per = cpg / 8 <= 4 inside a wave; 8 = both channel halves: two slabs)
+        float D = wave_sums<8>(V, lane);
         const int per = gn_per > 4 ? 4 : gn_per;
-        if (per >= 2) D += c64_swz<4>(D);                  // q ^ 1  (lane bit 2)
-        if (per >= 4) D += c64_dpp<0x4E>(D);               // q ^ 2  (lane bit 1)
-        const int i = (lane & 1) * 4 + (lane & 2) + ((lane >> 2) & 1);
+        D = group_sums<8>(D, per);
+        const int i = wave_sums_index<8>(lane);
         const int q = i & 3;
         if (lane < 8 && (q & (per - 1)) == 0) {
           const int split_n = gn_per > 4 ? 2 : 1;
@@ -334,8 +284,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       }
     }
     if (fuse_stats && L.gn_tickets) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (int p = c64_consumer_pad_barriers(nsteps, DEPTH); p > 0; --p) c64_barrier();   // the producers' padding steps
-    c64_barrier();                                         // matches the producers' final barrier (ticket of the last tile)
+    for (int p = c64_consumer_pad_barriers(nsteps, DEPTH); p > 0; --p) lds_barrier();   // the producers' padding steps
+    lds_barrier();                                         // matches the producers' final barrier (ticket of the last tile)
     return;
   }
 
@@ -374,14 +324,14 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
     // Two register sets: halo h lives in set h & 1.  The loads of halo s+2 are issued BEFORE halo s+1 is transformed and
     // written, so HBM requests are in flight during the prologue arithmetic (with one set the re-issue had to wait for
     // the transform: every CU computed while HBM idled, then every CU loaded — the two times added up).
-    c64_u32x4 hA[KU], hB[KU];
+    u32x4 hA[KU], hB[KU];
     const int tpi = tiles_x * tiles_y;                     // tiles per image
     int done_in_img = 0;                                   // tiles of the current image this workgroup has finished
     unsigned okmask = 0, okmask_nxt = 0;
-    float4 ca[2], cb[2], ca_n[2], cb_n[2];
+    float4 cf[4], nf[4];                                   // A0..3, A4..7, B0..3, B4..7 of the halo being written / issued
     h16x2 ah2[4], bh2[4];                                  // PRO == 3: the coefficients as packed f16 channel pairs
     longlong2 fs_n = make_longlong2(0, 0);                  // PRO == 2: (sum, sumsq) of the 8-channel unit's group, fixed point
-    auto issue = [&](int s, c64_u32x4(&h)[KU]) {           // loads of halo s (clamped to the last tile: harmless reloads)
+    auto issue = [&](int s, u32x4(&h)[KU]) {           // loads of halo s (clamped to the last tile: harmless reloads)
       int b, y0, x0;
       c64_tile(first + c64_tile_of_halo(s, nsteps) * stride, tiles_x, tiles_y, b, y0, x0);
       okmask_nxt = m_valid & ~((y0 == 0 ? m_top : 0u) | (y0 + TH == Hl ? m_bot : 0u) | (x0 == 0 ? m_left : 0u) |
@@ -390,82 +340,48 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
 #pragma unroll
       for (int k = 0; k < KU; ++k)
         h[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, ((okmask_nxt >> k) & 1u) ? voffk[k] : -1, soff, 0);
-      if constexpr (PRO == 1) {
-        const float* pa = L.pro_a + (size_t)b * 64 + slot * 8;
-        const float* pb = L.pro_b + (size_t)b * 64 + slot * 8;
-        ca_n[0] = *reinterpret_cast<const float4*>(pa);
-        ca_n[1] = *reinterpret_cast<const float4*>(pa + 4);
-        cb_n[0] = *reinterpret_cast<const float4*>(pb);
-        cb_n[1] = *reinterpret_cast<const float4*>(pb + 4);
-      }
+      if constexpr (PRO == 1) load_coeffs(nf, L.pro_a + (size_t)b * 64 + slot * 8, L.pro_b + (size_t)b * 64 + slot * 8);
       if constexpr (PRO >= 2) {
         // the raw material of the coefficients: this unit's group statistics and its folded gain / bias (P, Q); the
         // arithmetic happens in adopt(), a step later, when the loads have long landed
         const GnFold& f = L.pro_fold;
-        fs_n = *reinterpret_cast<const longlong2*>(f.acc + ((size_t)b * f.G + (slot * 8) / f.cpg) * 2);
-        const float* pp = f.P + (size_t)b * f.pq_stride + slot * 8;
-        const float* pq = f.Q + (size_t)b * f.pq_stride + slot * 8;
-        ca_n[0] = *reinterpret_cast<const float4*>(pp);
-        ca_n[1] = *reinterpret_cast<const float4*>(pp + 4);
-        cb_n[0] = *reinterpret_cast<const float4*>(pq);
-        cb_n[1] = *reinterpret_cast<const float4*>(pq + 4);
+        fs_n = *group_stats(f, b, slot * 8);
+        load_coeffs(nf, f.P + (size_t)b * f.pq_stride + slot * 8, f.Q + (size_t)b * f.pq_stride + slot * 8);
       }
     };
-    auto write = [&](int s, c64_u32x4(&h)[KU]) {           // halo s -> LDS buffer s & 1
+    auto write = [&](int s, u32x4(&h)[KU]) {           // halo s -> LDS buffer s & 1
       char* dst = ah + (size_t)c64_lds_buf(s) * AH_BYTES;
-      const float a8[8] = {ca[0].x, ca[0].y, ca[0].z, ca[0].w, ca[1].x, ca[1].y, ca[1].z, ca[1].w};
-      const float b8[8] = {cb[0].x, cb[0].y, cb[0].z, cb[0].w, cb[1].x, cb[1].y, cb[1].z, cb[1].w};
+      const float a8[8] = {cf[0].x, cf[0].y, cf[0].z, cf[0].w, cf[1].x, cf[1].y, cf[1].z, cf[1].w};
+      const float b8[8] = {cf[2].x, cf[2].y, cf[2].z, cf[2].w, cf[3].x, cf[3].y, cf[3].z, cf[3].w};
 #pragma unroll
       for (int k = 0; k < KU; ++k) {
-        c64_u32x4 v = h[k];
+        u32x4 v = h[k];
         if constexpr (PRO == 3) {
           v = h16_silu8(v, ah2, bh2);
         } else if constexpr (PRO) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float lo = c64_silu(fmaf(c64_lo(v[j]), a8[2 * j], b8[2 * j]));
-            const float hh = c64_silu(fmaf(c64_hi(v[j]), a8[2 * j + 1], b8[2 * j + 1]));
-            v[j] = c64_pack(lo, hh);
-          }
+          v = silu_affine8(v, a8, b8);
         }
         if constexpr (PRO != 0) {                          // (PRO == 0: the padding units arrived as zeros)
-          if (!((okmask >> k) & 1u)) v = c64_u32x4{0u, 0u, 0u, 0u};
+          if (!((okmask >> k) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
         }
-        *reinterpret_cast<c64_u32x4*>(dst + k * RPP * ROWB) = v;
+        *reinterpret_cast<u32x4*>(dst + k * RPP * ROWB) = v;
       }
     };
     auto adopt = [&]() {                                   // the validity mask and coefficients of the halo about to be written
       okmask = okmask_nxt;
       if constexpr (PRO == 1) {
-        ca[0] = ca_n[0]; ca[1] = ca_n[1]; cb[0] = cb_n[0]; cb[1] = cb_n[1];
-      }
-      if constexpr (PRO >= 2) {                            // A = rstd P, B = Q - mean A
-        float mean, rstd;
-        gn_fold_stats_raw(fs_n.x, fs_n.y, L.pro_fold.inv_n, mean, rstd);
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          ca[h2] = make_float4(rstd * ca_n[h2].x, rstd * ca_n[h2].y, rstd * ca_n[h2].z, rstd * ca_n[h2].w);
-          cb[h2] = make_float4(fmaf(-mean, ca[h2].x, cb_n[h2].x), fmaf(-mean, ca[h2].y, cb_n[h2].y),
-                               fmaf(-mean, ca[h2].z, cb_n[h2].z), fmaf(-mean, ca[h2].w, cb_n[h2].w));
-        }
-        if constexpr (PRO == 3) {
-          typedef __attribute__((ext_vector_type(2))) float f32x2;
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            ah2[2 * h2] = __builtin_convertvector((f32x2){ca[h2].x, ca[h2].y}, h16x2);
-            ah2[2 * h2 + 1] = __builtin_convertvector((f32x2){ca[h2].z, ca[h2].w}, h16x2);
-            bh2[2 * h2] = __builtin_convertvector((f32x2){cb[h2].x, cb[h2].y}, h16x2);
-            bh2[2 * h2 + 1] = __builtin_convertvector((f32x2){cb[h2].z, cb[h2].w}, h16x2);
-          }
-        }
+        for (int j = 0; j < 4; ++j) cf[j] = nf[j];
       }
+      if constexpr (PRO >= 2) fold_coeffs(cf, nf, fs_n, L.pro_fold.inv_n);   // A = rstd P, B = Q - mean A
+      if constexpr (PRO == 3) pack_coeffs_h16(cf, ah2, bh2);
     };
     static_assert(c64_reg_set(0, DEPTH) == 0 && c64_reg_set(1, DEPTH) == 1 && c64_issued_in_step(0, DEPTH) == 2);
     issue(0, hA);                                          // (c64_schedule.h: halo 0, write 0, halo 1)
     adopt();
     write(0, hA);
     issue(1, hB);
-    c64_barrier();                                         // halo 0 ready
+    lds_barrier();                                         // halo 0 ready
     auto ticket = [&](int s) {                             // tile s is complete and its partial sums have left their CU
       if (fuse_stats && L.gn_tickets && ptid < 64) {       // first producer wave: per-image arrival ticket
         const int t = first + s * stride;
@@ -495,15 +411,15 @@ __global__ __launch_bounds__(512) void conv3x3_c64_kernel(const ConvLaunch<bf16_
       adopt();
       issue(s + 2, hA);
       write(s + 1, hB);
-      c64_barrier();                                       // barrier s
+      lds_barrier();                                       // barrier s
       if (s > 0) ticket(s - 1);                            // the consumers stored tile s-1's partial sums before this barrier
       adopt();
       issue(s + 3, hB);
       write(s + 2, hA);
-      c64_barrier();                                       // barrier s+1
+      lds_barrier();                                       // barrier s+1
       if (s < nsteps) ticket(s);
     }
-    c64_barrier();
+    lds_barrier();
     if (n2 == nsteps) ticket(nsteps - 1);
   }
 }

@@ -5,6 +5,7 @@
 
 #include "blocks.h"
 #include "conv.h"
+#include "wave_ops.h"   // bf16x8, f32x16
 
 namespace prg {
 
@@ -13,9 +14,6 @@ namespace prg {
 // (the reference's group_norm computes its moments to ~1e-7).
 template <typename T>
 using StatAcc = std::conditional_t<std::is_same<T, float>::value, double, float>;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // ---------------------------------------------------------------------------------------------
 // shared epilogue

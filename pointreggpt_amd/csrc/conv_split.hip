@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       float v[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
       if (L.pro_a) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = silu_fast(fmaf(v[u], pa[u], pb[u]));
+        for (int u = 0; u < 8; ++u) v[u] = fast_silu(fmaf(v[u], pa[u], pb[u]));
       }
       if (hsrc[k] < 0) {
 #pragma unroll
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
         float v[8] = {h0[k].x, h0[k].y, h0[k].z, h0[k].w, h1[k].x, h1[k].y, h1[k].z, h1[k].w};
         if (L.pro_a) {
 #pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = silu_fast(fmaf(v[u], pa[u], pb[u]));
+          for (int u = 0; u < 8; ++u) v[u] = fast_silu(fmaf(v[u], pa[u], pb[u]));
         }
         if (hsrc[k] < 0) {
 #pragma unroll
@@ -980,7 +980,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
         float v[8] = {g0[k].x, g0[k].y, g0[k].z, g0[k].w, g1[k].x, g1[k].y, g1[k].z, g1[k].w};
         if (L.pro_a) {
 #pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = silu_fast(fmaf(v[u], pa[u], pb[u]));
+          for (int u = 0; u < 8; ++u) v[u] = fast_silu(fmaf(v[u], pa[u], pb[u]));
         }
         if (hsrc[k] < 0) {
 #pragma unroll

@@ -113,8 +113,8 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       float v0 = p == 0 ? hh0[r].x : p == 1 ? hh0[r].z : p == 2 ? hh1[r].x : hh1[r].z;
       float v1 = p == 0 ? hh0[r].y : p == 1 ? hh0[r].w : p == 2 ? hh1[r].y : hh1[r].w;
       if constexpr (PRO) {
-        v0 = silu_fast(fmaf(v0, pa[2 * p], pb[2 * p]));
-        v1 = silu_fast(fmaf(v1, pa[2 * p + 1], pb[2 * p + 1]));
+        v0 = fast_silu(fmaf(v0, pa[2 * p], pb[2 * p]));
+        v1 = fast_silu(fmaf(v1, pa[2 * p + 1], pb[2 * p + 1]));
       }
       if (hsrc[k] < 0) { v0 = 0.0f; v1 = 0.0f; }
       split2<!PRO>(v0, v1, hp2[p], lp2[p]);

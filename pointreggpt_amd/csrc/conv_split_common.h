@@ -1,14 +1,12 @@
 // conv_split_common.h — device helpers shared by the f16x3 convolution kernels (conv_split.hip, conv_split512.hip): the on-the-fly
-// hi / lo split of eight float32 channels, the fused prologue's SiLU, fragment loads, compile-time tap constants and the scheduling
+// hi / lo split of eight float32 channels, fragment loads, compile-time tap constants and the scheduling
 // pipeline that interleaves a consumer's fragment reads with its MFMAs.
 #pragma once
 #include "conv_epi.h"
 
 namespace prg {
 
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef h16x2 f16x2;   // (f16x8, f32x2: wave_ops.h, through conv_epi.h)
 
 // 8 consecutive channels -> their hi and lo halves as two 16-byte MFMA operand units
 template <bool MIX = true>
@@ -38,11 +36,6 @@ __device__ inline void split8(const float (&v)[8], uint4& hi, uint4& lo) {
   }
   hi = __builtin_bit_cast(uint4, h);
   lo = __builtin_bit_cast(uint4, l);
-}
-
-// SiLU of the fused prologue: hardware exp2 / reciprocal (1 ulp each) — ~2e-7 relative, the size of the contraction's own error
-__device__ inline float silu_fast(float x) {
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
 }
 
 __device__ inline f16x8 ld_frag(const uint4* p) { return __builtin_bit_cast(f16x8, *p); }

@@ -9,7 +9,7 @@
 //              accumulators (128 VGPRs); per tap and 16-channel k-step it reads 4 pixel + 2 weight fragments for 8 MFMAs
 //              (0.75 ds_read_b128 per MFMA), prefetched one call (8 MFMAs) ahead, across the phase barrier included.
 //              A phase (one tap of one 64-channel chunk) is 32 MFMAs = 1024 cycles per wave.  Tile end: bias, GroupNorm
-//              partial sums (the halving butterfly of conv_ws.hip), bf16, and DIRECT stores — a v_permlane32_swap pairs
+//              partial sums (w2_tile_stats: the halving butterfly of wave_ops.h), bf16, and DIRECT stores — pair_chunks pairs
 //              the two lane halves' channel quads, so every lane stores 16 contiguous bytes; no LDS stage, no drain;
 //   waves 4-7  PRODUCERS: weight tile ph+2 from registers into a 3-slot LDS ring and the loads of tile ph+5 (three
 //              register sets, three phases = ~3000 cycles between a load and its use); the halo of step s+1 written
@@ -36,58 +36,23 @@
 #include <type_traits>
 
 #include "conv.h"
+#include "wave_ops.h"
 
 namespace prg {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 w2_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float w2_f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int w2_u32x4;
-typedef __attribute__((ext_vector_type(8))) _Float16 w2_f16x8;
-
 namespace {
 
-constexpr int kCH = 64, BN = 128, ROWB = 144;
+constexpr int kCH = 64, BN = 128;
 
 template <int TW>
-struct W2Geom {
-  static constexpr int TH = 256 / TW, HP = TW + 2, HALO = (TH + 2) * HP;
-  static constexpr int NPT = 256, RPP = NPT / 8;             // producer threads; halo rows per pass
-  static constexpr int KU = (HALO + RPP - 1) / RPP;          // halo units per producer thread
-  static constexpr int HROWS = KU * RPP;                     // LDS rows per halo buffer (units past HALO land in the spare rows)
-  static constexpr size_t AH_BYTES = (size_t)HROWS * ROWB;
-  static constexpr size_t BW_BYTES = (size_t)BN * ROWB;
+struct W2Geom : HaloGeom<256 / TW, TW, 256> {
+  using H = HaloGeom<256 / TW, TW, 256>;
+  static constexpr size_t AH_BYTES = (size_t)H::HROWS * H::ROWB;   // LDS bytes per halo buffer (units past HALO land in the spare rows)
+  static constexpr size_t BW_BYTES = (size_t)BN * H::ROWB;
   static constexpr size_t LDS = 2 * AH_BYTES + 3 * BW_BYTES + BN * sizeof(float);
-  static_assert(KU == 11, "unit schedule below");
+  static_assert(H::KU == 11, "unit schedule below");
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
-
-__device__ inline float w2_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ inline float w2_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ inline uint32_t w2_pack(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ inline float w2_silu(float x) {
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
-}
-template <int CTRL>
-__device__ inline float w2_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-template <int XOR>
-__device__ inline float w2_swz(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (XOR << 10) | 0x1F));
-}
-
-// barrier that never waits for VMEM; LDS_DONE: this wave's LDS writes are complete first (producers)
-template <bool LDS_DONE>
-__device__ __forceinline__ void w2_barrier() {
-  if constexpr (LDS_DONE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  else asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // Tile schedule of one workgroup (workgroup b runs on XCD b % 8: observed placement, speed only).  With several output
 // channel tiles every XCD is pinned to ONE of them: its CUs stream the same weight slice, which stays in the XCD's L2.
@@ -118,11 +83,101 @@ struct W2Tiles {
   }
 };
 
+// Producer bookkeeping of both kernels: the step (one 64-channel chunk of one tile) that a halo or a weight tile belongs to.  The
+// producers hold three of them (the steps being consumed, written and issued); past the last step they stay there: harmless reloads.
+struct W2Step { int chunk, it, b, y0, x0, ph; };
+template <int TH, int TW>
+__device__ __forceinline__ W2Step w2_first_step(const W2Tiles& tm) {
+  W2Step s;
+  s.chunk = 0;
+  s.it = 0;
+  tm.decode(0, s.b, s.y0, s.x0, TH, TW);
+  s.ph = tm.phase(0);
+  return s;
+}
+template <int TH, int TW>
+__device__ __forceinline__ void w2_advance(W2Step& si, int& gC, int nsteps, int nchunks, const W2Tiles& tm) {   // gC: index of the last step reached
+  if (gC + 1 < nsteps) {
+    ++gC;
+    if (++si.chunk == nchunks) {
+      si.chunk = 0;
+      ++si.it;
+      tm.decode(si.it, si.b, si.y0, si.x0, TH, TW);
+      si.ph = tm.phase(si.it);
+    }
+  }
+}
+
+// Where the halo of stride-1 step si comes from: the address of channel 0 of its chunk at the halo origin (source pixel of halo
+// position (0, 0); may lie one row / column outside the image: only in-image offsets are ever dereferenced), bytes per source pixel,
+// and which tile edges lie on the image border (bits of hedge[]; 16 = past the halo end).  Hl x Wl: the tiled image; sh: x2 gather.
+template <int TH, int TW>
+__device__ __forceinline__ void w2_halo_source(const ConvLaunch<bf16_t>& L, const W2Step& si, int Hl, int Wl, int sh, const char*& base,
+                                               unsigned& cs2, unsigned& tedge) {
+  const ConvDesc& d = L.d;
+  const int c = si.chunk * kCH;
+  const bool first = c < d.C0;
+  const bf16_t* src = first ? L.src0 : L.src1;
+  const int cs = first ? d.C0 : d.C1;
+  const int cc = first ? c : c - d.C0;
+  cs2 = (unsigned)(cs * 2);
+  tedge = (si.y0 == 0 ? 1u : 0u) | (si.y0 + TH == Hl ? 2u : 0u) | (si.x0 == 0 ? 4u : 0u) | (si.x0 + TW == Wl ? 8u : 0u) | 16u;
+  const int64_t horg = ((int64_t)si.b * d.Hin + (si.y0 >> sh)) * d.Win + (si.x0 >> sh) - (d.Win + 1);
+  base = reinterpret_cast<const char*>(src) + (horg * cs + cc) * 2;
+}
+// ... and its prologue coefficients (8 channels from c0 = the chunk's channel of this thread's unit): the tables, or P / Q / statistics
+// of the in-kernel fold
+__device__ __forceinline__ void w2_coeff_source(const ConvLaunch<bf16_t>& L, bool fold, int b, int c0, const float*& ca, const float*& cb,
+                                                const longlong2*& acc) {
+  if (fold) {
+    const GnFold& f = L.pro_fold;
+    ca = f.P + (size_t)b * f.pq_stride + c0;
+    cb = f.Q + (size_t)b * f.pq_stride + c0;
+    acc = group_stats(f, b, c0);
+  } else {
+    const size_t o = (size_t)b * L.d.C0 + c0;
+    ca = L.pro_a + o;
+    cb = L.pro_b + o;
+  }
+}
+
 // phase p of a step: LDS row offset of its tap inside the halo, and the tap's index in the packed 3 x 3 weights
 template <int MODE, int HP>
 __device__ constexpr int w2_toff(int p) { return MODE == 1 ? (1 + p / 2) * HP + 1 + p % 2 : MODE == 2 ? (p / 2) * HP + p % 2 : (p / 3) * HP + p % 3; }
 template <int MODE>
 __device__ constexpr int w2_tapid(int p) { return MODE == 1 ? (1 + p / 2) * 3 + 1 + p % 2 : p; }
+
+// GroupNorm partial sums of a finished tile (tb, ty0, tx0), both kernels: V = the lane's [sum | sum of squares][ct][q] over its pixels;
+// one (sum, sumsq) per wave and group goes to the fixed-point accumulators or to the wave's slab
+template <int TW>
+__device__ __forceinline__ void w2_tile_stats(const ConvLaunch<bf16_t>& L, const W2Tiles& tm, const float (&V)[16], int tb, int ty0, int tx0,
+                                              int lane, int wm, int wn, int tiles_x, int tiles_y, int gn_per, int gn_per_sh) {
+  constexpr int TH = 256 / TW;
+  // 16 full-wave sums with 17 lane exchanges: wave_sums<16> (wave_ops.h) written out — called from here it changes how the
+  // compiler schedules the hoisted lane-bit masks in the entry block of every kernel of this file (same instructions, other order)
+  const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+  float A8[8], B4[4], C2[2];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + dpp_f32<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
+#pragma unroll
+  for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + dpp_f32<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
+#pragma unroll
+  for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + swz_xor<4>(b2 ? B4[j] : B4[2 + j]);
+  float D = (b3 ? C2[1] : C2[0]) + swz_xor<8>(b3 ? C2[0] : C2[1]);
+  D += swz_xor<16>(D);
+  D += __shfl_xor(D, 32, 64);
+  // lane (< 16) holds the wave total of value i = [sq][ct][q]; the chunks of one group are folded
+  D = group_sums<16>(D, gn_per);
+  const int i = wave_sums_index<16>(lane);
+  const int cc = i & 7;
+  if (lane < 16 && (cc & (gn_per - 1)) == 0) {
+    const int nsplit = tiles_x * tiles_y * 2;
+    const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
+    const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
+    if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
+    else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
+  }
+}
 
 // PRO 0: no prologue, 1: coefficient tables, 2: coefficients folded in-kernel (pro_fold), 3: as 2 on an f16 input with f16
 // weights (the h16 format of conv.h: packed-f16 prologue, v_mfma_f32_32x32x16_f16).  L.out_f16: f16 output (run-time flag).
@@ -136,7 +191,7 @@ template <int TW, int PRO, int MODE>
 __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16_t> L, const int tiles_x, const int tiles_y,
                                                            const int tiles_n, const int fuse_stats) {
   using G = W2Geom<TW>;
-  constexpr int TH = G::TH, HP = G::HP, KU = G::KU, RPP = G::RPP;
+  constexpr int TH = G::TH, HP = G::HP, KU = G::KU, RPP = G::RPP, ROWB = G::ROWB;
   constexpr int AH = (int)G::AH_BYTES, BW = (int)G::BW_BYTES;
   // phases (taps) per step; steps per loop iteration: the weight ring slot / register set of global tile NPH g + p is
   // (NPH g + p) % 3, a compile-time value once g % UNR is one (9 = 0, 4 = 1 mod 3)
@@ -190,29 +245,29 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     const int gn_per = fuse_stats ? (d.Cout / L.gn_groups) >> 3 : 1;   // 8-channel chunks per GroupNorm group
     const int gn_per_sh = 31 - __builtin_clz(gn_per);
     if (wn >= nwn) {                                         // idle channel half: only the barriers
-      for (int i = 0; i < 1 + nsteps_pad * NPH; ++i) w2_barrier<false>();
+      for (int i = 0; i < 1 + nsteps_pad * NPH; ++i) lds_barrier<false>();
       return;
     }
-    w2_f32x16 acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
       for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[ct][pt][e] = 0.0f;
-    w2_bf16x8 fw[2][2], fx[2][4];
-#define W2_LW(SET, CT, RING, CALL) fw[SET][CT] = *reinterpret_cast<const w2_bf16x8*>(wr + (RING) * BW + (CT) * 32 * ROWB + (CALL) * 32)
-#define W2_LX(SET, PT, BASE, TOFF, CALL) fx[SET][PT] = *reinterpret_cast<const w2_bf16x8*>(BASE + (PT) * PTB + (TOFF) * ROWB + (CALL) * 32)
+    bf16x8 fw[2][2], fx[2][4];
+#define W2_LW(SET, CT, RING, CALL) fw[SET][CT] = *reinterpret_cast<const bf16x8*>(wr + (RING) * BW + (CT) * 32 * ROWB + (CALL) * 32)
+#define W2_LX(SET, PT, BASE, TOFF, CALL) fx[SET][PT] = *reinterpret_cast<const bf16x8*>(BASE + (PT) * PTB + (TOFF) * ROWB + (CALL) * 32)
 #define W2_MM(SET, CT, PT)                                                                                                              \
   do {                                                                                                                                    \
     if constexpr (PRO == 3)                                                                                                               \
-      acc[CT][PT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(w2_f16x8, fw[SET][CT]), __builtin_bit_cast(w2_f16x8, fx[SET][PT]), \
+      acc[CT][PT] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fw[SET][CT]), __builtin_bit_cast(f16x8, fx[SET][PT]), \
                                                            acc[CT][PT], 0, 0, 0);                                                         \
     else                                                                                                                                  \
       acc[CT][PT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[SET][CT], fx[SET][PT], acc[CT][PT], 0, 0, 0);                              \
   } while (0)
 #define W2_SB() __builtin_amdgcn_sched_barrier(0)
-    w2_barrier<true>();                                      // halo 0 and weight tiles 0, 1 are in LDS; the bias too
+    lds_barrier<true>();                                      // halo 0 and weight tiles 0, 1 are in LDS; the bias too
     // Round 5: the accumulators START at the bias (here, and again at the end of every tile's epilogue, where the bias registers are
     // live anyway) instead of at zero: the epilogue's 128 bias additions per tile and wave are gone; the sum's rounding order changes
     // (bias first), far below the bf16 / f16 output rounding.
@@ -308,51 +363,18 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
                   pk[2 * q] = h16_pack(v[0], v[1]);
                   pk[2 * q + 1] = h16_pack(v[2], v[3]);
                 } else {
-                  pk[2 * q] = w2_pack(v[0], v[1]);
-                  pk[2 * q + 1] = w2_pack(v[2], v[3]);
+                  pk[2 * q] = pack_bf16(v[0], v[1]);
+                  pk[2 * q + 1] = pack_bf16(v[2], v[3]);
                 }
               }
-              // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
-              // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
-              // half 1 with those of chunk 2m+1 — one 16-byte store each.
 #pragma unroll
-              for (int m = 0; m < 2; ++m) {
-                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-                const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-                *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
-              }
+              for (int m = 0; m < 2; ++m)   // chunks 2m and 2m + 1: one 16-byte store per lane (pair_chunks)
+                *reinterpret_cast<u32x4*>(obase + pt * optb + ct * 64 + m * 32) = pair_chunks(pk[4 * m], pk[4 * m + 1], pk[4 * m + 2], pk[4 * m + 3]);
             }
           }
-          if (fuse_stats) {
-            // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
-            const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-            float A8[8], B4[4], C2[2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
-#pragma unroll
-            for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
-#pragma unroll
-            for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
-            float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
-            D += w2_swz<16>(D);
-            D += __shfl_xor(D, 32, 64);
-            // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
-            if (gn_per >= 2) D += w2_swz<8>(D);
-            if (gn_per >= 4) D += w2_swz<4>(D);
-            if (gn_per >= 8) D += w2_dpp<0x4E>(D);
-            const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
-            const int cc = i & 7;
-            if (lane < 16 && (cc & (gn_per - 1)) == 0) {
-              const int nsplit = tiles_x * tiles_y * 2;
-              const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
-              const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
-              if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
-              else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
-            }
-          }
+          if (fuse_stats) w2_tile_stats<TW>(L, tm, V, tb, ty0, tx0, lane, wm, wn, tiles_x, tiles_y, gn_per, gn_per_sh);
         }
-        w2_barrier<false>();   // every LDS read of this phase has been consumed by an MFMA above
+        lds_barrier<false>();   // every LDS read of this phase has been consumed by an MFMA above
       }
       { const char* t = xa; xa = xn; xn = t; }
       if constexpr (MODE == 2) {                             // xn (the buffer just left) serves step s + 2 next: its tile's phase
@@ -371,9 +393,9 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
       cstep(std::integral_constant<int, 0>{});
       if constexpr (UNR == 3) {
         if (g + 1 < nsteps) cstep(std::integral_constant<int, 1>{});
-        else for (int i = 0; i < NPH; ++i) w2_barrier<false>();
+        else for (int i = 0; i < NPH; ++i) lds_barrier<false>();
         if (g + 2 < nsteps) cstep(std::integral_constant<int, 2>{});
-        else for (int i = 0; i < NPH; ++i) w2_barrier<false>();
+        else for (int i = 0; i < NPH; ++i) lds_barrier<false>();
       }
     }
 #undef W2_LW
@@ -407,30 +429,15 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     const unsigned w_voff = (unsigned)((((slot >> 2) * d.CoutPad + row) * 32 + (slot & 3) * 8) * 2);
     const int wj_mask = (nwn == 2 && !dual) ? 3 : 1;         // Cout = 64: only 64 weight rows exist (the upper ones are re-read)
     const size_t wsub = (size_t)4 * wkch * d.CoutPad * 64;   // dual: bytes between the packings of two phases (rows 64-127 = phase dx = 1)
-    struct StepInfo { int chunk, it, b, y0, x0, ph; };
     int gC = 0;
-    auto advance = [&](StepInfo& si) {                       // past the last step it stays there: harmless reloads
-      if (gC + 1 < nsteps) {
-        ++gC;
-        if (++si.chunk == nchunks) {
-          si.chunk = 0;
-          ++si.it;
-          tm.decode(si.it, si.b, si.y0, si.x0, TH, TW);
-          si.ph = tm.phase(si.it);
-        }
-      }
-    };
-    StepInfo sA;
-    sA.chunk = 0;
-    sA.it = 0;
-    tm.decode(0, sA.b, sA.y0, sA.x0, TH, TW);
-    sA.ph = tm.phase(0);
-    StepInfo sB = sA;
+    auto advance = [&](W2Step& si) { w2_advance<TH, TW>(si, gC, nsteps, nchunks, tm); };
+    W2Step sA = w2_first_step<TH, TW>(tm);
+    W2Step sB = sA;
     advance(sB);
-    StepInfo sC = sB;
+    W2Step sC = sB;
     advance(sC);
 
-    w2_u32x4 wset[3][4], hreg[KU];
+    u32x4 wset[3][4], hreg[KU];
     float4 cf[4], nf[4];                                     // a0..3, a4..7, b0..3, b4..7 of the halo being written / issued
     unsigned hvalid = 0, hvalid_nxt = 0;
     const char* ld_base = nullptr;
@@ -441,34 +448,24 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     // pro_fold (common.h, GnFold): ld_ca / ld_cb point at P / Q and the coefficients are folded here from the image group's
     // fixed-point statistics (ld_acc) when a halo's coefficients are adopted: A = rstd P, B = Q - mean A
     constexpr bool pfold = PRO >= 2;
-    const long long* ld_acc = nullptr;
+    const longlong2* ld_acc = nullptr;
     longlong2 nacc = make_longlong2(0, 0);
     h16x2 ah2[4], bh2[4];                                    // PRO == 3: the adopted coefficients as packed f16 channel pairs
     auto fold_inplace = [&](float4* c) {
       if constexpr (PRO) {
-        if (pfold) {
-          float mean, rstd;
-          gn_fold_stats_raw(nacc.x, nacc.y, L.pro_fold.inv_n, mean, rstd);
+        if (pfold) fold_coeffs(c, c, nacc, L.pro_fold.inv_n);
+        if constexpr (PRO == 3) {   // pack_coeffs_h16 (wave_ops.h) written out: as a call it changes this kernel's register allocation
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {
-            c[h2] = make_float4(rstd * c[h2].x, rstd * c[h2].y, rstd * c[h2].z, rstd * c[h2].w);
-            c[2 + h2] = make_float4(fmaf(-mean, c[h2].x, c[2 + h2].x), fmaf(-mean, c[h2].y, c[2 + h2].y),
-                                    fmaf(-mean, c[h2].z, c[2 + h2].z), fmaf(-mean, c[h2].w, c[2 + h2].w));
-          }
-        }
-        if constexpr (PRO == 3) {
-          typedef __attribute__((ext_vector_type(2))) float f32x2;
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            ah2[2 * h2] = __builtin_convertvector((f32x2){c[h2].x, c[h2].y}, h16x2);
-            ah2[2 * h2 + 1] = __builtin_convertvector((f32x2){c[h2].z, c[h2].w}, h16x2);
-            bh2[2 * h2] = __builtin_convertvector((f32x2){c[2 + h2].x, c[2 + h2].y}, h16x2);
-            bh2[2 * h2 + 1] = __builtin_convertvector((f32x2){c[2 + h2].z, c[2 + h2].w}, h16x2);
+            ah2[2 * h2] = h16_pair(c[h2].x, c[h2].y);
+            ah2[2 * h2 + 1] = h16_pair(c[h2].z, c[h2].w);
+            bh2[2 * h2] = h16_pair(c[2 + h2].x, c[2 + h2].y);
+            bh2[2 * h2 + 1] = h16_pair(c[2 + h2].z, c[2 + h2].w);
           }
         }
       }
     };
-    auto issue_setup = [&](const StepInfo& si) {
+    auto issue_setup = [&](const W2Step& si) {
       if constexpr (MODE == 1) {
         // chunk = sub-pixel (dy, dx) of the 2 x 2 blocks, then 64 of its C0 channels.  Virtual pixel (y', x') of the chunk
         // is source pixel (2 y' + dy - 1, 2 x' + dx - 1): outside the image for y' = 0 with dy = 0 and for y' = Hout
@@ -481,45 +478,23 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
         const int64_t horg = ((int64_t)si.b * d.Hin + 2 * si.y0 + dy - 3) * d.Win + 2 * si.x0 + dx - 3;   // halo position (0, 0)
         ld_base = reinterpret_cast<const char*>(L.src0) + (horg * d.C0 + cc) * 2;
       } else {
-        const int c = si.chunk * kCH;
-        const bool first = c < d.C0;
-        const bf16_t* src = first ? L.src0 : L.src1;
-        const int cs = first ? d.C0 : d.C1;
-        const int cc = first ? c : c - d.C0;
-        ld_cs2 = (unsigned)(cs * 2);
-        ld_tedge = (si.y0 == 0 ? 1u : 0u) | (si.y0 + TH == Hl ? 2u : 0u) | (si.x0 == 0 ? 4u : 0u) | (si.x0 + TW == Wl ? 8u : 0u) | 16u;
-        const int sh = MODE == 2 ? 0 : d.ups;                 // (MODE 2: tile origins are source coordinates already)
-        const int64_t horg = ((int64_t)si.b * d.Hin + (si.y0 >> sh)) * d.Win + (si.x0 >> sh) - (d.Win + 1);
-        ld_base = reinterpret_cast<const char*>(src) + (horg * cs + cc) * 2;
+        w2_halo_source<TH, TW>(L, si, Hl, Wl, MODE == 2 ? 0 : d.ups, ld_base, ld_cs2, ld_tedge);   // (MODE 2: tile origins are source coordinates already)
       }
       ld_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ld_base), 0, 0x7ffffff0, 0x00020000);   // (base may lie before the tensor: only in-image offsets are ever in range AND valid)
       if constexpr (PRO) {
-        const int c0 = si.chunk * kCH + slot * 8;
-        if (pfold) {
-          const GnFold& f = L.pro_fold;
-          ld_ca = f.P + (size_t)si.b * f.pq_stride + c0;
-          ld_cb = f.Q + (size_t)si.b * f.pq_stride + c0;
-          ld_acc = f.acc + ((size_t)si.b * f.G + c0 / f.cpg) * 2;
-        } else {
-          const size_t o = (size_t)si.b * d.C0 + c0;
-          ld_ca = L.pro_a + o;
-          ld_cb = L.pro_b + o;
-        }
+        w2_coeff_source(L, pfold, si.b, si.chunk * kCH + slot * 8, ld_ca, ld_cb, ld_acc);
       }
       hvalid_nxt = 0;
     };
     auto issue_coeffs = [&](float4* dst) {
       if constexpr (PRO) {
-        dst[0] = *reinterpret_cast<const float4*>(ld_ca);
-        dst[1] = *reinterpret_cast<const float4*>(ld_ca + 4);
-        dst[2] = *reinterpret_cast<const float4*>(ld_cb);
-        dst[3] = *reinterpret_cast<const float4*>(ld_cb + 4);
-        if (pfold) nacc = *reinterpret_cast<const longlong2*>(ld_acc);
+        load_coeffs(dst, ld_ca, ld_cb);
+        if (pfold) nacc = *ld_acc;
       }
     };
     // Raw BUFFER loads from a descriptor based at the halo origin (round 3): a padding unit gets offset 0xffffffff and the
     // hardware's range check returns zeros — no always-mapped stand-in pixel, and without a prologue no select before the
-    // LDS write either (conv_c64.hip's producers, same idea).
+    // LDS write either (as conv_c64.hip's producers do, with one descriptor for the whole tensor).
     auto issue_unit = [&](int k) {                           // k is a compile-time constant at every call site
       const bool ok = (hedge[k] & ld_tedge) == 0;
       const unsigned voff = (__umul24(hpix[k], ld_cs2) + (unsigned)(slot * 16)) | (ok ? 0u : 0xffffffffu);   // (branch-free)
@@ -527,23 +502,18 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
       if constexpr (PRO) hvalid_nxt |= (ok ? 1u : 0u) << k;
     };
     auto write_unit = [&](int k, int bufoff) {
-      w2_u32x4 v = hreg[k];
+      u32x4 v = hreg[k];
       if constexpr (PRO == 3) {
         v = h16_silu8(v, ah2, bh2);
       } else if constexpr (PRO) {
         const float a8[8] = {cf[0].x, cf[0].y, cf[0].z, cf[0].w, cf[1].x, cf[1].y, cf[1].z, cf[1].w};
         const float b8[8] = {cf[2].x, cf[2].y, cf[2].z, cf[2].w, cf[3].x, cf[3].y, cf[3].z, cf[3].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float lo = w2_silu(fmaf(w2_lo(v[j]), a8[2 * j], b8[2 * j]));
-          const float hh = w2_silu(fmaf(w2_hi(v[j]), a8[2 * j + 1], b8[2 * j + 1]));
-          v[j] = w2_pack(lo, hh);
-        }
+        v = silu_affine8(v, a8, b8);
       }
       if constexpr (PRO) {                                   // (padding must be zero AFTER the transform; without one it arrived as zeros)
-        if (!((hvalid >> k) & 1u)) v = w2_u32x4{0u, 0u, 0u, 0u};
+        if (!((hvalid >> k) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
       }
-      *reinterpret_cast<w2_u32x4*>(Ah0 + bufoff + k * RPP * ROWB) = v;
+      *reinterpret_cast<u32x4*>(Ah0 + bufoff + k * RPP * ROWB) = v;
     };
     // weight tile of phase `ph` (its tap in the packed 3 x 3 layout) and 64-channel chunk; MODE 2: of sub-pixel `sub`'s 2 x 2 packing
     auto w_tile = [&](int ph, int chunk, int sub) -> const char* {
@@ -553,11 +523,11 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     auto w_issue = [&](int set, const char* p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        wset[set][j] = *reinterpret_cast<const w2_u32x4*>(p + (j & wj_mask) * 2048 + ((dual && j >= 2) ? wsub : (size_t)0));
+        wset[set][j] = *reinterpret_cast<const u32x4*>(p + (j & wj_mask) * 2048 + ((dual && j >= 2) ? wsub : (size_t)0));
     };
     auto w_write = [&](int set, int ring) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) *reinterpret_cast<w2_u32x4*>(Bw0 + ring * BW + j * 32 * ROWB) = wset[set][j];
+      for (int j = 0; j < 4; ++j) *reinterpret_cast<u32x4*>(Bw0 + ring * BW + j * 32 * ROWB) = wset[set][j];
     };
     // global weight tile t (t < 3 NPH) belongs to step t / NPH of (sA, sB, sC)
     auto chunk_of = [&](int t) { return t < NPH ? sA.chunk : t < 2 * NPH ? sB.chunk : sC.chunk; };
@@ -588,7 +558,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
     w_issue(0, w_tile(3 % NPH, chunk_of(3), sub_of(3)));
     w_issue(1, w_tile(4 % NPH, chunk_of(4), sub_of(4)));
     issue_setup(sC);
-    w2_barrier<true>();
+    lds_barrier<true>();
 
     // units of halo s+1 written (and re-issued for halo s+2) in phases 0 .. NPH-2: 2 2 2 1 1 1 1 1 (nine taps), 4 4 3 (four)
     constexpr int US9[10] = {0, 2, 4, 6, 7, 8, 9, 10, 11, 11};
@@ -617,7 +587,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256_kernel(const ConvLaunch<bf16
           advance(sC);
           issue_setup(sC);
         }
-        w2_barrier<true>();
+        lds_barrier<true>();
       }
     };
 #pragma unroll 1
@@ -649,13 +619,12 @@ typedef __attribute__((ext_vector_type(8))) int w2_i32x8;
 constexpr int MXROW = 80;
 
 template <int TW>
-struct W2MxGeom {
-  static constexpr int TH = 256 / TW, HP = TW + 2, HALO = (TH + 2) * HP;
-  static constexpr int RPP = 32, KU = (HALO + RPP - 1) / RPP, HROWS = KU * RPP;
-  static constexpr int AH = HROWS * MXROW, BW = BN * MXROW, HS = HROWS * 2, WS = BN * 2;
+struct W2MxGeom : HaloGeom<256 / TW, TW, 256, MXROW> {   // the same halo in rows of MXROW bytes (64 fp8 channels)
+  using H = HaloGeom<256 / TW, TW, 256, MXROW>;
+  static constexpr int AH = H::HROWS * MXROW, BW = BN * MXROW, HS = H::HROWS * 2, WS = BN * 2;
   static constexpr int OFF_B = 2 * AH, OFF_HS = OFF_B + 3 * BW, OFF_WS = OFF_HS + 2 * HS, OFF_BIAS = OFF_WS + 3 * WS;
   static constexpr size_t LDS = OFF_BIAS + BN * sizeof(float);
-  static_assert(KU == 11 && HS % 16 == 0 && WS % 16 == 0, "layout");
+  static_assert(H::KU == 11 && HS % 16 == 0 && WS % 16 == 0, "layout");
 };
 
 __device__ inline uint32_t w2_cvt4(float a, float b, float c, float d) {
@@ -698,7 +667,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     if (tid < BN) bias_lds[tid] = L.bias[tm.tn * BN + tid];
     const int gn_per = fuse_stats ? (d.Cout / L.gn_groups) >> 3 : 1;
     const int gn_per_sh = 31 - __builtin_clz(gn_per);
-    w2_f32x16 acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -725,7 +694,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
 #define W2X_MM(SET, CT, PT) \
   acc[CT][PT] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[SET][CT], fx[PT], acc[CT][PT], 0, 0, 0, sw[SET][CT], 0, sx[PT])
 #define W2X_SB() __builtin_amdgcn_sched_barrier(0)
-    w2_barrier<true>();                                      // halo 0, weight tiles 0 and 1, the bias
+    lds_barrier<true>();                                      // halo 0, weight tiles 0 and 1, the bias
     ldw(0, 0, 0); ldx(0, xa, sa, 0); ldw(0, 1, 0); ldx(1, xa, sa, 0); ldx(2, xa, sa, 0); ldx(3, xa, sa, 0);
     int chunk = 0, it = 0;
     // nine phases per step: the weight set of phase p alternates with the step parity GP -> two steps per loop iteration
@@ -747,6 +716,8 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
         ldx(3, bd, bs, toffN); W2X_SB();
         if (p == 8 && tile_end) {
           // tile finished.  Lane holds pixel (group pt, lpx), channels ct*32 + 8q + 4hi + {0..3} of the wave's 64.
+          // (conv3x3_w256_kernel's tile end with the bias added here.  Written twice: as one function the loops are unswitched
+          //  on the f16-output flag: the bf16 kernel's MODE 0 instantiations grow by 45 instructions, this kernel spills 2 VGPRs.)
           int tb, ty0, tx0;
           tm.decode(it, tb, ty0, tx0, TH, TW);
           char* const obase = reinterpret_cast<char*>(L.out) +
@@ -776,50 +747,17 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
                   V[8 + ct * 4 + q] = fmaf(v[r], v[r], V[8 + ct * 4 + q]);
                   acc[ct][pt][4 * q + r] = 0.0f;
                 }
-                pk[2 * q] = w2_pack(v[0], v[1]);
-                pk[2 * q + 1] = w2_pack(v[2], v[3]);
+                pk[2 * q] = pack_bf16(v[0], v[1]);
+                pk[2 * q + 1] = pack_bf16(v[2], v[3]);
               }
-              // lanes l and l + 32 hold the two channel quads of the same pixel and 8-channel chunk q: swapping the upper
-              // half of chunk 2m with the lower half of chunk 2m+1 leaves lane half 0 with all 8 channels of chunk 2m and
-              // half 1 with those of chunk 2m+1 — one 16-byte store each.
 #pragma unroll
-              for (int m = 0; m < 2; ++m) {
-                const auto s0 = __builtin_amdgcn_permlane32_swap(pk[4 * m], pk[4 * m + 2], false, false);
-                const auto s1 = __builtin_amdgcn_permlane32_swap(pk[4 * m + 1], pk[4 * m + 3], false, false);
-                const w2_u32x4 o = {(uint32_t)s0[0], (uint32_t)s1[0], (uint32_t)s0[1], (uint32_t)s1[1]};
-                *reinterpret_cast<w2_u32x4*>(obase + pt * optb + ct * 64 + m * 32) = o;
-              }
+              for (int m = 0; m < 2; ++m)   // chunks 2m and 2m + 1: one 16-byte store per lane (pair_chunks)
+                *reinterpret_cast<u32x4*>(obase + pt * optb + ct * 64 + m * 32) = pair_chunks(pk[4 * m], pk[4 * m + 1], pk[4 * m + 2], pk[4 * m + 3]);
             }
           }
-          if (fuse_stats) {
-            // 16 full-wave sums with 17 lane exchanges (the halving butterfly of conv_ws.hip): fixed order, deterministic
-            const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-            float A8[8], B4[4], C2[2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + w2_dpp<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
-#pragma unroll
-            for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + w2_dpp<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
-#pragma unroll
-            for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + w2_swz<4>(b2 ? B4[j] : B4[2 + j]);
-            float D = (b3 ? C2[1] : C2[0]) + w2_swz<8>(b3 ? C2[0] : C2[1]);
-            D += w2_swz<16>(D);
-            D += __shfl_xor(D, 32, 64);
-            // lane (< 16) holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]
-            if (gn_per >= 2) D += w2_swz<8>(D);
-            if (gn_per >= 4) D += w2_swz<4>(D);
-            if (gn_per >= 8) D += w2_dpp<0x4E>(D);
-            const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
-            const int cc = i & 7;
-            if (lane < 16 && (cc & (gn_per - 1)) == 0) {
-              const int nsplit = tiles_x * tiles_y * 2;
-              const int slab = ((ty0 / TH) * tiles_x + tx0 / TW) * 2 + wm;
-              const int grp = (((tm.tn * BN + wn * 64) >> 3) + cc) >> gn_per_sh;
-              if (L.gn_acc) gn_acc_add(L.gn_acc, L.gn_groups, tb, grp, i >> 3, D);   // fixed-point accumulators (common.h)
-              else L.gn_partials[(((size_t)tb * nsplit + slab) * L.gn_groups + grp) * 2 + (i >> 3)] = D;
-            }
-          }
+          if (fuse_stats) w2_tile_stats<TW>(L, tm, V, tb, ty0, tx0, lane, wm, wn, tiles_x, tiles_y, gn_per, gn_per_sh);
         }
-        w2_barrier<false>();
+        lds_barrier<false>();
       }
       { const char* t = xa; xa = xn; xn = t; t = sa; sa = sn; sn = t; }
       if (++chunk == nchunks) {
@@ -858,28 +796,15 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     char* const Bw0 = smem + G::OFF_B + (ptid >> 2) * MXROW + (ptid & 3) * 16;
     char* const Ws0 = smem + G::OFF_WS + (ptid & 15) * 16;
     const unsigned ld_dummy = (unsigned)(d.Win + 1);
-    struct StepInfo { int chunk, it, b, y0, x0; };
     int gC = 0;
-    auto advance = [&](StepInfo& si) {
-      if (gC + 1 < nsteps) {
-        ++gC;
-        if (++si.chunk == nchunks) {
-          si.chunk = 0;
-          ++si.it;
-          tm.decode(si.it, si.b, si.y0, si.x0, TH, TW);
-        }
-      }
-    };
-    StepInfo sA;
-    sA.chunk = 0;
-    sA.it = 0;
-    tm.decode(0, sA.b, sA.y0, sA.x0, TH, TW);
-    StepInfo sB = sA;
+    auto advance = [&](W2Step& si) { w2_advance<TH, TW>(si, gC, nsteps, nchunks, tm); };
+    W2Step sA = w2_first_step<TH, TW>(tm);
+    W2Step sB = sA;
     advance(sB);
-    StepInfo sC = sB;
+    W2Step sC = sB;
     advance(sC);
 
-    w2_u32x4 wset[3][2], wsc[3], hreg[KU];
+    u32x4 wset[3][2], wsc[3], hreg[KU];
     float4 cf[4], nf[4];
     unsigned hvalid = 0, hvalid_nxt = 0;
     const char* ld_base = nullptr;
@@ -889,61 +814,31 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     // pro_fold (common.h, GnFold): ld_ca / ld_cb point at P / Q and the coefficients are folded here from the image group's
     // fixed-point statistics (ld_acc) when a halo's coefficients are adopted: A = rstd P, B = Q - mean A
     constexpr bool pfold = PRO == 2;
-    const long long* ld_acc = nullptr;
+    const longlong2* ld_acc = nullptr;
     longlong2 nacc = make_longlong2(0, 0);
     auto fold_inplace = [&](float4* c) {
       if constexpr (PRO) {
-        if (pfold) {
-          float mean, rstd;
-          gn_fold_stats_raw(nacc.x, nacc.y, L.pro_fold.inv_n, mean, rstd);
-#pragma unroll
-          for (int h2 = 0; h2 < 2; ++h2) {
-            c[h2] = make_float4(rstd * c[h2].x, rstd * c[h2].y, rstd * c[h2].z, rstd * c[h2].w);
-            c[2 + h2] = make_float4(fmaf(-mean, c[h2].x, c[2 + h2].x), fmaf(-mean, c[h2].y, c[2 + h2].y),
-                                    fmaf(-mean, c[h2].z, c[2 + h2].z), fmaf(-mean, c[h2].w, c[2 + h2].w));
-          }
-        }
+        if (pfold) fold_coeffs(c, c, nacc, L.pro_fold.inv_n);
       }
     };
-    auto issue_setup = [&](const StepInfo& si) {
-      const int c = si.chunk * kCH;
-      const bool first = c < d.C0;
-      const bf16_t* src = first ? L.src0 : L.src1;
-      const int cs = first ? d.C0 : d.C1;
-      const int cc = first ? c : c - d.C0;
-      ld_cs2 = (unsigned)(cs * 2);
-      ld_tedge = (si.y0 == 0 ? 1u : 0u) | (si.y0 + TH == Hl ? 2u : 0u) | (si.x0 == 0 ? 4u : 0u) | (si.x0 + TW == Wl ? 8u : 0u) | 16u;
-      const int64_t horg = ((int64_t)si.b * d.Hin + (si.y0 >> d.ups)) * d.Win + (si.x0 >> d.ups) - (d.Win + 1);
-      ld_base = reinterpret_cast<const char*>(src) + (horg * cs + cc) * 2;
+    auto issue_setup = [&](const W2Step& si) {
+      w2_halo_source<TH, TW>(L, si, Hl, Wl, d.ups, ld_base, ld_cs2, ld_tedge);
       if constexpr (PRO) {
-        const int c0 = si.chunk * kCH + slot * 8;
-        if (pfold) {
-          const GnFold& f = L.pro_fold;
-          ld_ca = f.P + (size_t)si.b * f.pq_stride + c0;
-          ld_cb = f.Q + (size_t)si.b * f.pq_stride + c0;
-          ld_acc = f.acc + ((size_t)si.b * f.G + c0 / f.cpg) * 2;
-        } else {
-          const size_t o = (size_t)si.b * d.C0 + c0;
-          ld_ca = L.pro_a + o;
-          ld_cb = L.pro_b + o;
-        }
+        w2_coeff_source(L, pfold, si.b, si.chunk * kCH + slot * 8, ld_ca, ld_cb, ld_acc);
       }
       hvalid_nxt = 0;
     };
     auto issue_coeffs = [&](float4* dst) {
       if constexpr (PRO) {
-        dst[0] = *reinterpret_cast<const float4*>(ld_ca);
-        dst[1] = *reinterpret_cast<const float4*>(ld_ca + 4);
-        dst[2] = *reinterpret_cast<const float4*>(ld_cb);
-        dst[3] = *reinterpret_cast<const float4*>(ld_cb + 4);
-        if (pfold) nacc = *reinterpret_cast<const longlong2*>(ld_acc);
+        load_coeffs(dst, ld_ca, ld_cb);
+        if (pfold) nacc = *ld_acc;
       }
     };
     auto issue_unit = [&](int k) {
       const bool ok = (hedge[k] & ld_tedge) == 0;
       const unsigned pix = ok ? hpix[k] : ld_dummy;
       const unsigned voff = __umul24(pix, ld_cs2) + (unsigned)(slot * 16);
-      hreg[k] = *reinterpret_cast<const w2_u32x4*>(ld_base + voff);
+      hreg[k] = *reinterpret_cast<const u32x4*>(ld_base + voff);
       hvalid_nxt |= (ok ? 1u : 0u) << k;
     };
     // one unit = 8 channels of one halo pixel: optional prologue (its result rounded to bf16, like the tensor it replaces),
@@ -953,15 +848,13 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     // instead of returning NaN for the (448, 512) part of a block — probed, tools/micro/cvt_probe.hip).
     __builtin_amdgcn_s_setreg((1 | (23 << 6) | (0 << 11)), 1);          // hwreg(MODE, offset 23, 1 bit) = FP16_OVFL
     auto write_unit = [&](int k, int buf) {
-      w2_u32x4 v = hreg[k];
+      u32x4 v = hreg[k];
       if constexpr (PRO) {
         const float a8[8] = {cf[0].x, cf[0].y, cf[0].z, cf[0].w, cf[1].x, cf[1].y, cf[1].z, cf[1].w};
         const float b8[8] = {cf[2].x, cf[2].y, cf[2].z, cf[2].w, cf[3].x, cf[3].y, cf[3].z, cf[3].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          v[j] = w2_pack(w2_silu(fmaf(w2_lo(v[j]), a8[2 * j], b8[2 * j])), w2_silu(fmaf(w2_hi(v[j]), a8[2 * j + 1], b8[2 * j + 1])));
+        v = silu_affine8(v, a8, b8);
       }
-      if (!((hvalid >> k) & 1u)) v = w2_u32x4{0u, 0u, 0u, 0u};
+      if (!((hvalid >> k) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
       uint32_t m = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -987,14 +880,14 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     auto w_issue = [&](int set, int tap, int chunk) {
       const size_t tile = ((size_t)(tap * nchunks + chunk) * d.CoutPad + (size_t)tm.tn * BN);
       const char* p = reinterpret_cast<const char*>(L.w_mx) + tile * 64 + w_voff;
-      wset[set][0] = *reinterpret_cast<const w2_u32x4*>(p);
-      wset[set][1] = *reinterpret_cast<const w2_u32x4*>(p + 64 * 64);                     // rows 64 .. 127
-      wsc[set] = *reinterpret_cast<const w2_u32x4*>(reinterpret_cast<const char*>(L.w_mx_scale) + tile * 2 + (ptid & 15) * 16);
+      wset[set][0] = *reinterpret_cast<const u32x4*>(p);
+      wset[set][1] = *reinterpret_cast<const u32x4*>(p + 64 * 64);                     // rows 64 .. 127
+      wsc[set] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(L.w_mx_scale) + tile * 2 + (ptid & 15) * 16);
     };
     auto w_write = [&](int set, int ring) {
-      *reinterpret_cast<w2_u32x4*>(Bw0 + ring * G::BW) = wset[set][0];
-      *reinterpret_cast<w2_u32x4*>(Bw0 + ring * G::BW + 64 * MXROW) = wset[set][1];
-      *reinterpret_cast<w2_u32x4*>(Ws0 + ring * G::WS) = wsc[set];   // 16 copies of the same 256 bytes: no branch
+      *reinterpret_cast<u32x4*>(Bw0 + ring * G::BW) = wset[set][0];
+      *reinterpret_cast<u32x4*>(Bw0 + ring * G::BW + 64 * MXROW) = wset[set][1];
+      *reinterpret_cast<u32x4*>(Ws0 + ring * G::WS) = wsc[set];   // 16 copies of the same 256 bytes: no branch
     };
 
     issue_setup(sA);
@@ -1021,7 +914,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
     w_issue(0, 3, sA.chunk);
     w_issue(1, 4, sA.chunk);
     issue_setup(sC);
-    w2_barrier<true>();
+    lds_barrier<true>();
 
     constexpr int US[10] = {0, 2, 4, 6, 7, 8, 9, 10, 11, 11};
 #pragma unroll 1
@@ -1048,7 +941,7 @@ __global__ __launch_bounds__(512) void conv3x3_w256mx_kernel(const ConvLaunch<bf
           advance(sC);
           issue_setup(sC);
         }
-        w2_barrier<true>();
+        lds_barrier<true>();
       }
     }
   }

@@ -12,7 +12,7 @@
 //               pixels the "B" columns — so a lane ends up with four consecutive channels of one pixel: at the end of
 //               a tile it adds the bias (kept in LDS: a workgroup owns one channel tile), rounds to bf16, transposes
 //               through a per-wave LDS stage, and folds the GroupNorm partial sums of the output with a 17-exchange
-//               halving butterfly (DPP / ds_swizzle; fixed order: deterministic) straight to global.
+//               halving butterfly (wave_sums<16>, wave_ops.h: DPP / ds_swizzle; fixed order: deterministic) straight to global.
 //   waves 4-11  PRODUCERS, each stages an eighth of every weight tile and of every halo and drains finished tiles:
 //               * weights: six register sets hold the tiles of phases ph+2..ph+7; phase ph writes tile ph+2 into LDS ring
 //                 slot (ph+2) % 3 and re-issues that set for tile ph+8;
@@ -28,61 +28,28 @@
 // bookkeeping degrades to vmcnt(0) at the merges of such unrolled, branchy streams, which drains the prefetch queue
 // every phase and exposes the whole memory latency nine times per step — measured: 2x on the kernel.)
 // One raw s_barrier per phase (lgkmcnt(0) only, never vmcnt) is the only synchronisation.
-// LDS rows are padded to 144 bytes (WsGeom): conflict-free ds_read_b128 with purely immediate tap/unit/slot offsets.
+// LDS rows are padded to 144 bytes (HaloGeom, wave_ops.h): conflict-free ds_read_b128 with purely immediate tap/unit/slot offsets.
 //
 // Covers every 3x3 / stride 1 / pad 1 conv of the U-Nets at dim = 64 (widths multiples of 64): Block.proj, the last
 // down/up convs, Upsample's conv (x2 nearest gather folded into the halo load), skip concat as two sources.
 #include <atomic>
 
 #include "conv.h"
+#include "wave_ops.h"
 
 namespace prg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 namespace {
 
 constexpr int kCH = 64;   // channels per 128-byte pixel row (bf16)
 
-__device__ inline float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ inline float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ inline uint32_t pack_bf16(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// lane exchanges inside a wave without the LDS crossbar's address VGPR: DPP quad permute / ds_swizzle xor mask
-template <int CTRL>
-__device__ inline float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-template <int XOR>   // partner = lane ^ XOR, XOR < 32
-__device__ inline float swz_xor(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (XOR << 10) | 0x1F));
-}
-__device__ inline float fast_silu(float x) {
-  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
-}
-
-template <bool LDS_DONE = true>   // wait for this wave's own LDS operations first (writers always must)
-__device__ __forceinline__ void phase_barrier() {
-  if constexpr (LDS_DONE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
+// EIGHT producer waves (Producer): 512 threads stage the halo
 template <int TH, int TW, int BN>
-struct WsGeom {
+struct WsGeom : HaloGeom<TH, TW, 512> {
+  using H = HaloGeom<TH, TW, 512>;
   static constexpr int BM = TH * TW;
-  static constexpr int HP = TW + 2;
-  static constexpr int HALO = (TH + 2) * HP;
+  static constexpr int HP = H::HP, HALO = H::HALO, ROWB = H::ROWB;
   static constexpr int WAVES_N = BN / 64, WAVES_M = 4 / WAVES_N;
-  // LDS rows (one halo pixel / one weight row = 64 bf16) are padded from 128 to 144 bytes instead of XOR-swizzled:
-  // 36-dword stride makes every ds_read_b128 lane group (16 rows, one 16-byte unit each) hit 64 distinct banks
-  // (9 r mod 16 is a permutation), and keeps addresses linear so taps, units and ring slots are immediate offsets.
-  static constexpr int ROWB = 144;
   static constexpr size_t AH_BYTES = (size_t)HALO * ROWB;
   static constexpr size_t BW_BYTES = (size_t)BN * ROWB;
   static constexpr size_t RED_BYTES = 0;
@@ -182,11 +149,11 @@ struct Producer {
   // EIGHT producer waves (two per SIMD next to one consumer wave: 768 threads, <= 168 VGPRs): a producer's phase is a
   // dependent chain (wait -> LDS write -> address -> issue) that runs at 16-35 clk per instruction with one wave per
   // SIMD; two waves with half the work each overlap their chains.
-  static constexpr int NPT = 512;                      // producer threads
+  static constexpr int NPT = G::NPT;                   // producer threads
   static constexpr int NWL = BN * 8 / NPT;             // weight units per thread per tap (BN rows x 8 units / 512)
-  static constexpr int RPP = NPT / 8;                  // halo rows per pass (8 lanes per 128-byte row)
+  static constexpr int RPP = G::RPP;                   // halo rows per pass (8 lanes per 128-byte row)
   static constexpr int DRAIN_PHASES = 2048 / NPT;      // 16-byte units of a finished tile per thread
-  static constexpr int KU = (HALO + RPP - 1) / RPP;    // halo units per thread
+  static constexpr int KU = G::KU;                     // halo units per thread
   // units handled per phase (phases 0..7), at least two: the fused prologue of ONE unit is a latency-bound dependent
   // chain (~840 clk measured, tools/micro/coissue.hip); two units interleave to about the VALU throughput bound
   static constexpr int UPH = (KU + 7) / 8 > 2 ? (KU + 7) / 8 : 2;
@@ -389,18 +356,14 @@ struct Producer {
     if (hp < HALO && wr) {
       u32x4 v = hreg[K];
       if constexpr (PRO) {
+        // channels 2j, 2j + 1 of this thread's 8 (the halves of v[j]): coefficients a[] live in cf[.][0 .. 1], b[] two vectors further
+        float a8[8], b8[8];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          // v[j] holds channels 2j (low half) and 2j+1 of this thread's 8: coefficients a[2j], a[2j+1] live in
-          // cf[.][j / 2] elements (2j % 4, +1), b[] two vectors further
-          const float a_lo = __uint_as_float(cf[CS][j >> 1][(2 * j) & 3]);
-          const float a_hi = __uint_as_float(cf[CS][j >> 1][((2 * j) & 3) + 1]);
-          const float b_lo = __uint_as_float(cf[CS][2 + (j >> 1)][(2 * j) & 3]);
-          const float b_hi = __uint_as_float(cf[CS][2 + (j >> 1)][((2 * j) & 3) + 1]);
-          const float lo = fast_silu(fmaf(bf_lo(v[j]), a_lo, b_lo));
-          const float hi2 = fast_silu(fmaf(bf_hi(v[j]), a_hi, b_hi));
-          v[j] = pack_bf16(lo, hi2);
+        for (int u = 0; u < 8; ++u) {
+          a8[u] = __uint_as_float(cf[CS][u >> 2][u & 3]);
+          b8[u] = __uint_as_float(cf[CS][2 + (u >> 2)][u & 3]);
         }
+        v = silu_affine8(v, a8, b8);
       }
       if (!((hvalid >> K) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
       *reinterpret_cast<u32x4*>(Ah0 + (g_tgt & 1) * G::AH_BYTES + K * RPP * G::ROWB) = v;
@@ -485,7 +448,7 @@ struct Producer {
     if constexpr (LIVE && PH < DRAIN_PHASES) {
       if (draining) drain_store<PH>(dv);
     }
-    if constexpr (LIVE) phase_barrier();
+    if constexpr (LIVE) lds_barrier();
   }
   // GP = g & 1.  Writes halo g+1 (coefficient set (g+1)&1) and weight tiles 9g+2..9g+10; issues halo g+2 (set g&1) and
   // weight tiles 9g+5..9g+13.  LIVE = false is the issue-only "step -1" of the prologue: it puts exactly the loads a
@@ -578,7 +541,7 @@ struct Producer {
 #pragma unroll
         for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(cf[c][j])::"memory");
     }
-    phase_barrier();
+    lds_barrier();
   }
 };
 
@@ -642,7 +605,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
     // ring slot / halo buffer that no producer touches before phase p+2.
     // the workgroup's channel tile never changes (one Cout tile, or pinned to one): its bias lives in LDS
     if (tid < BN) bias_lds[tid] = L.bias[(tmap.pinned ? tmap.tn_fixed : 0) * BN + tid];
-    phase_barrier<true>();    // prologue barrier: first halo + weight tiles 0,1 are in LDS
+    lds_barrier<true>();    // prologue barrier: first halo + weight tiles 0,1 are in LDS
     // three fragment sets: the one being multiplied, the next call's, and the one being loaded two calls (256 MFMA
     // cycles) ahead; set of global call c is c % 3 (36 calls per step: the same code serves every step)
     bf16x8 fw[3][2], fx[3][2];
@@ -728,25 +691,13 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
             // 16 full-wave sums with 17 lane exchanges: each butterfly round halves the values a lane carries (it keeps
             // the half selected by its lane bit and sends the other half to its partner).  The rounds that move many
             // values use DPP quad permutes (VALU, no LDS crossbar); fixed order -> deterministic.
-            const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-            float A8[8], B4[4], C2[2];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) A8[j] = (b0 ? V[8 + j] : V[j]) + dpp_f32<0xB1>(b0 ? V[j] : V[8 + j]);          // lane ^ 1
-#pragma unroll
-            for (int j = 0; j < 4; ++j) B4[j] = (b1 ? A8[4 + j] : A8[j]) + dpp_f32<0x4E>(b1 ? A8[j] : A8[4 + j]);    // lane ^ 2
-#pragma unroll
-            for (int j = 0; j < 2; ++j) C2[j] = (b2 ? B4[2 + j] : B4[j]) + swz_xor<4>(b2 ? B4[j] : B4[2 + j]);
-            float D = (b3 ? C2[1] : C2[0]) + swz_xor<8>(b3 ? C2[0] : C2[1]);
-            D += swz_xor<16>(D);
-            D += __shfl_xor(D, 32, 64);
-            // lane (< 16) now holds the wave total of value i = 8 b0 + 4 b1 + 2 b2 + b3 = [sq][ct][q]: the 8-channel chunk
-            // ct*4 + q of this wave's 64 channels.  Fold the chunks of one GroupNorm group (per = cpg / 8 <= 8 of them,
-            // neighbours in q, then ct) and let the group's first chunk store: one partial per (wave row, group).
+            float D = wave_sums<16>(V, lane);
+            // lane (< 16) now holds the wave total of value i = [sq][ct][q]: the 8-channel chunk ct*4 + q of this wave's 64 channels.
+            // The chunks of one GroupNorm group are folded (per = cpg / 8 <= 8 of them, neighbours in q, then ct) and the group's
+            // first chunk stores: one partial per (wave row, group).
             const int per = gn_per;
-            if (per >= 2) D += swz_xor<8>(D);
-            if (per >= 4) D += swz_xor<4>(D);
-            if (per >= 8) D += dpp_f32<0x4E>(D);
-            const int i = (lane & 1) * 8 + (lane & 2) * 2 + ((lane >> 2) & 1) * 2 + ((lane >> 3) & 1);
+            D = group_sums<16>(D, per);
+            const int i = wave_sums_index<16>(lane);
             const int cc = i & 7;
             if (lane < 16 && (cc & (per - 1)) == 0) {
               const int nsplit = tiles_x * tiles_y * G::WAVES_M;
@@ -763,8 +714,8 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
 #pragma unroll
               for (int e = 0; e < 16; ++e) acc[ct][pt][e] = 0.0f;
         }
-        if (p == 8 && tile_end) phase_barrier<true>();   // the stage must be visible to the producer waves
-        else phase_barrier<false>();
+        if (p == 8 && tile_end) lds_barrier<true>();   // the stage must be visible to the producer waves
+        else lds_barrier<false>();
       }
       // next step
       { const char* t0 = xa[0]; xa[0] = xn[0]; xn[0] = t0; const char* t1 = xa[1]; xa[1] = xn[1]; xn[1] = t1; }
@@ -780,7 +731,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
 #undef PRG_LX
 #undef PRG_MM
 #undef PRG_SB
-    phase_barrier<false>();   // matches the producers' finish()
+    lds_barrier<false>();   // matches the producers' finish()
     return;
   }
 
@@ -788,7 +739,7 @@ __global__ __launch_bounds__(768) void conv3x3_ws_kernel(const ConvLaunch<bf16_t
   {
     Producer<TH, TW, BN, PRO> Pv(L, smem, tid - 256, tmap, nsteps, nchunks);
     Pv.prologue();
-    phase_barrier();
+    lds_barrier();
 #pragma unroll 1
     for (int g = 0; g < nsteps; g += 2) {
       Pv.template step<0, true>(g);

@@ -1,4 +1,4 @@
-// h16_silu8 (conv.h: GroupNorm affine + SiLU on packed f16 pairs, inline-asm transcendentals) against float arithmetic, every
+// h16_silu8 (wave_ops.h: GroupNorm affine + SiLU on packed f16 pairs, inline-asm transcendentals) against float arithmetic, every
 // f16 input in [-24, 24] x a few coefficient pairs; prints the worst absolute / relative error and any non-finite output.
 // build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I pointreggpt_amd/csrc -o tools/micro/h16_silu_probe tools/micro/h16_silu_probe.hip
 #include <cmath>
@@ -6,10 +6,10 @@
 #include <cstring>
 #include <vector>
 
-#include "conv.h"
+#include "wave_ops.h"
 using namespace prg;
 
-__global__ void probe(const h16_u32x4* in, h16_u32x4* out, const h16x2* ab, int n) {
+__global__ void probe(const u32x4* in, u32x4* out, const h16x2* ab, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   h16x2 a[4], b[4];
@@ -35,7 +35,7 @@ int main() {
   hipMalloc(&din, xs.size() * 2); hipMalloc(&dout, xs.size() * 2); hipMalloc(&dab, sizeof(abh));
   hipMemcpy(din, xs.data(), xs.size() * 2, hipMemcpyHostToDevice);
   hipMemcpy(dab, abh, sizeof(abh), hipMemcpyHostToDevice);
-  probe<<<(n + 255) / 256, 256>>>((const h16_u32x4*)din, (h16_u32x4*)dout, (const h16x2*)dab, n);
+  probe<<<(n + 255) / 256, 256>>>((const u32x4*)din, (u32x4*)dout,(const h16x2*)dab, n);
   std::vector<uint16_t> ys(xs.size());
   hipMemcpy(ys.data(), dout, ys.size() * 2, hipMemcpyDeviceToHost);
   double worst_abs = 0, worst_rel = 0;
