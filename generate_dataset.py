@@ -19,6 +19,9 @@ hard-coded literals, generate_dataset.py:32-55):
   --with_gt           also write every scene's gt.log while generating: both clouds of a pair are finished on the GPU and go
                       through generate_gt's voxel grid and overlap test in the batch that sampled them (same bytes as the
                       two-pass run).  `generate_gt.py` afterwards finds every scene done and is the gather step only
+  --clouds per_view   with --num_samples k: one cloud per view, sample-000001 .. sample-00000k.cloud.ply, each view alone in
+                      its own camera frame, instead of the k views fused into sample-000001 (the default, `fused`): C(k+1, 2)
+                      candidate pairs per scene for `--with_gt` or `generate_gt.py --num_samples k+1` (k = 1: the same files)
   --resume synthetic[:SEED]   deterministic synthetic weights instead of ./successive_ddnm_diffusion_results/model-<resume>.pt
 Under `torchrun --nproc-per-node N` every rank takes a contiguous block of [-start, -stop) (no collectives).
 Two datasets generated from the same scenes (same --synthetic and --noise_seed, e.g. in two --dtype modes) are compared cloud
@@ -65,6 +68,9 @@ def main():
     p.add_argument("--with_gt", action="store_true",
                    help="write each scene's gt.log in the batch that sampled it (clouds finished on the GPU; same bytes as "
                         "generate_gt.py would write); generate_gt.py afterwards only gathers metadata/gt.log")
+    p.add_argument("--clouds", default="fused", choices=["fused", "per_view"],
+                   help="fused = the views of a scene in one target cloud (the reference's layout); per_view = one cloud per "
+                        "view, every pair of a scene's clouds a candidate for gt.log")
     args = p.parse_args()
 
     from pointreggpt_amd import sharding
@@ -133,7 +139,7 @@ def main():
         generator.generate(start_scene_index=start, stop_scene_index=stop, num_samples=args.num_samples,
                            has_refine_step=False, depth_correction=depth_correction,
                            mask_threshold=args.mask_threshold, noise_seed=args.noise_seed, lanes=lanes,
-                           gt_log=args.with_gt)
+                           gt_log=args.with_gt, clouds=args.clouds)
     if args.device == "cuda":
         torch.cuda.synchronize()
 

@@ -114,6 +114,19 @@ int prg_occlusion_filter(const float* depth, const uint8_t* mask, float* out, in
 int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, int64_t max_cloud, double radius,
                        int32_t* counts, void* stream);
 
+/* prg_overlap_counts for an indexed list of pairs over a SET of clouds, so that a cloud that is in several pairs is stored (and
+ * voxel-gridded by the caller) once: pts (total,3) float64 DEVICE; offsets (n_clouds+1) int64 DEVICE, cloud c is rows
+ * [offsets[c], offsets[c+1]), offsets[0] may be > 0; pair_index (n_pairs,2) int32 DEVICE; counts (n_pairs,2) int32 DEVICE.  For
+ * (s, t) = pair_index[p]: counts[p] = (rows of cloud s that have a row of cloud t strictly within `radius`, the same from t's
+ * side) — prg_overlap_counts' decision: dx*dx + dy*dy + dz*dz in float64 summed left to right, strict < against radius*radius.
+ * A cloud may appear in any number of pairs, in either position; s == t is allowed, and then every finite row counts once.  An
+ * entry outside [0, n_clouds) makes that pair's counts (-1, -1): the kernel compares the two entries before it forms any address
+ * from them, reads no row of pts for such a pair, and no other pair is affected.  max_cloud = largest cloud.  1 <= n_pairs <=
+ * 65535, n_clouds >= 1, max_cloud > 0, radius > 0; anything else or a null pointer fails with PRG_E_INVALID before any device
+ * call.  counts is cleared by the call itself.  Asynchronous on `stream`; reads no device data on the host; allocates nothing. */
+int prg_overlap_counts_indexed(const double* pts, const int64_t* offsets, int n_clouds, const int32_t* pair_index, int n_pairs,
+                               int64_t max_cloud, double radius, int32_t* counts, void* stream);
+
 /* Nearest point of the other cloud, for a batch of cloud pairs in the layout of prg_overlap_counts (pts (total,3) float64
  * DEVICE, offsets (2*n_pairs+1) int64 DEVICE, offsets[0] may be > 0; max_cloud = largest cloud, < 2^31): d2 (total) float64
  * and idx (total) int32, DEVICE, one entry per row of pts.  For row i of cloud 2p, d2[i] = the smallest squared distance to a

@@ -69,6 +69,7 @@ PROTOTYPES = {
     "prg_apply_mask": (C.c_int, [_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P]),
     "prg_occlusion_filter": (C.c_int, [_P, _P, _P, _I, _I, _I, _F, _P]),
     "prg_overlap_counts": (C.c_int, [_P, _P, _I, _L, C.c_double, _P, _P]),
+    "prg_overlap_counts_indexed": (C.c_int, [_P, _P, _I, _P, _I, _L, C.c_double, _P, _P]),
     "prg_nearest_ragged_f64": (C.c_int, [_P, _P, _I, _L, _P, _P, _P]),
     "prg_radius_pairs_workspace_bytes": (C.c_size_t, [_L]),
     "prg_radius_count_ragged_f64": (C.c_int, [_P, _P, _I, _L, _L, C.c_double, _P, _P, C.c_size_t, _P]),

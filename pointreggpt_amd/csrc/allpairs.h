@@ -33,6 +33,20 @@ __device__ __forceinline__ PairSegments pair_segments(const int64_t* __restrict_
                       dir == 0 ? offs[2 * pair + 2] : offs[2 * pair + 1]};
 }
 
+// The indexed pair layout of prg_overlap_counts_indexed: offs (n_clouds + 1) are the segments of a SET of clouds and pair p is
+// the clouds (s, t) = pair_index[2p], pair_index[2p + 1] — any cloud in any number of pairs, in either position, s == t
+// included.  dir 0 queries cloud s against cloud t; dir 1 the other way round.  The two entries are read and compared with
+// [0, n_clouds) before any address is formed from them: a pair with an entry outside returns false and g is left alone.
+__device__ __forceinline__ bool indexed_pair_segments(const int64_t* __restrict__ offs, int n_clouds,
+                                                      const int32_t* __restrict__ pair_index, int pair, int dir,
+                                                      PairSegments& g) {
+  const int32_t s = pair_index[2 * pair], t = pair_index[2 * pair + 1];
+  if (s < 0 || s >= n_clouds || t < 0 || t >= n_clouds) return false;
+  const int32_t a = dir == 0 ? s : t, b = dir == 0 ? t : s;
+  g = PairSegments{offs[a], offs[a + 1], offs[b], offs[b + 1]};
+  return true;
+}
+
 // The all-pairs sweep: calls visit(k, j_local, d2) for every query k < Q of this thread — row slab + k * AP_TILE + threadIdx.x,
 // a query if it is below a1 — and every candidate row j of [b0, b1), j ascending, d2 = dist2(candidate, query).  The candidates
 // stream through `tile` (3 * AP_TILE doubles of LDS, structure of arrays, one row per thread to stage); the next tile is

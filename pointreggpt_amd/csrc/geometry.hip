@@ -266,13 +266,11 @@ __global__ void occlusion_filter_kernel(const float* __restrict__ depth, const u
 // float64, < r^2 like the KD-tree radius search)?  Clouds are a few thousand points after the 0.025 voxel grid, so
 // the exact all-pairs test with B streamed through LDS is microseconds per pair on one CU and needs no grid or tree;
 // one workgroup per (pair, direction, 256-query slab), a count per (pair, direction) by atomicAdd of integers (exact).
-// The distance and the segment decode are allpairs.h's.  The loop stays its own, not sweep<1>: one query per thread, no prefetch,
+// The distance and the segment decodes are allpairs.h's.  The loop stays its own, not sweep<1>: one query per thread, no prefetch,
 // and an early-out once a row is found, which the sweep would drop (68 VGPRs and 7 waves per SIMD against 60 and 8 here).
-__global__ __launch_bounds__(256) void overlap_count_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offs,
-                                                            double r2, int32_t* __restrict__ counts) {
-  __shared__ double tile[256 * 3];
-  const int pair = blockIdx.y, dir = blockIdx.z;
-  const PairSegments g = pair_segments(offs, pair, dir);
+// The body is written once, for the segments g of (pair, dir); the two kernels below differ in how they decode g.
+__device__ __forceinline__ void overlap_count_body(const double* __restrict__ pts, const PairSegments g, int pair, int dir,
+                                                   double r2, int32_t* __restrict__ counts, double* tile) {
   const int64_t a1 = g.a1, b1 = g.b1;
   const int64_t q = g.a0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g.a0 + (int64_t)blockIdx.x * 256 >= a1) return;          // whole slab beyond this cloud (uniform exit)
@@ -296,6 +294,30 @@ __global__ __launch_bounds__(256) void overlap_count_kernel(const double* __rest
   }
   const unsigned long long hits = __ballot(live && found);
   if ((threadIdx.x & 63) == 0 && hits) atomicAdd(counts + 2 * pair + dir, (int32_t)__popcll(hits));
+}
+
+__global__ __launch_bounds__(256) void overlap_count_kernel(const double* __restrict__ pts, const int64_t* __restrict__ offs,
+                                                            double r2, int32_t* __restrict__ counts) {
+  __shared__ double tile[256 * 3];
+  const int pair = blockIdx.y, dir = blockIdx.z;
+  overlap_count_body(pts, pair_segments(offs, pair, dir), pair, dir, r2, counts, tile);
+}
+
+// The same for an indexed list of pairs over a set of clouds.  A pair with an entry outside [0, n_clouds) reads no row: its two
+// counts become -1, written once per direction by the first thread of the first slab (the counts start at 0 and no workgroup
+// of such a pair adds to them).
+__global__ __launch_bounds__(256) void overlap_count_indexed_kernel(const double* __restrict__ pts,
+                                                                    const int64_t* __restrict__ offs, int n_clouds,
+                                                                    const int32_t* __restrict__ pair_index, double r2,
+                                                                    int32_t* __restrict__ counts) {
+  __shared__ double tile[256 * 3];
+  const int pair = blockIdx.y, dir = blockIdx.z;
+  PairSegments g;
+  if (!indexed_pair_segments(offs, n_clouds, pair_index, pair, dir, g)) {          // uniform over the workgroup
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[2 * pair + dir] = -1;
+    return;
+  }
+  overlap_count_body(pts, g, pair, dir, r2, counts, tile);
 }
 
 // ---- nearest point of the other cloud (dataset comparison) -----------------------------------------------------------
@@ -506,6 +528,19 @@ int prg_overlap_counts(const double* pts, const int64_t* offsets, int n_pairs, i
   PRG_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * 2 * (size_t)n_pairs, (hipStream_t)stream));
   const dim3 grid((unsigned)((max_cloud + 255) / 256), (unsigned)n_pairs, 2);
   overlap_count_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pts, offsets, radius * radius, counts);
+  PRG_LAUNCH_CHECK();
+  return PRG_OK;
+}
+
+int prg_overlap_counts_indexed(const double* pts, const int64_t* offsets, int n_clouds, const int32_t* pair_index, int n_pairs,
+                               int64_t max_cloud, double radius, int32_t* counts, void* stream) {
+  PRG_CHECK(pts && offsets && pair_index && counts, "prg_overlap_counts_indexed: null pointer");
+  PRG_CHECK(n_pairs > 0 && n_pairs <= 65535 && n_clouds >= 1 && max_cloud > 0 && radius > 0,
+            "prg_overlap_counts_indexed: bad arguments");
+  PRG_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * 2 * (size_t)n_pairs, (hipStream_t)stream));
+  const dim3 grid((unsigned)((max_cloud + 255) / 256), (unsigned)n_pairs, 2);
+  overlap_count_indexed_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pts, offsets, n_clouds, pair_index, radius * radius,
+                                                                      counts);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
 }

@@ -115,7 +115,7 @@ class Generator:
                  save_voxel_size=0.025, has_refine_step=False, depth_correction=None, mask_threshold=0.99,
                  noise_seed: Optional[int] = None, progress: bool = False, writer_threads: int = 0, stats: Optional[dict] = None,
                  seed_poses: Optional[bool] = None, lanes: Optional[list] = None, voxel_backend: str = "device",
-                 gt_log: bool = False):
+                 gt_log: bool = False, clouds: str = "fused"):
         """Same sequence as sd:2363-2694.  File output is asynchronous: every batch's clouds / images / text files are
         handed to the library's C++ writer pool (crop, voxel grid, PLY / PNG encoding on worker threads) and are
         produced while the GPU samples the next batch.  A batch's resume marker — the generated cloud of its LAST scene
@@ -141,11 +141,19 @@ class Generator:
         The memory clouds are uploaded once (also for num_samples == 1); the float64 views stay on the device; per batch ONE
         ragged buffer of 2B segments [memory_j | views of scene j] goes through `finish_clouds` (the views with pre = pose0,
         the crop box, post = pose0^-1; `save_voxel_size`), comes to the host once for the PLY writers (write-only jobs), and
-        through `voxel_grid_ragged` at generate_gt's 0.025 into one `prg_overlap_counts` launch.  Every file has the bytes of
+        through `voxel_grid_ragged` at generate_gt's 0.025 into one `prg_overlap_counts_indexed` launch.  Every file has the bytes of
         the default path followed by `generate_gt`; a batch's gt.log files are on disk before its resume marker is submitted.
-        Afterwards `generate_gt` finds every scene done and only `gather_gt` is left."""
+        Afterwards `generate_gt` finds every scene done and only `gather_gt` is left.
+        ``clouds``: "fused" (the default, the reference's layout): all `num_samples` views of a scene end in ONE target cloud,
+        sample-000001.cloud.ply, finished in the first view's camera frame.  "per_view": every view i = 1..num_samples gets its
+        own sample-{i:06d}.cloud.ply — `postprocess.finish_cloud(xyz_i[valid_i], pre=pose_i, crop=the box, voxel=save_voxel_size,
+        post=inv(pose_i))`, the view alone in its own camera frame — so that `generate_gt(num_samples=k+1)`, or `gt_log=True`
+        in the same pass, lists up to C(k+1, 2) pairs per scene for k chains.  Every other file and the memory update between
+        the views are the same in both modes, and for num_samples == 1 so are the clouds."""
         if voxel_backend not in ("device", "host"):
             raise ValueError("voxel_backend must be 'device' or 'host'")
+        if clouds not in ("fused", "per_view"):
+            raise ValueError("clouds must be 'fused' or 'per_view'")
         if gt_log and (self.device.type == "cpu" or voxel_backend != "device"):
             raise ValueError("gt_log=True needs the clouds on a HIP device (device='cuda', voxel_backend='device')")
         if self.device.type == "cpu":
@@ -176,7 +184,8 @@ class Generator:
         pairs = pairs[:max(1, len(batches))]
         kw = dict(num_samples=num_samples, memory_voxel_size=memory_voxel_size, save_voxel_size=save_voxel_size,
                   has_refine_step=has_refine_step, mask_threshold=mask_threshold, noise_seed=noise_seed, progress=progress,
-                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend, gt_log=gt_log)
+                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend, gt_log=gt_log,
+                  per_view=clouds == "per_view")
         n = len(pairs)
         wt = writer_threads if writer_threads <= 0 or n == 1 else max(1, writer_threads // n)
         results = [None] * n
@@ -217,7 +226,7 @@ class Generator:
 
     def _lane(self, batches, model, depth_correction, writer_threads, n_lanes, *, num_samples, memory_voxel_size,
               save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None,
-              voxel_backend="host", gt_log=False):
+              voxel_backend="host", gt_log=False, per_view=False):
         """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream."""
         S, dev = self.image_size, self.device
         if writer_threads <= 0 and n_lanes > 1:
@@ -225,7 +234,8 @@ class Generator:
         with PP.WriterPool(writer_threads) as pool:
             marker_prev = None                # deferred submission of the previous batch's resume marker
             n_pairs = 0
-            marker_index = num_samples // 2   # the cloud file the resume check looks for (0 or 1; never written beyond that)
+            # the cloud file the resume check looks for (fused: 0 or 1, never written beyond that; per view: always written)
+            marker_index = num_samples // 2
 
             def flush_marker():
                 nonlocal marker_prev
@@ -269,6 +279,7 @@ class Generator:
                 param_cond = self.G.param_vector(K_dev)
                 fragments: List[Optional[np.ndarray]] = [None] * batch
                 poses0 = None
+                poses = []                    # every view's poses (the per-view clouds are finished in their own frames)
                 on_device = (voxel_backend == "device" and num_samples > 1) or gt_log
                 if on_device:                 # the ONE upload of the memory clouds; from here on they stay on the device
                     mem_pts, mem_offs = self.G.upload_clouds(memory, dev)
@@ -279,6 +290,7 @@ class Generator:
                     pose = self._poses(idxs, sample_idx, noise_seed if seed_poses else None)
                     if sample_idx == 0:
                         poses0 = pose
+                    poses.append(pose)
                     pose_dev = torch.from_numpy(pose).to(dev)
                     if on_device:
                         rpj, hit = self.G.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
@@ -301,8 +313,8 @@ class Generator:
                     if gt_log:
                         views.append((xyz, valid))
                         if last_sample:
-                            finished = self._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views, poses0,
-                                                                 save_voxel_size)
+                            finished = self._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views,
+                                                                 poses if per_view else poses0, save_voxel_size)
                     # one blocking copy per tensor: the host waits here for the GPU while the pool writes the previous batch
                     rpj_host, crt_host, img_host = rpj.cpu().numpy(), rpj_c.cpu().numpy(), images.cpu().numpy()
                     if not gt_log:
@@ -321,6 +333,18 @@ class Generator:
                         pool.depth16(str(sdir / "sample-{:0>6d}.depth.png".format(sample_idx + 1)), img_host[j])
                         if gt_log:
                             continue                                                    # clouds: after the loop, from the device
+                        if per_view:                                                # the view alone, in its own frame
+                            if not last_sample and not on_device:                       # memory update (sd:2661-2680)
+                                merged = np.concatenate([memory[j], xyz_host[j][valid_host[j]]], axis=0)
+                                memory[j] = PP.native_voxel_down_sample(merged, memory_voxel_size).astype(np.float32)
+                            path = str(sdir / "sample-{:0>6d}.cloud.ply".format(sample_idx + 1))
+                            job = (lambda path=path, frag=xyz_host[j], fvalid=valid_host[j], T=pose[j].astype(np.float64):
+                                   pool.cloud(path, frag, fvalid, pre=T, crop=True, voxel=save_voxel_size, post=np.linalg.inv(T)))
+                            if j == batch - 1 and marker_index == sample_idx + 1:
+                                marker_cur = job
+                            else:
+                                job()
+                            continue
                         if num_samples == 1:
                             frag, fvalid = xyz_host[j], valid_host[j]                  # compaction happens in the worker
                         else:
@@ -350,92 +374,122 @@ class Generator:
             return n_pairs, jobs, pool.threads
 
 
-    # -- gt_log: both clouds of a pair finished on the device, the scene's gt.log written with them ---------------------------
+    # -- gt_log: every cloud of a scene finished on the device, the scene's gt.log written with them ---------------------------
     GT_VOXEL, GT_FACTOR, GT_MIN_POINTS = 0.025, 1.5, 1000      # generate_gt's fixed literals (generate_gt.py:68-102, 133-140)
+    _pair_tables: dict = {}            # (B, clouds per scene, device) -> the batch's (pairs,2) int32 index table on the device
 
-    def _finish_pairs_launch(self, mem_pts0, mem_offs0, mem_rows, views, poses0, save_voxel_size):
-        """Device work of a batch's pairs, nothing read back: -> (finished clouds, offsets (2B+1), statuses, overlap counts,
-        down-sampled offsets).  Segment 2j is scene j's source frame (its float32 memory widened to float64), segment 2j+1 its
-        views in view order; only the odd segments are moved by pose0 and back.  The crop box is applied to every segment and
-        is a no-op on the even ones: the memory IS `crop_aabb` of the source frame in float32, the bounds are float32 numbers,
-        and widening keeps every comparison."""
+    @classmethod
+    def _pair_table(cls, B, n_seg, dev):
+        """Every pair (s, t), s < t, of every scene's n_seg segments, scene-major and in `combinations` order, as rows
+        (n_seg * j + s, n_seg * j + t) of the batch's segment list: what prg_overlap_counts_indexed takes.  Uploaded once."""
+        from itertools import combinations
+        key = (B, n_seg, str(dev))
+        table = cls._pair_tables.get(key)
+        if table is None:
+            rows = [(n_seg * j + s, n_seg * j + t) for j in range(B) for s, t in combinations(range(n_seg), 2)]
+            table = cls._pair_tables[key] = torch.from_numpy(np.array(rows, dtype=np.int32)).to(dev)
+        return table
+
+    def _finish_pairs_launch(self, mem_pts0, mem_offs0, mem_rows, views, poses, save_voxel_size):
+        """Device work of a batch's pairs, nothing read back: -> (finished clouds, offsets (nB+1), statuses, overlap counts,
+        down-sampled offsets), n clouds per scene, scene-major.  Segment n*j is scene j's source frame (its float32 memory
+        widened to float64).  `poses` an array (B,4,4): fused, n = 2, segment 2j+1 is all the views in view order, moved by that
+        pose and back.  `poses` a list of one such array per view: per view, n = 1 + views, segment n*j+i is view i alone, moved
+        by ITS pose and back.  Either way the segments are offset arithmetic on `merge_memory`'s buffer [memory_j | view 1 rows
+        | ... | view k rows]; the source frames are not moved.  The crop box is applied to every segment and is a no-op on the
+        source frames: the memory IS `crop_aabb` of the source frame in float32, the bounds are float32 numbers, and widening
+        keeps every comparison.  Every cloud is voxel-gridded once at generate_gt's 0.025 and all B * C(n, 2) pairs of the batch
+        go through ONE prg_overlap_counts_indexed launch; the counts are in `_pair_table`'s order."""
         G_ = self.G
         B = len(mem_rows)
         dev = mem_pts0.device
+        per_view = isinstance(poses, (list, tuple))
         xyz = views[0][0] if len(views) == 1 else torch.cat([v[0] for v in views], dim=1)         # (B, n_views*HW, 3)
         valid = views[0][1] if len(views) == 1 else torch.cat([v[1] for v in views], dim=1)
         rows_v = xyz.shape[1]
+        rows_seg = views[0][0].shape[1] if per_view else rows_v                                   # rows of a view segment
+        n = 1 + (len(views) if per_view else 1)
         merged, mvalid, moffs = G_.merge_memory(mem_pts0, mem_offs0, xyz, valid)
-        shift = torch.arange(B, dtype=torch.int64, device=dev) * rows_v
-        offs2 = torch.empty((2 * B + 1,), dtype=torch.int64, device=dev)
-        offs2[0:2 * B:2] = moffs[:-1]
-        offs2[1:2 * B:2] = mem_offs0[1:] + shift
-        offs2[2 * B] = moffs[-1]
-        pre = np.zeros((2 * B, 4, 4), dtype=np.float64)
-        post = np.zeros((2 * B, 4, 4), dtype=np.float64)
-        has = np.zeros((2 * B,), dtype=np.uint8)
+        first = mem_offs0[1:] + torch.arange(B, dtype=torch.int64, device=dev) * rows_v           # scene j's first view row
+        offs = torch.empty((n * B + 1,), dtype=torch.int64, device=dev)
+        offs[0:n * B:n] = moffs[:-1]
+        for i in range(1, n):
+            offs[i:n * B:n] = first + (i - 1) * rows_seg
+        offs[n * B] = moffs[-1]
+        pre = np.zeros((n * B, 4, 4), dtype=np.float64)
+        post = np.zeros((n * B, 4, 4), dtype=np.float64)
+        has = np.zeros((n * B,), dtype=np.uint8)
         for j in range(B):
-            T = poses0[j].astype(np.float64)
-            pre[2 * j + 1], post[2 * j + 1], has[2 * j + 1] = T, np.linalg.inv(T), 1     # the same 16 doubles as the host path
-        fin, fin_offs, st_save = G_.finish_clouds(merged, mvalid, offs2, save_voxel_size, pre=pre, has_pre=has,
+            for i in range(1, n):
+                T = (poses[i - 1] if per_view else poses)[j].astype(np.float64)
+                pre[n * j + i], post[n * j + i], has[n * j + i] = T, np.linalg.inv(T), 1     # the same 16 doubles as the host path
+        fin, fin_offs, st_save = G_.finish_clouds(merged, mvalid, offs, save_voxel_size, pre=pre, has_pre=has,
                                                   crop=(PP.BBOX_MIN, PP.BBOX_MAX), post=post, has_post=has)
-        lib = G._lib.load()
         down, down_offs, st_gt = G_.voxel_grid_ragged(fin, None, fin_offs, self.GT_VOXEL)
-        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
         # max_cloud only bounds the query slabs: no finished cloud has more rows than went into it
-        G._lib.check(lib.prg_overlap_counts(G._lib.ptr(down), G._lib.ptr(down_offs), B, int(max(max(mem_rows), rows_v)),
-                                            float(self.GT_VOXEL * self.GT_FACTOR), G._lib.ptr(counts), G._lib.stream_ptr()),
-                     "prg_overlap_counts")
+        counts = G_.overlap_counts_indexed(down, down_offs, self._pair_table(B, n, dev), int(max(max(mem_rows), rows_seg)),
+                                           float(self.GT_VOXEL * self.GT_FACTOR))
         return fin, fin_offs, st_save, st_gt, counts, down_offs
 
     def _finish_pairs_write(self, pool, finished, idxs, sdirs, marker_index):
         """Host side: ONE copy of the finished clouds, the PLY files as write-only jobs, every scene's gt.log written before this
-        returns.  -> the batch's resume marker job (not yet submitted)."""
+        returns — one line per surviving pair (s, t), s < t, in `combinations` order.  -> the batch's resume marker job (not yet
+        submitted)."""
+        from itertools import combinations
         fin = finished[0]
         B = len(idxs)
         offs, d_offs, cnt = self._finish_pairs_words(finished, idxs)
+        n = (len(offs) - 1) // B
         pts = fin[:max(int(offs[-1]), 0)].cpu().numpy()
         marker = None
         for j, sdir in enumerate(sdirs):
-            for k in (0, 1):
-                job = (lambda path=str(sdir / "sample-{:0>6d}.cloud.ply".format(k)), pc=pts[offs[2 * j + k]:offs[2 * j + k + 1]]:
+            for k in range(n):
+                job = (lambda path=str(sdir / "sample-{:0>6d}.cloud.ply".format(k)), pc=pts[offs[n * j + k]:offs[n * j + k + 1]]:
                        pool.cloud(path, pc, None, crop=False, voxel=0))
                 if j == B - 1 and k == marker_index:
                     marker = job
                 else:
                     job()
+        combos = list(combinations(range(n), 2))
         for j, (idx, sdir) in enumerate(zip(idxs, sdirs)):
             lines = []
-            ratios, _why = self._pair_ratios(offs, d_offs, cnt, j)
-            if ratios is not None:
-                lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), 0, 1, ratios[0], ratios[1]))
+            for p, (s, t) in enumerate(combos):
+                ratios, _why = self._pair_ratios_at(offs, d_offs, cnt[len(combos) * j + p], n * j + s, n * j + t)
+                if ratios is not None:
+                    lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), s, t, ratios[0], ratios[1]))
             with open(sdir / "gt.log", "w") as f:
                 f.writelines(lines)
         return marker
 
     def _finish_pairs_words(self, finished, idxs):
-        """The small words of a finished batch in ONE copy, voxel statuses checked: -> (offsets (2B+1), down-sampled offsets (2B+1),
-        overlap counts (B,2)) on the host."""
+        """The small words of a finished batch in ONE copy, voxel statuses checked: -> (offsets (nB+1), down-sampled offsets
+        (nB+1), overlap counts (B * C(n, 2), 2)) on the host, n clouds per scene."""
         _fin, fin_offs, st_save, st_gt, counts, down_offs = finished
         B = len(idxs)
+        N = fin_offs.numel() - 1                                              # n * B segments
         small = torch.cat([fin_offs, down_offs, st_save.to(torch.int64), st_gt.to(torch.int64), counts.view(-1).to(torch.int64)])
         small = small.cpu().numpy()
-        offs, d_offs = small[:2 * B + 1], small[2 * B + 1:4 * B + 2]
-        st_save, st_gt, cnt = small[4 * B + 2:6 * B + 2], small[6 * B + 2:8 * B + 2], small[8 * B + 2:].reshape(B, 2)
-        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in (0, 1)]
+        offs, d_offs = small[:N + 1], small[N + 1:2 * N + 2]
+        st_save, st_gt, cnt = small[2 * N + 2:3 * N + 2], small[3 * N + 2:4 * N + 2], small[4 * N + 2:].reshape(-1, 2)
+        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in range(N // B)]
         self.G.check_voxel_status(st_save, names)
         self.G.check_voxel_status(st_gt, names)
         return offs, d_offs, cnt
 
     @classmethod
     def _pair_ratios(cls, offs, d_offs, cnt, j):
-        """generate_gt's filter on pair j of a finished batch: -> ((overlap of the source, of the target), None) when the pair gets
-        a gt.log line, (None, reason) when it does not."""
-        if offs[2 * j + 1] - offs[2 * j] < cls.GT_MIN_POINTS or offs[2 * j + 2] - offs[2 * j + 1] < cls.GT_MIN_POINTS:
+        """generate_gt's filter on pair j of a finished batch of two clouds per scene: -> ((overlap of the source, of the target),
+        None) when the pair gets a gt.log line, (None, reason) when it does not."""
+        return cls._pair_ratios_at(offs, d_offs, cnt[j], 2 * j, 2 * j + 1)
+
+    @classmethod
+    def _pair_ratios_at(cls, offs, d_offs, cnt, a, b):
+        """The general form: the pair of segments (a, b) of a finished batch, `cnt` that pair's two overlap counts."""
+        if offs[a + 1] - offs[a] < cls.GT_MIN_POINTS or offs[b + 1] - offs[b] < cls.GT_MIN_POINTS:
             return None, "a cloud has fewer than {} points".format(cls.GT_MIN_POINTS)
         with np.errstate(invalid="ignore", divide="ignore"):
-            o_s = float(np.float64(cnt[j, 0]) / np.float64(d_offs[2 * j + 1] - d_offs[2 * j]))
-            o_t = float(np.float64(cnt[j, 1]) / np.float64(d_offs[2 * j + 2] - d_offs[2 * j + 1]))
+            o_s = float(np.float64(cnt[0]) / np.float64(d_offs[a + 1] - d_offs[a]))
+            o_t = float(np.float64(cnt[1]) / np.float64(d_offs[b + 1] - d_offs[b]))
         if np.isnan(o_s) or np.isnan(o_t):
             return None, "an overlap ratio is NaN"
         if o_s < 0.1 and o_t < 0.1:
@@ -449,7 +503,8 @@ def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int
 
     The reference queries a KD-tree once per point in a Python loop (the wall-clock tail of a 10k-scene dataset); here the
     clouds of up to `scenes_per_launch` scenes are voxel-down-sampled by ONE ragged device call (`voxel='device'`; 'host' =
-    one by one in C++ on the calling thread, same ratios) and all their pairs go through ONE prg_overlap_counts launch.  `overlap='numpy-spec'` selects the numpy specification in postprocess.py instead — a test
+    one by one in C++ on the calling thread, same ratios), every cloud once however many of its scene's pairs it is in, and all
+    their pairs go through ONE prg_overlap_counts_indexed launch.  `overlap='numpy-spec'` selects the numpy specification in postprocess.py instead — a test
     hook for boxes without a GPU, never chosen implicitly."""
     from itertools import combinations
     if overlap not in ("hip", "numpy-spec"):
@@ -481,11 +536,19 @@ def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int
 
 
 def _finish_gt(todo, overlap: str, voxel: str = "device") -> None:
-    flat = [(src, tgt) for _n, _p, cand in todo for (_s, _t, src, tgt) in cand]
-    if overlap == "hip":
-        ratios = PP.overlap_ratios_hip(flat, voxel=voxel)
+    if overlap == "hip":             # every cloud uploaded and gridded once, however many of its scene's pairs it is in
+        clouds, pairs = [], []
+        for _n, _p, cand in todo:
+            at = {}                  # sample index -> position in `clouds`, within this scene
+            for (s, t, src, tgt) in cand:
+                for k, c in ((s, src), (t, tgt)):
+                    if k not in at:
+                        at[k] = len(clouds)
+                        clouds.append(c)
+                pairs.append((at[s], at[t]))
+        ratios = PP.overlap_ratios_indexed_hip(clouds, pairs, voxel=voxel)
     else:
-        ratios = [PP.compute_overlap_ratio(a, b) for a, b in flat]
+        ratios = [PP.compute_overlap_ratio(src, tgt) for _n, _p, cand in todo for (_s, _t, src, tgt) in cand]
     k = 0
     for scene_name, gt_path, cand in todo:
         lines = []

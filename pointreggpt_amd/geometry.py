@@ -281,6 +281,26 @@ def voxel_grid_ragged(pts: torch.Tensor, valid: Optional[torch.Tensor], offsets:
     return out[:total], out_offsets, status
 
 
+def overlap_counts_indexed(pts: torch.Tensor, offsets: torch.Tensor, pair_index: torch.Tensor, max_cloud: int, radius: float):
+    """prg_overlap_counts_indexed: pts (total,3) float64 and offsets (n_clouds+1) int64, a SET of ragged clouds, and pair_index
+    (n_pairs,2) int32, all device tensors.  -> counts (n_pairs,2) int32 on the device: for (s, t) = pair_index[p] the rows of
+    cloud s with a row of cloud t strictly within `radius`, and the same from t's side — `prg_overlap_counts`' decision, every
+    cloud stored once however many pairs it is in.  A pair with an entry outside [0, n_clouds) gets (-1, -1).  At most 65535
+    pairs per call.  Nothing synchronises."""
+    lib = _lib.load()
+    pts, offsets, _total = _ragged_f64(pts, offsets)
+    if not pair_index.is_cuda:
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pair_index.dtype == torch.int32 and pair_index.dim() == 2 and pair_index.shape[1] == 2
+    pair_index = pair_index.contiguous()
+    n_pairs = pair_index.shape[0]
+    counts = torch.empty((n_pairs, 2), dtype=torch.int32, device=pts.device)
+    _lib.check(lib.prg_overlap_counts_indexed(_lib.ptr(pts), _lib.ptr(offsets), offsets.numel() - 1, _lib.ptr(pair_index), n_pairs,
+                                              int(max_cloud), float(radius), _lib.ptr(counts), _lib.stream_ptr()),
+               "prg_overlap_counts_indexed")
+    return counts
+
+
 def nearest_ragged(pts: torch.Tensor, offsets: torch.Tensor, n_pairs: int, max_cloud: int):
     """Nearest point of the other cloud for `n_pairs` cloud pairs in one launch (prg_nearest_ragged_f64): pts (total,3)
     float64 and offsets (2*n_pairs+1) int64 as `prg_overlap_counts` takes them, both device tensors.  Returns (d2 (total)

@@ -1006,3 +1006,45 @@ def overlap_ratios_hip(pairs, voxel_size: float = 0.025, overlap_factor: float =
     with np.errstate(invalid="ignore", divide="ignore"):
         return [(float(cnt[i, 0] / np.float64(sizes[2 * i])), float(cnt[i, 1] / np.float64(sizes[2 * i + 1])))
                 for i in range(len(pairs))]
+
+
+def overlap_ratios_indexed_hip(clouds, pairs, voxel_size: float = 0.025, overlap_factor: float = 1.5, voxel: str = "device",
+                               device="cuda"):
+    """`overlap_ratios_hip` for pairs that share clouds: clouds = [(n,3), ...], pairs = [(s, t), ...] indices into it ->
+    [(overlap of cloud s, overlap of cloud t), ...] per pair, exactly as `compute_overlap_ratio(clouds[s], clouds[t])` defines
+    them.  Every cloud is uploaded and voxel-down-sampled ONCE, however many pairs it is in (`voxel` as in `overlap_ratios_hip`),
+    and the pairs go through prg_overlap_counts_indexed, 65535 per launch."""
+    import torch
+
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    if voxel not in ("device", "host"):
+        raise ValueError("voxel must be 'device' or 'host'")
+    pairs = [(int(s), int(t)) for s, t in pairs]
+    if any(not (0 <= s < len(clouds) and 0 <= t < len(clouds)) for s, t in pairs):
+        raise ValueError("a pair names a cloud that is not in the list")
+    if not pairs:
+        return []
+    raw = [_f64(c) for c in clouds]
+    if voxel == "host":
+        raw = [native_voxel_down_sample(c, voxel_size) for c in raw]
+    in_max = max(len(c) for c in raw)
+    if in_max == 0:
+        return [(float("nan"), float("nan"))] * len(pairs)
+    pts, d_offs = G.upload_clouds(raw, device, dtype=np.float64)
+    if voxel == "device":
+        pts, d_offs, status = G.voxel_grid_ragged(pts, None, d_offs, voxel_size)
+    index = torch.from_numpy(np.array(pairs, dtype=np.int32).reshape(-1, 2)).to(pts.device)
+    # max_cloud bounds the query slabs per cloud: the largest INPUT cloud is an upper bound of the largest down-sampled one
+    counts = torch.cat([G.overlap_counts_indexed(pts, d_offs, index[k:k + 65535], in_max, voxel_size * overlap_factor)
+                        for k in range(0, len(pairs), 65535)], dim=0)
+    if voxel == "device":
+        G.check_voxel_status(status.cpu().numpy(), ["cloud {}".format(k) for k in range(len(raw))])
+        sizes = np.diff(d_offs.cpu().numpy())
+    else:
+        sizes = np.array([len(c) for c in raw], dtype=np.int64)
+    cnt = counts.cpu().numpy().astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return [(float(cnt[i, 0] / np.float64(sizes[s])), float(cnt[i, 1] / np.float64(sizes[t]))) for i, (s, t) in enumerate(pairs)]

@@ -22,12 +22,21 @@ device — a random pose, the cut to a point limit, uniform per-point noise — 
 `corr` on the augmented clouds under the ground-truth `transform` (see `Augment`).  With `augment=None` (the default) the
 items are exactly the ones described above.
 
+Several views per scene: `PairStream(..., num_samples=k, clouds="per_view")` runs k views per scene as `generate` does (the
+scene memory updated on the device between the views) and yields, per scene and in `itertools.combinations` order, one item for
+every pair (s, t) of the scene's k + 1 clouds that gets a `gt.log` line — the rows of the files s and t of `generate(...,
+num_samples=k, clouds="per_view", gt_log=True)`, the line's two ratios, `corr` of exactly these two clouds — with the two
+extra keys `src_idx` = s and `tgt_idx` = t; `skipped` names every dropped pair as (scene, "pair (s, t): <reason>").  An
+augmented item of pair (s, t) draws from its own keys (`synthetic.augment_seed_pair(..., pair=(s, t))`).  With `clouds="fused"` (the
+default) and `num_samples=k` the stream yields the one fused pair per scene that `generate(num_samples=k, gt_log=True)` writes.
+
 The stream runs on the calling thread's current HIP stream.  It uses no writer pool and no lanes, writes no file and creates
 nothing under the generator's `samples_folder` (the folder itself is `Generator.__init__`'s doing).
 """
 from __future__ import annotations
 
 import pickle
+from itertools import combinations
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -73,18 +82,18 @@ def uniform_rotation(rng: np.random.Generator) -> np.ndarray:
     return q if np.linalg.det(q) > 0 else -q
 
 
-def augment_poses(noise_seed: int, scene: int, epoch: int, augment: Augment):
+def augment_poses(noise_seed: int, scene: int, epoch: int, augment: Augment, pair=None):
     """The poses of one scene's item -> (move_src, move_tgt, transform): float64 4x4 matrices built on the host, a move being
     None for a cloud that stays where it is.  `src_aug = rigid_move(src, move_src)`, `tgt_aug = rigid_move(tgt, move_tgt)`, and
     `transform` takes the augmented source into the augmented target's frame.
 
-    Drawn from `np.random.Generator(np.random.Philox(key=synthetic.augment_seed(noise_seed, scene, 2), counter=[0, 0, 0,
-    epoch]))` in this order: R (`uniform_rotation`), t = standard_normal(3) * translation, and for "both" R2.  "src":
+    Drawn from `np.random.Generator(np.random.Philox(key=synthetic.augment_seed_pair(noise_seed, scene, 2, pair), counter=[0, 0, 0,
+    epoch]))` (`pair`: the (s, t) of an item of a scene with per-view clouds; None or (0, 1): today's key) in this order: R (`uniform_rotation`), t = standard_normal(3) * translation, and for "both" R2.  "src":
     move_src = [[R^T, -R^T t], [0, 1]] (the loaders' `(src - t) @ R`), transform = [R | t].  "both": move_tgt = [R2 | 0],
     transform = R2 [R | t]."""
     if augment.rotation is None:
         return None, None, np.eye(4)
-    rng = np.random.Generator(np.random.Philox(key=synthetic.augment_seed(noise_seed, scene, 2), counter=[0, 0, 0, int(epoch)]))
+    rng = np.random.Generator(np.random.Philox(key=synthetic.augment_seed_pair(noise_seed, scene, 2, pair), counter=[0, 0, 0, int(epoch)]))
     R = uniform_rotation(rng)
     t = rng.standard_normal(3) * float(augment.translation)
     move_src, transform = np.eye(4), np.eye(4)
@@ -101,7 +110,8 @@ def augment_poses(noise_seed: int, scene: int, epoch: int, augment: Augment):
 class PairStream:
     def __init__(self, generator, depth_correction, *, start: int, stop: int, noise_seed: int,
                  matching_radius: Optional[float] = None, mask_threshold: float = 0.99, has_refine_step: bool = False,
-                 save_voxel_size: float = 0.025, to: str = "numpy", augment: Optional[Augment] = None, epoch: int = 0):
+                 save_voxel_size: float = 0.025, to: str = "numpy", augment: Optional[Augment] = None, epoch: int = 0,
+                 num_samples: int = 1, clouds: str = "fused", memory_voxel_size: float = 0.002):
         if to not in ("numpy", "torch"):
             raise ValueError("to must be 'numpy' or 'torch'")
         if generator.device.type == "cpu":
@@ -114,6 +124,11 @@ class PairStream:
             raise ValueError("augment must be a stream.Augment (or None)")
         if not 0 <= int(epoch) < 2 ** 32:
             raise ValueError("epoch must fit 32 bits")
+        if clouds not in ("fused", "per_view"):
+            raise ValueError("clouds must be 'fused' or 'per_view'")
+        if int(num_samples) < 1:
+            raise ValueError("num_samples must be >= 1")
+        self.num_samples, self.per_view, self.memory_voxel_size = int(num_samples), clouds == "per_view", memory_voxel_size
         self.augment, self.epoch = augment, int(epoch)
         self.generator = generator
         self.depth_correction = depth_correction
@@ -124,9 +139,9 @@ class PairStream:
         self.has_refine_step = has_refine_step
         self.save_voxel_size = save_voxel_size
         self.to = to
-        self.skipped: List[Tuple[int, str]] = []     # (scene, reason) of the scenes generate_gt's filter drops
+        self.skipped: List[Tuple[int, str]] = []     # (scene, reason) of the pairs generate_gt's filter drops
 
-    # -- the device sequence of one batch: Generator._lane for num_samples = 1 and gt_log=True, minus every file ---------------
+    # -- the device sequence of one batch: Generator._lane for gt_log=True, minus every file ------------------------------------
     @torch.no_grad()
     def _batch(self, idxs, info_train):
         gen = self.generator
@@ -141,33 +156,45 @@ class PairStream:
         memory = [PP.crop_aabb(f.astype(np.float32)).astype(np.float32) for f in frames]      # the scene "memory" (sd:2484-2490)
         param_cond = G_.param_vector(K_dev)
         mem_pts, mem_offs = G_.upload_clouds(memory, dev)
-        pose = gen._poses(idxs, 0, self.noise_seed)
-        pose_dev = torch.from_numpy(pose).to(dev)
-        rpj, hit = G_.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
-        prob = self.depth_correction(rpj)
-        _rpj_c, _hit_c, cond = G_.apply_mask(prob, rpj, hit, self.mask_threshold)
-        seeds = [synthetic.noise_seed(self.noise_seed, i, 0) for i in idxs]
-        images = gen.model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds, has_refine_step=self.has_refine_step)
-        prob2 = self.depth_correction(images)
-        images, _, _ = G_.apply_mask(prob2, images, None, self.mask_threshold, want_cond=False)
-        xyz, valid = G_.unproject_f64(images, K_dev, pose_dev)
-        return gen._finish_pairs_launch(mem_pts, mem_offs, [len(m) for m in memory], [(xyz, valid)], pose, self.save_voxel_size)
+        mem_pts0, mem_offs0 = mem_pts, mem_offs                                                # the source frame of the pairs
+        views, poses = [], []
+        for sample_idx in range(self.num_samples):
+            pose = gen._poses(idxs, sample_idx, self.noise_seed)
+            pose_dev = torch.from_numpy(pose).to(dev)
+            rpj, hit = G_.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
+            prob = self.depth_correction(rpj)
+            _rpj_c, _hit_c, cond = G_.apply_mask(prob, rpj, hit, self.mask_threshold)
+            seeds = [synthetic.noise_seed(self.noise_seed, i, sample_idx) for i in idxs]
+            images = gen.model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds, has_refine_step=self.has_refine_step)
+            prob2 = self.depth_correction(images)
+            images, _, _ = G_.apply_mask(prob2, images, None, self.mask_threshold, want_cond=False)
+            xyz, valid = G_.unproject_f64(images, K_dev, pose_dev)
+            views.append((xyz, valid))
+            poses.append(pose)
+            if sample_idx < self.num_samples - 1:                                              # memory update (sd:2661-2680)
+                merged, mvalid, moffs = G_.merge_memory(mem_pts, mem_offs, xyz, valid)
+                vg_out, mem_offs, vg_status = G_.voxel_grid_ragged(merged, mvalid, moffs, self.memory_voxel_size)
+                st_n = torch.cat([vg_status.to(torch.int64), mem_offs[-1:]]).cpu().numpy()
+                G_.check_voxel_status(st_n[:-1], ["scene-{:0>6d}".format(i) for i in idxs])
+                mem_pts = vg_out.to(torch.float32)[:max(int(st_n[-1]), 1)]
+        return gen._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views, poses if self.per_view else poses[0],
+                                        self.save_voxel_size)
 
     # -- the loaders' augmentation of the surviving pairs of a batch: one launch for all of them -------------------------------
-    def _augment(self, pts, sizes, scenes):
-        """pts / sizes: the ragged buffer of the pairs (segments 2k, 2k+1 = src, tgt of scenes[k]) -> (augmented buffer, its
-        sizes, int32 rows, [transform per pair])."""
+    def _augment(self, pts, sizes, scenes, pairs):
+        """pts / sizes: the ragged buffer of the pairs (segments 2k, 2k+1 = src, tgt of scenes[k]; pairs[k] = the (s, t) behind
+        them, or None) -> (augmented buffer, its sizes, int32 rows, [transform per pair])."""
         aug, G_ = self.augment, self.generator.G
         n = len(scenes)
         T = np.tile(np.eye(4), (2 * n, 1, 1))
         has_T = np.zeros(2 * n, dtype=np.uint8)
         seeds, transforms = [], []
         for k, scene in enumerate(scenes):
-            moves = augment_poses(self.noise_seed, scene, self.epoch, aug)
+            moves = augment_poses(self.noise_seed, scene, self.epoch, aug, pairs[k])
             for c in (0, 1):
                 if moves[c] is not None:
                     T[2 * k + c], has_T[2 * k + c] = moves[c], 1
-                seeds.append(synthetic.augment_seed(self.noise_seed, scene, c))
+                seeds.append(synthetic.augment_seed_pair(self.noise_seed, scene, c, pairs[k]))
             transforms.append(moves[2])
         res = G_.augment_clouds(pts, sizes, seeds=seeds, draw=self.epoch, noise=aug.noise, limit=aug.point_limit,
                                 T=T if has_T.any() else None, has_T=has_T if has_T.any() else None)
@@ -189,27 +216,35 @@ class PairStream:
             finished = self._batch(idxs, info_train)
             fin = finished[0]
             offs, d_offs, cnt = gen._finish_pairs_words(finished, idxs)          # the one copy of the small words
-            keep, ratios = [], []
+            n = (len(offs) - 1) // batch                                         # clouds per scene
+            combos = list(combinations(range(n), 2))
+            keep, ratios = [], []                                                # keep: (scene of the batch, s, t)
             for j, idx in enumerate(idxs):
-                r, why = gen._pair_ratios(offs, d_offs, cnt, j)
-                if r is None:
-                    self.skipped.append((idx, why))
-                else:
-                    keep.append(j)
-                    ratios.append(r)
+                for p, (s, t) in enumerate(combos):
+                    if n == 2:
+                        r, why = gen._pair_ratios(offs, d_offs, cnt, j)
+                    else:
+                        r, why = gen._pair_ratios_at(offs, d_offs, cnt[len(combos) * j + p], n * j + s, n * j + t)
+                    if r is None:
+                        self.skipped.append((idx, "pair ({}, {}): {}".format(s, t, why) if self.per_view else why))
+                    else:
+                        keep.append((j, s, t))
+                        ratios.append(r)
             if not keep:
                 continue
-            # one ragged buffer of the surviving pairs: segments (2k, 2k+1) = (source frame, generated view) of keep[k]
-            sizes = np.array([offs[2 * j + k + 1] - offs[2 * j + k] for j in keep for k in (0, 1)], dtype=np.int64)
+            # one ragged buffer of the surviving pairs: segments (2k, 2k+1) = the clouds (s, t) of keep[k]
+            segs = [n * j + c for j, s, t in keep for c in (s, t)]
+            sizes = np.array([offs[a + 1] - offs[a] for a in segs], dtype=np.int64)
             k_offs = np.zeros(len(sizes) + 1, dtype=np.int64)
             k_offs[1:] = np.cumsum(sizes)
-            if len(keep) == batch:
+            if n == 2 and len(keep) == batch:
                 pts = fin[int(offs[0]):int(offs[-1])]
             else:
-                pts = torch.cat([fin[int(offs[2 * j]):int(offs[2 * j + 2])] for j in keep], dim=0)
+                pts = torch.cat([fin[int(offs[a]):int(offs[a + 1])] for a in segs], dim=0)
             rows = transforms = None
             if self.augment is not None:
-                pts, sizes, rows, transforms = self._augment(pts, sizes, [idxs[j] for j in keep])
+                pts, sizes, rows, transforms = self._augment(pts, sizes, [idxs[j] for j, _s, _t in keep],
+                                                             [(s, t) if self.per_view else None for _j, s, t in keep])
                 k_offs[1:] = np.cumsum(sizes)
             corr = c_offs = None
             if self.matching_radius is not None:
@@ -228,9 +263,11 @@ class PairStream:
                 own = np.copy
             else:
                 own = torch.clone
-            for k, j in enumerate(keep):
+            for k, (j, s, t) in enumerate(keep):
                 item = dict(scene=idxs[j], src=own(pts[k_offs[2 * k]:k_offs[2 * k + 1]]), tgt=own(pts[k_offs[2 * k + 1]:k_offs[2 * k + 2]]),
                             overlap_src=ratios[k][0], overlap_tgt=ratios[k][1])
+                if self.per_view:
+                    item["src_idx"], item["tgt_idx"] = s, t
                 if corr is not None:
                     item["corr"] = own(corr[c_offs[k]:c_offs[k + 1]])
                 if rows is not None:

@@ -86,9 +86,18 @@ def augment_seed(base_seed: int, scene_index: int, cloud: int = 0) -> int:
     """64-bit Philox key of a scene's augmentation streams, built the way `noise_seed` is, with the tag word 0x6175676D
     ("augm"): cloud 0 = the source cloud's rows, 1 = the target cloud's rows (`postprocess.augment_cloud`'s seed), 2 = the pose
     stream (`stream.augment_poses`).  Shard-invariant: it depends on the run's seed and the two indices only."""
+    return augment_seed_pair(base_seed, scene_index, cloud)
+
+
+def augment_seed_pair(base_seed: int, scene_index: int, cloud: int = 0, pair=None) -> int:
+    """`augment_seed` for an item made of the cloud files (s, t) = `pair` of its scene: a scene with per-view clouds has several
+    pairs, and each gets its own draws.  The two words s, t are appended to `augment_seed`'s seed words — except for (0, 1), the
+    only pair of a scene with one target cloud, which like None gives `augment_seed`'s key."""
     if cloud not in (0, 1, 2):
         raise ValueError("cloud is 0 (src), 1 (tgt) or 2 (the pose stream)")
     words = [int(base_seed) & 0xFFFFFFFFFFFFFFFF, int(scene_index), 0x6175676D]
     if cloud:
         words.append(int(cloud))
+    if pair is not None and (int(pair[0]), int(pair[1])) != (0, 1):
+        words += [int(pair[0]), int(pair[1])]     # t >= 1 for s < t: no key is another's word list padded with zeros
     return int(np.random.SeedSequence(words).generate_state(1, np.uint64)[0])
