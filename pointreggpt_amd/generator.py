@@ -15,13 +15,15 @@ sd = /root/reference/denoising_diffusion_pytorch/successive_ddnm_diffusion.py
 """
 from __future__ import annotations
 
+import functools
 import os
 import pickle
 import shutil
 import sys
 import threading
+from itertools import combinations
 from pathlib import Path
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -29,9 +31,20 @@ import torch
 from . import geometry as G
 from . import postprocess as PP
 from . import synthetic
-from .sharding import num_to_groups
+from .scene_memory import DeviceMemory, HostMemory, HostRows
+from .sharding import index_batches
 
 PAIRS_PER_LAP = 20642   # real pairs per lap of the scene index; src/tgt swap on odd laps (sd:2397-2410)
+
+
+class FinishedPairs(NamedTuple):
+    """What `_finish_pairs_launch` leaves on the device, n clouds per scene, scene-major."""
+    points: torch.Tensor          # the finished clouds, one ragged float64 buffer
+    offsets: torch.Tensor         # (nB+1) int64
+    status_save: torch.Tensor     # (nB) voxel statuses of the finish at save_voxel_size
+    status_gt: torch.Tensor       # (nB) voxel statuses of the grid at GT_VOXEL
+    counts: torch.Tensor          # (B * C(n, 2), 2) overlap counts, in `_pair_rows` order
+    down_offsets: torch.Tensor    # (nB+1) int64 offsets of the clouds down-sampled at GT_VOXEL
 
 
 class Generator:
@@ -88,6 +101,13 @@ class Generator:
         depth[depth > 1] = 0
         return depth, K
 
+    def _train_info(self):
+        """The real-data scene index (sd:2352); None with synthetic input."""
+        if self.synthetic_seed is not None:
+            return None
+        with open("./dataset/indoor/metadata/train_info.pkl", "rb") as f:
+            return pickle.load(f)
+
     def _scene_inputs(self, abs_idx: int, info_train, scene_dir: Path):
         if self.synthetic_seed is not None:
             depth, K, _pose = synthetic.synth_scene(self.synthetic_seed, abs_idx, self.image_size)
@@ -131,19 +151,15 @@ class Generator:
         a run can be re-sharded / resumed reproducibly; False = numpy's global stream like the reference (single lane only).
         Default: True when the caller passes a `noise_seed` (ANY value, 0 included: `None` is the "no seed" sentinel) or lanes,
         False (the reference's unseeded behaviour) otherwise.
-        ``voxel_backend`` (num_samples > 1): where the scene memory lives between views.  "device" (the default on a HIP
-        device): one float32 ragged buffer on the GPU from the first upload on, updated by prg_merge_memory_f64 ->
-        prg_voxel_grid_ragged and read by the next view's z-buffer in place — no copy of the memory cloud to the host.
-        "host": the memory clouds are numpy arrays re-voxelised one by one in C++ on the calling thread (the only path of
-        a `device="cpu"` generator).  Both produce the same bytes.
+        ``voxel_backend`` (num_samples > 1): where the scene memory lives between views (`scene_memory`): "device" (the default
+        on a HIP device), `DeviceMemory`, no copy of the memory cloud to the host; "host", `HostMemory` (the only path of a
+        `device="cpu"` generator).  Both produce the same bytes.
         ``gt_log`` (HIP device only, `voxel_backend="device"`): finish both clouds of every scene on the GPU and write the
         scene's ``gt.log`` in the batch that sampled it — the line `generate_gt` would write after re-reading the two PLY files.
-        The memory clouds are uploaded once (also for num_samples == 1); the float64 views stay on the device; per batch ONE
-        ragged buffer of 2B segments [memory_j | views of scene j] goes through `finish_clouds` (the views with pre = pose0,
-        the crop box, post = pose0^-1; `save_voxel_size`), comes to the host once for the PLY writers (write-only jobs), and
-        through `voxel_grid_ragged` at generate_gt's 0.025 into one `prg_overlap_counts_indexed` launch.  Every file has the bytes of
-        the default path followed by `generate_gt`; a batch's gt.log files are on disk before its resume marker is submitted.
-        Afterwards `generate_gt` finds every scene done and only `gather_gt` is left.
+        The memory clouds are uploaded once (also for num_samples == 1), the float64 views stay on the device, and
+        `_finish_pairs_launch` does the rest; the clouds come to the host once for the PLY writers (write-only jobs).  Every file
+        has the bytes of the default path followed by `generate_gt`; a batch's gt.log files are on disk before its resume marker
+        is submitted.  Afterwards `generate_gt` finds every scene done and only `gather_gt` is left.
         ``clouds``: "fused" (the default, the reference's layout): all `num_samples` views of a scene end in ONE target cloud,
         sample-000001.cloud.ply, finished in the first view's camera frame.  "per_view": every view i = 1..num_samples gets its
         own sample-{i:06d}.cloud.ply — `postprocess.finish_cloud(xyz_i[valid_i], pre=pose_i, crop=the box, voxel=save_voxel_size,
@@ -161,15 +177,9 @@ class Generator:
         if seed_poses is None:
             seed_poses = noise_seed is not None or (lanes is not None and len(lanes) > 0)
         noise_seed = 0 if noise_seed is None else int(noise_seed)
-        info_train = None
-        if self.synthetic_seed is None:
-            with open("./dataset/indoor/metadata/train_info.pkl", "rb") as f:
-                info_train = pickle.load(f)
+        info_train = self._train_info()
         batches = []
-        first = start_scene_index
-        for batch in num_to_groups(stop_scene_index - start_scene_index, self.batch_size):
-            idxs = list(range(first, first + batch))
-            first += batch
+        for idxs in index_batches(start_scene_index, stop_scene_index, self.batch_size):
             # resume: skip a batch whose last scene already has its generated cloud (sd:2371-2381)
             done = self.samples_folder / "scene-{:0>6d}/sample-{:0>6d}.cloud.ply".format(idxs[-1], num_samples // 2)
             if done.is_file():
@@ -184,15 +194,14 @@ class Generator:
         pairs = pairs[:max(1, len(batches))]
         kw = dict(num_samples=num_samples, memory_voxel_size=memory_voxel_size, save_voxel_size=save_voxel_size,
                   has_refine_step=has_refine_step, mask_threshold=mask_threshold, noise_seed=noise_seed, progress=progress,
-                  seed_poses=seed_poses, info_train=info_train, voxel_backend=voxel_backend, gt_log=gt_log,
-                  per_view=clouds == "per_view")
+                  seed_poses=seed_poses, info_train=info_train, per_view=clouds == "per_view", gt_log=gt_log,
+                  on_device=(voxel_backend == "device" and num_samples > 1) or gt_log)      # where the scene memory lives
         n = len(pairs)
         wt = writer_threads if writer_threads <= 0 or n == 1 else max(1, writer_threads // n)
         results = [None] * n
         if n == 1:
             results[0] = self._lane(batches, pairs[0][0], pairs[0][1], wt, 1, **kw)
         else:
-            import threading
             errs = []
             stop = threading.Event()          # set by the first failing lane: the others stop at their next batch
             dev = self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
@@ -224,18 +233,46 @@ class Generator:
 
     _pose_lock = threading.Lock()      # guards numpy's process-wide legacy stream (seed_poses=False)
 
+    def _batch_setup(self, idxs, info_train, sdirs=None, each=None):
+        """A batch's inputs -> (K (B,3,3), K_dev, depth0 (B,1,S,S), param_cond, the scene "memory" clouds (sd:2484-2490): the
+        source frames of the whole batch in ONE unprojection (sd:2479-2483 does it per scene), cropped to the box one by one;
+        `each(j, K_j, depth0_j, cloud_j)` is called as soon as scene j is cropped)."""
+        K = np.zeros((len(idxs), 3, 3), dtype=np.float32)
+        depth0 = np.zeros((len(idxs), 1, self.image_size, self.image_size), dtype=np.float32)
+        for j, idx in enumerate(idxs):
+            depth0[j, 0], K[j] = self._scene_inputs(idx, info_train, None if sdirs is None else sdirs[j])
+        K_dev = torch.from_numpy(K).to(self.device)
+        frames = self.G.point_clouds(torch.from_numpy(depth0).to(self.device), K_dev, None)
+        clouds = []
+        for j, f in enumerate(frames):
+            clouds.append(PP.crop_aabb(f.astype(np.float32)).astype(np.float32))
+            if each is not None:                           # scene j's first files go to the writers while the next one is cropped
+                each(j, K[j], depth0[j, 0], clouds[j])
+        return K, K_dev, depth0, self.G.param_vector(K_dev), clouds
+
+    def _view(self, memory, pose, K, K_dev, param_cond, model, depth_correction, seeds, mask_threshold, has_refine_step):
+        """One view of every scene of a batch, launches only: the memory z-buffered into the cameras `pose`, corrected, the DDNM
+        condition, the sampler, corrected again, unprojected into the common frame in float64 (sd:2623-2628)."""
+        pose_dev = torch.from_numpy(pose).to(self.device)
+        rpj, hit = memory.project(pose, K, self.image_size, 0.1)
+        prob = depth_correction(rpj)
+        rpj_c, _hit_c, cond = self.G.apply_mask(prob, rpj, hit, mask_threshold)
+        images = model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds, has_refine_step=has_refine_step)
+        prob2 = depth_correction(images)
+        images, _, _ = self.G.apply_mask(prob2, images, None, mask_threshold, want_cond=False)
+        xyz, valid = self.G.unproject_f64(images, K_dev, pose_dev)
+        return rpj, rpj_c, images, xyz, valid
+
     def _lane(self, batches, model, depth_correction, writer_threads, n_lanes, *, num_samples, memory_voxel_size,
               save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None,
-              voxel_backend="host", gt_log=False, per_view=False):
-        """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream."""
-        S, dev = self.image_size, self.device
+              on_device=False, per_view=False, gt_log=False):
+        """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream.  Per
+        batch: set-up; per view: step, memory update, blocking copies, side files, clouds; then the resume marker."""
         if writer_threads <= 0 and n_lanes > 1:
             writer_threads = max(2, min(16, PP.rank_cpu_budget() // 2) // n_lanes)
         with PP.WriterPool(writer_threads) as pool:
-            marker_prev = None                # deferred submission of the previous batch's resume marker
-            n_pairs = 0
-            # the cloud file the resume check looks for (fused: 0 or 1, never written beyond that; per view: always written)
-            marker_index = num_samples // 2
+            marker_prev, n_pairs = None, 0    # marker_prev: deferred submission of the previous batch's resume marker
+            out = _Clouds(self, pool, num_samples, save_voxel_size, per_view, gt_log)
 
             def flush_marker():
                 nonlocal marker_prev
@@ -247,163 +284,74 @@ class Generator:
             for idxs in batches:
                 if stop is not None and stop.is_set():
                     break                      # another lane failed: do not sample this lane's whole share first
-                batch = len(idxs)
-                K = np.zeros((batch, 3, 3), dtype=np.float32)
-                depth0 = np.zeros((batch, 1, S, S), dtype=np.float32)
-                sdirs = []
-                for j, idx in enumerate(idxs):
-                    sdir = self.samples_folder / "scene-{:0>6d}".format(idx)
-                    if sdir.exists():
-                        shutil.rmtree(str(sdir), ignore_errors=True)
+                sdirs = [self.samples_folder / "scene-{:0>6d}".format(idx) for idx in idxs]
+                for sdir in sdirs:
+                    shutil.rmtree(str(sdir), ignore_errors=True)        # (a scene folder of an interrupted run, if there is one)
                     sdir.mkdir(parents=True, exist_ok=True)
-                    sdirs.append(sdir)
-                    depth0[j, 0], K[j] = self._scene_inputs(idx, info_train, sdir)
-                K_dev = torch.from_numpy(K).to(dev)
-                # the source frames of the whole batch in ONE unprojection (sd:2479-2483 does it per scene)
-                frames = self.G.point_clouds(torch.from_numpy(depth0).to(dev), K_dev, None)
-                memory: List[np.ndarray] = []
-                marker_cur = None
-                for j in range(batch):
-                    scene_pc = PP.crop_aabb(frames[j].astype(np.float32)).astype(np.float32)   # the scene "memory" (sd:2484-2490)
-                    memory.append(scene_pc)
-                    pool.text(str(sdirs[j] / "camera-intrinsics.txt"), K[j])
-                    pool.image01(str(sdirs[j] / "sample-{:0>6d}.image.png".format(0)), depth0[j, 0])
-                    job = (lambda path=str(sdirs[j] / "sample-{:0>6d}.cloud.ply".format(0)), pc=scene_pc:
-                           pool.cloud(path, pc, None, crop=False, voxel=save_voxel_size))
-                    if gt_log:
-                        pass                          # written with the generated cloud, from the device-finished buffer
-                    elif j == batch - 1 and marker_index == 0:
-                        marker_cur = job              # this batch's resume marker: written after everything else
-                    else:
-                        job()
-                param_cond = self.G.param_vector(K_dev)
-                fragments: List[Optional[np.ndarray]] = [None] * batch
-                poses0 = None
-                poses = []                    # every view's poses (the per-view clouds are finished in their own frames)
-                on_device = (voxel_backend == "device" and num_samples > 1) or gt_log
-                if on_device:                 # the ONE upload of the memory clouds; from here on they stay on the device
-                    mem_pts, mem_offs = self.G.upload_clouds(memory, dev)
-                mem_pts0, mem_offs0 = (mem_pts, mem_offs) if gt_log else (None, None)   # the source frame of the pair
-                views = []                    # gt_log: every sample's (xyz, valid) as unproject_f64 left them, on the device
-                finished = None
+                out.begin(idxs, sdirs)
+
+                def first_files(j, K_j, depth0_j, scene_pc):
+                    pool.text(str(sdirs[j] / "camera-intrinsics.txt"), K_j)
+                    pool.image01(str(sdirs[j] / "sample-{:0>6d}.image.png".format(0)), depth0_j)
+                    out.source(j, scene_pc)
+
+                K, K_dev, _depth0, param_cond, scene_pcs = self._batch_setup(idxs, info_train, sdirs, first_files)
+                memory = DeviceMemory.upload(self.G, scene_pcs, self.device) if on_device else HostMemory(self.G, scene_pcs, self.device)
+                names = ["scene-{:0>6d}".format(i) for i in idxs]
                 for sample_idx in range(num_samples):
                     pose = self._poses(idxs, sample_idx, noise_seed if seed_poses else None)
-                    if sample_idx == 0:
-                        poses0 = pose
-                    poses.append(pose)
-                    pose_dev = torch.from_numpy(pose).to(dev)
-                    if on_device:
-                        rpj, hit = self.G.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
-                    else:
-                        rpj, hit = self.G.project_clouds(memory, pose, K, S, dev, depth_scale=0.1)
-                    prob = depth_correction(rpj)
-                    rpj_c, hit_c, cond = self.G.apply_mask(prob, rpj, hit, mask_threshold)
                     seeds = [synthetic.noise_seed(noise_seed, i, sample_idx) for i in idxs]
-                    images = model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds,
-                                          has_refine_step=has_refine_step)
-                    prob2 = depth_correction(images)
-                    images, _, _ = self.G.apply_mask(prob2, images, None, mask_threshold, want_cond=False)
-                    xyz, valid = self.G.unproject_f64(images, K_dev, pose_dev)      # common frame, float64 (sd:2623-2628)
-                    last_sample = sample_idx == num_samples - 1
-                    vg_status = None
-                    if on_device and not last_sample:                               # memory update (sd:2661-2680), no host trip
-                        merged, mvalid, moffs = self.G.merge_memory(mem_pts, mem_offs, xyz, valid)
-                        vg_out, mem_offs, vg_status = self.G.voxel_grid_ragged(merged, mvalid, moffs, memory_voxel_size)
-                        mem_pts = vg_out.to(torch.float32)
-                    if gt_log:
-                        views.append((xyz, valid))
-                        if last_sample:
-                            finished = self._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views,
-                                                                 poses if per_view else poses0, save_voxel_size)
+                    rpj, rpj_c, images, xyz, valid = self._view(memory, pose, K, K_dev, param_cond, model, depth_correction, seeds,
+                                                                mask_threshold, has_refine_step)
+                    if sample_idx < num_samples - 1:                                # memory update (sd:2661-2680): queued
+                        memory.update(xyz, valid, memory_voxel_size)
+                    out.add_view(memory, pose, xyz, valid)                          # (gt_log: the finish is queued with the last)
                     # one blocking copy per tensor: the host waits here for the GPU while the pool writes the previous batch
                     rpj_host, crt_host, img_host = rpj.cpu().numpy(), rpj_c.cpu().numpy(), images.cpu().numpy()
-                    if not gt_log:
-                        xyz_host, valid_host = xyz.cpu().numpy(), valid.cpu().numpy()
-                    if vg_status is not None:     # B status words + the memory's row count: all the host learns of it
-                        st_n = torch.cat([vg_status.to(torch.int64), mem_offs[-1:]]).cpu().numpy()
-                        self.G.check_voxel_status(st_n[:-1], ["scene-{:0>6d}".format(i) for i in idxs])
-                        mem_pts = mem_pts[:max(int(st_n[-1]), 1)]
+                    rows = None if gt_log else HostRows.copy(xyz, valid)            # (gt_log: the views stay on the device)
+                    memory.settle(names, rows)
                     flush_marker()
-                    for j, idx in enumerate(idxs):
-                        sdir = sdirs[j]
+                    for j, sdir in enumerate(sdirs):
                         pool.image01(str(sdir / "reprojected.image.png"), rpj_host[j])
                         pool.text(str(sdir / "sample-{:0>6d}.pose.txt".format(sample_idx + 1)), np.linalg.inv(pose[j]))
                         pool.image01(str(sdir / "corrected.image.png"), crt_host[j])
                         pool.image01(str(sdir / "sample-{:0>6d}.image.png".format(sample_idx + 1)), img_host[j])
                         pool.depth16(str(sdir / "sample-{:0>6d}.depth.png".format(sample_idx + 1)), img_host[j])
-                        if gt_log:
-                            continue                                                    # clouds: after the loop, from the device
-                        if per_view:                                                # the view alone, in its own frame
-                            if not last_sample and not on_device:                       # memory update (sd:2661-2680)
-                                merged = np.concatenate([memory[j], xyz_host[j][valid_host[j]]], axis=0)
-                                memory[j] = PP.native_voxel_down_sample(merged, memory_voxel_size).astype(np.float32)
-                            path = str(sdir / "sample-{:0>6d}.cloud.ply".format(sample_idx + 1))
-                            job = (lambda path=path, frag=xyz_host[j], fvalid=valid_host[j], T=pose[j].astype(np.float64):
-                                   pool.cloud(path, frag, fvalid, pre=T, crop=True, voxel=save_voxel_size, post=np.linalg.inv(T)))
-                            if j == batch - 1 and marker_index == sample_idx + 1:
-                                marker_cur = job
-                            else:
-                                job()
-                            continue
-                        if num_samples == 1:
-                            frag, fvalid = xyz_host[j], valid_host[j]                  # compaction happens in the worker
-                        else:
-                            pc = xyz_host[j][valid_host[j]]
-                            fragments[j] = pc if sample_idx == 0 else np.concatenate([fragments[j], pc], axis=0)
-                            frag, fvalid = fragments[j], None
-                            if not last_sample and not on_device:                       # memory update (sd:2661-2680)
-                                merged = np.concatenate([memory[j], pc], axis=0)
-                                memory[j] = PP.native_voxel_down_sample(merged, memory_voxel_size).astype(np.float32)
-                        if last_sample:                                                 # sd:2640-2658
-                            path = str(sdir / "sample-{:0>6d}.cloud.ply".format(1))
-                            job = (lambda path=path, frag=frag, fvalid=fvalid, T=poses0[j].astype(np.float64):
-                                   pool.cloud(path, frag, fvalid, pre=T, crop=True, voxel=save_voxel_size, post=np.linalg.inv(T)))
-                            if j == batch - 1 and marker_index == 1:
-                                marker_cur = job
-                            else:
-                                job()
-                    if finished is not None:
-                        marker_cur = self._finish_pairs_write(pool, finished, idxs, sdirs, marker_index)
+                        memory.settle_scene(j)                                      # (host memory: this scene's grid, on this thread)
+                        out.write(j, rows)
                     if progress:
                         print("batch {:0>6d}-{:0>6d}: sample {}/{}".format(idxs[0], idxs[-1], sample_idx + 1, num_samples))
-                n_pairs += batch
+                n_pairs += len(idxs)
                 flush_marker()                # (only reached with a pending marker when the sample loop did not run)
-                marker_prev = marker_cur
+                marker_prev = out.marker
             flush_marker()
-            jobs = pool.wait()
-            return n_pairs, jobs, pool.threads
-
+            return n_pairs, pool.wait(), pool.threads
 
     # -- gt_log: every cloud of a scene finished on the device, the scene's gt.log written with them ---------------------------
     GT_VOXEL, GT_FACTOR, GT_MIN_POINTS = 0.025, 1.5, 1000      # generate_gt's fixed literals (generate_gt.py:68-102, 133-140)
-    _pair_tables: dict = {}            # (B, clouds per scene, device) -> the batch's (pairs,2) int32 index table on the device
+    GT_LINE = "{}\t{}\t{}\t{:.4f}\t{:.4f}\n"                   # a gt.log line: scene name, s, t, overlap of s, overlap of t
 
-    @classmethod
-    def _pair_table(cls, B, n_seg, dev):
+    @staticmethod
+    @functools.lru_cache(maxsize=None)
+    def _pair_table(B, n_seg, dev):
+        """`_pair_rows` as the (pairs, 2) int32 device table that prg_overlap_counts_indexed takes.  Uploaded once."""
+        return torch.from_numpy(np.array(Generator._pair_rows(B, n_seg), dtype=np.int32)).to(dev)
+
+    @staticmethod
+    def _pair_rows(B, n_seg):
         """Every pair (s, t), s < t, of every scene's n_seg segments, scene-major and in `combinations` order, as rows
-        (n_seg * j + s, n_seg * j + t) of the batch's segment list: what prg_overlap_counts_indexed takes.  Uploaded once."""
-        from itertools import combinations
-        key = (B, n_seg, str(dev))
-        table = cls._pair_tables.get(key)
-        if table is None:
-            rows = [(n_seg * j + s, n_seg * j + t) for j in range(B) for s, t in combinations(range(n_seg), 2)]
-            table = cls._pair_tables[key] = torch.from_numpy(np.array(rows, dtype=np.int32)).to(dev)
-        return table
+        (n_seg * j + s, n_seg * j + t) of the batch's segment list."""
+        return [(n_seg * j + s, n_seg * j + t) for j in range(B) for s, t in combinations(range(n_seg), 2)]
 
-    def _finish_pairs_launch(self, mem_pts0, mem_offs0, mem_rows, views, poses, save_voxel_size):
-        """Device work of a batch's pairs, nothing read back: -> (finished clouds, offsets (nB+1), statuses, overlap counts,
-        down-sampled offsets), n clouds per scene, scene-major.  Segment n*j is scene j's source frame (its float32 memory
-        widened to float64).  `poses` an array (B,4,4): fused, n = 2, segment 2j+1 is all the views in view order, moved by that
-        pose and back.  `poses` a list of one such array per view: per view, n = 1 + views, segment n*j+i is view i alone, moved
-        by ITS pose and back.  Either way the segments are offset arithmetic on `merge_memory`'s buffer [memory_j | view 1 rows
-        | ... | view k rows]; the source frames are not moved.  The crop box is applied to every segment and is a no-op on the
-        source frames: the memory IS `crop_aabb` of the source frame in float32, the bounds are float32 numbers, and widening
-        keeps every comparison.  Every cloud is voxel-gridded once at generate_gt's 0.025 and all B * C(n, 2) pairs of the batch
-        go through ONE prg_overlap_counts_indexed launch; the counts are in `_pair_table`'s order."""
-        G_ = self.G
-        B = len(mem_rows)
-        dev = mem_pts0.device
-        per_view = isinstance(poses, (list, tuple))
+    def _finish_pairs_launch(self, memory, views, poses, per_view, save_voxel_size) -> FinishedPairs:
+        """Device work of a batch's pairs, nothing read back.  Segment n*j is scene j's source frame (`memory.mem_pts0`, float32
+        widened to float64).  `poses`: one array (B,4,4) per view.  Fused: n = 2, segment 2j+1 is all the views in view order, moved
+        by the FIRST view's pose and back.  `per_view`: n = 1 + views, segment n*j+i is view i alone, moved by ITS pose and back.
+        Either way the segments are offset arithmetic on `merge_memory`'s buffer [memory_j | view 1 rows | ... | view k rows]; the
+        source frames are not moved, and the crop box, applied to every segment, is a no-op on them.  Every cloud
+        is gridded once at generate_gt's 0.025 and all B * C(n, 2) pairs go through ONE prg_overlap_counts_indexed launch."""
+        G_, mem_pts0, mem_offs0, mem_rows = self.G, memory.mem_pts0, memory.mem_offs0, memory.rows0
+        B, dev = len(mem_rows), mem_pts0.device
         xyz = views[0][0] if len(views) == 1 else torch.cat([v[0] for v in views], dim=1)         # (B, n_views*HW, 3)
         valid = views[0][1] if len(views) == 1 else torch.cat([v[1] for v in views], dim=1)
         rows_v = xyz.shape[1]
@@ -421,7 +369,7 @@ class Generator:
         has = np.zeros((n * B,), dtype=np.uint8)
         for j in range(B):
             for i in range(1, n):
-                T = (poses[i - 1] if per_view else poses)[j].astype(np.float64)
+                T = poses[i - 1][j].astype(np.float64)
                 pre[n * j + i], post[n * j + i], has[n * j + i] = T, np.linalg.inv(T), 1     # the same 16 doubles as the host path
         fin, fin_offs, st_save = G_.finish_clouds(merged, mvalid, offs, save_voxel_size, pre=pre, has_pre=has,
                                                   crop=(PP.BBOX_MIN, PP.BBOX_MAX), post=post, has_post=has)
@@ -429,52 +377,45 @@ class Generator:
         # max_cloud only bounds the query slabs: no finished cloud has more rows than went into it
         counts = G_.overlap_counts_indexed(down, down_offs, self._pair_table(B, n, dev), int(max(max(mem_rows), rows_seg)),
                                            float(self.GT_VOXEL * self.GT_FACTOR))
-        return fin, fin_offs, st_save, st_gt, counts, down_offs
+        return FinishedPairs(fin, fin_offs, st_save, st_gt, counts, down_offs)
 
-    def _finish_pairs_write(self, pool, finished, idxs, sdirs, marker_index):
-        """Host side: ONE copy of the finished clouds, the PLY files as write-only jobs, every scene's gt.log written before this
-        returns — one line per surviving pair (s, t), s < t, in `combinations` order.  -> the batch's resume marker job (not yet
-        submitted)."""
-        from itertools import combinations
-        fin = finished[0]
-        B = len(idxs)
+    def _finish_pairs_write(self, pool, finished, idxs, sdirs, submit):
+        """Host side: ONE copy of the finished clouds, the PLY files as write-only jobs handed to `submit(job, j, k)`, every
+        scene's gt.log written before this returns — one line per surviving pair (s, t), s < t, in `combinations` order."""
         offs, d_offs, cnt = self._finish_pairs_words(finished, idxs)
-        n = (len(offs) - 1) // B
-        pts = fin[:max(int(offs[-1]), 0)].cpu().numpy()
-        marker = None
+        n = (len(offs) - 1) // len(idxs)
+        pts = finished.points[:max(int(offs[-1]), 0)].cpu().numpy()
         for j, sdir in enumerate(sdirs):
             for k in range(n):
-                job = (lambda path=str(sdir / "sample-{:0>6d}.cloud.ply".format(k)), pc=pts[offs[n * j + k]:offs[n * j + k + 1]]:
-                       pool.cloud(path, pc, None, crop=False, voxel=0))
-                if j == B - 1 and k == marker_index:
-                    marker = job
-                else:
-                    job()
-        combos = list(combinations(range(n), 2))
-        for j, (idx, sdir) in enumerate(zip(idxs, sdirs)):
-            lines = []
-            for p, (s, t) in enumerate(combos):
-                ratios, _why = self._pair_ratios_at(offs, d_offs, cnt[len(combos) * j + p], n * j + s, n * j + t)
-                if ratios is not None:
-                    lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format("scene-{:0>6d}".format(idx), s, t, ratios[0], ratios[1]))
-            with open(sdir / "gt.log", "w") as f:
-                f.writelines(lines)
-        return marker
+                submit((lambda path=str(sdir / "sample-{:0>6d}.cloud.ply".format(k)), pc=pts[offs[n * j + k]:offs[n * j + k + 1]]:
+                        pool.cloud(path, pc, None, crop=False, voxel=0)), j, k)
+        lines = [[] for _ in idxs]
+        for j, s, t, ratios, _why in self._pair_walk(offs, d_offs, cnt, len(idxs)):
+            if ratios is not None:
+                lines[j].append(self.GT_LINE.format("scene-{:0>6d}".format(idxs[j]), s, t, *ratios))
+        for sdir, ln in zip(sdirs, lines):
+            (sdir / "gt.log").write_text("".join(ln))
 
     def _finish_pairs_words(self, finished, idxs):
         """The small words of a finished batch in ONE copy, voxel statuses checked: -> (offsets (nB+1), down-sampled offsets
         (nB+1), overlap counts (B * C(n, 2), 2)) on the host, n clouds per scene."""
-        _fin, fin_offs, st_save, st_gt, counts, down_offs = finished
-        B = len(idxs)
-        N = fin_offs.numel() - 1                                              # n * B segments
-        small = torch.cat([fin_offs, down_offs, st_save.to(torch.int64), st_gt.to(torch.int64), counts.view(-1).to(torch.int64)])
-        small = small.cpu().numpy()
-        offs, d_offs = small[:N + 1], small[N + 1:2 * N + 2]
-        st_save, st_gt, cnt = small[2 * N + 2:3 * N + 2], small[3 * N + 2:4 * N + 2], small[4 * N + 2:].reshape(-1, 2)
-        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in range(N // B)]
-        self.G.check_voxel_status(st_save, names)
-        self.G.check_voxel_status(st_gt, names)
-        return offs, d_offs, cnt
+        N = finished.offsets.numel() - 1                                      # n * B segments
+        small = torch.cat([finished.offsets, finished.down_offsets, finished.status_save.to(torch.int64),
+                           finished.status_gt.to(torch.int64), finished.counts.view(-1).to(torch.int64)]).cpu().numpy()
+        names = ["scene-{:0>6d} sample-{:0>6d}".format(i, k) for i in idxs for k in range(N // len(idxs))]
+        self.G.check_voxel_status(small[2 * N + 2:3 * N + 2], names)
+        self.G.check_voxel_status(small[3 * N + 2:4 * N + 2], names)
+        return small[:N + 1], small[N + 1:2 * N + 2], small[4 * N + 2:].reshape(-1, 2)
+
+    @classmethod
+    def _pair_walk(cls, offs, d_offs, cnt, B):
+        """Every pair of a finished batch (the words of `_finish_pairs_words`) in `_pair_rows` order: yields (j, s, t, ratios or
+        None, reason) — scene j of the batch, its clouds s < t, `_pair_ratios_at`'s answer (two clouds per scene: `_pair_ratios`')."""
+        n = (len(offs) - 1) // B
+        for p, (a, b) in enumerate(cls._pair_rows(B, n)):
+            j = a // n
+            ratios, why = cls._pair_ratios(offs, d_offs, cnt, j) if n == 2 else cls._pair_ratios_at(offs, d_offs, cnt[p], a, b)
+            yield j, a - n * j, b - n * j, ratios, why
 
     @classmethod
     def _pair_ratios(cls, offs, d_offs, cnt, j):
@@ -485,16 +426,85 @@ class Generator:
     @classmethod
     def _pair_ratios_at(cls, offs, d_offs, cnt, a, b):
         """The general form: the pair of segments (a, b) of a finished batch, `cnt` that pair's two overlap counts."""
-        if offs[a + 1] - offs[a] < cls.GT_MIN_POINTS or offs[b + 1] - offs[b] < cls.GT_MIN_POINTS:
-            return None, "a cloud has fewer than {} points".format(cls.GT_MIN_POINTS)
         with np.errstate(invalid="ignore", divide="ignore"):
             o_s = float(np.float64(cnt[0]) / np.float64(d_offs[a + 1] - d_offs[a]))
             o_t = float(np.float64(cnt[1]) / np.float64(d_offs[b + 1] - d_offs[b]))
+        why = cls._pair_dropped(offs[a + 1] - offs[a], offs[b + 1] - offs[b], o_s, o_t)
+        return ((o_s, o_t), None) if why is None else (None, why)
+
+    @classmethod
+    def _pair_too_small(cls, rows_a, rows_b):
+        """The size part of the rule: such a pair is dropped whatever its ratios, so none need be computed for it."""
+        return rows_a < cls.GT_MIN_POINTS or rows_b < cls.GT_MIN_POINTS
+
+    @classmethod
+    def _pair_dropped(cls, rows_a, rows_b, o_s, o_t):
+        """THE gt.log rule (generate_gt.py:133-140, 160-165) on a pair of saved clouds with `rows_a` / `rows_b` rows and overlap
+        ratios (o_s, o_t): None when the pair gets a line, the reason when it does not."""
+        if cls._pair_too_small(rows_a, rows_b):
+            return "a cloud has fewer than {} points".format(cls.GT_MIN_POINTS)
         if np.isnan(o_s) or np.isnan(o_t):
-            return None, "an overlap ratio is NaN"
+            return "an overlap ratio is NaN"
         if o_s < 0.1 and o_t < 0.1:
-            return None, "both overlap ratios are below 0.1"
-        return (o_s, o_t), None
+            return "both overlap ratios are below 0.1"
+        return None
+
+
+class _Clouds:
+    """Where a lane's clouds go, one of three ways chosen once per `generate` call.  `gt_log`: the views stay on the device and the
+    last one queues the finish of every cloud; otherwise the writer pool finishes them (crop, voxel grid, PLY) from host copies
+    of the views (`rows`), all the views of a scene in ONE cloud in the first view's frame, or `per_view` each alone in its own.
+    Per batch `begin`, then `source(j, cloud)` per scene; per view `add_view` before the blocking copies and `write(j, rows)` right
+    after scene j's side files, so that the writers get work scene by scene; then `marker` is the batch's resume marker (the
+    cloud file the resume check looks for), a job not yet submitted."""
+
+    def __init__(self, gen, pool, num_samples, save_voxel_size, per_view, gt_log):
+        self.gen, self.pool, self.num_samples, self.voxel, self.per_view, self.gt_log = gen, pool, num_samples, save_voxel_size, per_view, gt_log
+        self.source = self._no_source if gt_log else self._source              # (gt_log: cloud 0 comes from the device as well)
+        # (one view per scene: the fused cloud IS the view's, and the worker compacts it)
+        self.write = self._write_finished if gt_log else self._write_per_view if per_view or num_samples == 1 else self._write_fused
+
+    def begin(self, idxs, sdirs):
+        self.idxs, self.sdirs, self.marker, self.views, self.poses, self.frags = idxs, sdirs, None, [], [], [None] * len(idxs)
+
+    def submit(self, job, j, k):
+        """THE marker rule: cloud k of the batch's last scene is held back until everything else of the batch is on disk."""
+        if j == len(self.sdirs) - 1 and k == self.num_samples // 2:
+            self.marker = job
+        else:
+            job()
+
+    def cloud(self, j, k, pc, valid, T):
+        """Cloud k of scene j: `pc[valid]` moved by T, cropped, gridded, moved back (sd:2640-2658); T None: gridded as it is."""
+        path = str(self.sdirs[j] / "sample-{:0>6d}.cloud.ply".format(k))
+        self.submit(lambda: self.pool.cloud(path, pc, valid, pre=T, crop=T is not None, voxel=self.voxel,
+                                            post=None if T is None else np.linalg.inv(T)), j, k)
+
+    def _source(self, j, pc):
+        self.cloud(j, 0, pc, None, None)
+
+    def _no_source(self, j, pc):
+        pass
+
+    def add_view(self, memory, pose, xyz, valid):
+        self.poses.append(pose)
+        if self.gt_log:
+            self.views.append((xyz, valid))
+            if len(self.poses) == self.num_samples:
+                self.finished = self.gen._finish_pairs_launch(memory, self.views, self.poses, self.per_view, self.voxel)
+
+    def _write_finished(self, j, rows):                    # once, after the side files of the last view's last scene
+        if j == len(self.sdirs) - 1 and len(self.poses) == self.num_samples:
+            self.gen._finish_pairs_write(self.pool, self.finished, self.idxs, self.sdirs, self.submit)
+
+    def _write_per_view(self, j, rows):
+        self.cloud(j, len(self.poses), rows.xyz[j], rows.valid[j], self.poses[-1][j].astype(np.float64))
+
+    def _write_fused(self, j, rows):
+        first = len(self.poses) == 1
+        self.frags[j] = rows.compact(j) if first else np.concatenate([self.frags[j], rows.compact(j)], axis=0)
+        if len(self.poses) == self.num_samples:
+            self.cloud(j, 1, self.frags[j], None, self.poses[0][j].astype(np.float64))
 
 
 def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int, num_samples: int,
@@ -506,7 +516,6 @@ def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int
     one by one in C++ on the calling thread, same ratios), every cloud once however many of its scene's pairs it is in, and all
     their pairs go through ONE prg_overlap_counts_indexed launch.  `overlap='numpy-spec'` selects the numpy specification in postprocess.py instead — a test
     hook for boxes without a GPU, never chosen implicitly."""
-    from itertools import combinations
     if overlap not in ("hip", "numpy-spec"):
         raise ValueError("overlap must be 'hip' or 'numpy-spec'")
     data = Path(root) / dataset_name / "data"
@@ -524,9 +533,8 @@ def generate_gt(dataset_name: str, start_scene_index: int, stop_scene_index: int
             if not ps.exists() or not pt.exists():
                 continue
             src, tgt = PP.read_ply(str(ps)), PP.read_ply(str(pt))
-            if len(src) < 1000 or len(tgt) < 1000:
-                continue
-            cand.append((s, t, src, tgt))
+            if not Generator._pair_too_small(len(src), len(tgt)):
+                cand.append((s, t, src, tgt))
         todo.append((scene_name, gt_path, cand))
         if len(todo) >= scenes_per_launch:
             _finish_gt(todo, overlap, voxel)
@@ -549,18 +557,13 @@ def _finish_gt(todo, overlap: str, voxel: str = "device") -> None:
         ratios = PP.overlap_ratios_indexed_hip(clouds, pairs, voxel=voxel)
     else:
         ratios = [PP.compute_overlap_ratio(src, tgt) for _n, _p, cand in todo for (_s, _t, src, tgt) in cand]
-    k = 0
+    ratios = iter(ratios)            # in the order of the candidates
     for scene_name, gt_path, cand in todo:
-        lines = []
-        for (s, t, _src, _tgt) in cand:
-            o_s, o_t = ratios[k]
-            k += 1
-            if np.isnan(o_s) or np.isnan(o_t) or (o_s < 0.1 and o_t < 0.1):
-                continue
-            lines.append("{}\t{}\t{}\t{:.4f}\t{:.4f}\n".format(scene_name, s, t, o_s, o_t))
+        rated = [(s, t, len(src), len(tgt), *next(ratios)) for (s, t, src, tgt) in cand]
+        lines = [Generator.GT_LINE.format(scene_name, s, t, o_s, o_t) for s, t, ra, rb, o_s, o_t in rated
+                 if Generator._pair_dropped(ra, rb, o_s, o_t) is None]
         gt_path.parent.mkdir(exist_ok=True)
-        with open(gt_path, "w") as f:
-            f.writelines(lines)
+        gt_path.write_text("".join(lines))
 
 
 def gather_gt(dataset_name: str, start_index: int, stop_index: int, root: str = ".") -> None:

@@ -28,6 +28,15 @@ def num_to_groups(num: int, divisor: int) -> List[int]:
     return [divisor] * groups + ([rem] if rem > 0 else [])
 
 
+def index_batches(start: int, stop: int, batch: int) -> List[List[int]]:
+    """The indices [start, stop) in order, as one list per batch: `num_to_groups(stop - start, batch)` gives the sizes."""
+    out, first = [], start
+    for n in num_to_groups(stop - start, batch):
+        out.append(list(range(first, first + n)))
+        first += n
+    return out
+
+
 def job_seed(timeout_s: float = 120.0) -> int:
     """ONE fresh 63-bit seed per launch, the same on every rank.
 

@@ -35,8 +35,6 @@ nothing under the generator's `samples_folder` (the folder itself is `Generator.
 """
 from __future__ import annotations
 
-import pickle
-from itertools import combinations
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -45,7 +43,8 @@ import torch
 
 from . import postprocess as PP
 from . import synthetic
-from .sharding import num_to_groups
+from .scene_memory import DeviceMemory
+from .sharding import index_batches
 
 
 @dataclass(frozen=True)
@@ -141,44 +140,24 @@ class PairStream:
         self.to = to
         self.skipped: List[Tuple[int, str]] = []     # (scene, reason) of the pairs generate_gt's filter drops
 
-    # -- the device sequence of one batch: Generator._lane for gt_log=True, minus every file ------------------------------------
+    # -- the device sequence of one batch: the set-up, view step and scene memory of Generator._lane, no file, no image copy -----
     @torch.no_grad()
     def _batch(self, idxs, info_train):
         gen = self.generator
-        G_, S, dev = gen.G, gen.image_size, gen.device
-        batch = len(idxs)
-        K = np.zeros((batch, 3, 3), dtype=np.float32)
-        depth0 = np.zeros((batch, 1, S, S), dtype=np.float32)
-        for j, idx in enumerate(idxs):
-            depth0[j, 0], K[j] = gen._scene_inputs(idx, info_train, None)
-        K_dev = torch.from_numpy(K).to(dev)
-        frames = G_.point_clouds(torch.from_numpy(depth0).to(dev), K_dev, None)
-        memory = [PP.crop_aabb(f.astype(np.float32)).astype(np.float32) for f in frames]      # the scene "memory" (sd:2484-2490)
-        param_cond = G_.param_vector(K_dev)
-        mem_pts, mem_offs = G_.upload_clouds(memory, dev)
-        mem_pts0, mem_offs0 = mem_pts, mem_offs                                                # the source frame of the pairs
+        K, K_dev, _depth0, param_cond, scene_pcs = gen._batch_setup(idxs, info_train)
+        memory = DeviceMemory.upload(gen.G, scene_pcs, gen.device)
         views, poses = [], []
         for sample_idx in range(self.num_samples):
             pose = gen._poses(idxs, sample_idx, self.noise_seed)
-            pose_dev = torch.from_numpy(pose).to(dev)
-            rpj, hit = G_.project_cloud_buffer(mem_pts, mem_offs, pose, K, S, depth_scale=0.1)
-            prob = self.depth_correction(rpj)
-            _rpj_c, _hit_c, cond = G_.apply_mask(prob, rpj, hit, self.mask_threshold)
             seeds = [synthetic.noise_seed(self.noise_seed, i, sample_idx) for i in idxs]
-            images = gen.model.sample(param_cond=param_cond, img_cond=cond, seeds=seeds, has_refine_step=self.has_refine_step)
-            prob2 = self.depth_correction(images)
-            images, _, _ = G_.apply_mask(prob2, images, None, self.mask_threshold, want_cond=False)
-            xyz, valid = G_.unproject_f64(images, K_dev, pose_dev)
+            _rpj, _rpj_c, _images, xyz, valid = gen._view(memory, pose, K, K_dev, param_cond, gen.model, self.depth_correction, seeds,
+                                                          self.mask_threshold, self.has_refine_step)
             views.append((xyz, valid))
             poses.append(pose)
             if sample_idx < self.num_samples - 1:                                              # memory update (sd:2661-2680)
-                merged, mvalid, moffs = G_.merge_memory(mem_pts, mem_offs, xyz, valid)
-                vg_out, mem_offs, vg_status = G_.voxel_grid_ragged(merged, mvalid, moffs, self.memory_voxel_size)
-                st_n = torch.cat([vg_status.to(torch.int64), mem_offs[-1:]]).cpu().numpy()
-                G_.check_voxel_status(st_n[:-1], ["scene-{:0>6d}".format(i) for i in idxs])
-                mem_pts = vg_out.to(torch.float32)[:max(int(st_n[-1]), 1)]
-        return gen._finish_pairs_launch(mem_pts0, mem_offs0, [len(m) for m in memory], views, poses if self.per_view else poses[0],
-                                        self.save_voxel_size)
+                memory.update(xyz, valid, self.memory_voxel_size)
+                memory.settle(["scene-{:0>6d}".format(i) for i in idxs])
+        return gen._finish_pairs_launch(memory, views, poses, self.per_view, self.save_voxel_size)
 
     # -- the loaders' augmentation of the surviving pairs of a batch: one launch for all of them -------------------------------
     def _augment(self, pts, sizes, scenes, pairs):
@@ -205,31 +184,19 @@ class PairStream:
     def __iter__(self):
         gen = self.generator
         self.skipped = []
-        info_train = None
-        if gen.synthetic_seed is None:
-            with open("./dataset/indoor/metadata/train_info.pkl", "rb") as f:
-                info_train = pickle.load(f)
-        first = self.start
-        for batch in num_to_groups(self.stop - self.start, gen.batch_size):
-            idxs = list(range(first, first + batch))
-            first += batch
-            finished = self._batch(idxs, info_train)
-            fin = finished[0]
+        info_train = gen._train_info()
+        for idxs in index_batches(self.start, self.stop, gen.batch_size):
+            batch, finished = len(idxs), self._batch(idxs, info_train)
+            fin = finished.points
             offs, d_offs, cnt = gen._finish_pairs_words(finished, idxs)          # the one copy of the small words
             n = (len(offs) - 1) // batch                                         # clouds per scene
-            combos = list(combinations(range(n), 2))
             keep, ratios = [], []                                                # keep: (scene of the batch, s, t)
-            for j, idx in enumerate(idxs):
-                for p, (s, t) in enumerate(combos):
-                    if n == 2:
-                        r, why = gen._pair_ratios(offs, d_offs, cnt, j)
-                    else:
-                        r, why = gen._pair_ratios_at(offs, d_offs, cnt[len(combos) * j + p], n * j + s, n * j + t)
-                    if r is None:
-                        self.skipped.append((idx, "pair ({}, {}): {}".format(s, t, why) if self.per_view else why))
-                    else:
-                        keep.append((j, s, t))
-                        ratios.append(r)
+            for j, s, t, r, why in gen._pair_walk(offs, d_offs, cnt, batch):
+                if r is None:
+                    self.skipped.append((idxs[j], "pair ({}, {}): {}".format(s, t, why) if self.per_view else why))
+                else:
+                    keep.append((j, s, t))
+                    ratios.append(r)
             if not keep:
                 continue
             # one ragged buffer of the surviving pairs: segments (2k, 2k+1) = the clouds (s, t) of keep[k]

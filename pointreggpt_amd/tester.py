@@ -27,7 +27,8 @@ import torch
 from . import geometry as G
 from . import postprocess as PP
 from . import synthetic
-from .sharding import num_to_groups
+from .scene_memory import DeviceMemory, HostMemory, HostRows
+from .sharding import index_batches, num_to_groups
 
 
 class Tester:
@@ -116,35 +117,30 @@ class Tester:
         """Returns, per batch, the scenes' accumulated float32 clouds (before the final 0.025 grid written to disk).
         (The reference hands pc2depth_tensor the whole batch's intrinsics next to ONE scene's cloud, sd:2177-2184; the
         evident intent — each scene with its own intrinsics — is what runs here.)
-        `voxel_backend`: "device" (default on a HIP device) keeps the accumulated clouds on the GPU as one ragged buffer,
-        refreshed by prg_voxel_grid_ragged and copied back once per batch; "host" re-voxelises them one by one in C++ on the
-        calling thread.  Same bits either way."""
+        `voxel_backend`: "device" (default on a HIP device) keeps the accumulated clouds on the GPU (`scene_memory.DeviceMemory`),
+        copied back once per batch; "host" re-voxelises them one by one on the calling thread (`HostMemory`).  Same bits."""
         dev, S = self.device, self.image_size
         if voxel_backend not in ("device", "host"):
             raise ValueError("voxel_backend must be 'device' or 'host'")
         on_device = voxel_backend == "device" and self.device.type != "cpu"
-        names = None
         with PP.WriterPool() as pool:
             out = []
-            first = 0
-            for batch in num_to_groups(num_scenes, self.batch_size):
-                ids = list(range(first, first + batch))
-                first += batch
+            for ids in index_batches(0, num_scenes, self.batch_size):
+                batch = len(ids)
+                names = [f"scene-{i}" for i in ids]
                 K = self._intrinsics(batch)
                 K_dev = torch.from_numpy(K).to(dev)
                 absolute = np.stack([np.eye(4) for _ in range(batch)]).astype(np.float32)
                 param_cond = G.param_vector(K_dev)
                 images = self._sample(param_cond, None, ids, 0, noise)
-                if on_device:
-                    names = [f"scene-{i}" for i in ids]
+                if on_device:                       # the first grid, of the unconditional view alone
                     xyz, valid = G.unproject_f64(images, K_dev, None, clip=(0.5, 3.5))
-                    hw = xyz.shape[1]
-                    offs = torch.arange(batch + 1, dtype=torch.int64, device=xyz.device) * hw
+                    offs = torch.arange(batch + 1, dtype=torch.int64, device=xyz.device) * xyz.shape[1]
                     vg_out, scene_offs, vg_status = G.voxel_grid_ragged(xyz.view(-1, 3), valid.view(-1), offs, voxel_size)
-                    scene_pts = vg_out.to(torch.float32)
+                    memory = DeviceMemory(G, vg_out.to(torch.float32), scene_offs)
                 else:
-                    scene = [PP.native_voxel_down_sample(c, voxel_size).astype(np.float32)
-                             for c in G.point_clouds(images, K_dev, None, clip=(0.5, 3.5))]
+                    memory = HostMemory(G, [PP.native_voxel_down_sample(c, voxel_size).astype(np.float32)
+                                            for c in G.point_clouds(images, K_dev, None, clip=(0.5, 3.5))], dev)
                 img_host = images.cpu().numpy()
                 if on_device:
                     G.check_voxel_status(vg_status.cpu().numpy(), names)
@@ -155,34 +151,21 @@ class Tester:
                     relative = G.random_sample_transform(K, image_size=S)
                     absolute = relative @ absolute
                     # the accumulated clouds moved into the new cameras and z-buffered: one ragged launch (sd:2168-2190)
-                    if on_device:
-                        rpj, hit = G.project_cloud_buffer(scene_pts, scene_offs, absolute, K, S, depth_scale=0.1)
-                    else:
-                        rpj, hit = G.project_clouds(scene, absolute, K, S, dev, depth_scale=0.1)
+                    rpj, hit = memory.project(absolute, K, S, 0.1)
                     cond = torch.cat([rpj, hit.to(rpj.dtype)], dim=1) * 2 - 1
                     last = images
                     images = self._sample(param_cond, cond, ids, k, noise, has_refine_step)
-                    if on_device:                   # merge + grid refresh without a host trip (sd:2200-2228)
-                        xyz, valid = G.unproject_f64(images, K_dev, torch.from_numpy(absolute).to(dev), clip=(0.5, 3.5))
-                        merged, mvalid, moffs = G.merge_memory(scene_pts, scene_offs, xyz, valid)
-                        vg_out, scene_offs, vg_status = G.voxel_grid_ragged(merged, mvalid, moffs, voxel_size)
-                        scene_pts = vg_out.to(torch.float32)
-                    else:
-                        new = G.point_clouds(images, K_dev, torch.from_numpy(absolute).to(dev), clip=(0.5, 3.5))
+                    # the new view merged into the clouds, the grid refreshed (sd:2200-2228): queued here, finished after the copies
+                    xyz, valid = G.unproject_f64(images, K_dev, torch.from_numpy(absolute).to(dev), clip=(0.5, 3.5))
+                    memory.update(xyz, valid, voxel_size)
+                    rows = None if on_device else HostRows.copy(xyz, valid)
                     l_h, r_h, n_h = last.cpu().numpy(), rpj.cpu().numpy(), images.cpu().numpy()
-                    if on_device:
-                        st_n = torch.cat([vg_status.to(torch.int64), scene_offs[-1:]]).cpu().numpy()
-                        G.check_voxel_status(st_n[:-1], names)
-                        scene_pts = scene_pts[:max(int(st_n[-1]), 1)]
+                    memory.settle(names, rows)
                     for j, i in enumerate(ids):
                         pool.image01(str(self.samples_folder / f"scene-{i}-sample-{k}.png"),
                                      self._strip(l_h[j, 0], r_h[j, 0], n_h[j, 0]))
-                        if not on_device:
-                            merged = np.concatenate([scene[j].astype(np.float64), new[j]], axis=0)
-                            scene[j] = PP.native_voxel_down_sample(merged, voxel_size).astype(np.float32)
-                if on_device:                       # the ONE copy of the accumulated clouds back to the host
-                    o, p = scene_offs.cpu().numpy(), scene_pts.cpu().numpy()
-                    scene = [p[o[j]:o[j + 1]].copy() for j in range(batch)]
+                        memory.settle_scene(j)
+                scene = memory.clouds()             # (device: the ONE copy of the accumulated clouds back to the host)
                 for j, i in enumerate(ids):
                     pool.cloud(str(self.samples_folder / f"scene-{i}.ply"), scene[j], None, crop=False, voxel=0.025)
                 out.append(scene)
