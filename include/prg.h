@@ -438,8 +438,13 @@ int prg_debug_resblock_tail(const float* h, const float* s0, const float* s1, co
                             const float* b_res, const float* head_w, const float* head_b, float* out, int B, int N, int C0, int C1,
                             int Cout, int head_sigmoid, int in_place, void* stream);
 
-/* Kernel unit-test hook: ONE bf16 convolution through the library's own packer and dispatch with the fused options the forward
+/* Kernel unit-test hook: ONE convolution through the library's own packer and dispatch with the fused options the forward
  * pass sets on it: two sources, statistics of the output, a prologue on the input, a residual in the epilogue.
+ *   storage: PRG_CF_STORE_BF16 the launch of a PRG_BF16 handle, as described below.  PRG_CF_STORE_F16X3 / PRG_CF_STORE_F32: the float
+ *   launch of a PRG_F16X3 / PRG_F32 handle (the split-f16 kernels / the exact-f32 kernels): x0, x1 and the residual are copied
+ *   without rounding, out is the kernel's float32 output, the packer is called with that dtype, and PRG_CF_PRO_FOLD,
+ *   PRG_CF_RES_FOLD and PRG_CF_STATS_ACC are PRG_E_INVALID (the forward pass never sets them on a float launch: there are no
+ *   fixed-point accumulators in those modes).  Everything else is as below.
  *   Operands: x0 (B,C0,H,W), x1 (B,C1,H,W) float32 DEVICE (x1 NULL exactly when C1 = 0), converted to bf16; w (Cout,C0+C1,K,K),
  *   bias (Cout) float32 HOST; a NULL bias reaches the launch as NULL.  K = 1 (pad 0) or 3 (pad 1), stride 1.  C0, C1, Cout are
  *   multiples of 8; `groups` cuts Cout (and the folded tensor) into multiples of 8 channels.
@@ -454,10 +459,17 @@ int prg_debug_resblock_tail(const float* h, const float* s0, const float* s1, co
  *   group added in slab order, or the accumulators scaled back; acc_raw (B,groups,2) int64 HOST (all zero when the kernel declined
  *   the accumulators); coef_a, coef_b (B,Cout) float32 DEVICE: the GroupNorm coefficient tables the library's next step makes
  *   of them with gamma, beta (Cout) float32 HOST.  nsplit and acc_done are what the conv launch reported.
+ *   slabs (optional, with stats): float32 HOST with room for B * PRG_CF_MAX_SLABS * groups * 2 values; receives the raw slabs
+ *   [B][nslabs][groups][2] the sums were made of (nslabs = nsplit, or the statistics pass's count); nslabs = 0 and nothing written
+ *   when accumulators were used.
+ *   family, th, tw, bm, bn: what launch_conv chose (ConvChoice of conv_choose.h: family is a ConvFamily value, th x tw x bn the
+ *   tile of the 3x3 families, bm x bn of the implicit-GEMM ones).
  * out (B,Cout,H,W) float32 DEVICE.  Bad arguments fail with PRG_E_INVALID before any device call.  Synchronises.                 */
 enum { PRG_CF_PRO_NONE = 0, PRG_CF_PRO_TABLES = 1, PRG_CF_PRO_FOLD = 2 };
 enum { PRG_CF_RES_NONE = 0, PRG_CF_RES_ADD = 1, PRG_CF_RES_TABLES = 2, PRG_CF_RES_FOLD = 3 };
 enum { PRG_CF_STATS_OFF = 0, PRG_CF_STATS_SLABS = 1, PRG_CF_STATS_ACC = 2 };
+enum { PRG_CF_STORE_BF16 = 0, PRG_CF_STORE_F16X3 = 1, PRG_CF_STORE_F32 = 2 };
+enum { PRG_CF_MAX_SLABS = 1024 };
 typedef struct prg_conv_fused {
   const float* x0;
   const float* x1;
@@ -481,7 +493,9 @@ typedef struct prg_conv_fused {
   int32_t B, C0, C1, Cout, H, W, K, groups;
   int32_t prologue, residual_mode, in_place, stats;
   int32_t nsplit, acc_done, stats_pass;   /* out */
-  int32_t reserved;
+  int32_t storage;
+  int32_t family, th, tw, bm, bn, nslabs;   /* out */
+  float* slabs;
 } prg_conv_fused;
 int prg_debug_conv_fused(prg_conv_fused* args, void* stream);
 

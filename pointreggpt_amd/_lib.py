@@ -33,12 +33,19 @@ class ConvFusedC(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x0", "x1", "w", "bias", "pro_a", "pro_b", "residual", "res_a", "res_b", "fold_acc",
                                            "fold_p", "fold_q", "gamma", "beta", "out", "sums", "acc_raw", "coef_a", "coef_b")] +
                 [(n, C.c_int32) for n in ("B", "C0", "C1", "Cout", "H", "W", "K", "groups", "prologue", "residual_mode",
-                                          "in_place", "stats", "nsplit", "acc_done", "stats_pass", "reserved")])
+                                          "in_place", "stats", "nsplit", "acc_done", "stats_pass", "storage",
+                                          "family", "th", "tw", "bm", "bn", "nslabs")] +
+                [("slabs", C.c_void_p)])
 
 
 CF_PRO_NONE, CF_PRO_TABLES, CF_PRO_FOLD = 0, 1, 2
 CF_RES_NONE, CF_RES_ADD, CF_RES_TABLES, CF_RES_FOLD = 0, 1, 2, 3
 CF_STATS_OFF, CF_STATS_SLABS, CF_STATS_ACC = 0, 1, 2
+CF_STORE_BF16, CF_STORE_F16X3, CF_STORE_F32 = 0, 1, 2
+CF_MAX_SLABS = 1024
+# ConvFamily (csrc/conv_choose.h), as prg_conv_fused.family reports it
+CONV_FAMILIES = ("none", "igemm", "halo", "mx_halo", "c64", "ws", "w256", "w256mx", "split_halo", "split_ws", "split_p64", "split_w512",
+                 "split_igemm")
 
 
 class GnFoldC(C.Structure):

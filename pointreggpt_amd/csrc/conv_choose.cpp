@@ -20,14 +20,16 @@ static bool w256_fills(long total, int dflt, const ConvSwitches& sw) {
 
 // Fused GroupNorm statistics of the output, the two rules.  Kernels whose consumer wave rows each write a partial: a group must lie
 // inside one wave's 64 channels, as a power-of-two run of 8-channel units.  Kernels that reduce a whole bn-channel tile: a group of
-// 8-channel units inside the tile.  Either way at most kGnMaxSplit slabs per image.
+// 8-channel units whose width divides the tile.  Either way at most kGnMaxSplit slabs per image.
 static int wave_rows_fuse(const ConvFacts& L, int slabs) {
   const int cpg = L.gn_groups > 0 ? L.d.Cout / L.gn_groups : 0;
   return L.gn_partials && cpg % 8 == 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && slabs <= kGnMaxSplit;
 }
 static int tile_fuse(const ConvFacts& L, int bn, int slabs) {
   const int cpg = L.gn_groups > 0 ? L.d.Cout / L.gn_groups : 0;
-  return L.gn_partials && cpg % 8 == 0 && cpg <= bn && slabs <= kGnMaxSplit;
+  // bn % cpg: the tile reductions (conv_epi.h epilogue_stats, the split halo kernel's direct epilogue) give a tile bn / cpg whole
+  // groups starting at its first channel; a width that does not divide the tile (24 channels: 192 / 8) would straddle two tiles
+  return L.gn_partials && cpg % 8 == 0 && cpg <= bn && (cpg == 0 || bn % cpg == 0) && slabs <= kGnMaxSplit;
 }
 
 // th x tw-pixel tiles of an H x W image times bn-channel tiles, one workgroup each (the persistent kernels set their own grid)

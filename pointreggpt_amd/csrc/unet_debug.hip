@@ -1,10 +1,11 @@
-// unet_debug.hip — the prg_debug_* entries (prg.h): single convolutions, one bf16 convolution with the fused options of its launch
+// unet_debug.hip — the prg_debug_* entries (prg.h): single convolutions, one convolution of any storage mode with the fused options of its launch
 // (two sources, statistics, prologue, residual) and a ResnetBlock's Block pair through the library's own packer (pack_conv_host:
 // what a handle would pack for the same conv) and dispatch (launch_conv), on device buffers of their own;
 // the attention cores, the channel LayerNorm, the fused linear-attention blocks (pack_fused_attention / pack_split_attention)
 // and the fused ResnetBlock tail through the launch functions the forward calls, with the kernel chosen by argument;
 // the GroupNorm passes (statistics, coefficients, the fold from accumulators, the affine + SiLU pass) and the conditioning kernels
 // (cond_fold, linear, sinusoidal) of blocks.hip, each through its own launch function on buffers the hook owns.
+#include <cstring>
 #include <type_traits>
 
 #include "unet_layout.h"
@@ -177,6 +178,103 @@ int debug_affine_silu_t(const float* x, const float* A, const float* Bc, const f
   if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(d_o, out, B, HW, C, s);
   if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_affine_silu: stream synchronise failed");
   return rc;
+}
+
+// prg_debug_conv_fused after its checks: T = bf16_t with packing dtype PRG_BF16, or float with PRG_F16X3 / PRG_F32, so the packer,
+// DebugConv<T> and launch_conv<T> are those of a handle of that mode
+template <typename T>
+int debug_conv_fused_t(prg_conv_fused* a, const ConvDesc& d, int dtype, hipStream_t s) {
+  const int B = a->B, C0 = a->C0, C1 = a->C1, Cout = a->Cout, H = a->H, W = a->W, K = a->K, G = a->groups;
+  const int fold_C = a->prologue == PRG_CF_PRO_FOLD ? C0 : Cout;   // width of the tensor the folded norm belongs to
+  const bool folds = a->prologue == PRG_CF_PRO_FOLD || a->residual_mode == PRG_CF_RES_FOLD;
+  const char* nomem = "prg_debug_conv_fused: hipMalloc failed";
+  const int cin = C0 + C1, HW = H * W;
+  const size_t M = (size_t)B * HW;
+  const PackedConv<T> pk = pack_conv_host<T>(a->w, Cout, cin, K, dtype, ConvRole{});
+  DeviceBuffers own;
+  DebugConv<T> c(own, pk, B, cin, Cout, H, W, K, 1, d.pad, 0, G, nomem);
+  ConvLaunch<T>& L = c.L;
+  L.d.C0 = C0; L.d.C1 = C1;
+  T* d_x0 = own.alloc<T>(M * C0, nomem);
+  T* d_x1 = own.alloc<T>(M * C1, nomem);
+  T* d_res = a->residual ? own.alloc<T>(M * Cout, nomem) : nullptr;
+  L.src0 = d_x0; L.src1 = d_x1;
+  L.out = a->in_place ? d_res : own.alloc<T>(M * Cout, nomem);
+  L.bias = a->bias ? own.upload(a->bias, (size_t)Cout, nomem) : nullptr;   // (null stays null: the generic kernels take it)
+  L.residual = d_res;
+  GnFold in_fold{};
+  if (folds) {
+    std::vector<float> pq(2 * (size_t)fold_C);
+    for (int ch = 0; ch < fold_C; ++ch) { pq[ch] = a->fold_p[ch]; pq[fold_C + ch] = a->fold_q[ch]; }
+    in_fold.acc = reinterpret_cast<const long long*>(a->fold_acc);
+    in_fold.P = own.upload(pq, nomem); in_fold.Q = in_fold.P + fold_C; in_fold.pq_stride = 0;
+    in_fold.G = G; in_fold.cpg = fold_C / G; in_fold.inv_n = 1.0f / ((float)HW * (float)in_fold.cpg);
+  }
+  if (a->prologue == PRG_CF_PRO_TABLES) { L.pro_a = a->pro_a; L.pro_b = a->pro_b; }
+  if (a->prologue == PRG_CF_PRO_FOLD) {   // (the tables are scratch for kernels without the in-kernel fold, as in resblock())
+    L.pro_fold = in_fold;
+    L.pro_a = own.alloc<float>((size_t)2 * B * C0, nomem); L.pro_b = L.pro_a + (size_t)B * C0;
+  }
+  if (a->residual_mode == PRG_CF_RES_TABLES) { L.res_a = a->res_a; L.res_b = a->res_b; }
+  if (a->residual_mode == PRG_CF_RES_FOLD) L.res_fold = in_fold;
+  const size_t slab_floats = (size_t)B * kGnMaxSplit * G * 2, acc_count = (size_t)B * G * 2;
+  GnApply apply{};
+  GnFold out_fold{};
+  if (a->stats != PRG_CF_STATS_OFF) {
+    L.gn_partials = own.alloc<float>(slab_floats, nomem);
+    std::vector<float> gb(2 * (size_t)Cout);
+    for (int ch = 0; ch < Cout; ++ch) { gb[ch] = a->gamma[ch]; gb[Cout + ch] = a->beta[ch]; }
+    apply.gamma = own.upload(gb, nomem); apply.beta = apply.gamma + Cout;
+    if (a->stats == PRG_CF_STATS_ACC) {
+      L.gn_acc = own.alloc<long long>(acc_count, nomem);
+      out_fold.acc = L.gn_acc; out_fold.P = apply.gamma; out_fold.Q = apply.beta; out_fold.pq_stride = 0;
+      out_fold.G = G; out_fold.cpg = Cout / G; out_fold.inv_n = 1.0f / ((float)HW * (float)out_fold.cpg);
+    }
+  }
+  if (own.rc) return own.rc;
+  const char* nocopy = "prg_debug_conv_fused: copy failed";
+  if (L.gn_acc && hipMemsetAsync(L.gn_acc, 0, acc_count * sizeof(long long), s) != hipSuccess) return fail(PRG_E_HIP, nocopy);
+  int rc = launch_nchw_f32_to_nhwc<T>(a->x0, d_x0, B, HW, C0, s);
+  if (rc == PRG_OK && C1) rc = launch_nchw_f32_to_nhwc<T>(a->x1, d_x1, B, HW, C1, s);
+  if (rc == PRG_OK && d_res) rc = launch_nchw_f32_to_nhwc<T>(a->residual, d_res, B, HW, Cout, s);
+  int ns = 0, ad = 0, used = 0;
+  ConvChoice chosen;
+  if (rc == PRG_OK) rc = launch_conv<T>(L, s, a->stats ? &ns : nullptr, a->stats ? &ad : nullptr, &chosen);
+  a->family = chosen.family; a->th = chosen.th; a->tw = chosen.tw; a->bm = chosen.bm; a->bn = chosen.bn;
+  used = ns;
+  if (rc == PRG_OK && a->stats && ns == 0) {   // (NormStats::complete: the conv fused no statistics)
+    rc = launch_gn_stats<T>(L.out, L.gn_partials, B, HW, Cout, G, &used, s);
+    a->stats_pass = 1;
+  }
+  if (rc == PRG_OK && a->stats)                // (NormStats::tables)
+    rc = ad ? launch_gn_coeff_acc(out_fold, a->coef_a, a->coef_b, B, Cout, s)
+            : launch_gn_coeff(L.gn_partials, used, apply, a->coef_a, a->coef_b, B, HW, Cout, G, s);
+  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<T>(L.out, a->out, B, HW, Cout, s);
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_conv_fused: stream synchronise failed");
+  if (rc != PRG_OK || !a->stats) return rc;
+  a->nsplit = ns; a->acc_done = ad;
+  std::vector<long long> acc(acc_count, 0);
+  if (L.gn_acc && hipMemcpy(acc.data(), L.gn_acc, acc_count * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return fail(PRG_E_HIP, nocopy);
+  if (a->acc_raw) for (size_t i = 0; i < acc_count; ++i) a->acc_raw[i] = acc[i];
+  if (ad) {
+    for (size_t i = 0; i < acc_count; ++i) a->sums[i] = (double)acc[i] * (i & 1 ? 1.0 / 1048576.0 : 1.0 / 16777216.0);
+    return PRG_OK;
+  }
+  PRG_CHECK(used > 0 && used <= kGnMaxSplit, "prg_debug_conv_fused: slab count out of range");
+  std::vector<float> slabs((size_t)B * used * G * 2);
+  if (hipMemcpy(slabs.data(), L.gn_partials, slabs.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail(PRG_E_HIP, nocopy);
+  for (int b = 0; b < B; ++b)
+    for (int g = 0; g < G; ++g)
+      for (int w = 0; w < 2; ++w) {
+        double t = 0.0;
+        for (int k = 0; k < used; ++k) t += (double)slabs[(((size_t)b * used + k) * G + g) * 2 + w];
+        a->sums[((size_t)b * G + g) * 2 + w] = t;
+      }
+  if (a->slabs) {
+    std::memcpy(a->slabs, slabs.data(), slabs.size() * sizeof(float));
+    a->nslabs = used;
+  }
+  return PRG_OK;
 }
 
 }  // namespace
@@ -363,10 +461,11 @@ int prg_debug_block_pair(const float* x, const float* w1, const float* b1, const
   return rc;
 }
 
-// One bf16 convolution with the fused options of ConvLaunch, as the forward pass sets them (prg.h).
+// One convolution (bf16, or float storage: f16x3 / fp32) with the fused options of ConvLaunch, as the forward pass sets them (prg.h).
 int prg_debug_conv_fused(prg_conv_fused* a, void* stream) {
   PRG_CHECK(a != nullptr, "prg_debug_conv_fused: null argument struct");
   a->nsplit = a->acc_done = a->stats_pass = 0;
+  a->family = a->th = a->tw = a->bm = a->bn = a->nslabs = 0;
   const int B = a->B, C0 = a->C0, C1 = a->C1, Cout = a->Cout, H = a->H, W = a->W, K = a->K, G = a->groups;
   PRG_CHECK(a->x0 && a->w && a->out, "prg_debug_conv_fused: null pointer");
   PRG_CHECK(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)B * H * W <= (int64_t)1 << 22, "prg_debug_conv_fused: bad shape");
@@ -379,6 +478,11 @@ int prg_debug_conv_fused(prg_conv_fused* a, void* stream) {
   PRG_CHECK(a->residual_mode >= PRG_CF_RES_NONE && a->residual_mode <= PRG_CF_RES_FOLD, "prg_debug_conv_fused: bad residual mode");
   PRG_CHECK(a->stats >= PRG_CF_STATS_OFF && a->stats <= PRG_CF_STATS_ACC, "prg_debug_conv_fused: bad statistics mode");
   PRG_CHECK(a->in_place == 0 || a->in_place == 1, "prg_debug_conv_fused: in_place is 0 or 1");
+  PRG_CHECK(a->storage >= PRG_CF_STORE_BF16 && a->storage <= PRG_CF_STORE_F32, "prg_debug_conv_fused: bad storage mode");
+  const bool f32 = a->storage != PRG_CF_STORE_BF16;
+  // float launches have no fixed-point accumulators (acc_on() is bf16-only) and choose_split declines the folds
+  PRG_CHECK(!f32 || (a->prologue != PRG_CF_PRO_FOLD && a->residual_mode != PRG_CF_RES_FOLD && a->stats != PRG_CF_STATS_ACC),
+            "prg_debug_conv_fused: the folds and the accumulators belong to bf16 storage");
   ConvDesc d{};
   d.B = B; d.Hin = H; d.Win = W; d.C0 = C0; d.C1 = C1; d.ups = 0; d.KH = K; d.KW = K; d.stride = 1; d.pad = K == 3 ? 1 : 0;
   d.Hout = H; d.Wout = W; d.Cout = Cout;
@@ -386,7 +490,8 @@ int prg_debug_conv_fused(prg_conv_fused* a, void* stream) {
   const bool folds = a->prologue == PRG_CF_PRO_FOLD || a->residual_mode == PRG_CF_RES_FOLD;
   if (a->prologue != PRG_CF_PRO_NONE) {
     PRG_CHECK(K == 3 && C1 == 0, "prg_debug_conv_fused: the prologue belongs to a single-source 3x3 conv");
-    PRG_CHECK(conv_supports_prologue<bf16_t>(d), "prg_debug_conv_fused: no kernel with a prologue takes this shape");
+    PRG_CHECK(f32 ? conv_supports_prologue<float>(d) : conv_supports_prologue<bf16_t>(d),
+              "prg_debug_conv_fused: no kernel with a prologue takes this shape");
     PRG_CHECK(a->prologue != PRG_CF_PRO_TABLES || (a->pro_a && a->pro_b), "prg_debug_conv_fused: the table prologue needs pro_a and pro_b");
   }
   if (a->residual_mode != PRG_CF_RES_NONE) {
@@ -406,89 +511,9 @@ int prg_debug_conv_fused(prg_conv_fused* a, void* stream) {
     PRG_CHECK(a->gamma && a->beta && a->sums && a->coef_a && a->coef_b, "prg_debug_conv_fused: statistics need gamma, beta, sums, coef_a and coef_b");
     PRG_CHECK(a->stats != PRG_CF_STATS_ACC || a->acc_raw, "prg_debug_conv_fused: offered accumulators need acc_raw");
   }
-  hipStream_t s = (hipStream_t)stream;
-  const char* nomem = "prg_debug_conv_fused: hipMalloc failed";
-  const int cin = C0 + C1, HW = H * W;
-  const size_t M = (size_t)B * HW;
-  const PackedConv<bf16_t> pk = pack_conv_host<bf16_t>(a->w, Cout, cin, K, PRG_BF16, ConvRole{});
-  DeviceBuffers own;
-  DebugConv<bf16_t> c(own, pk, B, cin, Cout, H, W, K, 1, d.pad, 0, G, nomem);
-  ConvLaunch<bf16_t>& L = c.L;
-  L.d.C0 = C0; L.d.C1 = C1;
-  bf16_t* d_x0 = own.alloc<bf16_t>(M * C0, nomem);
-  bf16_t* d_x1 = own.alloc<bf16_t>(M * C1, nomem);
-  bf16_t* d_res = a->residual ? own.alloc<bf16_t>(M * Cout, nomem) : nullptr;
-  L.src0 = d_x0; L.src1 = d_x1;
-  L.out = a->in_place ? d_res : own.alloc<bf16_t>(M * Cout, nomem);
-  L.bias = a->bias ? own.upload(a->bias, (size_t)Cout, nomem) : nullptr;   // (null stays null: the generic kernels take it)
-  L.residual = d_res;
-  GnFold in_fold{};
-  if (folds) {
-    std::vector<float> pq(2 * (size_t)fold_C);
-    for (int ch = 0; ch < fold_C; ++ch) { pq[ch] = a->fold_p[ch]; pq[fold_C + ch] = a->fold_q[ch]; }
-    in_fold.acc = reinterpret_cast<const long long*>(a->fold_acc);
-    in_fold.P = own.upload(pq, nomem); in_fold.Q = in_fold.P + fold_C; in_fold.pq_stride = 0;
-    in_fold.G = G; in_fold.cpg = fold_C / G; in_fold.inv_n = 1.0f / ((float)HW * (float)in_fold.cpg);
-  }
-  if (a->prologue == PRG_CF_PRO_TABLES) { L.pro_a = a->pro_a; L.pro_b = a->pro_b; }
-  if (a->prologue == PRG_CF_PRO_FOLD) {   // (the tables are scratch for kernels without the in-kernel fold, as in resblock())
-    L.pro_fold = in_fold;
-    L.pro_a = own.alloc<float>((size_t)2 * B * C0, nomem); L.pro_b = L.pro_a + (size_t)B * C0;
-  }
-  if (a->residual_mode == PRG_CF_RES_TABLES) { L.res_a = a->res_a; L.res_b = a->res_b; }
-  if (a->residual_mode == PRG_CF_RES_FOLD) L.res_fold = in_fold;
-  const size_t slab_floats = (size_t)B * kGnMaxSplit * G * 2, acc_count = (size_t)B * G * 2;
-  GnApply apply{};
-  GnFold out_fold{};
-  if (a->stats != PRG_CF_STATS_OFF) {
-    L.gn_partials = own.alloc<float>(slab_floats, nomem);
-    std::vector<float> gb(2 * (size_t)Cout);
-    for (int ch = 0; ch < Cout; ++ch) { gb[ch] = a->gamma[ch]; gb[Cout + ch] = a->beta[ch]; }
-    apply.gamma = own.upload(gb, nomem); apply.beta = apply.gamma + Cout;
-    if (a->stats == PRG_CF_STATS_ACC) {
-      L.gn_acc = own.alloc<long long>(acc_count, nomem);
-      out_fold.acc = L.gn_acc; out_fold.P = apply.gamma; out_fold.Q = apply.beta; out_fold.pq_stride = 0;
-      out_fold.G = G; out_fold.cpg = Cout / G; out_fold.inv_n = 1.0f / ((float)HW * (float)out_fold.cpg);
-    }
-  }
-  if (own.rc) return own.rc;
-  const char* nocopy = "prg_debug_conv_fused: copy failed";
-  if (L.gn_acc && hipMemsetAsync(L.gn_acc, 0, acc_count * sizeof(long long), s) != hipSuccess) return fail(PRG_E_HIP, nocopy);
-  int rc = launch_nchw_f32_to_nhwc<bf16_t>(a->x0, d_x0, B, HW, C0, s);
-  if (rc == PRG_OK && C1) rc = launch_nchw_f32_to_nhwc<bf16_t>(a->x1, d_x1, B, HW, C1, s);
-  if (rc == PRG_OK && d_res) rc = launch_nchw_f32_to_nhwc<bf16_t>(a->residual, d_res, B, HW, Cout, s);
-  int ns = 0, ad = 0, used = 0;
-  if (rc == PRG_OK) rc = launch_conv<bf16_t>(L, s, a->stats ? &ns : nullptr, a->stats ? &ad : nullptr);
-  used = ns;
-  if (rc == PRG_OK && a->stats && ns == 0) {   // (NormStats::complete: the conv fused no statistics)
-    rc = launch_gn_stats<bf16_t>(L.out, L.gn_partials, B, HW, Cout, G, &used, s);
-    a->stats_pass = 1;
-  }
-  if (rc == PRG_OK && a->stats)                // (NormStats::tables)
-    rc = ad ? launch_gn_coeff_acc(out_fold, a->coef_a, a->coef_b, B, Cout, s)
-            : launch_gn_coeff(L.gn_partials, used, apply, a->coef_a, a->coef_b, B, HW, Cout, G, s);
-  if (rc == PRG_OK) rc = launch_nhwc_to_nchw_f32<bf16_t>(L.out, a->out, B, HW, Cout, s);
-  if (hipStreamSynchronize(s) != hipSuccess && rc == PRG_OK) rc = fail(PRG_E_HIP, "prg_debug_conv_fused: stream synchronise failed");
-  if (rc != PRG_OK || !a->stats) return rc;
-  a->nsplit = ns; a->acc_done = ad;
-  std::vector<long long> acc(acc_count, 0);
-  if (L.gn_acc && hipMemcpy(acc.data(), L.gn_acc, acc_count * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return fail(PRG_E_HIP, nocopy);
-  if (a->acc_raw) for (size_t i = 0; i < acc_count; ++i) a->acc_raw[i] = acc[i];
-  if (ad) {
-    for (size_t i = 0; i < acc_count; ++i) a->sums[i] = (double)acc[i] * (i & 1 ? 1.0 / 1048576.0 : 1.0 / 16777216.0);
-    return PRG_OK;
-  }
-  PRG_CHECK(used > 0 && used <= kGnMaxSplit, "prg_debug_conv_fused: slab count out of range");
-  std::vector<float> slabs((size_t)B * used * G * 2);
-  if (hipMemcpy(slabs.data(), L.gn_partials, slabs.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail(PRG_E_HIP, nocopy);
-  for (int b = 0; b < B; ++b)
-    for (int g = 0; g < G; ++g)
-      for (int w = 0; w < 2; ++w) {
-        double t = 0.0;
-        for (int k = 0; k < used; ++k) t += (double)slabs[(((size_t)b * used + k) * G + g) * 2 + w];
-        a->sums[((size_t)b * G + g) * 2 + w] = t;
-      }
-  return PRG_OK;
+  const int dtype = a->storage == PRG_CF_STORE_F16X3 ? PRG_F16X3 : a->storage == PRG_CF_STORE_F32 ? PRG_F32 : PRG_BF16;
+  if (f32) return debug_conv_fused_t<float>(a, d, dtype, (hipStream_t)stream);
+  return debug_conv_fused_t<bf16_t>(a, d, dtype, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@ selection function (csrc/conv_choose.cpp) for a descriptor, the options of the l
 test compares every answer with tests/golden/conv_dispatch.json.  The file was recorded (python tests/test_conv_dispatch.py
 --record) from the build that moved each launcher's conditions word for word into conv_choose.cpp
 (profiles/conv_dispatch_refactor_ab.txt has its checksums); a later form of the selection has to give the same table.
+Re-recorded once since, for one rule: tile_fuse asks that the group width divide the channel tile (bn % cpg == 0), so the cout192 /
+cout384 queries of edges() (groups of 24 / 48 channels) no longer fuse their statistics; the nine edge walks' digests moved, no other.
 
 The queries are derived here: walk() restates which convolutions UnetImpl::forward (csrc/unet.hip) launches and with which
 options, as far as the selection reads them; conv2's options depend on what conv1's choice reports (acc_done), as in the forward

@@ -55,12 +55,21 @@ def test_struct_layout_matches_the_header():
         off = (off + size - 1) // size * size
         assert getattr(_lib.ConvFusedC, name).offset == off, name
         off += size
-    assert C.sizeof(_lib.ConvFusedC) == (off + 7) // 8 * 8 == 19 * 8 + 16 * 4
+    assert C.sizeof(_lib.ConvFusedC) == (off + 7) // 8 * 8 == 20 * 8 + 22 * 4
+    # `storage` took the place of `reserved`: every earlier field keeps its offset, the out-fields and `slabs` follow it
+    assert _lib.ConvFusedC.storage.offset == 19 * 8 + 15 * 4 and _lib.ConvFusedC.stats_pass.offset == 19 * 8 + 14 * 4
+    assert [n for n, _ in fields[-8:]] == ["storage", "family", "th", "tw", "bm", "bn", "nslabs", "slabs"]
     hdr = header()
-    for group, names in (("PRO", ("NONE", "TABLES", "FOLD")), ("RES", ("NONE", "ADD", "TABLES", "FOLD")), ("STATS", ("OFF", "SLABS", "ACC"))):
+    for group, names in (("PRO", ("NONE", "TABLES", "FOLD")), ("RES", ("NONE", "ADD", "TABLES", "FOLD")), ("STATS", ("OFF", "SLABS", "ACC")),
+                         ("STORE", ("BF16", "F16X3", "F32"))):
         for value, n in enumerate(names):
             assert re.search(rf"PRG_CF_{group}_{n} = {value}\b", hdr), (group, n)
             assert getattr(_lib, f"CF_{group}_{n}") == value
+    assert re.search(r"PRG_CF_MAX_SLABS = 1024\b", hdr) and _lib.CF_MAX_SLABS == 1024
+    # the family names of the binding follow the enum of conv_choose.h
+    enum = re.search(r"enum ConvFamily \{(.*?)\};", open(os.path.join(ROOT, "pointreggpt_amd", "csrc", "conv_choose.h")).read(), flags=re.S)
+    names = re.findall(r"^\s*kConv(\w+)", enum.group(1), flags=re.M)
+    assert [re.sub(r"(?<!^)(?=[A-Z])", "_", n).lower().replace("w256_mx", "w256mx") for n in names] == list(_lib.CONV_FAMILIES), names
 
 
 @pytest.fixture(scope="module")
@@ -94,7 +103,8 @@ def test_rejects_bad_arguments_before_any_device_call(host):
                  dict(Cout=72, groups=8),                                            # cpg = 9
                  dict(x1=p), dict(C1=64),                                            # x1 / C1 mismatch, both ways
                  dict(prologue=3), dict(prologue=-1), dict(residual_mode=4), dict(residual_mode=-1), dict(stats=3), dict(stats=-1),
-                 dict(in_place=1), dict(in_place=2), dict(residual=p)]),             # residual / in_place without a residual mode
+                 dict(in_place=1), dict(in_place=2), dict(residual=p),               # residual / in_place without a residual mode
+                 dict(storage=3), dict(storage=-1), dict(storage=255)]),             # storage outside 0 .. 2
         (two, [dict(x1=None), dict(C1=0), dict(C1=12)]),
         (pro_t, [dict(x1=p, C1=64),                                                  # a prologue with C1 > 0
                  dict(H=12, W=12),                                                   # a prologue on a 12x12 image
@@ -111,6 +121,12 @@ def test_rejects_bad_arguments_before_any_device_call(host):
               dict(Cout=2048, groups=8), dict(Cout=1024, groups=128)]),
         (st_acc, [dict(K=1), dict(acc_raw=None)]),
     ]
+    # float storage: no folds and no accumulators (and a shape without a float kernel with a prologue: C0 % 32 != 0)
+    for store in (_lib.CF_STORE_F16X3, _lib.CF_STORE_F32):
+        bad += [(pro_f, [dict(storage=store)]), (res_f, [dict(storage=store)]), (st_acc, [dict(storage=store)]),
+                (dict(pro_t, storage=store), [dict(C0=72), dict(x1=p, C1=64), dict(H=12, W=12), dict(pro_a=None)]),
+                (dict(st, storage=store), [dict(K=1), dict(sums=None)]),
+                (dict(res_t, storage=store), [dict(K=3), dict(res_b=None)])]
     n = 0
     for good, changes in bad:
         for change in changes:

@@ -252,10 +252,11 @@ def conv_reference(d, images=None, dtype=torch.float64):
     return dict(images=idx, ref=ref, tol=tout + half_ulp_bf16(ref.abs() + tout), v=v, t32=t32)
 
 
-def reference(d, images=None, dtype=torch.float64, kernel=None, partials=0, from_output=None, core=None):
+def reference(d, images=None, dtype=torch.float64, kernel=None, partials=0, from_output=None, core=None, depth=None):
     """conv_reference (or a `core` it returned earlier) plus the statistics.  kernel / partials: the statistics producer
     (stat_depth) and, for the accumulator form, its partial count per image group; None = no statistics.  from_output: the
-    (len(images), Cout, H, W) bf16 output itself when launch_gn_stats produced the sums (kernel = "gn_stats")."""
+    (len(images), Cout, H, W) bf16 output itself when launch_gn_stats produced the sums (kernel = "gn_stats").  depth: the chain
+    length itself, for a producer stat_depth does not know (the float kernels: tests/test_conv_fused_f32_refs.py)."""
     out = dict(core if core is not None else conv_reference(d, images, dtype))
     if kernel is None:
         return out
@@ -266,7 +267,7 @@ def reference(d, images=None, dtype=torch.float64, kernel=None, partials=0, from
     npg = H * W * cpg
     if kernel == "gn_stats":
         v, t32 = from_output, torch.zeros_like(from_output)
-    depth = stat_depth(kernel, cpg, H * W, Cout)
+    depth = stat_depth(kernel, cpg, H * W, Cout) if depth is None else depth
     grp = lambda t: t.reshape(nb, G, cpg * H * W).sum(dim=2)
     S, Q = grp(v), grp(v * v)
     tS = grp(t32) + depth * EPS * grp(v.abs()) + partials * 2.0 ** -25

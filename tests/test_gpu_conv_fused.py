@@ -52,7 +52,9 @@ def cus():
 # ------------------------------------------------------------------------------------------------------------------------------
 # the hook
 # ------------------------------------------------------------------------------------------------------------------------------
-def run(d, stats=OFF, in_place=0):
+def run(d, stats=OFF, in_place=0, storage=_lib.CF_STORE_BF16, want_slabs=False):
+    """one call of the hook.  storage: bf16 (the default) or the float launches of tests/test_gpu_conv_fused_f32.py; want_slabs: the
+    raw slabs come back too.  `choice` is the kernel launch_conv reported: (family, th, tw, bm, bn)."""
     lib = _lib.load()
     B, C0, C1, Cout, H, W = d["shape"]
     G = d["groups"]
@@ -69,7 +71,7 @@ def run(d, stats=OFF, in_place=0):
         return a.ctypes.data
 
     a = _lib.ConvFusedC(B=B, C0=C0, C1=C1, Cout=Cout, H=H, W=W, K=d["K"], groups=G, prologue=PRO[d["pro"]], residual_mode=RES[d["res"]],
-                        in_place=in_place, stats=stats)
+                        in_place=in_place, stats=stats, storage=storage)
     a.x0 = dev(d["x0"])
     a.x1 = dev(d["x1"]) if C1 else None
     a.w = host(d["w"])
@@ -94,11 +96,19 @@ def run(d, stats=OFF, in_place=0):
         a.sums, a.coef_a, a.coef_b = sums.ctypes.data, coef[0].data_ptr(), coef[1].data_ptr()
         if stats == ACC:
             a.acc_raw = raw.ctypes.data
+    slabs = np.full((B * _lib.CF_MAX_SLABS * G * 2,), -7.0, dtype=np.float32) if want_slabs and stats != OFF else None
+    if slabs is not None:
+        a.slabs = slabs.ctypes.data
     rc = lib.prg_debug_conv_fused(C.byref(a), _lib.stream_ptr())
     _lib.check(rc, "prg_debug_conv_fused")
     big = big.cpu()
     assert bool((big[:GUARD] == 7.0).all()) and bool((big[GUARD + n_out:] == 7.0).all()), "guard floats were written"
-    got = dict(out=big[GUARD:GUARD + n_out].reshape(B, Cout, H, W).double(), flags=(a.nsplit, a.acc_done, a.stats_pass))
+    got = dict(out=big[GUARD:GUARD + n_out].reshape(B, Cout, H, W).double(), flags=(a.nsplit, a.acc_done, a.stats_pass),
+               choice=(_lib.CONV_FAMILIES[a.family], a.th, a.tw, a.bm, a.bn))
+    if slabs is not None:
+        used = B * a.nslabs * G * 2
+        assert bool((slabs[used:] == -7.0).all()), "slabs were written past nslabs"
+        got["slabs"] = torch.from_numpy(slabs[:used].copy()).reshape(B, a.nslabs, G, 2).double()
     if stats != OFF:
         coef = coef.cpu().double()
         got.update(sums=torch.from_numpy(sums), coef_a=coef[0], coef_b=coef[1], raw=torch.from_numpy(raw))
@@ -144,17 +154,18 @@ def chunks(B):
 class Refs:
     """conv_reference of one input set, computed once per chunk and shared by the variants that leave the output unchanged"""
 
-    def __init__(self, d, skip=()):
+    def __init__(self, d, skip=(), conv_ref=conv_reference, chunks_of=chunks):
         self.d = d
-        self.cores = [(dt, conv_reference(d, [i for i in im if i not in skip], dt)) for dt, im in chunks(d["shape"][0])]
+        self.cores = [(dt, conv_ref(d, [i for i in im if i not in skip], dt)) for dt, im in chunks_of(d["shape"][0])]
 
-    def check(self, label, got, kernel=None, partials=0):
+    def check(self, label, got, kernel=None, partials=0, full_ref=None, ratio_fn=ratios):
+        """full_ref(core, got) / ratio_fn: another module's reference on a core of its conv_ref, and its comparison"""
         worst = {}
         for dt, core in self.cores:
             idx = core["images"]
-            ref = reference(self.d, kernel=kernel, partials=partials, core=core,
-                            from_output=got["out"][idx] if kernel == "gn_stats" else None)
-            for k, v in ratios(label, got, ref, show=False).items():
+            ref = full_ref(core, got) if full_ref else reference(self.d, kernel=kernel, partials=partials, core=core,
+                                                                 from_output=got["out"][idx] if kernel == "gn_stats" else None)
+            for k, v in ratio_fn(label, got, ref, show=False).items():
                 worst[k] = max(worst.get(k, 0.0), v)
         print(f"{label}: largest error / tolerance " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
         assert max(worst.values()) <= 1.0, (label, worst)
