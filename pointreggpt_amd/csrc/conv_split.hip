@@ -13,57 +13,13 @@
 //
 // Weights are split once at load (pack_conv_weight_split); activations while the halo / the gather tile is written to LDS
 // (v_cvt_pk_f16_f32, one subtraction: 2.5 VALU instructions per element), after the optional fused GroupNorm + SiLU
-// prologue.  LDS rows are 128 bytes per pixel and 32-channel chunk — 64 B of hi halves, 64 B of lo halves — with the
-// 16-byte XOR swizzle of conv.hip, so the tile shapes, the epilogue (conv_epi.h) and the GroupNorm statistics slabs are the
-// parity kernels' own.  Reference: Block.proj / res_conv / to_qkv / to_out / Downsample / Upsample, sd:583-796.
-#include <atomic>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <type_traits>
-
+// prologue.  In LDS a pixel's 32-channel chunk is 64 B of hi halves and 64 B of lo halves: the 3x3 halo kernels pad it to 144
+// bytes (SplitGeom, conv_split_common.h) and store straight from the accumulator registers (direct epilogue); the gather kernel
+// keeps 128-byte rows with the 16-byte XOR swizzle of conv.hip, and its epilogue is conv_epi.h's.  The GroupNorm statistics slabs
+// are the parity kernels' own.  Reference: Block.proj / res_conv / to_qkv / to_out / Downsample / Upsample, sd:583-796.
 #include "conv_split_common.h"
 
 namespace prg {
-
-// acc += a * w with split operands: the two cross terms first (small), then the leading term
-__device__ inline void mma3(const f16x8& ah, const f16x8& al, const f16x8& wh, const f16x8& wl, f32x16& c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, c, 0, 0, 0);
-}
-
-// all tiles of a wave: term-major, so that back-to-back MFMAs never wait on the same accumulator
-template <int TM>
-__device__ inline void mma3_tiles(const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&wh)[2], const f16x8 (&wl)[2],
-                                  f32x16 (&acc)[TM][2]) {
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], wh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], wl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], wh[j], acc[i][j], 0, 0, 0);
-}
-
-template <int TM>
-__device__ inline void flush_acc(f32x16 (&acc)[TM][2], f32x16 (&tot)[TM][2]) {
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        tot[i][j][e] += acc[i][j][e];
-        acc[i][j][e] = 0.0f;
-      }
-}
 
 // ---------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1: halo tile in LDS (structure of conv3x3_halo_kernel, conv.hip)
@@ -91,14 +47,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     const ConvLaunch<float> L, const int tiles_x, const int tiles_y, const int tiles_n, const int fuse_stats) {
   constexpr int NW = 4, BN = 64;
   constexpr int CH = 32;                       // channels per chunk: one LDS row = 64 B of hi halves + 64 B of lo halves
-  constexpr int HP = TW + 2, HALO = (TH + 2) * HP;
-  constexpr int PITCH = 144;                   // halo pixel pitch in bytes (128 + 16: consecutive pixels on distinct 16-byte slots)
-  // halo ROW stride: a multiple of 256 bytes (16 slots).  A 16-wide tile puts lanes 16-31 of a fragment load one halo row below
-  // lanes 0-15; with the natural stride (18 x 144 B = 2 slots mod 16) two lanes of every ds_read_b128 lane group met on a bank
-  // (SQ_LDS_BANK_CONFLICT above SQ_ACTIVE_INST_LDS); with a stride of 0 mod 16 slots the two half rows interleave exactly.
-  constexpr int RSTRIDE = (HP * PITCH + 255) / 256 * 256;
-  constexpr int NH = (HALO + 63) / 64;         // staging passes per chunk (64 halo pixels each)
-  constexpr int HBYTES = (TH + 2) * RSTRIDE;
+  using G = SplitGeom<TH, TW>;                 // 256 staging threads: NH passes of 64 halo pixels per chunk
+  constexpr int HP = G::HP, HALO = G::HALO, PITCH = G::PITCH, RSTRIDE = G::RSTRIDE, HBYTES = G::HBYTES, NH = G::NH;
   constexpr int WPW = BN / 8 / NW;             // global_load_lds wave-instructions (8 rows each) per wave and weight tile
   constexpr int DIST = 8 - NH;                 // taps between a staging pass's load and its conversion / LDS write (last write at tap 7:
                                                // tap 8's body already issues the next chunk's first fragment loads)
@@ -107,13 +57,12 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const Ah = smem;                                 // [2][HALO] rows of PITCH bytes: units 0-3 hi, 4-7 lo
   char* const Bs = smem + 2 * HBYTES;                    // [NS][64][128 B], 16-byte units XOR-swizzled by (row >> 1) & 7
-  float* stage = reinterpret_cast<float*>(smem);         // epilogue scratch aliases the main-loop images
 
   const ConvDesc& d = L.d;
   const int nblk = tiles_x * tiles_y * tiles_n * d.B;
-  // Workgroup b runs on XCD b % 8 (observed).  With 2 / 4 / 8 output-channel tiles every XCD is pinned to ONE of them, so its
-  // 4 MB L2 holds that tile's weight slice (512 -> 512: 1.2 MB of the 9.4 MB set) instead of streaming the whole set through;
-  // otherwise each XCD gets a contiguous run of tiles (xcd_remap).
+  // Tile decode (written out in halo, ws and w512: as a call it reorders the entry block's scalar code).  Workgroup b runs on XCD
+  // b % 8 (observed).  With 2 / 4 / 8 output-channel tiles every XCD is pinned to ONE of them, so its 4 MB L2 holds that tile's
+  // weight slice (512 -> 512: 1.2 MB of the 9.4 MB set) instead of streaming it all; otherwise contiguous runs of tiles (xcd_remap).
   int tn, lin;
   if (tiles_n > 1 && 8 % tiles_n == 0 && nblk % 8 == 0) {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = 8 / tiles_n;
@@ -142,11 +91,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     hsrc[k] = -1;
     if (hp < HALO) {
       const int hy = hp / HP, hx = hp - hy * HP;
-      int y = y0 - 1 + hy, x = x0 - 1 + hx;
-      if ((unsigned)y < (unsigned)Hl && (unsigned)x < (unsigned)Wl) {
-        if (d.ups) { y >>= 1; x >>= 1; }
-        hsrc[k] = (b * d.Hin + y) * d.Win + x;
-      }
+      hsrc[k] = halo_source(d, b, y0 - 1 + hy, x0 - 1 + hx, Hl, Wl, d.ups);
     }
   }
   // fragment addresses: one per-lane base each, everything else immediate
@@ -168,8 +113,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 
   // one staging pass: load (global -> registers) and, one tap later, prologue + split + write (registers -> LDS)
   float4 hh0[NH], hh1[NH];                     // one register pair per pass: a pass is written DIST taps after its load
-  auto halo_load = [&](int chunk, auto K) {   // always issued (padding lanes read the tensor's first bytes and are zeroed when
-    constexpr int k = decltype(K)::value;      // written): the counted vmcnt waits below need a fixed number of loads per body
+  auto halo_load = [&](int chunk, auto K) {   // (chunk_source + load_unit written out: as calls they reorder this kernel's listing)
+    constexpr int k = decltype(K)::value;
     const int c = chunk * CH + q * 8;
     const bool first = c < d.C0;
     const float* base = first ? L.src0 : L.src1;
@@ -180,60 +125,33 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   };
   float pa[8], pb[8];                          // fused prologue coefficients of this thread's 8 channels (chunk being staged)
   auto pro_load = [&](int chunk) {
-    if (L.pro_a) {
-      const float4* a4 = reinterpret_cast<const float4*>(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8);
-      const float4* b4 = reinterpret_cast<const float4*>(L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8);
-      const float4 a0 = a4[0], a1 = a4[1], b0 = b4[0], b1 = b4[1];
-      pa[0] = a0.x; pa[1] = a0.y; pa[2] = a0.z; pa[3] = a0.w; pa[4] = a1.x; pa[5] = a1.y; pa[6] = a1.z; pa[7] = a1.w;
-      pb[0] = b0.x; pb[1] = b0.y; pb[2] = b0.z; pb[3] = b0.w; pb[4] = b1.x; pb[5] = b1.y; pb[6] = b1.z; pb[7] = b1.w;
-    }
+    if (L.pro_a) load_pro8(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8, L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8, pa, pb);
   };
   auto halo_write = [&](int buf, auto K) {
     constexpr int k = decltype(K)::value;
-    if (k * 64 + 63 < HALO || prow + k * 64 < HALO) {
-      const float4 h0 = hh0[k], h1 = hh1[k];
-      float v[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-      if (L.pro_a) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = fast_silu(fmaf(v[u], pa[u], pb[u]));
-      }
-      if (hsrc[k] < 0) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = 0.0f;
-      }
-      uint4 vh, vl;
-      if (L.pro_a) split8<false>(v, vh, vl);
-      else split8(v, vh, vl);
-      char* p = Ah + buf * HBYTES + w_lane[k];
-      *reinterpret_cast<uint4*>(p) = vh;
-      *reinterpret_cast<uint4*>(p + 64) = vl;
-    }
+    if (k * 64 + 63 < HALO || prow + k * 64 < HALO)
+      finish_unit(hh0[k], hh1[k], L.pro_a != nullptr, pa, pb, hsrc[k] < 0, Ah + buf * HBYTES + w_lane[k]);
   };
 
-  // Weight tiles: the LDS destination of a global_load_lds wave-instruction is lane-linear (base + lane * 16 = eight 128-byte
-  // rows), so the XOR swizzle the fragment reads apply sits on the per-lane SOURCE address: LDS unit p of row n holds source
-  // unit p ^ ((n >> 1) & 7).
+  // weight tiles: LDS-DMA, lane-linear destination, the XOR swizzle on the per-lane source address (conv_split_common.h)
   const char* wtile = reinterpret_cast<const char*>(L.w_split + (size_t)tn * BN * 64);
   const size_t wstep = (size_t)d.CoutPad * 128;                                   // bytes between (tap, chunk) tiles
   int wsrc[WPW];
 #pragma unroll
   for (int r = 0; r < WPW; ++r) {
-    const int n = (wave * WPW + r) * 8 + (lane >> 3);
-    wsrc[r] = n * 128 + (((lane & 7) ^ ((n >> 1) & 7)) << 4);
+    wsrc[r] = swizzled_unit((wave * WPW + r) * 8 + (lane >> 3), lane & 7);
   }
   auto gload_b = [&](int chunk, int tap, int slot) {
     const char* p = wtile + (size_t)(tap * L.split_kchunks + chunk) * wstep;
 #pragma unroll
-    for (int r = 0; r < WPW; ++r)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                       (__attribute__((address_space(3))) void*)(Bs + (slot * BN + (wave * WPW + r) * 8) * 128), 16, 0, 0);
+    for (int r = 0; r < WPW; ++r) weight_dma_rows(p + wsrc[r], Bs + (slot * BN + (wave * WPW + r) * 8) * 128);
   };
 
-  f32x16 acc[2], tot[2];
+  f32x16 acc[1][2], tot[1][2];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[j][e] = 0.0f; tot[j][e] = 0.0f; }
+    for (int e = 0; e < 16; ++e) { acc[0][j][e] = 0.0f; tot[0][j][e] = 0.0f; }
 
   const int niter = nchunks * 9;
   // weight tiles 0 .. NS - 1 and chunk 0's halo (all passes in flight at once: one HBM latency per tile, not NH)
@@ -273,8 +191,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   // fragment loads of (chunk buffer cb, tap T) into register set S; ring slot T % NS (9 taps per chunk and NS = 3) or runtime
   auto reads = [&](auto SET, auto TAP, int cb, int slot) {
     constexpr int S = decltype(SET)::value, T = decltype(TAP)::value;
-    constexpr int toff = (T / 3) * RSTRIDE + (T % 3) * PITCH;
-    const char* A = Ah + cb * HBYTES + a_lane + toff;
+    const char* A = Ah + cb * HBYTES + a_lane + G::tap(T);
     const char* Bb = Bs + slot * (BN * 128);
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
@@ -290,15 +207,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   auto mfmas = [&](auto SET) {
     constexpr int S = decltype(SET)::value;
 #pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      // term-major: back-to-back MFMAs never wait on the same accumulator; the two cross terms first (small), then hi * hi
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[S][st][1], fw[S][st][2 * j], acc[j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[S][st][0], fw[S][st][2 * j + 1], acc[j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[S][st][0], fw[S][st][2 * j], acc[j], 0, 0, 0);
-    }
+    for (int st = 0; st < 2; ++st) mfma3<1>(fa[S][st], fw[S][st], acc);
   };
 
   // one tap of chunk c; P = parity of the chunk (register set of tap T = (T + P) & 1)
@@ -330,12 +239,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if constexpr (T < 8) reads(IC<1 - S>(), IC<T + 1>(), c & 1, NS == 3 ? (T + 1) % 3 : (it + 1) & 1);
     else if (more) reads(IC<1 - S>(), IC<0>(), (c + 1) & 1, NS == 3 ? 0 : (it + 1) & 1);
     mfmas(IC<S>());
-    if constexpr (T == 8) {                    // the 288-term partial of this channel chunk
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { tot[j][e] += acc[j][e]; acc[j][e] = 0.0f; }
-    }
+    if constexpr (T == 8) flush_acc<1>(acc, tot);   // the 288-term partial of this channel chunk
   };
   auto chunk_body = [&](auto PAR, int c) {
     body(PAR, IC<0>(), c); body(PAR, IC<1>(), c); body(PAR, IC<2>(), c);
@@ -351,23 +255,17 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     if (c + 1 < nchunks) chunk_body(IC<1>(), c + 1);
   }
 
-  double gs, gq;
-  [[maybe_unused]] auto row_to_m = [&](int r) -> int64_t {
-    const int p = wave * 32 + r;
-    return ((int64_t)b * d.Hout + y0 + p / TW) * d.Wout + x0 + p % TW;
-  };
   if (L.split_scale) {                         // undo the packer's per-channel power-of-two weight scale (exact)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const float sc = L.split_scale[tn * BN + j * 32 + l31];
 #pragma unroll
-      for (int e = 0; e < 16; ++e) tot[j][e] *= sc;
+      for (int e = 0; e < 16; ++e) tot[0][j][e] *= sc;
     }
   }
   // DIRECT epilogue: the accumulator layout already has lanes 0-31 = 32 consecutive channels of ONE pixel (register e of half hi
   // is pixel row (e & 3) + 8 (e >> 2) + 4 hi), so a dword store per register writes two full 128-byte lines per wave-instruction —
   // no LDS transpose, no barrier; the GroupNorm partial sums come from lane reductions (a group's channels are adjacent lanes).
-  (void)stage; (void)gs; (void)gq;
   {
     const int cpg = L.gn_groups > 0 ? d.Cout / L.gn_groups : 8;
     float sj[2], qj[2];
@@ -380,7 +278,7 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
       for (int e = 0; e < 16; ++e) {
         const int p = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
         const size_t m = ((size_t)b * d.Hout + y0 + p / TW) * d.Wout + x0 + p % TW;
-        const float v = tot[j][e] + bv;
+        const float v = tot[0][j][e] + bv;
         L.out[m * d.Cout + ch] = v;
         s1 += v;
         q1 = fmaf(v, v, q1);
@@ -457,9 +355,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
                                                                   const int tiles_n, const int fuse_stats) {
   constexpr int TH = 8, TW = 16, BN = 128, CH = 32;
   constexpr int NT = UP ? 4 : 9;                         // taps per channel chunk
-  constexpr int HP = TW + 2, HALO = (TH + 2) * HP, PITCH = 144;
-  constexpr int RSTRIDE = (HP * PITCH + 255) / 256 * 256, HBYTES = (TH + 2) * RSTRIDE;   // (row stride 0 mod 16 slots: see above)
-  constexpr int NHP = (HALO * 4 + 127) / 128;            // halo staging passes of the 128 halo-producer threads (6)
+  using G = SplitGeom<TH, TW, 128>;                      // 128 halo-producer threads: six staging passes
+  constexpr int HP = G::HP, HALO = G::HALO, PITCH = G::PITCH, RSTRIDE = G::RSTRIDE, HBYTES = G::HBYTES, NHP = G::NH;
   constexpr int WPW = BN / 8 / 2;                        // global_load_lds instructions per weight-producer wave and tile (8)
   static_assert(NS == 4 && NHP <= 6, "ring");
 
@@ -498,17 +395,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
     int wsrc[WPW];
 #pragma unroll
     for (int r = 0; r < WPW; ++r) {
-      const int n = (pw * WPW + r) * 8 + (lane >> 3);
-      wsrc[r] = n * 128 + (((lane & 7) ^ ((n >> 1) & 7)) << 4);
+      wsrc[r] = swizzled_unit((pw * WPW + r) * 8 + (lane >> 3), lane & 7);
     }
     auto gload_b = [&](int it) {
       const int c = it / NT, tap = it - NT * c;
       const char* p = wtile + (size_t)(tap * L.split_kchunks + c) * wstep;
       char* dst = Bs + ((it & (NS - 1)) * BN + pw * WPW * 8) * 128;
-#pragma unroll
-      for (int r = 0; r < WPW; ++r)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                         (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
+      weight_dma<WPW>(p, wsrc, dst);
     };
     gload_b(0);
     if (niter > 1) gload_b(1);
@@ -536,54 +429,24 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
       hsrc[k] = -1;
       if (hp < HALO) {
         const int hy = hp / HP, hx = hp - hy * HP;
-        int y = y0 - 1 + hy, x = x0 - 1 + hx;
-        if ((unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws) {
-          if (!UP && d.ups) { y >>= 1; x >>= 1; }
-          hsrc[k] = (b * d.Hin + y) * d.Win + x;
-        }
+        hsrc[k] = halo_source(d, b, y0 - 1 + hy, x0 - 1 + hx, Hs, Ws, !UP && d.ups);
       }
     }
     float4 gA0[NHP], gA1[NHP], gB0[NHP], gB1[NHP];        // (UP: two chunks in flight; otherwise only set A)
     auto load_chunk_set = [&](int chunk, float4 (&g0)[NHP], float4 (&g1)[NHP]) {
-      const int c = chunk * CH + q * 8;
-      const bool first = c < d.C0;
-      const float* base = first ? L.src0 : L.src1;
-      const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
+      const ChunkSrc s = chunk_source(L, chunk * CH + q * 8);
 #pragma unroll
-      for (int k = 0; k < NHP; ++k) {
-        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-        g0[k] = p[0];
-        g1[k] = p[1];
-      }
+      for (int k = 0; k < NHP; ++k) load_unit(s, hsrc[k], g0[k], g1[k]);
     };
-    float4 (&g0)[NHP] = gA0;
-    float4 (&g1)[NHP] = gA1;
-    auto load_chunk = [&](int chunk) {
-      const int c = chunk * CH + q * 8;
-      const bool first = c < d.C0;
-      const float* base = first ? L.src0 : L.src1;
-      const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
-#pragma unroll
-      for (int k = 0; k < NHP; ++k) {
-        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-        g0[k] = p[0];
-        g1[k] = p[1];
-      }
-    };
+    auto load_chunk = [&](int chunk) { load_chunk_set(chunk, gA0, gA1); };
     float pa[8], pb[8];
     auto pro_load = [&](int chunk) {
-      if (L.pro_a) {
-        const float4* a4 = reinterpret_cast<const float4*>(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8);
-        const float4* b4 = reinterpret_cast<const float4*>(L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8);
-        const float4 a0 = a4[0], a1 = a4[1], b0 = b4[0], b1 = b4[1];
-        pa[0] = a0.x; pa[1] = a0.y; pa[2] = a0.z; pa[3] = a0.w; pa[4] = a1.x; pa[5] = a1.y; pa[6] = a1.z; pa[7] = a1.w;
-        pb[0] = b0.x; pb[1] = b0.y; pb[2] = b0.z; pb[3] = b0.w; pb[4] = b1.x; pb[5] = b1.y; pb[6] = b1.z; pb[7] = b1.w;
-      }
+      if (L.pro_a) load_pro8(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8, L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8, pa, pb);
     };
     auto write_pass_set = [&](int buf, auto K, const float4 (&h0)[NHP], const float4 (&h1)[NHP]) {
       constexpr int k = decltype(K)::value;
       const int hp = prow + k * 32;
-      if (hp < HALO) {
+      if (hp < HALO) {                                     // (finish_unit written out: as a call + 9 / + 11 instructions in this kernel)
         float v[8] = {h0[k].x, h0[k].y, h0[k].z, h0[k].w, h1[k].x, h1[k].y, h1[k].z, h1[k].w};
         if (L.pro_a) {
 #pragma unroll
@@ -687,35 +550,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
   const int pho = UP ? (ph >> 1) * RSTRIDE + (ph & 1) * PITCH : 0;   // UP: the phase's 2 x 2 window starts at halo position (dy, dx)
   auto reads = [&](auto ST, auto TAP, int cb, int slot) {
     constexpr int st = decltype(ST)::value, T = decltype(TAP)::value;
-    constexpr int toff = UP ? (T / 2) * RSTRIDE + (T % 2) * PITCH : (T / 3) * RSTRIDE + (T % 3) * PITCH;
-    const char* A = Ah + cb * HBYTES + toff + st * 32 + pho;
-    const char* Bb = Bs + slot * (BN * 128);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      fa[st][2 * i] = ld_frag(reinterpret_cast<const uint4*>(A + a_lane[i]));
-      fa[st][2 * i + 1] = ld_frag(reinterpret_cast<const uint4*>(A + a_lane[i] + 64));
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      fw[st][2 * j] = ld_frag(reinterpret_cast<const uint4*>(Bb + b_lane[st][0] + j * 4096));
-      fw[st][2 * j + 1] = ld_frag(reinterpret_cast<const uint4*>(Bb + b_lane[st][1] + j * 4096));
-    }
+    constexpr int toff = UP ? G::tap_up(T) : G::tap(T);
+    consumer_reads(Ah + cb * HBYTES + toff + st * 32 + pho, Bs + slot * (BN * 128), a_lane, b_lane[st], fa[st], fw[st]);
   };
-  auto mfmas = [&](auto ST) {
-    constexpr int st = decltype(ST)::value;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i + 1], fw[st][2 * j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i], fw[st][2 * j + 1], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i], fw[st][2 * j], acc[i][j], 0, 0, 0);
-  };
+  auto mfmas = [&](auto ST) { mfma3<2>(fa[decltype(ST)::value], fw[decltype(ST)::value], acc); };
   auto body = [&](auto TAP, int c) {
     constexpr int T = decltype(TAP)::value;
     const int it = c * NT + T;
@@ -737,14 +575,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_ws_kernel(const ConvLaun
     mfmas(IC<1>());
     interleave_8_reads_12_mfmas();
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (T == NT - 1) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.0f; }
-    }
+    if constexpr (T == NT - 1) flush_acc<2>(acc, tot);
   };
   asm volatile("s_barrier" ::: "memory");                // the producers' prologue: chunk 0's halo, weight tiles 0 and 1
   reads(IC<0>(), IC<0>(), 0, 0);
@@ -851,9 +682,8 @@ template <int NS>
 __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLaunch<float> L, const int tiles_x, const int tiles_y,
                                                                    const int ntiles, const int fuse_stats) {
   constexpr int TH = 16, TW = 16, BN = 64, CH = 32, NT = 9;
-  constexpr int HP = TW + 2, HALO = (TH + 2) * HP, PITCH = 144;
-  constexpr int RSTRIDE = (HP * PITCH + 255) / 256 * 256, HBYTES = (TH + 2) * RSTRIDE;
-  constexpr int NHP = (HALO * 4 + 127) / 128;            // halo staging passes of the 128 halo-producer threads (11)
+  using G = SplitGeom<TH, TW, 128>;                      // 128 halo-producer threads: eleven staging passes
+  constexpr int HP = G::HP, HALO = G::HALO, PITCH = G::PITCH, RSTRIDE = G::RSTRIDE, HBYTES = G::HBYTES, NHP = G::NH;
   constexpr int WPW = BN / 8 / 2;                        // global_load_lds instructions per weight-producer wave and tile (4)
   static_assert(NS == 4 && NHP == 11, "ring / passes");
 
@@ -869,15 +699,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
   // rows run at the same time on one L2.
   int t_first, t_stride, t_count;
   {
-    const int G = (int)gridDim.x, bid = (int)blockIdx.x;
-    if ((G & 7) == 0) {
-      const int xcd = bid & 7, idx = bid >> 3, per = G >> 3;
+    const int NG = (int)gridDim.x, bid = (int)blockIdx.x;
+    if ((NG & 7) == 0) {
+      const int xcd = bid & 7, idx = bid >> 3, per = NG >> 3;
       const int q = ntiles >> 3, r = ntiles & 7;
       const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
       const int cnt = q + (xcd < r ? 1 : 0);
       t_first = start + idx; t_stride = per; t_count = idx < cnt ? (cnt - idx + per - 1) / per : 0;
     } else {
-      t_first = bid; t_stride = G; t_count = bid < ntiles ? (ntiles - bid + G - 1) / G : 0;
+      t_first = bid; t_stride = NG; t_count = bid < ntiles ? (ntiles - bid + NG - 1) / NG : 0;
     }
   }
   const int nchunks_total = t_count * nchunks, niter = nchunks_total * NT;
@@ -892,18 +722,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     int wsrc[WPW];
 #pragma unroll
     for (int r = 0; r < WPW; ++r) {
-      const int n = (pw * WPW + r) * 8 + (lane >> 3);
-      wsrc[r] = n * 128 + (((lane & 7) ^ ((n >> 1) & 7)) << 4);
+      wsrc[r] = swizzled_unit((pw * WPW + r) * 8 + (lane >> 3), lane & 7);
     }
     const char* wtile = reinterpret_cast<const char*>(L.w_split);
     int c_n = 0, tap_n = 0;                              // (chunk, tap) of the next tile to fetch: the sequence repeats per pixel tile
     auto gload_next = [&](int it) {
       const char* p = wtile + (size_t)(tap_n * L.split_kchunks + c_n) * wstep;
       char* dst = Bs + ((it & (NS - 1)) * BN + pw * WPW * 8) * 128;
-#pragma unroll
-      for (int r = 0; r < WPW; ++r)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                         (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
+      weight_dma<WPW>(p, wsrc, dst);
       if (++tap_n == NT) { tap_n = 0; if (++c_n == nchunks) c_n = 0; }
     };
     gload_next(0);
@@ -942,7 +768,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
 #pragma unroll
       for (int k = 0; k < NHP; ++k) {
         hsrc[k] = -1;
-        if (hyx[k] >= 0) {
+        if (hyx[k] >= 0) {                               // (halo_source written out: as a call it reorders this kernel's listing)
           int y = y0 - 1 + (hyx[k] >> 8), x = x0 - 1 + (hyx[k] & 255);
           if ((unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws) {
             if (d.ups) { y >>= 1; x >>= 1; }
@@ -953,46 +779,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     };
     float4 g0[NHP], g1[NHP];
     auto load_chunk = [&](int chunk) {
-      const int c = chunk * CH + q * 8;
-      const bool first = c < d.C0;
-      const float* base = first ? L.src0 : L.src1;
-      const int Cs = first ? d.C0 : d.C1, cc = first ? c : c - d.C0;
+      const ChunkSrc s = chunk_source(L, chunk * CH + q * 8);
 #pragma unroll
-      for (int k = 0; k < NHP; ++k) {
-        const float4* p = reinterpret_cast<const float4*>(base + (hsrc[k] >= 0 ? (size_t)hsrc[k] * Cs + cc : (size_t)0));
-        g0[k] = p[0];
-        g1[k] = p[1];
-      }
+      for (int k = 0; k < NHP; ++k) load_unit(s, hsrc[k], g0[k], g1[k]);
     };
     float pa[8], pb[8];
     auto pro_load = [&](int chunk) {
-      if (L.pro_a) {
-        const float4* a4 = reinterpret_cast<const float4*>(L.pro_a + (size_t)img * d.C0 + chunk * CH + q * 8);
-        const float4* b4 = reinterpret_cast<const float4*>(L.pro_b + (size_t)img * d.C0 + chunk * CH + q * 8);
-        const float4 a0 = a4[0], a1 = a4[1], b0 = b4[0], b1 = b4[1];
-        pa[0] = a0.x; pa[1] = a0.y; pa[2] = a0.z; pa[3] = a0.w; pa[4] = a1.x; pa[5] = a1.y; pa[6] = a1.z; pa[7] = a1.w;
-        pb[0] = b0.x; pb[1] = b0.y; pb[2] = b0.z; pb[3] = b0.w; pb[4] = b1.x; pb[5] = b1.y; pb[6] = b1.z; pb[7] = b1.w;
-      }
+      if (L.pro_a) load_pro8(L.pro_a + (size_t)img * d.C0 + chunk * CH + q * 8, L.pro_b + (size_t)img * d.C0 + chunk * CH + q * 8, pa, pb);
     };
     auto write_pass = [&](int buf, auto K) {
       constexpr int k = decltype(K)::value;
-      if (hyx[k] >= 0) {
-        float v[8] = {g0[k].x, g0[k].y, g0[k].z, g0[k].w, g1[k].x, g1[k].y, g1[k].z, g1[k].w};
-        if (L.pro_a) {
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = fast_silu(fmaf(v[u], pa[u], pb[u]));
-        }
-        if (hsrc[k] < 0) {
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = 0.0f;
-        }
-        uint4 vh, vl;
-        if (L.pro_a) split8<false>(v, vh, vl);
-        else split8(v, vh, vl);
-        char* p = Ah + buf * HBYTES + wl[k];
-        *reinterpret_cast<uint4*>(p) = vh;
-        *reinterpret_cast<uint4*>(p + 64) = vl;
-      }
+      if (hyx[k] >= 0) finish_unit(g0[k], g1[k], L.pro_a != nullptr, pa, pb, hsrc[k] < 0, Ah + buf * HBYTES + wl[k]);
     };
     set_tile(0);
     pro_load(0);
@@ -1060,35 +857,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
   f16x8 fa[2][4], fw[2][4];                              // [k16 step][A: (hi, lo) x row tile | W: (hi, lo) x column tile]
   auto reads = [&](auto ST, auto TAP, int cb, int slot) {
     constexpr int st = decltype(ST)::value, T = decltype(TAP)::value;
-    constexpr int toff = (T / 3) * RSTRIDE + (T % 3) * PITCH;
-    const char* A = Ah + cb * HBYTES + toff + st * 32;
-    const char* Bb = Bs + slot * (BN * 128);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      fa[st][2 * i] = ld_frag(reinterpret_cast<const uint4*>(A + a_lane[i]));
-      fa[st][2 * i + 1] = ld_frag(reinterpret_cast<const uint4*>(A + a_lane[i] + 64));
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      fw[st][2 * j] = ld_frag(reinterpret_cast<const uint4*>(Bb + b_lane[st][0] + j * 4096));
-      fw[st][2 * j + 1] = ld_frag(reinterpret_cast<const uint4*>(Bb + b_lane[st][1] + j * 4096));
-    }
+    consumer_reads(Ah + cb * HBYTES + G::tap(T) + st * 32, Bs + slot * (BN * 128), a_lane, b_lane[st], fa[st], fw[st]);
   };
-  auto mfmas = [&](auto ST) {
-    constexpr int st = decltype(ST)::value;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i + 1], fw[st][2 * j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i], fw[st][2 * j + 1], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[st][2 * i], fw[st][2 * j], acc[i][j], 0, 0, 0);
-  };
+  auto mfmas = [&](auto ST) { mfma3<2>(fa[decltype(ST)::value], fw[decltype(ST)::value], acc); };
   // one tap of global chunk g (halo buffer g & 1); `more` = another chunk (of this or of the next tile) follows
   auto body = [&](auto TAP, int g, bool more, bool first) {
     constexpr int T = decltype(TAP)::value;
@@ -1109,21 +880,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_p64_kernel(const ConvLau
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (T == NT - 1) {                         // the 288-term partial of this channel chunk
       // (a tile's FIRST partial is assigned, not added to a zeroed total: 0 + x = x, and the epilogue no longer zeroes 64 registers)
-      if (first) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { tot[i][j][e] = acc[i][j][e]; acc[i][j][e] = 0.0f; }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.0f; }
-      }
+      flush_acc<2>(acc, tot, first);
     }
   };
   asm volatile("s_barrier" ::: "memory");                // barrier(0): the producers' prologue — tile 0's first halo, weight tiles 0 and 1
@@ -1339,20 +1096,20 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const ConvLaun
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
       const int unit = 2 * st + hi;
-      f16x8 ah[TM], al[TM], wh[2], wl[2];
+      f16x8 fa[2 * TM], fw[4];                               // (hi, lo) per row tile / per column tile
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int r = wm * WM + i * 32 + l31, sw = (r >> 1) & 7;
-        ah[i] = ld_frag(Ab + r * 8 + (unit ^ sw));
-        al[i] = ld_frag(Ab + r * 8 + ((4 + unit) ^ sw));
+        fa[2 * i] = ld_frag(Ab + r * 8 + (unit ^ sw));
+        fa[2 * i + 1] = ld_frag(Ab + r * 8 + ((4 + unit) ^ sw));
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int n = wn * 64 + j * 32 + l31, sw = (n >> 1) & 7;
-        wh[j] = ld_frag(Bb + n * 8 + (unit ^ sw));
-        wl[j] = ld_frag(Bb + n * 8 + ((4 + unit) ^ sw));
+        fw[2 * j] = ld_frag(Bb + n * 8 + (unit ^ sw));
+        fw[2 * j + 1] = ld_frag(Bb + n * 8 + ((4 + unit) ^ sw));
       }
-      mma3_tiles<TM>(ah, al, wh, wl, acc);
+      mfma3<TM>(fa, fw, acc);
     }
     if ((it & 7) == 7 || it + 1 == niter) flush_acc<TM>(acc, tot);   // 256-term partials
   };
@@ -1393,7 +1150,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_split_kernel(const ConvLaun
 // conv3x3_split_kernel<TH, TW, NS> (weight ring slots NS: two workgroups must fit a CU)
 template <int TH, int TW>
 struct SplitHalo {
-  static constexpr int RSTRIDE = ((TW + 2) * 144 + 255) / 256 * 256, HB = (TH + 2) * RSTRIDE;
+  static constexpr int HB = SplitGeom<TH, TW>::HBYTES;
   static constexpr int NS = (2 * HB + 3 * 8192) * 2 <= 160 * 1024 ? 3 : 2;
   static constexpr size_t lds0 = (size_t)2 * HB + NS * 8192 + 512;      // (+ the statistics scratch of the direct epilogue)
   static constexpr size_t lds = lds0 < kEpilogueLds ? kEpilogueLds : lds0;
@@ -1401,7 +1158,7 @@ struct SplitHalo {
 
 // The f16x3 families of this file; when each is chosen: conv_choose.cpp, choose_split.  > 64 KB of dynamic LDS needs the opt-in.
 int launch_conv_split(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s) {
-  constexpr int HB10 = 10 * ((18 * 144 + 255) / 256 * 256), HB18 = 18 * ((18 * 144 + 255) / 256 * 256);
+  constexpr int HB10 = SplitGeom<8, 16>::HBYTES, HB18 = SplitGeom<16, 16>::HBYTES;
   constexpr size_t ig128 = (size_t)2 * (128 + 128) * 8 * 16, ig64 = (size_t)2 * (128 + 64) * 8 * 16;
   static_assert(ig128 >= kEpilogueLds && ig64 >= kEpilogueLds, "the gather kernel's staging covers the epilogue scratch");
   static ConvKernel<ConvTileKernel<float>> tab[] = {

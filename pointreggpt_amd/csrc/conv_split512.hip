@@ -15,9 +15,6 @@
 // expression, same GroupNorm slab partition: a wave's 128 pixels are one 8 x 16 tile of that kernel), so the two are bit-identical
 // (tests/test_gpu_f16x3.py::test_f16x3_one_wave_per_simd_kernel).  Dispatch: choose_split (conv_choose.cpp); the same-box A/B is
 // profiles/r06_ab_split_w512.txt.
-#include <atomic>
-#include <cstdlib>
-
 #include "conv_split_common.h"
 
 namespace prg {
@@ -26,9 +23,8 @@ template <int NS, bool PRO>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_split_w512_kernel(
     const ConvLaunch<float> L, const int tiles_x, const int tiles_y, const int tiles_n, const int fuse_stats) {
   constexpr int TH = 16, TW = 16, BN = 128, CH = 32, NT = 9;
-  constexpr int HP = TW + 2, HALO = (TH + 2) * HP, PITCH = 144;
-  constexpr int RSTRIDE = (HP * PITCH + 255) / 256 * 256, HBYTES = (TH + 2) * RSTRIDE;
-  constexpr int NHP = (HALO * 4 + 255) / 256;            // halo staging passes of the 256 threads, 64 halo pixels each (6)
+  using G = SplitGeom<TH, TW>;                           // 256 staging threads, 64 halo pixels per pass: six passes
+  constexpr int HP = G::HP, HALO = G::HALO, RSTRIDE = G::RSTRIDE, HBYTES = G::HBYTES, NHP = G::NH;
   constexpr int WPW = BN / 8 / 4;                        // global_load_lds instructions per wave and weight tile (4)
   static_assert(NS == 3 && NHP == 6 && NT % NS == 0, "ring / passes");
 
@@ -38,8 +34,8 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 
   const ConvDesc& d = L.d;
   const int nblk = tiles_x * tiles_y * tiles_n * d.B;
-  int tn, lin;
-  if (tiles_n > 1 && 8 % tiles_n == 0 && nblk % 8 == 0) {  // every XCD pinned to one output-channel tile (its weight slice stays in L2)
+  int tn, lin;                                           // (tile decode: conv3x3_split_kernel's, conv_split.hip)
+  if (tiles_n > 1 && 8 % tiles_n == 0 && nblk % 8 == 0) {
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, per = 8 / tiles_n;
     tn = xcd % tiles_n;
     lin = idx * per + xcd / tiles_n;
@@ -70,40 +66,21 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
     w_lane[k] = 0;
     if (hp < HALO) {
       const int hy = hp / HP, hx = hp - hy * HP;
-      int y = y0 - 1 + hy, x = x0 - 1 + hx;
-      if ((unsigned)y < (unsigned)Hs && (unsigned)x < (unsigned)Ws) {
-        if (d.ups) { y >>= 1; x >>= 1; }
-        hsrc[k] = (b * d.Hin + y) * d.Win + x;
-      }
-      w_lane[k] = hy * RSTRIDE + hx * PITCH + q * 16;
+      hsrc[k] = halo_source(d, b, y0 - 1 + hy, x0 - 1 + hx, Hs, Ws, d.ups);
+      w_lane[k] = G::at(hy, hx) + q * 16;
     }
   }
   // passes [K0, K0 + 3) of a chunk are loaded together (taps 0 and 3) and share ONE set of three staging register pairs
   float4 hh0[3], hh1[3];
-  const float* hbase = nullptr;                          // source tensor / row pitch / channel offset of the chunk being staged
-  int hCs = 0, hcc = 0;
-  auto halo_chunk = [&](int chunk) {
-    const int c = chunk * CH + q * 8;
-    const bool first = c < d.C0;
-    hbase = first ? L.src0 : L.src1;
-    hCs = first ? d.C0 : d.C1;
-    hcc = first ? c : c - d.C0;
-  };
-  auto halo_load1 = [&](auto K) {                        // always issued (padding lanes read the tensor's first bytes and are zeroed
-    constexpr int k = decltype(K)::value, r = k % 3;     // when written): the counted waits need a fixed number of loads
-    const float4* p = reinterpret_cast<const float4*>(hbase + (hsrc[k] >= 0 ? (size_t)hsrc[k] * hCs + hcc : (size_t)0));
-    hh0[r] = p[0];
-    hh1[r] = p[1];
+  ChunkSrc hs = {nullptr, 0, 0};                         // source tensor / row pitch / channel offset of the chunk being staged
+  auto halo_chunk = [&](int chunk) { hs = chunk_source(L, chunk * CH + q * 8); };
+  auto halo_load1 = [&](auto K) {
+    constexpr int k = decltype(K)::value, r = k % 3;
+    load_unit(hs, hsrc[k], hh0[r], hh1[r]);
   };
   float pa[8], pb[8];
   auto pro_load = [&](int chunk) {
-    if constexpr (PRO) {
-      const float4* a4 = reinterpret_cast<const float4*>(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8);
-      const float4* b4 = reinterpret_cast<const float4*>(L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8);
-      const float4 a0 = a4[0], a1 = a4[1], b0 = b4[0], b1 = b4[1];
-      pa[0] = a0.x; pa[1] = a0.y; pa[2] = a0.z; pa[3] = a0.w; pa[4] = a1.x; pa[5] = a1.y; pa[6] = a1.z; pa[7] = a1.w;
-      pb[0] = b0.x; pb[1] = b0.y; pb[2] = b0.z; pb[3] = b0.w; pb[4] = b1.x; pb[5] = b1.y; pb[6] = b1.z; pb[7] = b1.w;
-    }
+    if constexpr (PRO) load_pro8(L.pro_a + (size_t)b * d.C0 + chunk * CH + q * 8, L.pro_b + (size_t)b * d.C0 + chunk * CH + q * 8, pa, pb);
   };
   // one pass = four pair slices (prologue + split of two channels) and a write slice: five MFMA shadows
   uint32_t hp2[4], lp2[4];
@@ -134,20 +111,16 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   // ---- weight tiles: LDS-DMA, lane-linear destination, the XOR swizzle on the per-lane source address ----
   int wsrc[WPW];
 #pragma unroll
-  for (int r = 0; r < WPW; ++r) {
-    const int n = (wave * WPW + r) * 8 + (lane >> 3);
-    wsrc[r] = n * 128 + (((lane & 7) ^ ((n >> 1) & 7)) << 4);
-  }
+  for (int r = 0; r < WPW; ++r) wsrc[r] = swizzled_unit((wave * WPW + r) * 8 + (lane >> 3), lane & 7);
   auto dma_piece = [&](int chunk, int tap, int slot, auto R) {
     constexpr int r = decltype(R)::value;
     const char* p = wtile + (size_t)(tap * L.split_kchunks + chunk) * wstep;
     char* dst = Bs + (slot * BN + wave * WPW * 8) * 128;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p + wsrc[r]),
-                                     (__attribute__((address_space(3))) void*)(dst + r * 1024), 16, 0, 0);
+    weight_dma_rows(p + wsrc[r], dst + r * 1024);
   };
 
   // ---- fragments ----
-  const int a_lane = (wm * 8 + (l31 >> 4)) * RSTRIDE + (l31 & 15) * PITCH + hi * 16;   // row tile i: + 2 i RSTRIDE
+  const int a_lane = (wm * 8 + (l31 >> 4)) * RSTRIDE + (l31 & 15) * G::PITCH + hi * 16;   // row tile i: + 2 i RSTRIDE
   int b_lane[2][2];
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   // fragment R (0 .. 7: A rows, 8 .. 11: weight columns) of k16 step ST of tap TAP
   auto read_slot = [&](auto ST, auto TAP, auto R, int cb) {
     constexpr int st = decltype(ST)::value, T = decltype(TAP)::value, r = decltype(R)::value;
-    constexpr int toff = (T / 3) * RSTRIDE + (T % 3) * PITCH;
+    constexpr int toff = G::tap(T);
     if constexpr (r < 8) {
       fa[st][r] = ld_frag(reinterpret_cast<const uint4*>(Ah + cb * HBYTES + toff + st * 32 + a_lane + (r >> 1) * 2 * RSTRIDE + (r & 1) * 64));
     } else {
@@ -241,14 +214,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       }
       __builtin_amdgcn_sched_barrier(0);
     });
-    if constexpr (T == NT - 1) {                         // the 288-term partial of this channel chunk
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) tot[i][j][e] += acc[i][j][e];
-    }
+    if constexpr (T == NT - 1) flush_acc<4, false>(acc, tot);   // the 288-term partial of this channel chunk
   };
   auto chunk_taps = [&](auto MORE, int c) {
     body(IC<0>(), MORE, c); body(IC<1>(), MORE, c); body(IC<2>(), MORE, c); body(IC<3>(), MORE, c); body(IC<4>(), MORE, c);
@@ -339,7 +305,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 
 // conv3x3_split_w512_kernel<NS, PRO>; when it is chosen: conv_choose.cpp, choose_split
 int launch_conv_split_w512(const ConvChoice& c, const ConvLaunch<float>& L, hipStream_t s) {
-  constexpr int NS = 3, HB = 18 * ((18 * 144 + 255) / 256 * 256);
+  constexpr int NS = 3, HB = SplitGeom<16, 16>::HBYTES;
   constexpr size_t lds = (size_t)2 * HB + NS * 128 * 128;
   static ConvKernel<ConvTileKernel<float>> tab[] = {{conv_key(0), &conv3x3_split_w512_kernel<NS, false>, 256, lds, 152 * 1024},
                                                     {conv_key(1), &conv3x3_split_w512_kernel<NS, true>, 256, lds, 152 * 1024}};

@@ -9,8 +9,10 @@ give the same bits): the conditional dim-64 U-Net at 128 x 128 with B = 2 and 16
 weight preparation, the MaskUnet's 3-channel stems, a dim-16 network on the generic paths and an 8-step sampler chain with and
 without graph capture.  They also cover every branch of the forward pass's host code (csrc/unet.hip): small shapes (B = 2 at
 64 x 64, and at 40 x 40 where tiles do not divide and the second conv of a block has no fused prologue) under each switch that
-moves a ResnetBlock onto another path, and the debug taps, which turn the fused head off.  The library reads its PRG_* switches
-once per process: every switch setting runs in a child of its own."""
+moves a ResnetBlock onto another path, and the debug taps, which turn the fused head off.  The f16x3 networks reach every
+instantiation of conv_split.hip / conv_split512.hip but conv3x3_split_kernel<4, 32, 2> (choose_conv at 256 CUs); the kind
+"conv_fused" launches that one alone (prg_debug_conv_fused).  The library reads its PRG_* switches once per process: every switch
+setting runs in a child of its own."""
 import json
 import os
 import subprocess
@@ -51,13 +53,32 @@ GROUPS = [
     ({"PRG_SPLIT_P64": "1"}, SMALL("f16x3")),
     ({"PRG_SPLIT_W512": "2"}, SMALL("f16x3")),
     ({"PRG_SPLIT_FULLATTN": "0", "PRG_SPLIT_LA_ONLINE": "0"}, SMALL("f16x3")),
+    ({}, [("conv_fused", 64, 2, 12, "f16x3")]),
 ]
+# kind "conv_fused": one f16x3 3x3 conv through the test hook, statistics off and as slabs.  (tag, (B, C0, C1, Cout, H, W), prologue,
+# expected (family, th, tw)): the smallest shapes of tests/test_gpu_conv_fused_f32.py that select the 4 x 32 split halo tile
+CONV_FUSED = [("two_source", (2, 64, 64, 64, 12, 32), None, ("split_halo", 4, 32)),
+              ("prologue", (2, 64, 0, 128, 12, 32), "tables", ("split_halo", 4, 32))]
 
 
 def case_name(env, case):
     kind, dim, B, S, mode = case
     tag = "".join(f"+{k}={v}" for k, v in sorted(env.items()))
     return f"{kind}{dim}_B{B}_S{S}_{mode}{tag}"
+
+
+def run_conv_fused(name, res):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from test_conv_fused_f32_refs import F16X3, make_case32
+    from test_gpu_conv_fused import OFF, SLABS, run
+    for i, (tag, shape, pro, want) in enumerate(CONV_FUSED):
+        d = make_case32(shape, pro=pro, seed=900 + i)
+        for stats in (OFF, SLABS):
+            got = run(d, stats=stats, storage=F16X3, want_slabs=True)
+            assert got["choice"][:3] == want, (tag, got["choice"])
+            for k in ("out", "slabs", "sums", "coef_a", "coef_b"):
+                if k in got:
+                    res[f"{name}:{tag}:stats{stats}:{k}"] = got[k].numpy()
 
 
 def run_group(index, out):
@@ -71,6 +92,9 @@ def run_group(index, out):
     res = {}
     for case in cases:
         kind, dim, B, S, mode = case
+        if kind == "conv_fused":
+            run_conv_fused(case_name(env, case), res)
+            continue
         g = torch.Generator().manual_seed(1000 + dim + B + S)
         taps = ()
         if kind in ("maskunet", "maskunet_taps"):
