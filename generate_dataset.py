@@ -22,6 +22,11 @@ hard-coded literals, generate_dataset.py:32-55):
   --clouds per_view   with --num_samples k: one cloud per view, sample-000001 .. sample-00000k.cloud.ply, each view alone in
                       its own camera frame, instead of the k views fused into sample-000001 (the default, `fused`): C(k+1, 2)
                       candidate pairs per scene for `--with_gt` or `generate_gt.py --num_samples k+1` (k = 1: the same files)
+  --overlap LO HI     choose every view's pose for a PREDICTED overlap of the source cloud in [LO, HI] (e.g. 0.1 0.3, a 3DLoMatch-
+                      style split): --pose_candidates N (16) candidate poses per scene and view, the reference's ranges times
+                      --pose_spread S (3.0), are scored against the source frame on the GPU before the chain runs; the first in
+                      band is generated.  Keyed by (seed, scene, view): the same poses whatever the batch, shard or resume.
+                      Without it the poses are drawn as the reference draws them
   --resume synthetic[:SEED]   deterministic synthetic weights instead of ./successive_ddnm_diffusion_results/model-<resume>.pt
 Under `torchrun --nproc-per-node N` every rank takes a contiguous block of [-start, -stop) (no collectives).
 Two datasets generated from the same scenes (same --synthetic and --noise_seed, e.g. in two --dtype modes) are compared cloud
@@ -71,6 +76,11 @@ def main():
     p.add_argument("--clouds", default="fused", choices=["fused", "per_view"],
                    help="fused = the views of a scene in one target cloud (the reference's layout); per_view = one cloud per "
                         "view, every pair of a scene's clouds a candidate for gt.log")
+    p.add_argument("--overlap", default=None, type=float, nargs=2, metavar=("LO", "HI"),
+                   help="choose every view's pose for a predicted overlap of the source cloud in [LO, HI], 0 <= LO < HI <= 1")
+    p.add_argument("--pose_candidates", default=16, type=int, help="with --overlap: candidate poses per scene and view")
+    p.add_argument("--pose_spread", default=3.0, type=float,
+                   help="with --overlap: the reference's pose ranges (angles, xy jitter) are multiplied by this")
     args = p.parse_args()
 
     from pointreggpt_amd import sharding
@@ -135,11 +145,13 @@ def main():
         # PRG_JOB_SEED replay it) and a scene's noise key does not depend on the shard that produced it
         args.noise_seed = sharding.job_seed() if args.synthetic is None else int(args.synthetic)
     print("[rank {}/{}] noise seed: {}  scenes [{}, {})".format(rank, world, args.noise_seed, start, stop))
+    search = {} if args.overlap is None else dict(overlap=tuple(args.overlap), pose_candidates=args.pose_candidates,
+                                                  pose_spread=args.pose_spread)
     if stop > start:
         generator.generate(start_scene_index=start, stop_scene_index=stop, num_samples=args.num_samples,
                            has_refine_step=False, depth_correction=depth_correction,
                            mask_threshold=args.mask_threshold, noise_seed=args.noise_seed, lanes=lanes,
-                           gt_log=args.with_gt, clouds=args.clouds)
+                           gt_log=args.with_gt, clouds=args.clouds, **search)
     if args.device == "cuda":
         torch.cuda.synchronize()
 

@@ -80,6 +80,33 @@ int prg_project_points_zbuffer(const float* points, const int64_t* offsets, cons
                                float* depth, uint8_t* mask, int B, int H, int W, float depth_scale,
                                void* stream);
 
+/* Candidate camera poses scored before a chain is spent on one: points / offsets as prg_project_points_zbuffer takes them (ragged
+ * float32 clouds, CSR offsets (B+1) int64, DEVICE, offsets[0] may be > 0), poses (B,N,4,4) float32 DEVICE — candidate c of scene
+ * b —, K (B,3,3) DEVICE, counts (B,N,3) int32 DEVICE, cleared by the call.  Every row of cloud b is moved by poses[b,c] and
+ * projected with prg_project_points_zbuffer's arithmetic (the same fma chain, round-half-even, z > 0 and in-frame test), and
+ * counts[b,c] = (in_frame, seen, covered):
+ *   in_frame  rows the z-buffer takes;
+ *   covered   pixels of that candidate's z-buffer that received a row: the set bytes of prg_project_points_zbuffer's mask for the
+ *             same pose;
+ *   seen      rows the z-buffer takes whose float32 z <= zmin(pixel) + z_tol (a float32 sum) and, with `box`, whose MOVED
+ *             coordinates q satisfy lo <= q <= hi componentwise: the box is applied in the target camera frame, where the
+ *             reference crops the target cloud (sd:2641-2650).  Rows that tie for a pixel's nearest depth are all seen.
+ * A NaN row fails z > 0 and counts nowhere.  box: 6 floats on the HOST (lo xyz, hi xyz), read during the call, or NULL = no box.
+ * Two passes, scatter then count, over per-candidate z-buffers in `workspace` (DEVICE, 4-byte aligned, contents are scratch): it
+ * may be smaller than B*N*H*W*4 bytes, the call then works through the candidates in chunks of workspace_bytes / (B*H*W*4), a
+ * quotient that must be at least 1.  The counts are integers from atomicMin / atomicAdd on 32-bit words: they depend neither on
+ * the order of execution nor on the chunking.  1 <= B, N <= 65535, H, W >= 1, H*W < 2^31, z_tol finite and >= 0; anything else,
+ * a null pointer other than box or a workspace that is too small fails with PRG_E_INVALID before any device call.  Asynchronous
+ * on `stream`; reads no device data on the host; allocates nothing.
+ *
+ * prg_pose_candidate_workspace_bytes: B*N*H*W*4 capped at 256 MiB (a whole number of candidates per scene), never less than one
+ * candidate per scene; 0 for a size below 1.  Host-only arithmetic: no device call, usable without a GPU; returns the size, not a
+ * PRG_E_* code.                                                                                                                 */
+size_t prg_pose_candidate_workspace_bytes(int B, int N, int H, int W);
+int prg_pose_candidate_counts(const float* points, const int64_t* offsets, const float* poses, const float* K, int B, int N,
+                              int H, int W, const float* box, float z_tol, int32_t* counts, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* reproject_tensor (sd:268-286) fused: unproject depth*depth_unit, move by pose, z-buffer into the same
  * camera, store z*out_scale.  One kernel, no intermediate point cloud in HBM.                              */
 int prg_reproject_zbuffer(const float* depth, const float* K, const float* pose, float* depth_out,

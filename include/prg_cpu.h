@@ -31,6 +31,10 @@ int prg_cpu_pc2depth(const float* pc, const uint8_t* valid, const float* K, floa
                      int H, int W);                                                                    /* sd:212-265 */
 int prg_cpu_project_points_zbuffer(const float* points, const int64_t* offsets, const float* pose, const float* K,
                                    float* depth, uint8_t* mask, int B, int H, int W, float depth_scale);   /* sd:2531-2552 */
+/* twin of prg_pose_candidate_counts (prg.h), the bit-exact comparator of its kernels: the same arguments with HOST pointers, no
+ * workspace and no stream; one z-buffer per (scene, candidate) at a time.  counts (B,N,3) = (in_frame, seen, covered).           */
+int prg_cpu_pose_candidate_counts(const float* points, const int64_t* offsets, const float* poses, const float* K, int B, int N,
+                                  int H, int W, const float* box, float z_tol, int32_t* counts);
 int prg_cpu_reproject_zbuffer(const float* depth, const float* K, const float* pose, float* depth_out, uint8_t* mask_out,
                               int B, int H, int W, float depth_unit, float clip_lo, float clip_hi, float out_scale);  /* sd:268-286 */
 int prg_cpu_unproject_f64(const float* depth, const float* K, const float* pose, double* xyz, uint8_t* valid, int B, int H,

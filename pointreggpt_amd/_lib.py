@@ -70,6 +70,8 @@ PROTOTYPES = {
     "prg_depth2pc": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
     "prg_pc2depth": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "prg_project_points_zbuffer": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "prg_pose_candidate_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "prg_pose_candidate_counts": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, C.c_size_t, _P]),
     "prg_reproject_zbuffer": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P]),
     "prg_unproject_f64": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
     "prg_depth_augment": (C.c_int, [_P, _P, _I, _I, _I, _P]),

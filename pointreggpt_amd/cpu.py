@@ -33,6 +33,7 @@ PROTOTYPES = {
     "prg_cpu_depth2pc": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F]),
     "prg_cpu_pc2depth": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "prg_cpu_project_points_zbuffer": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F]),
+    "prg_cpu_pose_candidate_counts": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P]),
     "prg_cpu_reproject_zbuffer": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F]),
     "prg_cpu_unproject_f64": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F]),
     "prg_cpu_depth_augment": (C.c_int, [_P, _P, _I, _I, _I]),
@@ -232,6 +233,8 @@ class ops:
     intrinsic_transform = staticmethod(_G.intrinsic_transform)
     random_sample_pose = staticmethod(_G.random_sample_pose)
     param_vector = staticmethod(_G.param_vector)
+    pose_candidates = staticmethod(_G.pose_candidates)
+    select_pose_candidates = staticmethod(_G.select_pose_candidates)
 
     @staticmethod
     def pc2depth_tensor(pc, valid, intrinsic, *, image_size):
@@ -279,6 +282,30 @@ class ops:
         check(load().prg_cpu_project_points_zbuffer(_p(pts), _p(o), _p(P), _p(K), _p(depth), _p(mask), B, S, S, float(depth_scale)),
               "prg_cpu_project_points_zbuffer")
         return depth, mask.view(torch.bool)
+
+    @staticmethod
+    def upload_clouds(clouds, device=None, dtype=np.float32):
+        """`geometry.upload_clouds` without the upload: the ragged HOST buffer (pts (max(total,1),3), offsets (B+1) int64)."""
+        offs = np.zeros(len(clouds) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([len(c) for c in clouds])
+        pts = torch.from_numpy(np.concatenate([np.asarray(c, dtype=dtype).reshape(-1, 3) for c in clouds], 0)
+                               if offs[-1] else np.zeros((1, 3), dtype)).contiguous()
+        return pts, torch.from_numpy(offs)
+
+    @staticmethod
+    def pose_candidate_counts(pts, offs, poses, K, S, *, box=None, z_tol=_G.POSE_Z_TOL):
+        """prg_cpu_pose_candidate_counts: `geometry.pose_candidate_counts` on host tensors -> counts (B,N,3) int32."""
+        pts, o, P, Kt = _t(pts).view(-1, 3), _t(offs, torch.int64), _t(poses), _t(K)
+        B = o.numel() - 1
+        if P.dim() != 4 or P.shape[0] != B or tuple(P.shape[2:]) != (4, 4) or tuple(Kt.shape) != (B, 3, 3):
+            raise ValueError("pose_candidate_counts: poses (B,N,4,4) and K (B,3,3) for the B clouds of offs")
+        N = P.shape[1]
+        H, W = _G._image_hw(S)
+        b6 = _G._box6(box)
+        counts = torch.empty((B, N, 3), dtype=torch.int32)
+        check(load().prg_cpu_pose_candidate_counts(_p(pts), _p(o), _p(P), _p(Kt), B, N, H, W, None if b6 is None else b6.ctypes.data,
+                                                   float(z_tol), _p(counts)), "prg_cpu_pose_candidate_counts")
+        return counts
 
     @staticmethod
     def unproject_f64(depth, intrinsic, pose, *, depth_unit=_G.DEPTH_UNIT_M, clip=(0.5, 10.0)):

@@ -492,6 +492,48 @@ int prg_cpu_project_points_zbuffer(const float* pts, const int64_t* offs, const 
   return PRG_OK;
 }
 
+// twin of prg_pose_candidate_counts: one z-buffer per (scene, candidate), filled and then read, rows in order
+int prg_cpu_pose_candidate_counts(const float* pts, const int64_t* offs, const float* poses, const float* K, int B, int N, int H,
+                                  int W, const float* box, float z_tol, int32_t* counts) {
+  CPU_CHECK(pts && offs && poses && K && counts, "prg_cpu_pose_candidate_counts: null pointer");
+  CPU_CHECK(B >= 1 && B <= 65535 && N >= 1 && N <= 65535, "prg_cpu_pose_candidate_counts: B and N must be in 1..65535");
+  CPU_CHECK(H >= 1 && W >= 1 && (int64_t)H * W <= 0x7FFFFFFF, "prg_cpu_pose_candidate_counts: bad image size");
+  CPU_CHECK(z_tol >= 0.0f && z_tol <= std::numeric_limits<float>::max(), "prg_cpu_pose_candidate_counts: z_tol must be finite and >= 0");
+  const size_t HW = (size_t)H * W;
+  std::vector<float> zb(HW);
+  std::vector<float> q;                                   // the moved rows of one (scene, candidate)
+  for (int b = 0; b < B; ++b) {
+    const Cam c = load_cam(K, b);
+    const int64_t n = offs[b + 1] - offs[b];
+    q.resize((size_t)(n > 0 ? n : 0) * 3);
+    for (int k = 0; k < N; ++k) {
+      const float* P = poses + ((size_t)b * N + k) * 16;
+      int32_t* out = counts + ((size_t)b * N + k) * 3;
+      std::fill(zb.begin(), zb.end(), kInf);
+      for (int64_t i = 0; i < n; ++i) {
+        const float* p = pts + (offs[b] + i) * 3;
+        se3_apply(P, p[0], p[1], p[2], q[i * 3], q[i * 3 + 1], q[i * 3 + 2]);
+        splat(zb.data(), c, q[i * 3], q[i * 3 + 1], q[i * 3 + 2], H, W);
+      }
+      int32_t in_frame = 0, seen = 0, covered = 0;
+      for (int64_t i = 0; i < n; ++i) {
+        const float x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
+        if (!(z > 0.0f)) continue;
+        const float fc = std::nearbyintf(x * c.fx / z + c.cx), fr = std::nearbyintf(y * c.fy / z + c.cy);
+        if (!(fc >= 0.0f && fc < (float)W && fr >= 0.0f && fr < (float)H)) continue;
+        ++in_frame;
+        const float zmin = zb[(size_t)(int)fr * W + (int)fc];
+        bool s = z <= zmin + z_tol;
+        if (box) s = s && x >= box[0] && x <= box[3] && y >= box[1] && y <= box[4] && z >= box[2] && z <= box[5];
+        seen += s ? 1 : 0;
+      }
+      for (size_t p = 0; p < HW; ++p) covered += zb[p] != kInf ? 1 : 0;
+      out[0] = in_frame; out[1] = seen; out[2] = covered;
+    }
+  }
+  return PRG_OK;
+}
+
 int prg_cpu_reproject_zbuffer(const float* depth, const float* K, const float* pose, float* out, uint8_t* mask, int B, int H,
                               int W, float unit, float lo, float hi, float out_scale) {
   CPU_CHECK(depth && K && pose && out && depth != out && B > 0 && H > 0 && W > 0, "prg_cpu_reproject_zbuffer: bad arguments");

@@ -6,37 +6,11 @@
 //
 // sd = denoising_diffusion_pytorch/successive_ddnm_diffusion.py, dc = depth_correction_pytorch/depth_correction.py
 #include "allpairs.h"
+#include "camera.h"
 
 namespace prg {
 
-static constexpr uint32_t kEmpty = 0xFFFFFFFFu;  // z-buffer sentinel: above every positive float's bit pattern
-
-struct Cam {
-  float fx, fy, cx, cy;
-};
-__device__ inline Cam load_cam(const float* K, int b) {
-  const float* k = K + (size_t)b * 9;
-  return Cam{k[0], k[4], k[2], k[5]};
-}
-
-// rotate + translate exactly like `pc @ R^T + t` on the host: fma chain over k = 0,1,2, then a separate add.
-__device__ inline void se3_apply(const float* P, float x, float y, float z, float& ox, float& oy, float& oz) {
-  // P row-major 4x4: R[j][k] = P[j*4+k], t[j] = P[j*4+3]
-  float v;
-  v = x * P[0]; v = __fmaf_rn(y, P[1], v); v = __fmaf_rn(z, P[2], v); ox = v + P[3];
-  v = x * P[4]; v = __fmaf_rn(y, P[5], v); v = __fmaf_rn(z, P[6], v); oy = v + P[7];
-  v = x * P[8]; v = __fmaf_rn(y, P[9], v); v = __fmaf_rn(z, P[10], v); oz = v + P[11];
-}
-
-// project one camera-frame point and min-merge it into the z-buffer (sd:225-258)
-__device__ inline void splat(uint32_t* zbuf, const Cam& c, float x, float y, float z, int H, int W) {
-  if (!(z > 0.0f)) return;  // also rejects NaN
-  float fc = rintf(x * c.fx / z + c.cx);  // torch.round = round-half-even
-  float fr = rintf(y * c.fy / z + c.cy);
-  if (!(fc >= 0.0f && fc < (float)W && fr >= 0.0f && fr < (float)H)) return;
-  int col = (int)fc, row = (int)fr;
-  atomicMin(zbuf + (size_t)row * W + col, __float_as_uint(z));
-}
+// Cam, se3_apply and splat: camera.h (shared with posesearch.hip)
 
 // ---- depth2pc_tensor (sd:176-209) ------------------------------------------------------------
 __global__ void depth2pc_kernel(const float* __restrict__ depth, const float* __restrict__ K, float* __restrict__ pc,

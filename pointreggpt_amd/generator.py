@@ -47,6 +47,14 @@ class FinishedPairs(NamedTuple):
     down_offsets: torch.Tensor    # (nB+1) int64 offsets of the clouds down-sampled at GT_VOXEL
 
 
+class PoseSearch(NamedTuple):
+    """`generate(overlap=...)`: the overlap target of a run, checked by `Generator._pose_search`."""
+    band: tuple                   # (lo, hi) of the predicted overlap of the source cloud
+    n: int                        # candidates per (scene, view)
+    spread: float                 # multiplies the reference's pose ranges
+    seed: int                     # keys the candidate streams: the synthetic seed, or noise_seed with real data
+
+
 class Generator:
     def __init__(self, diffusion_model, folder: Optional[str], *, batch_size=16, samples_folder="./samples",
                  results_folder="./results", synthetic_seed: Optional[int] = None, device="cuda", **_ignored):
@@ -129,13 +137,56 @@ class Generator:
             out.append(synthetic.synth_pose(rng))
         return np.stack(out)
 
+    # -- overlap-targeted poses: candidates scored against the source frame before a chain is spent on one -----------------------
+    def _pose_search(self, overlap, pose_candidates, pose_spread, noise_seed, seed_poses) -> Optional["PoseSearch"]:
+        """The `overlap=` / `pose_candidates=` / `pose_spread=` keywords of `generate` and `PairStream`, checked -> what
+        `_view_poses` takes; None for overlap=None."""
+        if overlap is None:
+            return None
+        band = G.check_overlap_band(overlap)
+        if int(pose_candidates) != pose_candidates or not 1 <= pose_candidates <= 65535:
+            raise ValueError("pose_candidates must be an integer in 1..65535")
+        if not (np.isfinite(pose_spread) and pose_spread > 0):
+            raise ValueError("pose_spread must be finite and > 0")
+        if self.synthetic_seed is None and not seed_poses:
+            raise ValueError("overlap=(lo, hi) needs a seed to key the pose candidates: pass noise_seed (numpy's global stream, "
+                             "seed_poses=False, cannot)")
+        seed = self.synthetic_seed if self.synthetic_seed is not None else noise_seed
+        return PoseSearch(band, int(pose_candidates), float(pose_spread), int(seed))
+
+    def _search_source(self, memory, scene_pcs):
+        """The clouds the candidates are scored against, a batch's source frames as one ragged float32 buffer -> (pts, offs, rows):
+        `DeviceMemory`'s `mem_pts0` / `mem_offs0`, which are on the device already; otherwise the list, uploaded (with
+        device="cpu": laid out for the twin)."""
+        if isinstance(memory, DeviceMemory):
+            return memory.mem_pts0, memory.mem_offs0, memory.rows0
+        return (*self.G.upload_clouds(scene_pcs, self.device), [len(c) for c in scene_pcs])
+
+    def _view_poses(self, idxs, sample_idx, pose_seed, K, source, search):
+        """The poses of one view of a batch -> (pose (B,4,4) float32, predicted): `_poses`' draw and None without a search; with
+        one, per scene the candidate `select_pose_candidates` picks from `pose_candidates(seed, scene, sample_idx, n, spread)`,
+        all B * n scored against the scenes' source frames by ONE `pose_candidate_counts` call — box = the crop box, z_tol =
+        0.0375 — and the host learns B * n * 3 integers in one blocking copy.  predicted: [(ratio, in band), ...] per scene."""
+        if search is None:
+            return self._poses(idxs, sample_idx, pose_seed), None
+        pts, offs, rows = source
+        cands = np.stack([self.G.pose_candidates(search.seed, i, sample_idx, search.n, search.spread) for i in idxs])
+        counts = self.G.pose_candidate_counts(pts, offs, cands, K, self.image_size, box=(PP.BBOX_MIN, PP.BBOX_MAX),
+                                              z_tol=G.POSE_Z_TOL).cpu().numpy()
+        pose, predicted = np.empty((len(idxs), 4, 4), dtype=np.float32), []
+        for j in range(len(idxs)):
+            c, r, ok = self.G.select_pose_candidates(counts[j], rows[j], search.band)
+            pose[j] = cands[j, c]
+            predicted.append((r, ok))
+        return pose, predicted
+
     # -- the pipeline ----------------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, start_scene_index, stop_scene_index, num_samples, memory_voxel_size=0.002,
                  save_voxel_size=0.025, has_refine_step=False, depth_correction=None, mask_threshold=0.99,
                  noise_seed: Optional[int] = None, progress: bool = False, writer_threads: int = 0, stats: Optional[dict] = None,
                  seed_poses: Optional[bool] = None, lanes: Optional[list] = None, voxel_backend: str = "device",
-                 gt_log: bool = False, clouds: str = "fused"):
+                 gt_log: bool = False, clouds: str = "fused", overlap=None, pose_candidates: int = 16, pose_spread: float = 3.0):
         """Same sequence as sd:2363-2694.  File output is asynchronous: every batch's clouds / images / text files are
         handed to the library's C++ writer pool (crop, voxel grid, PLY / PNG encoding on worker threads) and are
         produced while the GPU samples the next batch.  A batch's resume marker — the generated cloud of its LAST scene
@@ -165,7 +216,16 @@ class Generator:
         own sample-{i:06d}.cloud.ply — `postprocess.finish_cloud(xyz_i[valid_i], pre=pose_i, crop=the box, voxel=save_voxel_size,
         post=inv(pose_i))`, the view alone in its own camera frame — so that `generate_gt(num_samples=k+1)`, or `gt_log=True`
         in the same pass, lists up to C(k+1, 2) pairs per scene for k chains.  Every other file and the memory update between
-        the views are the same in both modes, and for num_samples == 1 so are the clouds."""
+        the views are the same in both modes, and for num_samples == 1 so are the clouds.
+        ``overlap``: None (the default) draws one pose per (scene, view) as the reference does — the code path, the calls and every
+        file's bytes of a run that never mentions the keyword.  (lo, hi) with 0 <= lo < hi <= 1 chooses every view's pose for the
+        overlap it is PREDICTED to give (`_view_poses`): ``pose_candidates`` candidates per (scene, view) from
+        `geometry.pose_candidates` — the reference's pose ranges times ``pose_spread`` — are scored against the scene's source
+        frame on the device (`geometry.pose_candidate_counts`), and the first whose share of seen source rows lies in [lo, hi]
+        goes exactly where the drawn pose went: the view step, pose.txt, the finish.  The candidates are keyed by (seed, scene,
+        view) — the synthetic seed, or `noise_seed` with real data — and depend on nothing else; real data with
+        `seed_poses=False` raises ValueError.  `stats["pose_search"]` = {views, in_band, predicted: [(scene, view, ratio), ...]},
+        and each rank prints one summary line."""
         if voxel_backend not in ("device", "host"):
             raise ValueError("voxel_backend must be 'device' or 'host'")
         if clouds not in ("fused", "per_view"):
@@ -177,6 +237,7 @@ class Generator:
         if seed_poses is None:
             seed_poses = noise_seed is not None or (lanes is not None and len(lanes) > 0)
         noise_seed = 0 if noise_seed is None else int(noise_seed)
+        search = self._pose_search(overlap, pose_candidates, pose_spread, noise_seed, seed_poses)
         info_train = self._train_info()
         batches = []
         for idxs in index_batches(start_scene_index, stop_scene_index, self.batch_size):
@@ -194,7 +255,7 @@ class Generator:
         pairs = pairs[:max(1, len(batches))]
         kw = dict(num_samples=num_samples, memory_voxel_size=memory_voxel_size, save_voxel_size=save_voxel_size,
                   has_refine_step=has_refine_step, mask_threshold=mask_threshold, noise_seed=noise_seed, progress=progress,
-                  seed_poses=seed_poses, info_train=info_train, per_view=clouds == "per_view", gt_log=gt_log,
+                  seed_poses=seed_poses, info_train=info_train, per_view=clouds == "per_view", gt_log=gt_log, search=search,
                   on_device=(voxel_backend == "device" and num_samples > 1) or gt_log)      # where the scene memory lives
         n = len(pairs)
         wt = writer_threads if writer_threads <= 0 or n == 1 else max(1, writer_threads // n)
@@ -230,6 +291,16 @@ class Generator:
         if stats is not None:
             stats.update(pairs=sum(r[0] for r in results), writer_jobs=sum(r[1] for r in results),
                          writer_threads=sum(r[2] for r in results), lanes=n)
+        if search is not None:
+            predicted = sorted(p for r in results for p in r[3])
+            in_band = sum(1 for p in predicted if p[3])
+            if stats is not None:
+                stats["pose_search"] = dict(views=len(predicted), in_band=in_band, predicted=[p[:3] for p in predicted])
+            if predicted:
+                r = np.array([p[2] for p in predicted])
+                print("pose search: {} views, {} predicted inside [{:g}, {:g}] ({} candidates, spread {:g}); predicted overlap "
+                      "min / median / max {:.3f} / {:.3f} / {:.3f}".format(len(predicted), in_band, *search.band, search.n,
+                                                                           search.spread, r.min(), float(np.median(r)), r.max()))
 
     _pose_lock = threading.Lock()      # guards numpy's process-wide legacy stream (seed_poses=False)
 
@@ -265,13 +336,14 @@ class Generator:
 
     def _lane(self, batches, model, depth_correction, writer_threads, n_lanes, *, num_samples, memory_voxel_size,
               save_voxel_size, has_refine_step, mask_threshold, noise_seed, progress, seed_poses, info_train, stop=None,
-              on_device=False, per_view=False, gt_log=False):
+              on_device=False, per_view=False, gt_log=False, search=None):
         """One lane's share of the batches (all of them with a single lane), on the calling thread's current stream.  Per
         batch: set-up; per view: step, memory update, blocking copies, side files, clouds; then the resume marker."""
         if writer_threads <= 0 and n_lanes > 1:
             writer_threads = max(2, min(16, PP.rank_cpu_budget() // 2) // n_lanes)
         with PP.WriterPool(writer_threads) as pool:
             marker_prev, n_pairs = None, 0    # marker_prev: deferred submission of the previous batch's resume marker
+            predicted = []                    # (scene, view, predicted overlap, in band) of every searched pose
             out = _Clouds(self, pool, num_samples, save_voxel_size, per_view, gt_log)
 
             def flush_marker():
@@ -298,8 +370,11 @@ class Generator:
                 K, K_dev, _depth0, param_cond, scene_pcs = self._batch_setup(idxs, info_train, sdirs, first_files)
                 memory = DeviceMemory.upload(self.G, scene_pcs, self.device) if on_device else HostMemory(self.G, scene_pcs, self.device)
                 names = ["scene-{:0>6d}".format(i) for i in idxs]
+                source = None if search is None else self._search_source(memory, scene_pcs)
                 for sample_idx in range(num_samples):
-                    pose = self._poses(idxs, sample_idx, noise_seed if seed_poses else None)
+                    pose, found = self._view_poses(idxs, sample_idx, noise_seed if seed_poses else None, K, source, search)
+                    if found is not None:
+                        predicted += [(i, sample_idx + 1, r, ok) for i, (r, ok) in zip(idxs, found)]
                     seeds = [synthetic.noise_seed(noise_seed, i, sample_idx) for i in idxs]
                     rpj, rpj_c, images, xyz, valid = self._view(memory, pose, K, K_dev, param_cond, model, depth_correction, seeds,
                                                                 mask_threshold, has_refine_step)
@@ -325,7 +400,7 @@ class Generator:
                 flush_marker()                # (only reached with a pending marker when the sample loop did not run)
                 marker_prev = out.marker
             flush_marker()
-            return n_pairs, pool.wait(), pool.threads
+            return n_pairs, pool.wait(), pool.threads, predicted
 
     # -- gt_log: every cloud of a scene finished on the device, the scene's gt.log written with them ---------------------------
     GT_VOXEL, GT_FACTOR, GT_MIN_POINTS = 0.025, 1.5, 1000      # generate_gt's fixed literals (generate_gt.py:68-102, 133-140)

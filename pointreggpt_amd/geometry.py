@@ -86,6 +86,69 @@ def random_sample_pose(batch_size: int, center=(0, 0, 3), rng=None) -> np.ndarra
     return T.astype(np.float32)
 
 
+POSE_STREAM = 0x706F7365     # "pose": the word that keys the candidate streams apart from every other use of the seed
+POSE_Z_TOL = 0.0375          # metres behind its pixel's nearest depth a row may lie and still count as seen (the occlusion filter's)
+
+
+def pose_candidates(seed: int, scene: int, sample_idx: int, n: int, spread: float = 1.0) -> np.ndarray:
+    """`n` candidate camera motions for view `sample_idx` of scene `scene` -> (n, 4, 4) float32.  `random_sample_pose`'s
+    construction (sd:417-443: rotation about X then Y around a pivot 3 m ahead, xy jitter) with the two angle ranges (±7.5°,
+    ±15°) and the jitter's σ (1/3 m) multiplied by `spread`; spread = 1 stays inside the reference's ranges.
+    The draws come from `np.random.Generator(PCG64(SeedSequence([seed, scene, POSE_STREAM, sample_idx])))`, one stream per (scene,
+    view), in this fixed order: per candidate theta (one uniform), phi (one uniform), then three normals (the third, z's, is drawn
+    and dropped like the reference's).  So a scene's candidates depend on nothing but the four keys — not on the batch, the lane,
+    the shard or a resume — and the first k of n candidates are the k candidates of a shorter list."""
+    n = int(n)
+    if n < 1 or not (np.isfinite(spread) and spread > 0):
+        raise ValueError("pose_candidates: n >= 1 and a finite spread > 0")
+    if min(int(seed), int(scene), int(sample_idx)) < 0:
+        raise ValueError("pose_candidates: seed, scene and sample_idx must be >= 0")
+    rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), int(scene), POSE_STREAM, int(sample_idx)])))
+    theta, phi, jitter = np.empty(n), np.empty(n), np.empty((n, 3))
+    for c in range(n):
+        theta[c] = (rng.random() * (np.pi / 12) - np.pi / 24) * spread
+        phi[c] = (rng.random() * (np.pi / 6) - np.pi / 12) * spread
+        jitter[c] = rng.standard_normal(3) / 3 * spread
+    jitter[:, -1] = 0
+    rot = Rotation.from_euler("XYZ", np.stack((theta, phi, np.zeros(n)), axis=-1)).as_matrix()
+    center = np.array((0, 0, 3))
+    T = np.stack([np.eye(4) for _ in range(n)])
+    T[:, :3, :3] = rot
+    T[:, :3, 3] = center - rot @ center + jitter
+    return T.astype(np.float32)
+
+
+def select_pose_candidates(counts, rows: int, band) -> Tuple[int, float, bool]:
+    """Which of one scene's candidates to generate: counts (N,3) integers (in_frame, seen, covered) as `pose_candidate_counts`
+    returns them for the scene, rows = the rows of its source cloud, band = (lo, hi).  On the host, in float64: r_c = seen_c /
+    rows; the FIRST c in index order with lo <= r_c <= hi wins; if none is in band, the c with the smallest max(lo - r_c, r_c - hi),
+    ties to the lowest c; rows == 0 gives c = 0 (r = 0).  -> (c, r_c, in band)."""
+    lo, hi = float(band[0]), float(band[1])
+    seen = np.asarray(counts, dtype=np.int64).reshape(-1, 3)[:, 1].astype(np.float64)
+    if len(seen) < 1:
+        raise ValueError("select_pose_candidates: no candidate")
+    if int(rows) <= 0:
+        return 0, 0.0, bool(lo <= 0.0 <= hi)
+    r = seen / np.float64(rows)
+    inside = np.nonzero((r >= lo) & (r <= hi))[0]
+    if len(inside):
+        c = int(inside[0])
+        return c, float(r[c]), True
+    c = int(np.argmin(np.maximum(lo - r, r - hi)))          # argmin: the first of equal values
+    return c, float(r[c]), False
+
+
+def check_overlap_band(band) -> Tuple[float, float]:
+    """(lo, hi) of an overlap target as floats; ValueError unless 0 <= lo < hi <= 1."""
+    try:
+        lo, hi = (float(v) for v in band)
+    except (TypeError, ValueError):
+        raise ValueError("overlap must be a pair (lo, hi)") from None
+    if not 0.0 <= lo < hi <= 1.0:
+        raise ValueError("overlap must satisfy 0 <= lo < hi <= 1")
+    return lo, hi
+
+
 # ------------------------------------------------------------------------------------------------
 # device ops (HIP)
 # ------------------------------------------------------------------------------------------------
@@ -229,6 +292,54 @@ def project_cloud_buffer(pts: torch.Tensor, d_offs: torch.Tensor, poses: np.ndar
                                               _lib.ptr(mask), B, S, S, float(depth_scale), _lib.stream_ptr()),
                "prg_project_points_zbuffer")
     return depth, mask.view(torch.bool)
+
+
+def _image_hw(S) -> Tuple[int, int]:
+    """An image size as the generator passes it (one int, square) or as (H, W)."""
+    if isinstance(S, (int, np.integer)):
+        return int(S), int(S)
+    H, W = S
+    return int(H), int(W)
+
+
+def _box6(box) -> Optional[np.ndarray]:
+    """(lo, hi) -> the 6 float32 the scoring call reads on the host (lo xyz, hi xyz); None stays None."""
+    if box is None:
+        return None
+    return np.concatenate([np.asarray(box[0], dtype=np.float32).reshape(3), np.asarray(box[1], dtype=np.float32).reshape(3)])
+
+
+def pose_candidate_counts(pts: torch.Tensor, offs: torch.Tensor, poses, K, S, *, box=None, z_tol: float = POSE_Z_TOL,
+                          workspace_bytes: Optional[int] = None) -> torch.Tensor:
+    """prg_pose_candidate_counts: N candidate poses per scene scored against the scene's cloud, which already lives on the device
+    as `project_cloud_buffer` takes it (pts (rows,3) float32 ragged, offs (B+1) int64 CSR).  poses (B,N,4,4) and K (B,3,3):
+    numpy or tensors (uploaded when on the host); S: the image size, an int or (H, W); box: (lo, hi) in the TARGET camera frame or
+    None; z_tol in metres.  -> counts (B,N,3) int32 ON THE DEVICE: (in_frame, seen, covered) per candidate, bit for bit
+    `postprocess.pose_candidate_counts` (which states the definition).  The workspace is a cached torch allocation of
+    prg_pose_candidate_workspace_bytes, or of `workspace_bytes` when given (a smaller one makes the call chunk the candidates;
+    the counts are the same).  Host synchronisations: none — the caller's copy of the B*N*3 integers is the only one."""
+    lib = _lib.load()
+    if not (pts.is_cuda and offs.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    assert pts.dtype == torch.float32 and offs.dtype == torch.int64
+    dev = pts.device
+    pts, offs = pts.contiguous().view(-1, 3), offs.contiguous()
+    B = offs.numel() - 1
+    P = (poses if torch.is_tensor(poses) else torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float32))).to(dev, torch.float32)
+    Kd = (K if torch.is_tensor(K) else torch.from_numpy(np.ascontiguousarray(K, dtype=np.float32))).to(dev, torch.float32)
+    if P.dim() != 4 or P.shape[0] != B or tuple(P.shape[2:]) != (4, 4) or tuple(Kd.shape) != (B, 3, 3):
+        raise ValueError("pose_candidate_counts: poses (B,N,4,4) and K (B,3,3) for the B clouds of offs")
+    P, Kd = P.contiguous(), Kd.contiguous()
+    N = P.shape[1]
+    H, W = _image_hw(S)
+    b6 = _box6(box)
+    counts = torch.empty((B, N, 3), dtype=torch.int32, device=dev)
+    nbytes = int(lib.prg_pose_candidate_workspace_bytes(B, N, H, W)) if workspace_bytes is None else int(workspace_bytes)
+    ws = _voxel_workspace(dev, nbytes) if workspace_bytes is None else torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    _lib.check(lib.prg_pose_candidate_counts(_lib.ptr(pts), _lib.ptr(offs), _lib.ptr(P), _lib.ptr(Kd), B, N, H, W,
+                                             None if b6 is None else b6.ctypes.data, float(z_tol), _lib.ptr(counts), _lib.ptr(ws),
+                                             nbytes, _lib.stream_ptr()), "prg_pose_candidate_counts")
+    return counts
 
 
 def unproject_f64(depth: torch.Tensor, intrinsic: torch.Tensor, pose: Optional[torch.Tensor], *,

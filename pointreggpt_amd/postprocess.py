@@ -391,6 +391,94 @@ def augment_clouds_hip(clouds, *, seeds, draw: int = 0, noise: float = 0.0, limi
     return [(out[o[c]:o[c + 1]].copy(), rows[o[c]:o[c + 1]].copy()) for c in range(len(clouds))]
 
 
+def _fma32(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
+    """fmaf(a, b, c) on float32 arrays, exactly: the product of two float32 is exact in float64; its sum with c is rounded to
+    ODD there (TwoSum gives the error; an inexact even result moves one step towards the true value), and a 53-bit round-to-odd
+    value rounds to float32 like the exact one."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+    fix = np.isfinite(s) & np.isfinite(e) & (e != 0) & ((s.view(np.int64) & 1) == 0)
+    step = np.where((e > 0) == (s > 0), 1, -1).astype(np.int64)
+    s = np.where(fix, (s.view(np.int64) + step).view(np.float64), s)
+    with np.errstate(over="ignore"):
+        return s.astype(np.float32)
+
+
+def _se3_apply32(P: np.ndarray, pts: np.ndarray) -> np.ndarray:
+    """`pc @ R^T + t` as the kernels evaluate it (camera.h): per output j a float32 product, two fmaf in k order, one add."""
+    P, pts = np.asarray(P, dtype=np.float32).reshape(4, 4), np.asarray(pts, dtype=np.float32).reshape(-1, 3)
+    out = np.empty_like(pts)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for j in range(3):
+            v = pts[:, 0] * P[j, 0]
+            v = _fma32(pts[:, 1], np.broadcast_to(P[j, 1], v.shape), v)
+            v = _fma32(pts[:, 2], np.broadcast_to(P[j, 2], v.shape), v)
+            out[:, j] = v + P[j, 3]
+    return out
+
+
+def pose_candidate_counts(clouds, poses, K, S, *, box=None, z_tol: float = 0.0375, box_frame: str = "target",
+                          swap_rc: bool = False) -> np.ndarray:
+    """THE definition of prg_pose_candidate_counts / prg_cpu_pose_candidate_counts in numpy: clouds [(n_b,3) float32, ...], poses
+    (B,N,4,4) float32, K (B,3,3) float32, S the image size (an int, or (H, W)) -> counts (B,N,3) int32 = (in_frame, seen, covered)
+    per (scene, candidate).  Every row p of cloud b is moved to q = R p + t by poses[b,c] in float32 (`_se3_apply32`) and
+    projected like the z-buffer of `project_clouds`: the row is taken iff q.z > 0 (NaN fails) and col = rint(q.x*fx/q.z + cx),
+    row = rint(q.y*fy/q.z + cy) (float32 throughout, round half to even) lie in [0, W) x [0, H).
+      in_frame  the taken rows;
+      covered   the pixels with a taken row;
+      seen      the taken rows with float32 q.z <= zmin(pixel) + z_tol — zmin the smallest q.z of the pixel's taken rows, the sum
+                in float32 — and, with box = (lo, hi), lo <= q <= hi componentwise in float32: the box is tested on the MOVED
+                row, in the target camera frame, where the reference crops the target cloud (sd:2641-2650).
+    `box_frame="source"` (the box on the unmoved row) and `swap_rc` (H and W exchanged in the frame test and the pixel index) are
+    two wrong readings, kept for the tests that show a test set tells them apart."""
+    poses, K = np.asarray(poses, dtype=np.float32), np.asarray(K, dtype=np.float32)
+    H, W = (int(S), int(S)) if isinstance(S, (int, np.integer)) else (int(S[0]), int(S[1]))
+    if swap_rc:
+        H, W = W, H
+    B, N = poses.shape[0], poses.shape[1]
+    assert len(clouds) == B and poses.shape[2:] == (4, 4) and K.shape == (B, 3, 3)
+    tol = np.float32(z_tol)
+    lo = hi = None
+    if box is not None:
+        lo, hi = np.asarray(box[0], dtype=np.float32).reshape(3), np.asarray(box[1], dtype=np.float32).reshape(3)
+    counts = np.zeros((B, N, 3), dtype=np.int32)
+    for b in range(B):
+        p = np.asarray(clouds[b], dtype=np.float32).reshape(-1, 3)
+        fx, fy, cx, cy = K[b, 0, 0], K[b, 1, 1], K[b, 0, 2], K[b, 1, 2]
+        for c in range(N):
+            q = _se3_apply32(poses[b, c], p)
+            x, y, z = q[:, 0], q[:, 1], q[:, 2]
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                fc, fr = np.rint(x * fx / z + cx), np.rint(y * fy / z + cy)
+                take = (z > 0) & (fc >= 0) & (fc < np.float32(W)) & (fr >= 0) & (fr < np.float32(H))
+            pix = fr[take].astype(np.int64) * W + fc[take].astype(np.int64)
+            zt = z[take]
+            zmin = np.full(H * W, np.inf, dtype=np.float32)
+            np.minimum.at(zmin, pix, zt)
+            with np.errstate(invalid="ignore"):
+                seen = zt <= zmin[pix] + tol
+            if lo is not None:
+                r = (p if box_frame == "source" else q)[take]
+                seen &= np.all((r >= lo) & (r <= hi), axis=1)
+            counts[b, c] = (int(take.sum()), int(seen.sum()), len(np.unique(pix)))
+    return counts
+
+
+def pose_candidate_counts_hip(clouds, poses, K, S, *, box=None, z_tol: float = 0.0375, device="cuda", workspace_bytes=None):
+    """`pose_candidate_counts` for clouds that are on the host, through the kernels: the clouds uploaded once as one ragged float32
+    buffer, ONE prg_pose_candidate_counts call (`geometry.pose_candidate_counts`), one copy back -> (B,N,3) int32 numpy."""
+    from . import _lib
+    from . import geometry as G
+    _lib.load()
+    _lib.require_gpu()
+    pts, offs = G.upload_clouds([np.asarray(c, dtype=np.float32).reshape(-1, 3) for c in clouds], device)
+    return G.pose_candidate_counts(pts, offs, poses, K, S, box=box, z_tol=z_tol, workspace_bytes=workspace_bytes).cpu().numpy()
+
+
 def _check_radius_limit(radius, limit) -> None:
     if not (np.isfinite(radius) and radius > 0):
         raise ValueError("radius must be finite and > 0")

@@ -30,6 +30,11 @@ extra keys `src_idx` = s and `tgt_idx` = t; `skipped` names every dropped pair a
 augmented item of pair (s, t) draws from its own keys (`synthetic.augment_seed_pair(..., pair=(s, t))`).  With `clouds="fused"` (the
 default) and `num_samples=k` the stream yields the one fused pair per scene that `generate(num_samples=k, gt_log=True)` writes.
 
+Overlap-targeted poses: `PairStream(..., overlap=(lo, hi), pose_candidates=16, pose_spread=3.0)` chooses every view's pose as
+`generate(overlap=...)` does (`Generator._view_poses`: candidates keyed per (seed, scene, view), scored against the scene's
+source frame on the device) and adds `predicted_overlap` to every item of the scene: a tuple with the predicted share of seen
+source rows of each of its views, in view order.  With `overlap=None` (the default) nothing is scored and the key is absent.
+
 The stream runs on the calling thread's current HIP stream.  It uses no writer pool and no lanes, writes no file and creates
 nothing under the generator's `samples_folder` (the folder itself is `Generator.__init__`'s doing).
 """
@@ -110,7 +115,8 @@ class PairStream:
     def __init__(self, generator, depth_correction, *, start: int, stop: int, noise_seed: int,
                  matching_radius: Optional[float] = None, mask_threshold: float = 0.99, has_refine_step: bool = False,
                  save_voxel_size: float = 0.025, to: str = "numpy", augment: Optional[Augment] = None, epoch: int = 0,
-                 num_samples: int = 1, clouds: str = "fused", memory_voxel_size: float = 0.002):
+                 num_samples: int = 1, clouds: str = "fused", memory_voxel_size: float = 0.002, overlap=None,
+                 pose_candidates: int = 16, pose_spread: float = 3.0):
         if to not in ("numpy", "torch"):
             raise ValueError("to must be 'numpy' or 'torch'")
         if generator.device.type == "cpu":
@@ -128,6 +134,7 @@ class PairStream:
         if int(num_samples) < 1:
             raise ValueError("num_samples must be >= 1")
         self.num_samples, self.per_view, self.memory_voxel_size = int(num_samples), clouds == "per_view", memory_voxel_size
+        self.search = generator._pose_search(overlap, pose_candidates, pose_spread, int(noise_seed), True)
         self.augment, self.epoch = augment, int(epoch)
         self.generator = generator
         self.depth_correction = depth_correction
@@ -147,8 +154,12 @@ class PairStream:
         K, K_dev, _depth0, param_cond, scene_pcs = gen._batch_setup(idxs, info_train)
         memory = DeviceMemory.upload(gen.G, scene_pcs, gen.device)
         views, poses = [], []
+        source = None if self.search is None else gen._search_source(memory, scene_pcs)
+        self._predicted = [() for _ in idxs]                                                   # per scene: one ratio per view
         for sample_idx in range(self.num_samples):
-            pose = gen._poses(idxs, sample_idx, self.noise_seed)
+            pose, found = gen._view_poses(idxs, sample_idx, self.noise_seed, K, source, self.search)
+            if found is not None:
+                self._predicted = [p + (r,) for p, (r, _ok) in zip(self._predicted, found)]
             seeds = [synthetic.noise_seed(self.noise_seed, i, sample_idx) for i in idxs]
             _rpj, _rpj_c, _images, xyz, valid = gen._view(memory, pose, K, K_dev, param_cond, gen.model, self.depth_correction, seeds,
                                                           self.mask_threshold, self.has_refine_step)
@@ -235,6 +246,8 @@ class PairStream:
                             overlap_src=ratios[k][0], overlap_tgt=ratios[k][1])
                 if self.per_view:
                     item["src_idx"], item["tgt_idx"] = s, t
+                if self.search is not None:
+                    item["predicted_overlap"] = self._predicted[j]
                 if corr is not None:
                     item["corr"] = own(corr[c_offs[k]:c_offs[k + 1]])
                 if rows is not None:
