@@ -14,38 +14,15 @@
 // rows of the projection weights in registers as MFMA fragments (no LDS copy: 29-46 KB of LDS per block, several
 // blocks per CU); the LDS tiles have rows padded to C+8 / 136 / 72 bf16 so the 16 lanes of a ds_read_b128 group hit
 // distinct banks.
-// MFMA: v_mfma_f32_32x32x16_bf16, D[i][j] = sum_k A[i][k] B[k][j]; lane l supplies A[l&31][8(l>>5)..+7] and
-// B[8(l>>5)..+7][l&31] and receives D[(r&3) + 8(r>>2) + 4(l>>5)][l&31] in register r.
+// MFMA: v_mfma_f32_32x32x16_bf16; its operand and accumulator layout is attn_common.h's.
 // The LayerNorm gain of PreNorm is folded into the projection weights on the host (unet.hip).
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
-#include "blocks.h"
-#include "wave_ops.h"
+#include "attn_common.h"
 
 namespace prg {
 
 namespace {
-
-constexpr int kTP = 64;              // pixels per tile
-constexpr int kHid = 128;            // heads x dim_head
-constexpr int kTilesPerBlock = 8;
-// Linear attention: tiles per block as a function of the image size ONLY (a batch-independent slab structure keeps a
-// scene's result identical for every batch size): 8 from 64 x 64 pixels up, fewer for the small levels, whose launches
-// otherwise fill a quarter of the CUs with blocks that walk four tiles in series (16 x 16: 64 blocks -> 256).
-// (measured round 3: 16 or 32 tiles per la_ctx block 73-75 against 72 us, 4 or 16 per la_out block 105-108 against 99 us)
-constexpr int kLaCtxTpb = 8, kLaOutTpb = 8;
-__host__ __device__ inline int la_tpb(int ntiles) {             // la_kmax / la_ctx (the slab structure of the partials)
-  const int t = ntiles / 8;
-  return t < 1 ? 1 : (t > kLaCtxTpb ? kLaCtxTpb : t);
-}
-__host__ __device__ inline int la_out_tpb(int ntiles) {         // la_out (pixels are independent there: any partition)
-  const int t = ntiles / 8;
-  return t < 1 ? 1 : (t > kLaOutTpb ? kLaOutTpb : t);
-}
-constexpr int kLdO = kHid + 8;       // LDS row stride of 128-wide rows (bf16 elements)
-constexpr float kLnEps = 1e-5f;
 
 __device__ inline float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
@@ -55,13 +32,6 @@ struct Geo {
   static constexpr int VPT = C / 32;      // 16-byte vectors per thread of a 64 x C tile (4 threads per pixel row)
   static constexpr int KK = C / 16;       // MFMA k-steps over C
 };
-
-// sum over the four lanes of a quad (quad_perm [1,0,3,2] then [2,3,0,1]), every lane gets the total
-__device__ inline float quad_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  return v;
-}
 
 // ---- x tile: global -> registers -> LayerNorm -> LDS ------------------------------------------------------------
 // thread t: pixel row t >> 2, vectors (t & 3) + 4 i (interleaved so that a row's four threads read one contiguous run)
@@ -123,26 +93,6 @@ __device__ inline void stage_rows(__bf16* dst, const bf16_t* src, int nrows) {
   }
 }
 
-__device__ inline bf16x8 frag(const __bf16* rows, int ld, int l31, int hi, int kk) {
-  return *reinterpret_cast<const bf16x8*>(rows + l31 * ld + kk * 16 + hi * 8);
-}
-
-// k-step fragments of 32 rows [r0, r0 + 32) of a row-major [.][COLS] bf16 matrix, straight from global memory into
-// registers (each wave keeps its own rows for the whole block: no LDS copy, so several blocks fit on a CU)
-template <int COLS>
-__device__ inline void load_wfrags(bf16x8 (&w)[COLS / 16], const bf16_t* mat, int r0, int l31, int hi) {
-#pragma unroll
-  for (int kk = 0; kk < COLS / 16; ++kk)
-    w[kk] = *reinterpret_cast<const bf16x8*>(mat + (size_t)(r0 + l31) * COLS + kk * 16 + hi * 8);
-}
-
-__device__ inline f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.0f;
-  return z;
-}
-
 // =====================================================================================================
 // pass 1: column maxima of k per slab
 // =====================================================================================================
@@ -155,9 +105,9 @@ __global__ __launch_bounds__(256) void la_kmax_fused_kernel(const bf16_t* __rest
   const int b = blockIdx.y, slab = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int ntiles = (N + kTP - 1) / kTP;
-  const int tpb = la_tpb(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
+  const int tpb = tiles_per_block(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
   bf16x8 wk[G::KK];                                    // k rows 32 wave .. + 32 of the projection
-  load_wfrags<C>(wk, wqkv, kHid + 32 * wave, l31, hi);
+  load_wfrags<C>(wk, wqkv, kHidden + 32 * wave, l31, hi);
   float m = -INFINITY;                                 // column 32 wave + l31, this lane's pixel rows
   XTile<C> xt;
   if (t0 < t1) xt.load(x, (int64_t)b * N + (int64_t)t0 * kTP, min(kTP, N - t0 * kTP));
@@ -177,13 +127,13 @@ __global__ __launch_bounds__(256) void la_kmax_fused_kernel(const bf16_t* __rest
     for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int px = pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int px = pt * 32 + acc_row(r, hi);
         if (px < valid) m = fmaxf(m, acc[pt][r]);
       }
     __syncthreads();
   }
   m = fmaxf(m, __shfl_xor(m, 32, 64));
-  if (hi == 0) pmax[((size_t)b * nslab + slab) * kHid + 32 * wave + l31] = m;
+  if (hi == 0) pmax[((size_t)b * nslab + slab) * kHidden + 32 * wave + l31] = m;
 }
 
 // =====================================================================================================
@@ -214,14 +164,14 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_ctx_
   const int b = blockIdx.y, slab = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int ntiles = (N + kTP - 1) / kTP;
-  const int tpb = la_tpb(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
+  const int tpb = tiles_per_block(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
   bf16x8 wk[G::KK], wv[G::KK];                         // k and v rows of head `wave`
-  load_wfrags<C>(wk, wqkv, kHid + 32 * wave, l31, hi);
-  load_wfrags<C>(wv, wqkv, 2 * kHid + 32 * wave, l31, hi);
+  load_wfrags<C>(wk, wqkv, kHidden + 32 * wave, l31, hi);
+  load_wfrags<C>(wv, wqkv, 2 * kHidden + 32 * wave, l31, hi);
   f32x16 kinit0 = zero16();                            // the k accumulators' initial value: minus the column maximum
   if constexpr (!KSTAT) {
     float m = -INFINITY;                               // (fixed-order reduce of la_kmax's slab maxima)
-    for (int s2 = 0; s2 < nslab; ++s2) m = fmaxf(m, pmax[((size_t)b * nslab + s2) * kHid + 32 * wave + l31]);
+    for (int s2 = 0; s2 < nslab; ++s2) m = fmaxf(m, pmax[((size_t)b * nslab + s2) * kHidden + 32 * wave + l31]);
 #pragma unroll
     for (int e = 0; e < 16; ++e) kinit0[e] = -m;
   }
@@ -255,7 +205,7 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_ctx_
         for (int s2 = 0; s2 < 8; ++s2) {
           const int r = 8 * i + s2;
           float pe = __builtin_amdgcn_exp2f(k1[r]);
-          if constexpr (!FULL) pe = (pt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) < valid ? pe : 0.0f;
+          if constexpr (!FULL) pe = (pt * 32 + acc_row(r, hi)) < valid ? pe : 0.0f;
           if constexpr (!PSUM_MFMA) ssum += pe;
           pa[s2] = (__bf16)pe;
           vb[s2] = (__bf16)v1[r];
@@ -277,14 +227,14 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_ctx_
   if constexpr (PSUM_MFMA) {
     if (l31 == 0) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sump[ph * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] = psum[r];
+      for (int r = 0; r < 16; ++r) sump[ph * 32 + acc_row(r, hi)] = psum[r];
     }
   } else {
     ssum += __shfl_xor(ssum, 32, 64);
     if (hi == 0) sump[ph * 32 + l31] = ssum;
   }
 #pragma unroll
-  for (int r = 0; r < 16; ++r) ctxp[ph * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = ctx[r];
+  for (int r = 0; r < 16; ++r) ctxp[ph * 1024 + acc_row(r, hi) * 32 + l31] = ctx[r];
 }
 
 // =====================================================================================================
@@ -317,7 +267,7 @@ __global__ __launch_bounds__(256) void la_fin_fused_kernel(const float* __restri
       c += ctxp[(ph + s2) * 1024 + idx];
       s += sump[(ph + s2) * 32 + d];
     }
-    const int slot = (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);
+    const int slot = kslot(d);
     ctxT[((size_t)b * 4 + h) * 1024 + e * 32 + slot] = f32_to_bf16(c / s * scale);
   }
 }
@@ -352,7 +302,7 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
   const int b = blockIdx.y, slab = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int ntiles = (N + kTP - 1) / kTP;
-  const int tpb = la_out_tpb(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
+  const int tpb = tiles_per_block(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
   bf16x8 wq[G::KK];                                    // q rows of head `wave`
   load_wfrags<C>(wq, wqkv, 32 * wave, l31, hi);
   // ctx^T rows e = l31 of head `wave`; k-slot s of half hi in k-step i is d = 16 i + 8 (s >> 2) + 4 hi + (s & 3):
@@ -365,13 +315,12 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
   int yrt[NA], ypt[NA];
 #pragma unroll
   for (int a = 0; a < NA; ++a) {
-    if (RT == 2) { yrt[a] = wave & 1; ypt[a] = wave >> 1; }
-    else if (RT <= 4) { yrt[a] = wave; ypt[a] = a; }
-    else { yrt[a] = wave * NR + (a >> 1); ypt[a] = a & 1; }
+    yrt[a] = y_row_tile<RT>(wave, a);
+    ypt[a] = y_pix_tile<RT>(wave, a);
   }
-  bf16x8 wo[NR][kHid / 16];                            // to_out rows of this wave's y row tile(s)
+  bf16x8 wo[NR][kHidden / 16];                            // to_out rows of this wave's y row tile(s)
 #pragma unroll
-  for (int r = 0; r < NR; ++r) load_wfrags<kHid>(wo[r], wout, yrt[RT > 4 ? 2 * r : 0] * 32, l31, hi);
+  for (int r = 0; r < NR; ++r) load_wfrags<kHidden>(wo[r], wout, yrt[RT > 4 ? 2 * r : 0] * 32, l31, hi);
   XTile<C> xt;
   if (t0 < t1) xt.load(x, (int64_t)b * N + (int64_t)t0 * kTP, min(kTP, N - t0 * kTP));
   for (int t = t0; t < t1; ++t) {
@@ -456,7 +405,7 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
 #pragma unroll
     for (int a = 0; a < NA; ++a) ya[a] = zero16();
 #pragma unroll
-    for (int kk = 0; kk < kHid / 16; ++kk) {
+    for (int kk = 0; kk < kHidden / 16; ++kk) {
 #pragma unroll
       for (int a = 0; a < NA; ++a)
         ya[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wo[RT > 4 ? (a >> 1) : 0][kk],
@@ -467,7 +416,7 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
       float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int c = yrt[a] * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int c = yrt[a] * 32 + acc_row(r, hi);
         ya[a][r] += bias_l[c];
         s1 += ya[a][r];
         s2 = fmaf(ya[a][r], ya[a][r], s2);
@@ -527,21 +476,16 @@ __global__ __launch_bounds__(256, C == 64 ? 3 : (C == 128 ? 2 : 1)) void la_out_
 // K goes to LDS row-major, V transposed with the keys of each 32-key tile stored in the order the S^T accumulator
 // registers supply them as the B operand (same trick as la_out): no shuffle between the two MFMAs.
 // =====================================================================================================
-template <int NT>   // key tiles of 32 (N = 32 NT)
-__global__ __launch_bounds__(256) void full_attn_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out) {
-  constexpr int N = 32 * NT, LDK = 40, LDV = N + 8;
-  __shared__ __attribute__((aligned(16))) __bf16 Ks[N * LDK];
-  __shared__ __attribute__((aligned(16))) __bf16 Vt[32 * LDV];
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-  const bf16_t* base = qkv + (size_t)b * N * 384;
-  for (int i = tid; i < N * 4; i += 256) {
+// ---- what the two kernels of the core share ----
+// K and V^T of one (image, head) into LDS (all 256 threads): K row-major [N][LDK]; V^T [32][LDV], each 32-key tile in k-slot order
+template <int N, int LDK, int LDV>
+__device__ inline void stage_kv(__bf16* Ks, __bf16* Vt, const bf16_t* base, int h) {
+  for (int i = threadIdx.x; i < N * 4; i += 256) {
     const int key = i >> 2, u = i & 3;
     *reinterpret_cast<uint4*>(Ks + key * LDK + u * 8) =
-        *reinterpret_cast<const uint4*>(base + (size_t)key * 384 + 128 + h * 32 + u * 8);
-    const uint4 vv = *reinterpret_cast<const uint4*>(base + (size_t)key * 384 + 256 + h * 32 + u * 8);
-    const int d = key & 31;
-    const int pos = (key & ~31) + (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);
+        *reinterpret_cast<const uint4*>(base + (size_t)key * 3 * kHidden + kHidden + h * kDimHead + u * 8);
+    const uint4 vv = *reinterpret_cast<const uint4*>(base + (size_t)key * 3 * kHidden + 2 * kHidden + h * kDimHead + u * 8);
+    const int pos = (key & ~31) + kslot(key & 31);
     const uint32_t w[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -549,17 +493,43 @@ __global__ __launch_bounds__(256) void full_attn_mfma_kernel(const bf16_t* __res
       reinterpret_cast<uint16_t*>(Vt)[(u * 8 + 2 * j + 1) * LDV + pos] = (uint16_t)(w[j] >> 16);
     }
   }
+}
+// S^T of key tile kt (keys as rows) against the lane's query, whose two k-step fragments are q0 and q1; unscaled
+template <int LDK>
+__device__ inline f32x16 score_tile(const __bf16* Ks, int kt, const bf16x8& q0, const bf16x8& q1, int l31, int hi) {
+  f32x16 sa = zero16();
+  sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 0), q0, sa, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 1), q1, sa, 0, 0, 0);
+}
+// O^T / l of the lane's query: channels 8 g4 + {0..3} from op on (op already points at the head's 4 hi)
+__device__ inline void store_out(bf16_t* op, const f32x16& oacc, float inv) {
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    uint2 w;
+    w.x = pack_bf16(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
+    w.y = pack_bf16(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
+    *reinterpret_cast<uint2*>(op + 8 * g4) = w;
+  }
+}
+
+template <int NT>   // key tiles of 32 (N = 32 NT)
+__global__ __launch_bounds__(256) void full_attn_mfma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out) {
+  constexpr int N = 32 * NT, LDK = 40, LDV = N + 8;
+  __shared__ __attribute__((aligned(16))) __bf16 Ks[N * LDK];
+  __shared__ __attribute__((aligned(16))) __bf16 Vt[32 * LDV];
+  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
+  const bf16_t* base = qkv + (size_t)b * N * 3 * kHidden;
+  stage_kv<N, LDK, LDV>(Ks, Vt, base, h);
   __syncthreads();
   for (int qt = wave; qt < NT; qt += 4) {
-    const bf16_t* qp = base + (size_t)(qt * 32 + l31) * 384 + h * 32 + hi * 8;
+    const bf16_t* qp = base + (size_t)(qt * 32 + l31) * 3 * kHidden + h * kDimHead + hi * 8;
     const bf16x8 q0 = *reinterpret_cast<const bf16x8*>(qp), q1 = *reinterpret_cast<const bf16x8*>(qp + 16);
     f32x16 sacc[NT];
     float m = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) {
-      sacc[kt] = zero16();
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 0), q0, sacc[kt], 0, 0, 0);
-      sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 1), q1, sacc[kt], 0, 0, 0);
+      sacc[kt] = score_tile<LDK>(Ks, kt, q0, q1, l31, hi);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         sacc[kt][r] *= 0.17677669529663687f;
@@ -580,20 +550,12 @@ __global__ __launch_bounds__(256) void full_attn_mfma_kernel(const bf16_t* __res
           l += pv;
           pb[s2] = (__bf16)pv;
         }
-        oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(Vt + l31 * LDV + kt * 32 + i * 16 + hi * 8), pb, oacc, 0, 0, 0);
+        oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Vt + kt * 32, LDV, l31, hi, i), pb, oacc, 0, 0, 0);
       }
     }
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
-    bf16_t* op = out + ((size_t)b * N + qt * 32 + l31) * 128 + h * 32 + 4 * hi;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      uint2 w;
-      w.x = pack_bf16(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
-      w.y = pack_bf16(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
-      *reinterpret_cast<uint2*>(op + 8 * g4) = w;
-    }
+    store_out(out + ((size_t)b * N + qt * 32 + l31) * kHidden + h * kDimHead + 4 * hi, oacc, inv);
   }
 }
 
@@ -611,31 +573,16 @@ __global__ __launch_bounds__(256) void full_attn_mfma_big_kernel(const bf16_t* _
   __bf16* Vt = Ks + N * LDK;                                    // [32][LDV]
   const int h = blockIdx.x, b = blockIdx.y, qs = blockIdx.z, tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-  const bf16_t* base = qkv + (size_t)b * N * 384;
-  for (int i = tid; i < N * 4; i += 256) {
-    const int key = i >> 2, u = i & 3;
-    *reinterpret_cast<uint4*>(Ks + key * LDK + u * 8) =
-        *reinterpret_cast<const uint4*>(base + (size_t)key * 384 + 128 + h * 32 + u * 8);
-    const uint4 vv = *reinterpret_cast<const uint4*>(base + (size_t)key * 384 + 256 + h * 32 + u * 8);
-    const int d = key & 31;
-    const int pos = (key & ~31) + (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);
-    const uint32_t w[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      reinterpret_cast<uint16_t*>(Vt)[(u * 8 + 2 * j) * LDV + pos] = (uint16_t)(w[j] & 0xffffu);
-      reinterpret_cast<uint16_t*>(Vt)[(u * 8 + 2 * j + 1) * LDV + pos] = (uint16_t)(w[j] >> 16);
-    }
-  }
+  const bf16_t* base = qkv + (size_t)b * N * 3 * kHidden;
+  stage_kv<N, LDK, LDV>(Ks, Vt, base, h);
   __syncthreads();
   for (int qt = qs * 4 + wave; qt < NT; qt += 4 * QS) {
-    const bf16_t* qp = base + (size_t)(qt * 32 + l31) * 384 + h * 32 + hi * 8;
+    const bf16_t* qp = base + (size_t)(qt * 32 + l31) * 3 * kHidden + h * kDimHead + hi * 8;
     const bf16x8 q0 = *reinterpret_cast<const bf16x8*>(qp), q1 = *reinterpret_cast<const bf16x8*>(qp + 16);
     float m = -INFINITY;
 #pragma unroll 2
     for (int kt = 0; kt < NT; ++kt) {
-      f32x16 sa = zero16();
-      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 0), q0, sa, 0, 0, 0);
-      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 1), q1, sa, 0, 0, 0);
+      const f32x16 sa = score_tile<LDK>(Ks, kt, q0, q1, l31, hi);
 #pragma unroll
       for (int r = 0; r < 16; ++r) m = fmaxf(m, sa[r] * 0.17677669529663687f);
     }
@@ -644,9 +591,7 @@ __global__ __launch_bounds__(256) void full_attn_mfma_big_kernel(const bf16_t* _
     f32x16 oacc = zero16();
 #pragma unroll 2
     for (int kt = 0; kt < NT; ++kt) {
-      f32x16 sa = zero16();
-      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 0), q0, sa, 0, 0, 0);
-      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Ks + kt * 32 * LDK, LDK, l31, hi, 1), q1, sa, 0, 0, 0);
+      const f32x16 sa = score_tile<LDK>(Ks, kt, q0, q1, l31, hi);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         bf16x8 pb;
@@ -656,20 +601,12 @@ __global__ __launch_bounds__(256) void full_attn_mfma_big_kernel(const bf16_t* _
           l += pv;
           pb[s2] = (__bf16)pv;
         }
-        oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(Vt + l31 * LDV + kt * 32 + i * 16 + hi * 8), pb, oacc, 0, 0, 0);
+        oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag(Vt + kt * 32, LDV, l31, hi, i), pb, oacc, 0, 0, 0);
       }
     }
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;
-    bf16_t* op = out + ((size_t)b * N + qt * 32 + l31) * 128 + h * 32 + 4 * hi;
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      uint2 w;
-      w.x = pack_bf16(oacc[4 * g4] * inv, oacc[4 * g4 + 1] * inv);
-      w.y = pack_bf16(oacc[4 * g4 + 2] * inv, oacc[4 * g4 + 3] * inv);
-      *reinterpret_cast<uint2*>(op + 8 * g4) = w;
-    }
+    store_out(out + ((size_t)b * N + qt * 32 + l31) * kHidden + h * kDimHead + 4 * hi, oacc, inv);
   }
 }
 
@@ -677,187 +614,6 @@ template <int C>
 size_t lds_kmax() { return (size_t)kTP * Geo<C>::LDW * 2; }
 template <int C>
 size_t lds_out() { return (size_t)2 * kTP * Geo<C>::LDW * 2 + (size_t)kTP * kLdO * 2 + (size_t)kTP * (C / 32 > 4 ? C / 32 : 4) * 2 * 4 + (size_t)2 * C * 4; }
-
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return fail(PRG_E_HIP, std::string("hipFuncSetAttribute(fused attention): ") + hipGetErrorString(e));
-  return PRG_OK;
-}
-
-int la_slabs(int N) { const int nt = ceil_div(N, kTP); return ceil_div(nt, la_tpb(nt)); }
-int tail_slabs(int N) { return ceil_div(ceil_div(N, kTP), kTilesPerBlock); }
-
-// =====================================================================================================
-// ResnetBlock tail with the 1x1 res_conv folded in (sd:731-734):
-//   out = SiLU(h * A[b][c] + Bc[b][c]) + Wres . cat[s0, s1] + bres          (A, Bc: GroupNorm folded by gn_coeff)
-// Unfused this is a 1x1 conv launch (reads both sources, writes res) plus the flat pass (reads h and res, writes out);
-// fused, res never exists in HBM: -268 MB per level-0 block.  64-pixel tiles; the source tile and the h tile go
-// through LDS (coalesced 16-byte global accesses on both sides), Wres lives in registers as MFMA fragments, the
-// accumulator has pixels as columns so a lane owns four consecutive channels of one pixel.
-// Reads in flight: two register sets per block (tiles t+1 and t+2 while tile t is worked on) and the per-channel
-// coefficients in LDS instead of 48 registers per lane: 148 / 210 / 250 VGPRs, 3 / 2 / 2 blocks per CU, 144 / 160 / 192 KB
-// of tile reads in flight per CU for <128,64> / <192,128> / <256,128> (one set and the coefficients in registers: 48 / 80 /
-// 96 KB).  Measured: the launches do not get faster for it; only the head launch does, by its weights in LDS.
-// =====================================================================================================
-constexpr int kTailDepth = 2;        // register sets of a tail block = tiles of reads in flight per block
-template <int CIN, int COUT>
-__global__ __launch_bounds__(256, COUT == 64 ? 3 : 2) void resblock_tail_fused_kernel(
-    const bf16_t* __restrict__ h, const float* __restrict__ A, const float* __restrict__ Bc, const bf16_t* __restrict__ s0, int C0,
-    const bf16_t* __restrict__ s1, int C1, const bf16_t* __restrict__ wres, const float* __restrict__ bres, bf16_t* __restrict__ out,
-    int N, const float* __restrict__ head_w, const float* __restrict__ head_b, float* __restrict__ head_out, int head_sigmoid,
-    const GnFold fold) {
-  constexpr int LDX = CIN + 8, LDH = COUT + 8;
-  constexpr int RT = COUT / 32, NA = RT / 2;          // row tiles of 32 channels; accumulators per wave
-  constexpr int XV = CIN / 32, HV = COUT / 32;        // 16-byte vectors per thread of the source / h tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* xs = reinterpret_cast<__bf16*>(smem);       // [64][LDX]
-  __bf16* hs = xs + kTP * LDX;                        // [64][LDH]
-  float* cf = reinterpret_cast<float*>(hs + kTP * LDH);   // [4][COUT]: A | Bc | bres of this image | head_w
-  const int b = blockIdx.y, slab = blockIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
-  const int row = threadIdx.x >> 2, part = threadIdx.x & 3;
-  const int ntiles = (N + kTP - 1) / kTP;
-  const int t0 = slab * kTilesPerBlock, t1 = min(t0 + kTilesPerBlock, ntiles);
-  const int yrt = RT == 2 ? (wave & 1) : wave;
-  int ypt[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a) ypt[a] = RT == 2 ? (wave >> 1) : a;
-  bf16x8 wr[CIN / 16];
-  load_wfrags<CIN>(wr, wres, yrt * 32, l31, hi);
-  // The image's coefficients, one channel per thread, once per block into LDS (48 registers per lane as quads: the
-  // third wave per SIMD); barrier (1) of the first tile publishes them.  Per channel the same operations as a handle's
-  // gn_coeff pass: the GroupNorm fold from the image's fixed-point statistics, or the A / Bc tables.
-  if (threadIdx.x < COUT) {
-    const int c = threadIdx.x;
-    float a, bb;
-    if (fold.acc) {
-      float mean, rstd;
-      gn_fold_stats(fold, b, c / fold.cpg, mean, rstd);
-      a = rstd * fold.P[(size_t)b * fold.pq_stride + c];
-      bb = fmaf(-mean, a, fold.Q[(size_t)b * fold.pq_stride + c]);
-    } else {
-      a = A[(size_t)b * COUT + c];
-      bb = Bc[(size_t)b * COUT + c];
-    }
-    cf[c] = a;
-    cf[COUT + c] = bb;
-    cf[2 * COUT + c] = bres[c];
-    if (head_out) cf[3 * COUT + c] = head_w[c];        // (a global load inside the loop would wait for the tiles in flight)
-  }
-  const float hb = head_out ? head_b[0] : 0.0f;
-  // Two register sets: while tile t is worked on, tiles t+1 and t+2 are on their way (two tiles of reads in flight per
-  // block).  h of a later tile is never written before this block has read it: a block writes only its own tiles, after
-  // reading them, so `out` may be `h`.
-  struct Tile { u32x4 x[XV], h[HV]; };
-  Tile ta, tb;
-  // Every load is issued for every lane, so that the waits on a register set stay counted (a load under a branch makes the
-  // compiler drain the whole queue): rows past the image's or the block's last pixel re-read that pixel (one line per
-  // wave; their columns of the MFMA and their LDS rows are never stored).
-  const int plast = min(t1 * kTP, N) - 1;
-  auto load_tile = [&](Tile& T, int t) {
-    const int64_t pix = (int64_t)b * N + min(t * kTP + row, plast);
-#pragma unroll
-    for (int i = 0; i < XV; ++i) {
-      const int c = (part + 4 * i) * 8;
-      const bf16_t* p = c < C0 ? s0 + pix * C0 + c : s1 + pix * C1 + (c - C0);
-      T.x[i] = *reinterpret_cast<const u32x4*>(p);
-    }
-#pragma unroll
-    for (int i = 0; i < HV; ++i) T.h[i] = *reinterpret_cast<const u32x4*>(h + pix * COUT + (part + 4 * i) * 8);
-  };
-  auto do_tile = [&](Tile& T, int t) {
-    const int valid = t < t1 ? min(kTP, N - t * kTP) : 0;
-#pragma unroll
-    for (int i = 0; i < XV; ++i) *reinterpret_cast<u32x4*>(xs + row * LDX + (part + 4 * i) * 8) = T.x[i];
-#pragma unroll
-    for (int i = 0; i < HV; ++i) *reinterpret_cast<u32x4*>(hs + row * LDH + (part + 4 * i) * 8) = T.h[i];
-    __syncthreads();                                                                            // (1) tiles staged
-    load_tile(T, t + kTailDepth);
-    // this lane's 16 channels: yrt*32 + 8 g4 + 4 hi + {0..3}; one 32-pixel half after the other (16 accumulators live)
-#pragma unroll
-    for (int a = 0; a < NA; ++a) {
-      f32x16 ya = zero16();
-#pragma unroll
-      for (int kk = 0; kk < CIN / 16; ++kk)
-        ya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[kk], frag(xs + ypt[a] * 32 * LDX, LDX, l31, hi, kk), ya, 0, 0, 0);
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int c0 = yrt * 32 + 8 * g4 + 4 * hi;
-        const float4 ca = *reinterpret_cast<const float4*>(cf + c0);
-        const float4 cb = *reinterpret_cast<const float4*>(cf + COUT + c0);
-        const float4 cr = *reinterpret_cast<const float4*>(cf + 2 * COUT + c0);
-        const float a4[4] = {ca.x, ca.y, ca.z, ca.w};
-        const float b4[4] = {cb.x, cb.y, cb.z, cb.w};
-        const float r4[4] = {cr.x, cr.y, cr.z, cr.w};
-        __bf16* hp = hs + (ypt[a] * 32 + l31) * LDH + c0;
-        const uint2 hw = *reinterpret_cast<const uint2*>(hp);
-        const float hx[4] = {bf_lo(hw.x), bf_hi(hw.x), bf_lo(hw.y), bf_hi(hw.y)};
-        float y[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = Elem<bf16_t>::silu(fmaf(hx[j], a4[j], b4[j])) + (ya[4 * g4 + j] + r4[j]);
-        uint2 w;
-        w.x = pack_bf16(y[0], y[1]);
-        w.y = pack_bf16(y[2], y[3]);
-        *reinterpret_cast<uint2*>(hp) = w;            // each (pixel, channel quad) is owned by exactly one lane
-      }
-    }
-    __syncthreads();                                                                            // (2) out tile in hs
-    if (head_out) {
-      // the network's last layer (1x1 conv to one channel) on the tile: four lanes share a pixel's channels
-      float acc = 0.0f;
-#pragma unroll
-      for (int i = 0; i < HV; ++i) {
-        const uint4 v = *reinterpret_cast<const uint4*>(hs + row * LDH + (part + 4 * i) * 8);
-        const float* w = cf + 3 * COUT + (part + 4 * i) * 8;
-        const uint32_t q[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc = fmaf(bf_lo(q[j]), w[2 * j], acc);
-          acc = fmaf(bf_hi(q[j]), w[2 * j + 1], acc);
-        }
-      }
-      acc += __shfl_xor(acc, 1, 64);
-      acc += __shfl_xor(acc, 2, 64);
-      if (part == 0 && row < valid) {
-        const float y = acc + hb;
-        head_out[(int64_t)b * N + (int64_t)t * kTP + row] = head_sigmoid ? 1.0f / (1.0f + expf(-y)) : y;
-      }
-    } else if (row < valid) {
-#pragma unroll
-      for (int i = 0; i < HV; ++i)
-        *reinterpret_cast<uint4*>(out + ((int64_t)b * N + (int64_t)t * kTP + row) * COUT + (part + 4 * i) * 8) =
-            *reinterpret_cast<const uint4*>(hs + row * LDH + (part + 4 * i) * 8);
-    }
-    __syncthreads();                                                                            // (3) tiles free
-  };
-  load_tile(ta, t0);
-  load_tile(tb, t0 + 1);
-  // (one back edge and no exit between the two halves, so that the compiler's waits stay counted: with an odd number of
-  // tiles the second half runs once on a tile past the block's last one and stores nothing)
-  for (int t = t0; t < t1; t += kTailDepth) {
-    do_tile(ta, t);
-    do_tile(tb, t + 1);
-  }
-}
-
-template <int CIN, int COUT>
-int launch_tail(const bf16_t* h, const float* A, const float* Bc, const bf16_t* s0, int C0, const bf16_t* s1, int C1,
-                const bf16_t* wres, const float* bres, bf16_t* out, int B, int N, hipStream_t s, const GnFold& fold,
-                const float* head_w = nullptr, const float* head_b = nullptr, float* head_out = nullptr, int head_sigmoid = 0) {
-  const size_t lds = (size_t)kTP * (CIN + 8 + COUT + 8) * 2 + (size_t)4 * COUT * 4;
-  static DeviceOnce attr;   // one-time opt-in; atomic: lanes launch from several host threads (idempotent call)
-  if (!attr.done()) {
-    int rc = set_lds(&resblock_tail_fused_kernel<CIN, COUT>, lds);
-    if (rc) return rc;
-    attr.mark();
-  }
-  resblock_tail_fused_kernel<CIN, COUT><<<dim3(tail_slabs(N), B), 256, lds, s>>>(h, A, Bc, s0, C0, s1, C1, wres, bres, out, N, head_w, head_b,
-                                                                                 head_out, head_sigmoid, fold);
-  PRG_LAUNCH_CHECK();
-  return PRG_OK;
-}
-
 
 template <int C>
 constexpr bool kPsumDefault = C >= 128;   // (measured: C = 64 58 against 70 us with it, C = 128 21.4 against 22.8, C = 256 23.7 against 25.6)
@@ -877,9 +633,9 @@ int launch_c(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const floa
     if ((rc = set_lds(&la_out_fused_kernel<C, true>, lds_out<C>()))) return rc;
     attr.mark();
   }
-  const int nslab = la_slabs(N);
+  const int nslab = slabs(N);
   float* pmax = ws;
-  float* ctxp = pmax + (size_t)B * nslab * kHid;
+  float* ctxp = pmax + (size_t)B * nslab * kHidden;
   float* sump = ctxp + (size_t)B * 4 * nslab * 1024;
   bf16_t* ctxT = reinterpret_cast<bf16_t*>(sump + (size_t)B * 4 * nslab * 32);
   const dim3 grid(nslab, B);
@@ -891,17 +647,16 @@ int launch_c(const bf16_t* x, const bf16_t* wqkv, const bf16_t* wout, const floa
   static const int psum_env = env_int("PRG_LA_PSUM", -1);
   const int psum_sel = psum_override >= 0 ? psum_override : psum_env;
   const bool psum = psum_sel > 0 || (psum_sel < 0 && kPsumDefault<C>);
-#define PRG_LA_CTX_GO(PS, KS) la_ctx_fused_kernel<C, PS, KS><<<grid, 256, lds_kmax<C>(), s>>>(x, wqkv, pmax, ctxp, sump, N, nslab)
-  if (kshift) { if (psum) PRG_LA_CTX_GO(true, true); else PRG_LA_CTX_GO(false, true); }
-  else { if (psum) PRG_LA_CTX_GO(true, false); else PRG_LA_CTX_GO(false, false); }
-#undef PRG_LA_CTX_GO
+  const auto la_ctx = kshift ? (psum ? &la_ctx_fused_kernel<C, true, true> : &la_ctx_fused_kernel<C, false, true>)
+                             : (psum ? &la_ctx_fused_kernel<C, true, false> : &la_ctx_fused_kernel<C, false, false>);
+  la_ctx<<<grid, 256, lds_kmax<C>(), s>>>(x, wqkv, pmax, ctxp, sump, N, nslab);
   PRG_LAUNCH_CHECK();
   la_fin_fused_kernel<<<dim3(4, B), 256, 0, s>>>(ctxp, sump, ctxT, N, nslab);
   PRG_LAUNCH_CHECK();
   // (the q shifts of the four heads follow the 128 k shifts)
   const int nt = ceil_div(N, kTP);
-  const dim3 ogrid(ceil_div(nt, la_out_tpb(nt)), B);
-  if (kshift) la_out_fused_kernel<C, true><<<ogrid, 256, lds_out<C>(), s>>>(x, wqkv, wout, bias, out_g, ctxT, out, N, kshift + kHid);
+  const dim3 ogrid(ceil_div(nt, tiles_per_block(nt)), B);
+  if (kshift) la_out_fused_kernel<C, true><<<ogrid, 256, lds_out<C>(), s>>>(x, wqkv, wout, bias, out_g, ctxT, out, N, kshift + kHidden);
   else la_out_fused_kernel<C, false><<<ogrid, 256, lds_out<C>(), s>>>(x, wqkv, wout, bias, out_g, ctxT, out, N, nullptr);
   PRG_LAUNCH_CHECK();
   return PRG_OK;
@@ -939,35 +694,11 @@ int launch_full_attention_mfma(const bf16_t* qkv, bf16_t* out, int B, int N, hip
   return PRG_OK;
 }
 
-bool resblock_tail_fused_supported(int C0, int C1, int Cout) {
-  const int cin = C0 + C1;
-  return C0 % 8 == 0 && C1 % 8 == 0 && ((cin == 128 && Cout == 64) || (cin == 192 && Cout == 128) || (cin == 256 && Cout == 128));
-}
-
-// out (B, N, Cout) <- SiLU(h * A + Bc) + wres [Cout][C0+C1] . cat[s0 (B,N,C0), s1 (B,N,C1)] + bres.  out may alias h.
-int launch_resblock_tail_fused(const bf16_t* h, const float* A, const float* Bc, const bf16_t* s0, int C0, const bf16_t* s1,
-                               int C1, const bf16_t* wres, const float* bres, bf16_t* out, int B, int N, int Cout,
-                               hipStream_t s,
-                               const float* head_w, const float* head_b, float* head_out, int head_sigmoid, const GnFold* fold) {
-  PRG_CHECK(resblock_tail_fused_supported(C0, C1, Cout) && bres, "fused resblock tail: unsupported shape");
-  PRG_CHECK(!head_out || (Cout == 64 && head_w && head_b), "fused resblock tail: the head needs Cout = 64");
-  GnFold f{};
-  if (fold && fold->acc) {
-    f = *fold;
-    PRG_CHECK(f.cpg % 4 == 0 && f.G * f.cpg == Cout && f.P && f.Q, "fused resblock tail: bad GroupNorm fold");
-  } else {
-    PRG_CHECK(A && Bc, "fused resblock tail: no coefficients");
-  }
-  if (Cout == 64) return launch_tail<128, 64>(h, A, Bc, s0, C0, s1, C1, wres, bres, out, B, N, s, f, head_w, head_b, head_out, head_sigmoid);
-  if (C0 + C1 == 192) return launch_tail<192, 128>(h, A, Bc, s0, C0, s1, C1, wres, bres, out, B, N, s, f);   // up level 2
-  return launch_tail<256, 128>(h, A, Bc, s0, C0, s1, C1, wres, bres, out, B, N, s, f);
-}
-
 bool linattn_fused_supported(int C) { return C == 64 || C == 128 || C == 256; }
 
 size_t linattn_fused_ws_floats(int B, int N) {
-  const size_t ns = la_slabs(N);
-  return (size_t)B * ns * kHid + (size_t)B * 4 * ns * 1024 + (size_t)B * 4 * ns * 32 + (size_t)B * 4 * 1024 / 2 + 64;
+  const size_t ns = slabs(N);
+  return (size_t)B * ns * kHidden + (size_t)B * 4 * ns * 1024 + (size_t)B * 4 * ns * 32 + (size_t)B * 4 * 1024 / 2 + 64;
 }
 
 // x, out: (B, N, C) bf16.  wqkv: [384][C] with the PreNorm gain folded in (q | k | v rows, head-major); wout: [C][128].
@@ -975,7 +706,7 @@ int launch_linear_attention_fused(const bf16_t* x, const bf16_t* wqkv, const bf1
                                   const float* out_g, bf16_t* out, float* ws, int B, int N, int C, const float* kshift,
                                   hipStream_t s, int psum_override) {
   PRG_CHECK(linattn_fused_supported(C), "fused linear attention: unsupported width");
-  PRG_CHECK(la_slabs(N) <= 4096, "fused linear attention: too many slabs");
+  PRG_CHECK(slabs(N) <= 4096, "fused linear attention: too many slabs");
   if (C == 64) return launch_c<64>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);
   if (C == 256) return launch_c<256>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);
   return launch_c<128>(x, wqkv, wout, bias, out_g, out, ws, B, N, kshift, s, psum_override);

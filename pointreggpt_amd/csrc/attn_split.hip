@@ -14,13 +14,8 @@
 // then drop is below 2^-22 of the largest term of the sum it enters.
 // The unfused float32 path (blocks.hip) moves ~7 GB per level-0 instance at B = 64 (LayerNorm out, the 384-channel qkv tensor
 // written once and read three times, ...): 2.0 ms; this file reads x four times and writes it once.
-// MFMA: v_mfma_f32_32x32x16_f16, D[i][j] = sum_k A[i][k] B[k][j]; lane l supplies A[l&31][8(l>>5)..+7] and
-// B[8(l>>5)..+7][l&31] and receives D[(r&3) + 8(r>>2) + 4(l>>5)][l&31] in register r.
-#include <atomic>
-#include <cstdlib>
-
-#include "blocks.h"
-#include "wave_ops.h"
+// MFMA: v_mfma_f32_32x32x16_f16; its operand and accumulator layout is attn_common.h's.
+#include "attn_common.h"
 
 namespace prg {
 
@@ -29,27 +24,6 @@ namespace {
 typedef f16x8 h8;
 typedef __attribute__((ext_vector_type(4))) _Float16 h4;
 
-constexpr int kTP = 64;              // pixels per tile
-constexpr int kHid = 128;            // heads x dim_head
-constexpr int kLdO = kHid + 8;       // LDS row stride of the 128-wide attention-output rows (halves)
-constexpr float kLnEps = 1e-5f;
-
-__host__ __device__ inline int sp_tpb(int ntiles) {      // tiles per block: a function of the image size only (batch-independent slabs)
-  const int t = ntiles / 8;
-  return t < 1 ? 1 : (t > 8 ? 8 : t);
-}
-
-__device__ inline f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) z[e] = 0.0f;
-  return z;
-}
-__device__ inline float quad_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  return v;
-}
 // acc += A B with both operands split: the two cross terms first (small), then hi * hi
 __device__ inline f32x16 mma3(const h8& ah, const h8& al, const h8& bh, const h8& bl, f32x16 c) {
   c = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, c, 0, 0, 0);
@@ -119,17 +93,6 @@ struct XTileF {
   }
 };
 
-__device__ inline h8 frag(const _Float16* rows, int ld, int l31, int hi, int kk) {
-  return *reinterpret_cast<const h8*>(rows + l31 * ld + kk * 16 + hi * 8);
-}
-// k-step fragments of rows [r0, r0 + 32) of a row-major [.][COLS] f16 matrix, global -> registers (kept for the whole block)
-template <int COLS>
-__device__ inline void load_wfrags(h8 (&w)[COLS / 16], const uint16_t* mat, int r0, int l31, int hi) {
-#pragma unroll
-  for (int kk = 0; kk < COLS / 16; ++kk)
-    w[kk] = *reinterpret_cast<const h8*>(mat + (size_t)(r0 + l31) * COLS + kk * 16 + hi * 8);
-}
-
 // =====================================================================================================
 // la_ctx: per slab (column maxima of k, sums of p = exp2(k - max), p^T v)
 // =====================================================================================================
@@ -152,12 +115,12 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_ctx_split_kernel(cons
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   float* const scw = reinterpret_cast<float*>(xl + kTP * G::LDW) + 32 * wave;   // ONLINE: this wave's 32 rescale factors
   const int ntiles = N / kTP;
-  const int tpb = sp_tpb(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
+  const int tpb = tiles_per_block(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
   h8 wkh[G::KK], wkl[G::KK], wvh[G::KK], wvl[G::KK];     // k and v rows of head `wave`
-  load_wfrags<C>(wkh, wqkv_h, kHid + 32 * wave, l31, hi);
-  load_wfrags<C>(wkl, wqkv_l, kHid + 32 * wave, l31, hi);
-  load_wfrags<C>(wvh, wqkv_h, 2 * kHid + 32 * wave, l31, hi);
-  load_wfrags<C>(wvl, wqkv_l, 2 * kHid + 32 * wave, l31, hi);
+  load_wfrags<C>(wkh, wqkv_h, kHidden + 32 * wave, l31, hi);
+  load_wfrags<C>(wkl, wqkv_l, kHidden + 32 * wave, l31, hi);
+  load_wfrags<C>(wvh, wqkv_h, 2 * kHidden + 32 * wave, l31, hi);
+  load_wfrags<C>(wvl, wqkv_l, 2 * kHidden + 32 * wave, l31, hi);
   XTileF<C> xt;
   float m = -INFINITY;                                 // maximum of column d = 32 wave + l31 of k (log2 units: the rows carry log2 e)
   if (t0 < t1) xt.load(x, (int64_t)b * N + (int64_t)t0 * kTP);
@@ -241,11 +204,11 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_ctx_split_kernel(cons
   const size_t ph_ = ((size_t)b * 4 + wave) * nslab + slab;
   if (l31 == 0) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) sump[ph_ * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] = psum[r];
+    for (int r = 0; r < 16; ++r) sump[ph_ * 32 + acc_row(r, hi)] = psum[r];
   }
   if (hi == 0) maxp[ph_ * 32 + l31] = m;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) ctxp[ph_ * 1024 + ((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = ctx[r];
+  for (int r = 0; r < 16; ++r) ctxp[ph_ * 1024 + acc_row(r, hi) * 32 + l31] = ctx[r];
 }
 
 // =====================================================================================================
@@ -292,7 +255,7 @@ __global__ __launch_bounds__(256) void la_fin_split_kernel(const float* __restri
     const float val = (float)(c / s * scale);
     _Float16 vh, vl;
     split1(val, vh, vl);
-    const int slot = (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);
+    const int slot = (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);   // kslot(d) spelled out: as a call 58 -> 60 VGPRs
     const size_t o = ((size_t)b * 4 + h) * 1024 + e * 32 + slot;
     ctxT_h[o] = __builtin_bit_cast(uint16_t, vh);
     ctxT_l[o] = __builtin_bit_cast(uint16_t, vl);
@@ -329,7 +292,7 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_out_split_kernel(cons
   const int b = blockIdx.y, slab = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int ntiles = N / kTP;
-  const int tpb = sp_tpb(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
+  const int tpb = tiles_per_block(ntiles), t0 = slab * tpb, t1 = min(t0 + tpb, ntiles);
   h8 wqh[G::KK], wql[G::KK];                             // q rows of head `wave`
   load_wfrags<C>(wqh, wqkv_h, 32 * wave, l31, hi);
   load_wfrags<C>(wql, wqkv_l, 32 * wave, l31, hi);
@@ -344,12 +307,12 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_out_split_kernel(cons
   int yrt[NA], ypt[NA];                                  // y accumulators of this wave: row tile / pixel tile
 #pragma unroll
   for (int a = 0; a < NA; ++a) {
-    if (RT == 2) { yrt[a] = wave & 1; ypt[a] = wave >> 1; }
-    else { yrt[a] = wave; ypt[a] = a; }
+    yrt[a] = y_row_tile<RT>(wave, a);
+    ypt[a] = y_pix_tile<RT>(wave, a);
   }
-  h8 woh[kHid / 16], wol[kHid / 16];                     // to_out rows of this wave's y row tile
-  load_wfrags<kHid>(woh, wout_h, yrt[0] * 32, l31, hi);
-  load_wfrags<kHid>(wol, wout_l, yrt[0] * 32, l31, hi);
+  h8 woh[kHidden / 16], wol[kHidden / 16];                     // to_out rows of this wave's y row tile
+  load_wfrags<kHidden>(woh, wout_h, yrt[0] * 32, l31, hi);
+  load_wfrags<kHidden>(wol, wout_l, yrt[0] * 32, l31, hi);
   XTileF<C> xt;
   if (t0 < t1) xt.load(x, (int64_t)b * N + (int64_t)t0 * kTP);
   for (int t = t0; t < t1; ++t) {
@@ -403,7 +366,7 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_out_split_kernel(cons
 #pragma unroll
     for (int a = 0; a < NA; ++a) ya[a] = zero16();
 #pragma unroll
-    for (int kk = 0; kk < kHid / 16; ++kk)
+    for (int kk = 0; kk < kHidden / 16; ++kk)
 #pragma unroll
       for (int a = 0; a < NA; ++a)
         ya[a] = mma3(woh[kk], wol[kk], frag(oh + ypt[a] * 32 * kLdO, kLdO, l31, hi, kk), frag(ol + ypt[a] * 32 * kLdO, kLdO, l31, hi, kk), ya[a]);
@@ -412,7 +375,7 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 1) void la_out_split_kernel(cons
       float s1 = 0.0f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int c = yrt[a] * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int c = yrt[a] * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;   // acc_row(r, hi) spelled out: as a call the sum reassociates (C = 64: 1046 -> 1039 instructions)
         ya[a][r] += bias_l[c];
         s1 += ya[a][r];
       }
@@ -484,10 +447,11 @@ int launch_c(const float* x, const uint16_t* wqkv_h, const uint16_t* wqkv_l, con
              const float* bias, const float* out_g, float* out, float* ws, int B, int N, hipStream_t s) {
   static DeviceOnce attr;
   if (!attr.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&la_out_split_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_out<C>()));
+    int rc = set_lds(&la_out_split_kernel<C>, lds_out<C>());
+    if (rc) return rc;
     attr.mark();
   }
-  const int ntiles = N / kTP, nslab = ceil_div(ntiles, sp_tpb(ntiles));
+  const int nslab = slabs(N);
   float* ctxp = ws;
   float* sump = ctxp + (size_t)B * 4 * nslab * 1024;
   float* maxp = sump + (size_t)B * 4 * nslab * 32;
@@ -544,8 +508,7 @@ __global__ __launch_bounds__(256) void full_attn_split_kernel(const float* __res
       if (with_v) {
         const float4 va = *reinterpret_cast<const float4*>(kp + 128), vc = *reinterpret_cast<const float4*>(kp + 132);
         const float vv[8] = {va.x, va.y, va.z, va.w, vc.x, vc.y, vc.z, vc.w};
-        const int d = key & 31;
-        const int pos = (key & ~31) + (d >> 4) * 16 + ((d >> 2) & 1) * 8 + ((d >> 3) & 1) * 4 + (d & 3);
+        const int pos = (key & ~31) + kslot(key & 31);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           _Float16 sh_, sl_;
@@ -575,6 +538,7 @@ __global__ __launch_bounds__(256) void full_attn_split_kernel(const float* __res
     f32x16 sa = zero16();
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
+      // frag(Kh + kt * 32 * LDK, LDK, l31, hi, ks) spelled out: through the call every instantiation is an instruction longer
       const h8 kh = *reinterpret_cast<const h8*>(Kh + (kt * 32 + l31) * LDK + ks * 16 + hi * 8);
       const h8 kl = *reinterpret_cast<const h8*>(Kl + (kt * 32 + l31) * LDK + ks * 16 + hi * 8);
       sa = mma3(kh, kl, qh[ks], ql[ks], sa);
@@ -628,9 +592,7 @@ __global__ __launch_bounds__(256) void full_attn_split_kernel(const float* __res
             l[qi] += pv;
             SPLIT_TO(pv, ph, pl, s2);
           }
-          const h8 vh = *reinterpret_cast<const h8*>(Vh + l31 * LDV + kt * 32 + i * 16 + hi * 8);
-          const h8 vl = *reinterpret_cast<const h8*>(Vl + l31 * LDV + kt * 32 + i * 16 + hi * 8);
-          oacc[qi] = mma3(vh, vl, ph, pl, oacc[qi]);
+          oacc[qi] = mma3(frag(Vh + kt * 32, LDV, l31, hi, i), frag(Vl + kt * 32, LDV, l31, hi, i), ph, pl, oacc[qi]);
         }
       }
     }
@@ -654,7 +616,8 @@ int launch_fa(const float* qkv, float* out, int B, hipStream_t s) {
   constexpr size_t lds = (size_t)(2 * KB * 40 + 2 * 32 * (KB + 8)) * 2;
   static DeviceOnce attr_set;
   if (!attr_set.done()) {
-    PRG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(full_attn_split_kernel<NT, QS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc = set_lds(&full_attn_split_kernel<NT, QS>, lds);
+    if (rc) return rc;
     attr_set.mark();
   }
   full_attn_split_kernel<NT, QS><<<dim3(4, B, QS), 256, lds, s>>>(qkv, out);
@@ -669,7 +632,7 @@ bool linattn_split_supported(int C, int N) {
 }
 
 size_t linattn_split_ws_floats(int B, int N) {
-  const int ntiles = N / kTP, nslab = ceil_div(ntiles, sp_tpb(ntiles));
+  const int nslab = slabs(N);
   return (size_t)B * 4 * nslab * (1024 + 64) + (size_t)B * 4 * 1024 + 64;   // slabs (ctx, sum, max) + ctx^T halves (2 x f16 = 1 float each)
 }
 

@@ -45,8 +45,6 @@ size_t linattn_ws_floats(int B, int N);
 template <typename T>
 int launch_linear_attention(const T* qkv, T* out, float* ws, int B, int N, hipStream_t s);
 
-// Residual(PreNorm(LinearAttention)) fused for the bf16 path (attn_fused.hip): x, out (B, N, C); wqkv [384][C] bf16 with
-// the PreNorm gain folded in, wout [C][128] bf16.  ws: at least linattn_fused_ws_floats(B, N) floats.
 // f16x3 mode (attn_split.hip): fused Residual(PreNorm(LinearAttention)) on float32 activations, split-f16 contractions
 bool linattn_split_supported(int C, int N);
 size_t linattn_split_ws_floats(int B, int N);
@@ -56,6 +54,8 @@ int launch_linear_attention_split(const float* x, const uint16_t* wqkv_h, const 
 // f16x3 mode: the bottleneck attention core (sd:789-795) on split-f16 MFMAs, float32 in / out (attn_split.hip)
 bool full_attention_split_supported(int N);
 int launch_full_attention_split(const float* qkv, float* out, int B, int N, hipStream_t s);
+// Residual(PreNorm(LinearAttention)) fused for the bf16 path (attn_fused.hip): x, out (B, N, C); wqkv [384][C] bf16 with
+// the PreNorm gain folded in, wout [C][128] bf16.  ws: at least linattn_fused_ws_floats(B, N) floats.
 bool linattn_fused_supported(int C);
 size_t linattn_fused_ws_floats(int B, int N);
 // kshift: [128 + 4] static softmax shifts — a bound on |k| per column, then a bound on |q| per head (see unet.hip) — or
@@ -64,7 +64,7 @@ int launch_linear_attention_fused(const bf16_t* x, const bf16_t* wqkv, const bf1
                                   const float* out_g, bf16_t* out, float* ws, int B, int N, int C, const float* kshift,
                                   hipStream_t s, int psum_override = -1);
 
-// ResnetBlock tail with the 1x1 res_conv folded in (attn_fused.hip), bf16 path.  wres: [Cout][C0+C1] bf16.
+// ResnetBlock tail with the 1x1 res_conv folded in (resblock_tail.hip), bf16 path.  wres: [Cout][C0+C1] bf16.
 bool resblock_tail_fused_supported(int C0, int C1, int Cout);
 // head_out != null (Cout = 64 only): the Unet's final 1x1 conv to one channel (+ optional sigmoid) is applied to the tile
 // in LDS and ONLY its float32 result (B, N) is written — the 64-channel tensor never reaches HBM.
@@ -75,7 +75,7 @@ int launch_resblock_tail_fused(const bf16_t* h, const float* A, const float* Bc,
                                const float* head_w = nullptr, const float* head_b = nullptr, float* head_out = nullptr,
                                int head_sigmoid = 0, const GnFold* fold = nullptr);
 
-// Attention core on MFMA (bf16 path, N in {64, 128, 256} tokens) (attn_fused.hip)
+// Attention core on MFMA (bf16 path, N in {64, 128, 256, 512, 1024} tokens) (attn_fused.hip)
 bool full_attention_mfma_supported(int N);
 int launch_full_attention_mfma(const bf16_t* qkv, bf16_t* out, int B, int N, hipStream_t s);
 

@@ -344,7 +344,7 @@ struct UnetImpl : prg_unet {
   }
 
   // The three forms of a block's tail, out <- SiLU(GroupNorm(out)) + res(cat[s0, s1]):
-  //   Fused (bf16): one kernel with the 1x1 res_conv inside (attn_fused.hip), which can also apply the network's head;
+  //   Fused (bf16): one kernel with the 1x1 res_conv inside (resblock_tail.hip), which can also apply the network's head;
   //   ResEpilogue (bf16, f16x3): a res_conv the fused kernel does not cover (up levels 0-1: 768 -> 512, 384 -> 256) takes the
   //     tail into ITS epilogue, out = Wres . cat[s0, s1] + b + SiLU(GroupNorm(h)): one launch, `res` never materialised either;
   //   Plain: `res` from its own conv (or the identity skip), then one elementwise pass (exact fp32 keeps these passes).

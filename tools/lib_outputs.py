@@ -11,8 +11,11 @@ without graph capture.  They also cover every branch of the forward pass's host 
 64 x 64, and at 40 x 40 where tiles do not divide and the second conv of a block has no fused prologue) under each switch that
 moves a ResnetBlock onto another path, and the debug taps, which turn the fused head off.  The f16x3 networks reach every
 instantiation of conv_split.hip / conv_split512.hip but conv3x3_split_kernel<4, 32, 2> (choose_conv at 256 CUs); the kind
-"conv_fused" launches that one alone (prg_debug_conv_fused).  The library reads its PRG_* switches once per process: every switch
-setting runs in a child of its own."""
+"conv_fused" launches that one alone (prg_debug_conv_fused).  The network cases reach the fused ResnetBlock tail, linear attention
+with the library's own choice of row-sum form and the bf16 bottleneck core at N = 64 and 256 only; the kinds "attention_core",
+"attention_block" and "resblock_tail" launch every instantiation of attn_fused.hip, attn_split.hip and resblock_tail.hip through
+the test hooks, on the small shapes of tests/test_gpu_attention.py and tests/test_gpu_resblock_tail.py.  The library reads its
+PRG_* switches once per process: every switch setting runs in a child of its own."""
 import json
 import os
 import subprocess
@@ -54,6 +57,9 @@ GROUPS = [
     ({"PRG_SPLIT_W512": "2"}, SMALL("f16x3")),
     ({"PRG_SPLIT_FULLATTN": "0", "PRG_SPLIT_LA_ONLINE": "0"}, SMALL("f16x3")),
     ({}, [("conv_fused", 64, 2, 12, "f16x3")]),
+    ({}, [("attention_core", 0, 0, 0, m) for m in ("bf16", "f16x3")] + [("attention_block", 0, 0, 0, m) for m in ("bf16", "f16x3")]),
+    ({"PRG_SPLIT_LA_ONLINE": "0"}, [("attention_block", 0, 0, 0, "f16x3")]),
+    ({}, [("resblock_tail", 0, 0, 0, "bf16")]),
 ]
 # kind "conv_fused": one f16x3 3x3 conv through the test hook, statistics off and as slabs.  (tag, (B, C0, C1, Cout, H, W), prologue,
 # expected (family, th, tw)): the smallest shapes of tests/test_gpu_conv_fused_f32.py that select the 4 x 32 split halo tile
@@ -81,6 +87,49 @@ def run_conv_fused(name, res):
                     res[f"{name}:{tag}:stats{stats}:{k}"] = got[k].numpy()
 
 
+def run_attention(kind, mode, name, res):
+    """attention_core: the bottleneck core's matrix-pipe kernels (full_attn_mfma_kernel<2, 4, 8>, full_attn_mfma_big_kernel<16, 2>,
+    <32, 4>, <32, 2>; full_attn_split_kernel<4, 1>, <8, 2>, <16, 4>, <32, 4>, <8, 1>, <32, 2> on the tests' shapes, and <16, 1>, which
+    needs B >= 32 at N = 512).  attention_block: bf16 every la_kmax<C>, la_ctx<C, *, *> and la_out<C, *> (family E keeps the static bound at
+    every width) with a partial tile (N = 100) and a short last slab (576); f16x3 la_ctx_split<C, online>, la_out_split<C>."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from test_attention_refs import FULL_MFMA_N, FULL_SPLIT_N, block_case
+    from test_gpu_attention import core_case, run_block, run_core
+    if kind == "attention_core":
+        big = [(32, 1024)] if mode == "bf16" else [(32, 256), (32, 512), (32, 1024)]
+        for B, N in [(3, n) for n in (FULL_MFMA_N if mode == "bf16" else FULL_SPLIT_N)] + big:
+            for fam in ("F1", "F2"):
+                res[f"{name}:{fam}:B{B}:N{N}"] = run_core(core_case(fam, B, N, mode, 0), mode, 0, 1).numpy()
+    elif mode == "bf16":
+        for Cc in (64, 128, 256):
+            for N in (100, 576):
+                W, x = block_case(Cc, 3, N, "E", "bf16")[:2]
+                for shift_mode in (0, 1):
+                    for psum in (0, 1):
+                        rc, out, used = run_block(W, x, "bf16", shift_mode, psum)
+                        assert rc == 0 and used == shift_mode, (Cc, N, shift_mode, psum, rc, used)
+                        res[f"{name}:C{Cc}:N{N}:shift{shift_mode}:psum{psum}"] = out.numpy()
+    else:
+        for Cc in (64, 128):
+            W, x = block_case(Cc, 3, 576, "R", "f16x3")[:2]
+            rc, out, used = run_block(W, x, "f16x3", -1, -1)
+            assert rc == 0 and used == 0, (Cc, rc, used)
+            res[f"{name}:C{Cc}:N576"] = out.numpy()
+
+
+def run_resblock_tail(name, res):
+    """resblock_tail_fused_kernel<128, 64>, <192, 128>, <256, 128>: a partial second tile and a second block of one tile"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from test_gpu_resblock_tail import CONFIGS, T_TILES, inputs, run
+    for C0, C1, Cout in CONFIGS:
+        for N in (100, 64 * T_TILES + 64):
+            d = inputs(C0, C1, Cout, 3, N, "normal", 1000 * Cout + 10 * N + 3 + C0)
+            for ip in (0, 1):
+                res[f"{name}:{C0}+{C1}->{Cout}:N{N}:in_place{ip}"] = run(d, False, False, ip).numpy()
+                for sigmoid in (False, True) if Cout == 64 else ():
+                    res[f"{name}:{C0}+{C1}->{Cout}:N{N}:in_place{ip}:head:sigmoid{int(sigmoid)}"] = run(d, True, sigmoid, ip).numpy()
+
+
 def run_group(index, out):
     import numpy as np
     import torch
@@ -94,6 +143,12 @@ def run_group(index, out):
         kind, dim, B, S, mode = case
         if kind == "conv_fused":
             run_conv_fused(case_name(env, case), res)
+            continue
+        if kind in ("attention_core", "attention_block"):
+            run_attention(kind, mode, case_name(env, case), res)
+            continue
+        if kind == "resblock_tail":
+            run_resblock_tail(case_name(env, case), res)
             continue
         g = torch.Generator().manual_seed(1000 + dim + B + S)
         taps = ()
