@@ -741,6 +741,55 @@ int prg_debug_sampler_step_objective(float* x, const float* u, const float* img_
                                      const prg_step* step, int objective, float p, float q, float keep_p,
                                      const float* keep_u, int B, int HW, int reps, float* avg_us, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Checkpoint validation (csrc/validate.hip): the forward process, the training loss of one network output, and the sums of
+ * the depth-correction metrics.  GaussianDiffusion.q_sample / p_losses (sd:1448-1497), MaskTrainer.compute_metrics
+ * (dc:1229-1250).  All pointers are DEVICE pointers unless marked HOST.  Streaming kernels, asynchronous on `stream`, no atomics,
+ * no host synchronisation, nothing allocated: per-block partials go to the caller's `workspace` of at least
+ * prg_validate_workspace_bytes(B, HW) bytes, 16-byte aligned.  Every float32 step written fl(..) is one rounded operation
+ * (the library is built with -ffp-contract=off), which is what torch computes.
+ *
+ * Noise: `noise` (B,HW) float32 stored normals, or NULL; then `seeds` (B) uint64 DEVICE, one Philox4x32-10 key per sample:
+ * counter {pixel quad q, draw, 0x76616C64 ("vald"), 0}, four normals per call for pixels 4q .. 4q + 3 by the sampler's
+ * Box-Muller arithmetic (the sampler's own streams carry 0x70726721 and 0x6B656570 as third word: no draw is shared with a chain
+ * of the same seeds).  Exactly one of noise and seeds is non-NULL; Philox noise needs HW % 4 == 0.  A sample's numbers depend on
+ * its own row, seed and coefficients only, never on B or on the other samples of the launch.
+ *
+ * Summation order of every float64 sum below: fixed, a function of HW alone (stated in csrc/validate.hip and, in numpy, as
+ * pointreggpt_amd.validate.ordered_sum).
+ *
+ * Bad arguments (a NULL pointer where none is allowed, B < 1 or > 65535, HW < 1 or > 2^30, both or neither of noise and seeds,
+ * HW % 4 != 0 with Philox noise, an unknown objective or loss type, a workspace that is too small) fail with PRG_E_INVALID
+ * before any device call.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* Host-only arithmetic: no device call, usable without a GPU; returns the size (0 for B or HW out of range), not a PRG_E_* code. */
+size_t prg_validate_workspace_bytes(int B, int HW);
+
+/* x_t[b][i] = fl(fl(a[b] * x0[b][i]) + fl(s[b] * n[b][i])): two rounded float32 products and one addition (sd:1451-1453).
+ * x0, x_t (B,HW) float32; a[b] = sqrt_alphas_cumprod[t_b], s[b] = sqrt_one_minus_alphas_cumprod[t_b], (B) float32, gathered by
+ * the host from its float32 buffers like the reference's extract().  noise_out (B,HW) or NULL: the normals n that were used. */
+int prg_q_sample(const float* x0, const float* a, const float* s, const float* noise, const uint64_t* seeds, uint32_t draw,
+                 int B, int HW, float* x_t, float* noise_out, void* stream);
+
+/* The loss of the network output u (B,HW) without materialising the target (sd:1476-1497).  Per pixel in float32:
+ * target = x0 (objective 0, pred_x0), n (1, pred_noise) or fl(fl(a[b] * n) - fl(s[b] * x0)) (2, pred_v; sd:1164-1167);
+ * d = fl(u - target); term = |d| (loss_type 0, l1) or fl(d * d) (1, l2).  Per sample: the terms widened to float64 and added in
+ * the fixed order; out[b][0] = sum / HW (the unweighted mean), out[b][1] = out[b][0] * (double)w[b], w[b] = loss_weight[t_b].
+ * out (B,2) float64.  n is the stored `noise`, or regenerated from (seeds, draw) exactly as prg_q_sample draws it.  A NaN in
+ * one sample's input makes that sample's two numbers NaN and touches no other sample's. */
+int prg_diffusion_loss(const float* u, const float* x0, const float* noise, const uint64_t* seeds, uint32_t draw, const float* a,
+                       const float* s, const float* w, int objective, int loss_type, int B, int HW, void* workspace,
+                       size_t workspace_bytes, double* out, void* stream);
+
+/* The sums of compute_metrics.  prob, input, label (B,HW) float32; mask (B,HW) float32 or NULL: then the label mask is
+ * (|fl(label - input)| < tol) ? 1 : 0 in float32, PairedDepthDataset's rule (dc:941).  Per pixel: o = prob > threshold,
+ * m = mask > threshold (float32 comparisons: NaN and a value exactly at the threshold are false); out = o ? input : 0,
+ * lab = m ? label : 0, d = fl(lab - out).  Per sample: counts[b][2 * m + o] (B,4) int64 (the rows of the reference's bincount
+ * matrix: label mask major, output mask minor); sums[b] = (sum |d|, sum fl(d * d)) (B,2) float64 in the fixed order. */
+int prg_mask_metrics(const float* prob, const float* input, const float* label, const float* mask, float threshold, float tol,
+                     int B, int HW, void* workspace, size_t workspace_bytes, int64_t* counts, double* sums, void* stream);
+
 /* Wall-clock free timing hook for bench.py: average duration in milliseconds of the dominant kernel class
  * (implicit-GEMM convolution launches) measured with HIP events on the run's own stream during the last
  * prg_sampler_run when profiling was enabled with prg_sampler_set_profile(h, 1) (forces eager launches).

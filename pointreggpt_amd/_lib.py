@@ -139,6 +139,10 @@ PROTOTYPES = {
     "prg_sampler_set_objective": (C.c_int, [_P, _I, _P, _P, _I]),
     "prg_sampler_set_keep_draws": (C.c_int, [_P, _P, _L]),
     "prg_sampler_get_profile_shapes": (C.c_int, [_P, _P, _I, C.POINTER(C.c_int32)]),
+    "prg_validate_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "prg_q_sample": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _I, _I, _P, _P, _P]),
+    "prg_diffusion_loss": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, _P, _I, _I, _I, _I, _P, C.c_size_t, _P, _P]),
+    "prg_mask_metrics": (C.c_int, [_P, _P, _P, _P, _F, _F, _I, _I, _P, C.c_size_t, _P, _P, _P]),
     "prg_host_crop_aabb": (C.c_int, [_P, _L, _P, _P, _P, C.POINTER(_L)]),
     "prg_host_voxel_down_sample": (C.c_int, [_P, _L, C.c_double, _P, C.POINTER(_L)]),
     "prg_host_write_ply": (C.c_int, [C.c_char_p, _P, _L]),

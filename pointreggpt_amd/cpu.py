@@ -187,6 +187,26 @@ class GaussianDiffusion(_diff.GaussianDiffusion):
     def close(self):
         pass
 
+    # validation on the host: the numpy specifications of the three kernels plus prg_cpu_unet_forward (validate.py)
+    def _val_device(self):
+        return torch.device("cpu")
+
+    def _val_noise(self, x0, noise, seeds, draw):
+        from . import validate as V
+        if noise is not None:
+            return noise.numpy()
+        return V.philox_normals(seeds, draw, x0[0].numel()).reshape(tuple(x0.shape))
+
+    def _val_q_sample(self, x0, a, s, noise, seeds, draw):
+        from . import validate as V
+        return torch.from_numpy(V.q_sample_spec(x0.numpy(), a.numpy(), s.numpy(), self._val_noise(x0, noise, seeds, draw)))
+
+    def _val_loss(self, u, x0, a, s, w, noise, seeds, draw):
+        from . import validate as V
+        nz = None if self.objective == "pred_x0" else self._val_noise(x0, noise, seeds, draw)
+        return torch.from_numpy(V.diffusion_loss_spec(u.numpy(), x0.numpy(), nz, a.numpy(), s.numpy(), w.numpy(), self.objective,
+                                                      self.loss_type))
+
     @torch.no_grad()
     def sample(self, *, param_cond, img_cond=None, disable_tqdm=True, has_refine_step=False, noise=None,
                seeds: Optional[Sequence[int]] = None, keep_draws=None, **_unused):

@@ -4,9 +4,11 @@
 
 namespace prg {
 
-// third Philox counter word: the normals use 0x70726721, the keep-mask uniforms this one ("keep")
+// third Philox counter word: the normals use 0x70726721, the keep-mask uniforms "keep", the noise of the validation path's
+// forward process (validate.hip) "vald": a validation run with a generation run's seeds shares no draw with its chains
 constexpr uint32_t PHILOX_DOMAIN_NORMAL = 0x70726721u;
 constexpr uint32_t PHILOX_DOMAIN_KEEP = 0x6B656570u;
+constexpr uint32_t PHILOX_DOMAIN_VALIDATE = 0x76616C64u;
 
 // What every instantiation of sampler_step_kernel receives.  The objective-0 instantiations receive this part ALONE: their kernel
 // arguments, and with them their code, are what they were before the objectives existed.

@@ -12,20 +12,7 @@
 namespace prg {
 
 // ---- noise from Philox4x32-10 (philox.h): key = per-scene seed, counter = (pixel quad, draw index, stream tag) ----
-// four standard normals for (scene key, draw index, pixel quad): two Box-Muller pairs
-__device__ inline float4 philox_normal4(uint64_t key, uint32_t draw, uint32_t quad) {
-  uint32_t c[4] = {quad, draw, PHILOX_DOMAIN_NORMAL, 0u};
-  philox4x32_10(c, key);
-  const float k = 2.3283064365386963e-10f;  // 2^-32
-  const float u0 = ((float)c[0] + 0.5f) * k, u1 = ((float)c[1] + 0.5f) * k;
-  const float u2 = ((float)c[2] + 0.5f) * k, u3 = ((float)c[3] + 0.5f) * k;
-  const float r0 = sqrtf(-2.0f * logf(fminf(fmaxf(u0, 1e-12f), 1.0f)));
-  const float r1 = sqrtf(-2.0f * logf(fminf(fmaxf(u2, 1e-12f), 1.0f)));
-  float s0, c0, s1, c1;
-  sincosf(6.283185307179586f * u1, &s0, &c0);
-  sincosf(6.283185307179586f * u3, &s1, &c1);
-  return make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
-}
+// the normals are philox_normal4 (philox.h) under the sampler's own tag, PHILOX_DOMAIN_NORMAL
 
 // four uniforms in [0,1) on the 2^-24 grid (torch's float32 uniform_ grid, 0 included) for the DDNM keep mask of (scene key,
 // draw index, pixel quad): word i >> 8, exactly representable, serves pixel 4 * quad + i.  The third counter word separates
@@ -72,7 +59,7 @@ __device__ inline void sampler_step_image(const SamplerStepCore& a, const prg_st
       if (a.noise)
         nz = *reinterpret_cast<const float4*>(a.noise + ((size_t)(k + 1) * a.B + b) * a.HW + (size_t)q * 4);
       else
-        nz = philox_normal4(a.seeds[b], (uint32_t)(k + 1), (uint32_t)q);
+        nz = philox_normal4(a.seeds[b], (uint32_t)(k + 1), (uint32_t)q, PHILOX_DOMAIN_NORMAL);
     }
     const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
     const float cds[4] = {cd.x, cd.y, cd.z, cd.w}, cms[4] = {cm.x, cm.y, cm.z, cm.w};
@@ -161,7 +148,7 @@ __global__ void sampler_init_kernel(float* __restrict__ x, const float* __restri
     if (noise)
       v = *reinterpret_cast<const float4*>(noise + o);
     else
-      v = philox_normal4(seeds[b], 0u, (uint32_t)q);
+      v = philox_normal4(seeds[b], 0u, (uint32_t)q, PHILOX_DOMAIN_NORMAL);
     *reinterpret_cast<float4*>(x + o) = v;
   }
 }

@@ -44,20 +44,26 @@ def cosine_beta_schedule(timesteps: int, s=0.008) -> torch.Tensor:
 
 BETA_SCHEDULES = {"linear": linear_beta_schedule, "cosine": cosine_beta_schedule, "sigmoid": sigmoid_beta_schedule}
 OBJECTIVES = {"pred_x0": 0, "pred_noise": 1, "pred_v": 2}     # the codes of prg_sampler_set_objective (include/prg.h)
+LOSS_TYPES = {"l1": 0, "l2": 1}                               # the codes of prg_diffusion_loss
 
 
-def make_schedule(timesteps: int, beta_schedule: str = "sigmoid") -> Dict[str, torch.Tensor]:
-    """The float32 buffers GaussianDiffusion registers (sd:1056-1134), from the float64 betas of the named schedule.
-    A beta >= 1 (the linear schedule below 21 timesteps) makes alphas_cumprod <= 0 and every chain NaN: the reference samples
-    on in silence, this raises."""
+def _schedule64(timesteps: int, beta_schedule: str):
+    """The float64 betas of the named schedule and their alphas_cumprod, checked (sd:1047-1057)."""
     if beta_schedule not in BETA_SCHEDULES:
         raise ValueError(f"unknown beta schedule {beta_schedule}")
     betas = BETA_SCHEDULES[beta_schedule](timesteps)
     if bool((betas >= 1).any()):
         raise ValueError(f"beta_schedule='{beta_schedule}' with timesteps={timesteps} has a beta >= 1 "
                          f"(max {float(betas.max()):.4g}): the chain would be NaN; the linear schedule needs timesteps >= 21")
+    return betas, torch.cumprod(1.0 - betas, dim=0)
+
+
+def make_schedule(timesteps: int, beta_schedule: str = "sigmoid") -> Dict[str, torch.Tensor]:
+    """The float32 buffers GaussianDiffusion registers (sd:1056-1134), from the float64 betas of the named schedule.
+    A beta >= 1 (the linear schedule below 21 timesteps) makes alphas_cumprod <= 0 and every chain NaN: the reference samples
+    on in silence, this raises."""
+    betas, ac = _schedule64(timesteps, beta_schedule)
     alphas = 1.0 - betas
-    ac = torch.cumprod(alphas, dim=0)
     ac_prev = torch.nn.functional.pad(ac[:-1], (1, 0), value=1.0)
     post_var = betas * (1.0 - ac_prev) / (1.0 - ac)
     buf = {
@@ -71,6 +77,26 @@ def make_schedule(timesteps: int, beta_schedule: str = "sigmoid") -> Dict[str, t
         "loss_weight": ac / (1 - ac),
     }
     return {k: v.to(torch.float32) for k, v in buf.items()}
+
+
+def loss_weight(timesteps: int, beta_schedule: str, objective: str, min_snr_loss_weight: bool = False,
+                min_snr_gamma=5) -> torch.Tensor:
+    """The reference's per-timestep loss weight of an objective (sd:1138-1151): computed in float64 from the signal-to-noise
+    ratio alphas_cumprod / (1 - alphas_cumprod), clipped at min_snr_gamma on request, stored as float32."""
+    _betas, ac = _schedule64(timesteps, beta_schedule)
+    snr = ac / (1 - ac)
+    clipped = snr.clone()
+    if min_snr_loss_weight:
+        clipped.clamp_(max=min_snr_gamma)
+    if objective == "pred_noise":
+        w = clipped / snr
+    elif objective == "pred_x0":
+        w = clipped
+    elif objective == "pred_v":
+        w = clipped / (snr + 1)
+    else:
+        raise ValueError(f"unknown objective {objective}")
+    return w.to(torch.float32)
 
 
 def ddim_times(total: int, steps: int) -> List[int]:
@@ -93,8 +119,8 @@ class GaussianDiffusion:
     in the reference, sigmoid here); it is refused with ``ValueError`` instead of sampling from the wrong schedule in silence."""
 
     def __init__(self, model: Unet, *, image_size, timesteps=1000, sampling_timesteps=None, loss_type="l1",
-                 objective=None, beta_schedule=None, ddim_sampling_eta=1.0, is_ddnm_sampling=True,
-                 ddnm_sampling_dropout=0.0, ddnm_dropout_schedule="none"):
+                 objective=None, beta_schedule=None, ddim_sampling_eta=1.0, min_snr_loss_weight=False, min_snr_gamma=5,
+                 is_ddnm_sampling=True, ddnm_sampling_dropout=0.0, ddnm_dropout_schedule="none"):
         given = (objective is not None, beta_schedule is not None)
         objective = "pred_x0" if objective is None else objective
         beta_schedule = "sigmoid" if beta_schedule is None else beta_schedule
@@ -106,6 +132,8 @@ class GaussianDiffusion:
             raise ValueError(f"unknown objective {objective}: one of {', '.join(OBJECTIVES)}")
         if beta_schedule not in BETA_SCHEDULES:
             raise ValueError(f"unknown beta schedule {beta_schedule}: one of {', '.join(BETA_SCHEDULES)}")
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"invalid loss type {loss_type}: one of {', '.join(LOSS_TYPES)}")
         if not 0.0 <= float(ddnm_sampling_dropout) <= 1.0:
             raise ValueError(f"ddnm_sampling_dropout must lie in [0, 1], got {ddnm_sampling_dropout}")
         if ddnm_dropout_schedule not in ("none", "linear"):
@@ -121,6 +149,10 @@ class GaussianDiffusion:
         self.beta_schedule = beta_schedule
         for k, v in make_schedule(self.num_timesteps, beta_schedule).items():
             setattr(self, k, v)
+        # the training objective's weight (sd:1138-1151); pred_x0 without the min-SNR clip is make_schedule's own entry
+        self.loss_type = loss_type
+        self.min_snr_loss_weight, self.min_snr_gamma = bool(min_snr_loss_weight), min_snr_gamma
+        self.loss_weight = loss_weight(self.num_timesteps, beta_schedule, objective, self.min_snr_loss_weight, min_snr_gamma)
         # the refine row of the ancestral sampler is p_sample(t = 0) whose posterior mean the kernel takes to be x0 itself
         # (sd:1173-1176, 1307-1314): true of the schedule built here, not assumed of every schedule
         assert float(self.posterior_mean_coef1[0]) == 1.0 and float(self.posterior_mean_coef2[0]) == 0.0, \
@@ -313,6 +345,74 @@ class GaussianDiffusion:
                                        _lib.ptr(out), _lib.stream_ptr()), "prg_sampler_run")
         self._keepalive = (pc, cond, nz, ku)   # the run is asynchronous: keep inputs alive until the next call
         return out
+
+    # -- validation: the training objective on held-out images (sd:1448-1510) ------------------------
+    def _val_q_sample(self, x0, a, s, noise, seeds, draw):
+        from . import validate as V
+        return V.q_sample_hip(x0, a.to(x0.device), s.to(x0.device), noise, seeds=seeds, draw=draw)
+
+    def _val_loss(self, u, x0, a, s, w, noise, seeds, draw):
+        from . import validate as V
+        dev = x0.device
+        return V.diffusion_loss_hip(u, x0, a.to(dev), s.to(dev), w.to(dev), self.objective, self.loss_type, noise, seeds=seeds, draw=draw)
+
+    def _val_device(self):
+        _lib.require_gpu()
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def _val_inputs(self, x_start, t, noise, seeds):
+        """x0 and the stored noise on the path's device, the timesteps on the host, and the per-sample coefficients gathered from
+        the float32 buffers like the reference's extract() (sd:968-971)."""
+        dev = self._val_device()
+        x0 = torch.as_tensor(x_start).to(device=dev, dtype=torch.float32).contiguous()
+        B = x0.shape[0]
+        t = torch.as_tensor(t).to(device="cpu", dtype=torch.int64).reshape(-1)
+        if t.shape[0] != B or int(t.min()) < 0 or int(t.max()) >= self.num_timesteps:
+            raise ValueError(f"t: one timestep in [0, {self.num_timesteps}) per sample")
+        if noise is not None and seeds is not None:
+            raise ValueError("stored noise or Philox seeds, not both")
+        nz = None
+        if noise is not None:
+            nz = torch.as_tensor(noise).to(device=dev, dtype=torch.float32).contiguous()
+            assert nz.shape == x0.shape, "noise has x_start's shape"
+        elif seeds is None:
+            seeds = range(B)                                  # sample()'s default keys
+        return x0, t, nz, (None if nz is not None else list(seeds)), self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t]
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, *, seeds=None, draw=0):
+        """x_t = sqrt_alphas_cumprod[t] x_start + sqrt_one_minus_alphas_cumprod[t] noise (sd:1448-1453), prg_q_sample.  ``noise``:
+        stored normals of x_start's shape; otherwise on-device Philox keyed per sample by ``seeds`` (default 0..B-1) at draw
+        index ``draw``, under the validation path's own stream tag: no draw is shared with a chain of the same seeds."""
+        x0, _t, nz, seeds, a, s = self._val_inputs(x_start, t, noise, seeds)
+        return self._val_q_sample(x0, a, s, nz, seeds, draw)
+
+    @torch.no_grad()
+    def p_losses(self, x_start, t, param_cond, *, noise=None, seeds=None, draw=0, per_sample=False):
+        """The training loss of x_start (B,1,S,S) in [-1,1] at the timesteps t (B,) (sd:1464-1497): prg_q_sample -> Unet.forward ->
+        prg_diffusion_loss.  With Philox noise the noise is never stored: the loss kernel draws it again.  Returns the batch mean
+        of the weighted losses (float64, 0-dim); ``per_sample=True``: the (B,2) float64 table [unweighted mean, weighted loss]."""
+        x0, t, nz, seeds, a, s = self._val_inputs(x_start, t, noise, seeds)
+        x_t = self._val_q_sample(x0, a, s, nz, seeds, draw)
+        u = self.model(x_t, t.to(x_t.device), torch.as_tensor(param_cond).to(device=x_t.device, dtype=torch.float32))
+        table = self._val_loss(u, x0, a, s, self.loss_weight[t], nz, seeds, draw)
+        return table if per_sample else table[:, 1].mean()
+
+    def forward(self, data_dict, *, seed=0, draw=0, **kwargs):
+        """The reference's forward (sd:1499-1510) with keyed draws: ``img`` (B,1,S,S) in [0,1] normalised to [-1,1], ``intrinsic``
+        (B,3,3) -> param_vector; the timesteps are ``validate.timesteps(seed, scenes, draw, T)`` and, unless the caller passes
+        noise or seeds, the noise keys ``synthetic.noise_seed(seed, scene)``, with scenes = data_dict["scene"] (default 0..B-1):
+        the same (seed, scene, draw) gives the same t and the same noise whatever the batch or the shard."""
+        from . import geometry as G
+        from . import synthetic, validate as V
+        img = torch.as_tensor(data_dict["img"])
+        B, _c, h, w = img.shape
+        assert h == self.image_size and w == self.image_size, f"height and width of image must be {self.image_size}"
+        scenes = [int(i) for i in data_dict.get("scene", range(B))]
+        t = torch.from_numpy(V.timesteps(seed, scenes, draw, self.num_timesteps))
+        if kwargs.get("noise") is None and kwargs.get("seeds") is None:
+            kwargs["seeds"] = [synthetic.noise_seed(seed, i) for i in scenes]
+        return self.p_losses(img.to(torch.float32) * 2 - 1, t, G.param_vector(torch.as_tensor(data_dict["intrinsic"])), draw=draw, **kwargs)
 
     def last_profile(self, batch: int, refine: bool = False) -> dict:
         lib = _lib.load()

@@ -831,6 +831,147 @@ def g24_objectives():
     save("G24_objectives", **out)
 
 
+G25_T = (0, 500, 999)
+
+
+def g25_stub_output(x, t, pc):
+    """The stub network of G25: a fixed elementwise function of (x, t, param_cond), one rounded float32 operation per step, so
+    that numpy restates it bit for bit (tests/test_validation_spec.py does)."""
+    tf = (t.to(torch.float32) * 1e-3).reshape(-1, 1, 1, 1)
+    p0 = (pc[:, 0] * 0.01).reshape(-1, 1, 1, 1)
+    return (x * 0.75 + tf * 0.25) - p0
+
+
+def g25_validation():
+    """GaussianDiffusion.q_sample / predict_v / p_losses (sd:1164-1167, 1448-1497) and MaskTrainer.compute_metrics (dc:1229-1275)
+    of the reference itself.  B = 3, S = 32, T = 1000, t = (0, 500, 999), a stub network (g25_stub_output).  Per schedule: x_t and
+    the pred_v target.  Per (objective, schedule, min-SNR): the float32 loss_weight array.  Per (objective, schedule, loss type,
+    min-SNR): p_losses with 8 threads and with 1, and a float64 recomputation from the reference's own float32 terms.  One real
+    network (G24's: dim 16, weight seed 9, S = 32, B = 2, pred_x0 / sigmoid, l1): p_losses and the per-sample unweighted means.
+    compute_metrics: two batches per threshold (0.5, 0.99) through one AverageMeter set, and a batch whose two masks are empty."""
+    import types
+    import torch.nn.functional as F
+
+    class _Stub(torch.nn.Module):
+        channels = out_dim = 1
+        random_or_learned_sinusoidal_cond = False
+
+        def forward(self, x, t, pc):
+            return g25_stub_output(x, t, pc)
+
+    B, S, T = 3, 32, 1000
+    gen = torch.Generator().manual_seed(2501)
+    x0 = torch.rand((B, 1, S, S), generator=gen) * 2 - 1
+    noise = torch.randn((B, 1, S, S), generator=gen)
+    t = torch.tensor(G25_T)
+    pc = torch.tensor([[37.87, 38.02, 16.25, 16.0], [36.5, 36.7, 16.25, 16.0], [40.0, 40.0, 16.0, 16.0]])
+    out = {"x0": x0, "noise": noise, "t": t, "pc": pc}
+
+    def ref(model, S_, objective, schedule, loss_type="l1", min_snr=False):
+        return sd.GaussianDiffusion(model, image_size=S_, timesteps=T, loss_type=loss_type, objective=objective, beta_schedule=schedule,
+                                    min_snr_loss_weight=min_snr, min_snr_gamma=5)
+
+    def terms_of(d, model, x0_, t_, pc_, noise_):
+        """The reference's own float32 terms: loss_fn(model_out, target, reduction='none') as p_losses forms them."""
+        x = d.q_sample(x_start=x0_, t=t_, noise=noise_)
+        u = model(x, t_, pc_)
+        target = {"pred_noise": noise_, "pred_x0": x0_}.get(d.objective)
+        if target is None:
+            target = d.predict_v(x0_, t_, noise_)
+        return u, d.loss_fn(u, target, reduction="none").reshape(len(x0_), -1)
+
+    gap = 0.0
+    stub = _Stub()
+    for schedule in ("sigmoid", "cosine", "linear"):
+        d0 = ref(stub, S, "pred_v", schedule)
+        out[f"{schedule}_x_t"] = d0.q_sample(x_start=x0, t=t, noise=noise)
+        out[f"{schedule}_v"] = d0.predict_v(x0, t, noise)
+        if schedule == "sigmoid":
+            out["sigmoid_u"] = stub(out["sigmoid_x_t"], t, pc)
+        for objective in ("pred_x0", "pred_noise", "pred_v"):
+            for min_snr in (False, True):
+                key = f"{objective}_{schedule}_snr{int(min_snr)}"
+                for loss_type in ("l1", "l2"):
+                    d = ref(stub, S, objective, schedule, loss_type, min_snr)
+                    assert torch.equal(d.q_sample(x_start=x0, t=t, noise=noise), out[f"{schedule}_x_t"])   # objective-independent
+                    out[key + "_loss_weight"] = d.loss_weight
+                    res = {}
+                    for threads in (8, 1):
+                        torch.set_num_threads(threads)
+                        res[threads] = d.p_losses(x0, t, pc, noise=noise)
+                    torch.set_num_threads(8)
+                    _u, terms = terms_of(d, stub, x0, t, pc, noise)
+                    assert terms.dtype == torch.float32
+                    f64 = (terms.to(torch.float64).mean(dim=1) * d.loss_weight[t].to(torch.float64)).mean()
+                    out[f"{key}_{loss_type}_loss"], out[f"{key}_{loss_type}_loss_1thread"] = res[8], res[1]
+                    out[f"{key}_{loss_type}_loss_f64"] = f64
+                    if float(f64) != 0.0:
+                        gap = max(gap, abs(float(res[8]) - float(f64)) / abs(float(f64)), abs(float(res[1]) - float(f64)) / abs(float(f64)))
+    print(f"  largest relative gap between the reference's float32 loss and its float64 recomputation: {gap:.2e}")
+    out["f32_f64_gap"] = np.float64(gap)
+
+    # ---- one real network: G24's ----
+    m = ref_unet(16, 9)
+    pc2 = pc[:2].clone()
+    depth, _K, _pose = synthetic.synth_batch(3, range(2), S)
+    rx0 = torch.from_numpy(depth) * 2 - 1
+    rnoise = torch.randn((2, 1, S, S), generator=gen)
+    rt = torch.tensor([100, 700])
+    d = ref(m, S, "pred_x0", "sigmoid", "l1")
+    res = {}
+    for threads in (8, 1):
+        torch.set_num_threads(threads)
+        _u, terms = terms_of(d, m, rx0, rt, pc2, rnoise)
+        res[threads] = (d.p_losses(rx0, rt, pc2, noise=rnoise), terms.mean(dim=1))
+    torch.set_num_threads(8)
+    out.update(net_x0=rx0, net_noise=rnoise, net_t=rt, net_pc=pc2, net_loss=res[8][0], net_loss_1thread=res[1][0],
+               net_unweighted=res[8][1], net_unweighted_1thread=res[1][1])
+    print(f"  real network: p_losses = {float(res[8][0]):.6f}, unweighted per sample {res[8][1].tolist()}, "
+          f"|8 threads - 1 thread| = {float((res[8][1] - res[1][1]).abs().max()):.2e}")
+
+    # ---- compute_metrics, called unbound on a namespace ----
+    def trainer():
+        return types.SimpleNamespace(accelerator=types.SimpleNamespace(is_main_process=True), metrics={"current": {}})
+
+    def matrix_of(data, prob, thr):
+        return torch.bincount(2 * (data["mask"] > thr).flatten() + (prob > thr).flatten(), minlength=4).reshape((2, 2))
+
+    def batch(seed, empty=False):
+        g = torch.Generator().manual_seed(seed)
+        inp = torch.rand((2, 1, 16, 16), generator=g)
+        lab = inp + (torch.rand((2, 1, 16, 16), generator=g) - 0.5) * 0.02
+        prob = torch.rand((2, 1, 16, 16), generator=g)
+        prob[0, 0, 0, :4] = 0.5                      # exactly at the threshold: not output
+        prob[1, 0, 1, :4] = torch.tensor(0.99)
+        mask = (torch.abs(lab - inp) < 0.005).to(dtype=torch.float32)
+        if empty:
+            prob, mask = prob * 0.25, torch.zeros_like(mask)
+        return {"input_img": inp, "label_img": lab, "mask": mask}, prob
+
+    KEYS = ("MSE", "MAE", "SAE", "mIoU", "PAcc", "FP")
+    batches = {"a": batch(2511), "b": batch(2512), "empty": batch(2513, empty=True)}
+    for name, (data, prob) in batches.items():
+        out.update({f"mask_{name}_input": data["input_img"], f"mask_{name}_label": data["label_img"], f"mask_{name}_mask": data["mask"],
+                    f"mask_{name}_prob": prob})
+    for thr in (0.5, 0.99):
+        tag = f"thr{int(thr * 100)}"
+        tr = trainer()
+        for name in ("a", "b"):
+            data, prob = batches[name]
+            dc.MaskTrainer.compute_metrics(tr, data, prob, mask_threshold=thr)
+            out[f"mask_{name}_{tag}_values"] = np.array([float(tr.metrics["current"][k].val) for k in KEYS], dtype=np.float64)
+            out[f"mask_{name}_{tag}_matrix"] = matrix_of(data, prob, thr)
+        out[f"mask_{tag}_avg"] = np.array([float(tr.metrics["current"][k].avg) for k in KEYS], dtype=np.float64)
+        tr = trainer()
+        data, prob = batches["empty"]
+        dc.MaskTrainer.compute_metrics(tr, data, prob, mask_threshold=thr)
+        out[f"mask_empty_{tag}_values"] = np.array([float(tr.metrics["current"][k].val) for k in KEYS], dtype=np.float64)
+        out[f"mask_empty_{tag}_matrix"] = matrix_of(data, prob, thr)
+    out["mask_keys"] = np.array(KEYS)
+    save("G25_validation", **out)
+    assert os.path.getsize(os.path.join(OUT, "G25_validation.npz")) < 256 * 1024
+
+
 def spec_fixture():
     import json
     spec = {"unet64": [[k, list(v.shape)] for k, v in sd.Unet(dim=64, param_cond_dim=4).state_dict().items()],
@@ -849,7 +990,7 @@ if __name__ == "__main__":
             ("g12", g12_end_to_end), ("g12b", g12b_envelope), ("g13", g13_unet_128), ("g14", g14_chain_128),
             ("g15", g15_maskunet_128), ("g16", g16_unet_256), ("g17", g17_ddim_cond_gt1), ("g18", g18_refine_and_tester), ("g19", g19_chain1000_64),
             ("g20", g20_ddim250_128), ("g21", g21_ddim250_256), ("g21b", g21b_ddim250_256), ("g22", g22_chain1000_128), ("g23", g23_ddnm_dropout),
-            ("g24", g24_objectives), ("spec", spec_fixture)]
+            ("g24", g24_objectives), ("g25", g25_validation), ("spec", spec_fixture)]
     for name, fn in jobs:
         if not only or name in only:
             fn()
