@@ -215,6 +215,31 @@ int prg_radius_select_ragged_f64(const double* pts, const int64_t* offsets, int 
                                  const int64_t* table_offsets, const int32_t* index_base, const int32_t* pad, int32_t* table,
                                  void* stream);
 
+/* Oriented surface normals from neighbour tables: per row the eigenvector of the smallest eigenvalue of its neighbourhood's
+ * scatter matrix, turned towards its cloud's viewpoint, and the surface variation lambda_min / (lambda_0 + lambda_1 + lambda_2) —
+ * bit for bit `postprocess.estimate_normals`, which states every operation in order (float64, no fma, IEEE / and sqrt: sums
+ * over the slots as 8 partial sums, slot s to partial s mod 8, combined by a fixed tree; two passes, mean then scatter matrix;
+ * 6 cyclic Jacobi sweeps; the normal is not renormalised).
+ * pts (total,3) float64 DEVICE: a stack of C clouds, cloud c = rows [offsets[c], offsets[c+1]) (offsets (C+1) int64 DEVICE).
+ * table (Q, limit) int32 DEVICE with indices into the stack and table_offsets (C+1) int64 DEVICE: table row table_offsets[c] + i
+ * belongs to row offsets[c] + i of pts — what prg_radius_select_ragged_f64 writes for the self-search of every cloud with
+ * index_base = the cloud's first row.  count (Q) int32 DEVICE: the matches of each table row before truncation; the valid slots
+ * of a row are its first k = min(count, limit), the others are never read.  pad (C) int32 DEVICE or NULL, select's argument:
+ * accepted so that select's arguments pass through unchanged, and not read — validity is by count alone.  A valid slot's index
+ * is clamped into the row's own cloud before pts is read (on select's output that changes nothing).  Q: the rows of table, count
+ * and of the outputs; table rows outside [table_offsets[0], table_offsets[C]) are neither read nor written.
+ * viewpoints (C,3) float64 DEVICE: the normal n of row p is negated iff (nx*(vx-px) + ny*(vy-py)) + nz*(vz-pz) < 0.  A row with
+ * k < min_neighbors, or with a non-finite coordinate, gets (0, 0, 1) and variation 0 and is not oriented.
+ * normals (Q,3) float64 DEVICE; variation (Q) float64 DEVICE or NULL; scatter (Q,6) float64 DEVICE or NULL — the debug form: the
+ * six sums xx, xy, xz, yy, yz, zz before the decomposition, NULL in every product call.  Every element of an owned row is
+ * written exactly once by one thread (no atomics, no workspace) and nothing else is; pts, table and count are not written.
+ * 1 <= C <= 65535, 0 <= Q < 2^31, 1 <= limit <= 1024, min_neighbors >= 3, no output may be pts; anything else or a null required
+ * pointer fails with PRG_E_INVALID before any device call.  Q == 0 returns 0 without a launch (the pointers may then be NULL).
+ * Asynchronous on `stream`; reads no device data on the host; allocates nothing.                                               */
+int prg_normals_ragged_f64(const double* pts, const int64_t* offsets, int C, const int32_t* table, const int64_t* table_offsets,
+                           const int32_t* pad, const int32_t* count, int64_t Q, int limit, const double* viewpoints,
+                           int min_neighbors, double* normals, double* variation, double* scatter, void* stream);
+
 /* Node patches: the point-to-node partition of a coarse-to-fine registration network as per-node tables.  d2 (total) float64 and
  * assign (total) int32, DEVICE: the d2 and idx prg_nearest_ragged_f64 wrote for the buffer [points_0 | nodes_0 | points_1 |
  * nodes_1 | ...] with these `offsets` (2*n_pairs+1 int64 DEVICE, offsets[0] may be > 0) — "pair" c is cloud c: segment 2c its

@@ -84,6 +84,7 @@ PROTOTYPES = {
     "prg_radius_count_ragged_f64": (C.c_int, [_P, _P, _I, _L, _L, C.c_double, _P, _P, C.c_size_t, _P]),
     "prg_radius_fill_ragged_f64": (C.c_int, [_P, _P, _I, _L, C.c_double, _P, _L, _P, _P]),
     "prg_radius_select_ragged_f64": (C.c_int, [_P, _P, _I, _L, _P, _P, _L, _I, _P, _P, _P, _P, _P]),
+    "prg_normals_ragged_f64": (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _P]),
     "prg_patch_tables_ragged": (C.c_int, [_P, _P, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _P]),
     "prg_patch_overlap_ragged_f64": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, C.c_double, _P, _L, _L, _P, _P, _P]),
     "prg_patch_corr_labels_f64": (C.c_int, [_P, _L, _P, _L, _I, _P, _L, C.c_double, _P, _P]),

@@ -589,6 +589,92 @@ def neighbor_pyramid(points: torch.Tensor, lengths, *, num_stages: int, voxel_si
     return out
 
 
+def normals_from_tables(points: torch.Tensor, lengths, table: torch.Tensor, count: torch.Tensor, *, viewpoints=None,
+                        min_neighbors: int = 3, want_variation: bool = False):
+    """Oriented normals of a stack of C clouds from neighbour tables the caller already holds — `neighbor_pyramid(...)
+    ["neighbors"][0]` and `["counts"]["neighbors"][0]`, or `estimate_normals`' own search: ONE launch of prg_normals_ragged_f64,
+    bit for bit `postprocess.estimate_normals` per cloud (which states the definition).  points (N,3) float64 or float32 device
+    tensor (float32 is widened, which is exact), the clouds one after the other; lengths (C,) their rows (device tensor, numpy or
+    a list); table (N, limit) int32 with indices into the stack, row t for row t of points; count (N,) int32, the matches before
+    truncation.  viewpoints: (C,3), host or device, or None for the origin; every cloud's normals face its own.
+    Returns normals (N,3) float64 on the device; with want_variation (normals, variation (N,)).  No host synchronisation: a
+    device `lengths` is summed on the device."""
+    lib = _lib.load()
+    if not (points.is_cuda and table.is_cuda and count.is_cuda):
+        raise _lib.PrgError("expected tensors on the HIP device (this package has no CPU path)")
+    if points.dtype not in (torch.float64, torch.float32):
+        raise _lib.PrgError("normals_from_tables: points must be float64 or float32")
+    if int(min_neighbors) != min_neighbors or min_neighbors < 3:
+        raise ValueError("min_neighbors must be an integer >= 3")
+    dev = points.device
+    pts = points.contiguous().view(-1, 3).to(torch.float64)
+    N = pts.shape[0]
+    lens = lengths.to(torch.int64).view(-1) if torch.is_tensor(lengths) else _dev_i64(np.asarray(lengths).reshape(-1), dev)
+    C = lens.numel()
+    if table.dtype != torch.int32 or count.dtype != torch.int32 or table.dim() != 2 or table.shape[0] != N or count.numel() != N:
+        raise ValueError("table must be (rows of points, limit) int32 and count (rows of points,) int32")
+    if not 1 <= C <= 65535:
+        raise ValueError("1..65535 clouds")
+    if viewpoints is None:
+        views = torch.zeros((C, 3), dtype=torch.float64, device=dev)
+    elif torch.is_tensor(viewpoints):
+        views = viewpoints.to(device=dev, dtype=torch.float64).contiguous().view(-1, 3)
+    else:
+        views = torch.from_numpy(np.ascontiguousarray(viewpoints, dtype=np.float64).reshape(-1, 3)).to(dev)
+    if views.shape[0] != C:
+        raise ValueError("one viewpoint per cloud")
+    offsets = torch.zeros((C + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=offsets[1:])
+    normals = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    variation = torch.empty((N,), dtype=torch.float64, device=dev) if want_variation else None
+    if N:
+        _lib.check(lib.prg_normals_ragged_f64(_lib.ptr(pts), _lib.ptr(offsets), C, _lib.ptr(table.contiguous()), _lib.ptr(offsets),
+                                              None, _lib.ptr(count.contiguous()), N, int(table.shape[1]), _lib.ptr(views),
+                                              int(min_neighbors), _lib.ptr(normals), _lib.ptr(variation), None,
+                                              _lib.stream_ptr()), "prg_normals_ragged_f64")
+    return (normals, variation) if want_variation else normals
+
+
+def estimate_normals(points: torch.Tensor, lengths, *, radius: float = 0.1, limit: int = 30, viewpoints=None,
+                     min_neighbors: int = 3, want_variation: bool = False):
+    """Oriented surface normals of a stack of C clouds on the device, bit for bit `postprocess.estimate_normals_cloud(cloud_c,
+    radius, limit, viewpoints[c])` per cloud: per row the PCA normal of its `limit` nearest rows within `radius` (itself
+    included; open3d's KDTreeSearchParamHybrid(radius, max_nn=limit)), turned towards its cloud's viewpoint.  points (N,3)
+    float64 or float32 device tensor, the clouds one after the other; lengths (C,) their rows (device tensor, numpy or a list);
+    viewpoints (C,3), host or device, or None: the origin for every cloud.  Returns normals (N,3) float64 on the device, and
+    (normals, variation (N,)) with want_variation.  A host tensor raises PrgError: there is no CPU path.
+
+    The pair buffer [c, c for every cloud] of a self-search is assembled as `neighbor_pyramid` does for one level (ONE device
+    `cat` of row slices, 2 N rows), then ONE count / fill / select (`_neighbor_tables`) and ONE launch of the normals kernel
+    (`normals_from_tables`).  Host synchronisations: one for `lengths` if it is a device tensor (the slices need it), and the
+    8-byte list size of the search; the normals kernel adds none."""
+    if not points.is_cuda:
+        raise _lib.PrgError("expected a tensor on the HIP device (this package has no CPU path)")
+    if points.dtype not in (torch.float64, torch.float32):
+        raise _lib.PrgError("estimate_normals: points must be float64 or float32")
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and > 0")
+    if int(limit) != limit or not 1 <= limit <= 1024:
+        raise ValueError("limit must be an integer in 1..1024")
+    dev = points.device
+    pts = points.contiguous().view(-1, 3).to(torch.float64)
+    lens = (lengths.cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)).astype(np.int64).reshape(-1)
+    C, N = len(lens), pts.shape[0]
+    if C < 1 or (lens < 0).any() or int(lens.sum()) != N:
+        raise ValueError("lengths do not add up to the rows of points")
+    o = np.concatenate([[0], np.cumsum(lens)])
+    if N:
+        buf = torch.cat([pts[o[c]:o[c + 1]] for c in range(C) for _ in range(2) if lens[c]], 0)
+        offs = np.concatenate([[0], np.cumsum(np.repeat(lens, 2))])
+        table, _, count = _neighbor_tables(buf, _dev_i64(offs, dev), C, int(lens.max()), float(radius), int(limit),
+                                           _dev_i32(o[:C], dev), _dev_i32([N] * C, dev), query_rows=N)
+    else:
+        table = torch.empty((0, int(limit)), dtype=torch.int32, device=dev)
+        count = torch.empty((0,), dtype=torch.int32, device=dev)
+    return normals_from_tables(pts, lens, table, count, viewpoints=viewpoints, min_neighbors=min_neighbors,
+                               want_variation=want_variation)
+
+
 def _host_offsets(o, what: str) -> np.ndarray:
     """CSR offsets as a host int64 array; a device tensor is copied back (one synchronisation)."""
     o = (o.cpu().numpy() if torch.is_tensor(o) else np.asarray(o)).astype(np.int64).reshape(-1)

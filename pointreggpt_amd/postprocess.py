@@ -533,6 +533,158 @@ def radius_neighbors_hip(pairs, radius: float, limit: int, device="cuda"):
     return [(table[to[p]:to[p + 1]].copy(), count[to[p]:to[p + 1]].copy()) for p in range(len(pairs))]
 
 
+NORMALS_LANES = 8        # partial sums per row of estimate_normals (the lanes of a row in csrc/normals.hip)
+NORMALS_SWEEPS = 6       # cyclic Jacobi sweeps (tests/test_normals_spec.py: a seventh changes no output bit on its inputs)
+
+
+def _normals_sum(x: np.ndarray, k: np.ndarray) -> np.ndarray:
+    """x (N, limit), k (N,) valid slots per row -> (N,): THE sum over the slots of estimate_normals.  NORMALS_LANES = 8 partial
+    sums per row, each starting at +0.0; slot s < k is added to partial s mod 8, s ascending; the partials are combined by the
+    tree ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)).  Slots >= k are not part of it, whatever they hold."""
+    part = np.zeros((x.shape[0], NORMALS_LANES), dtype=np.float64)
+    for s in range(x.shape[1]):
+        live = s < k
+        if not live.any():
+            break
+        part[:, s % NORMALS_LANES] += np.where(live, x[:, s], 0.0)          # p + 0.0 == p, bit for bit: p is never -0.0
+    pair = part[:, 0::2] + part[:, 1::2]
+    quad = pair[:, 0::2] + pair[:, 1::2]
+    return quad[:, 0] + quad[:, 1]
+
+
+def _normals_rotate(A, V, p: int, q: int):
+    """One Jacobi rotation of estimate_normals in the (p, q) plane, on rows where A[p][q] != 0; A: 3x3 nested lists of (N,)
+    arrays kept symmetric, V: the same for the eigenvectors."""
+    r = 3 - p - q
+    apq = A[p][q]
+    do = apq != 0.0
+    theta = (A[q][q] - A[p][p]) / (2.0 * apq)
+    t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+    c = 1.0 / np.sqrt(t * t + 1.0)
+    s = t * c
+    h = t * apq
+    app, aqq = A[p][p] - h, A[q][q] + h
+    apr, aqr = c * A[p][r] - s * A[q][r], s * A[p][r] + c * A[q][r]
+    A[p][p], A[q][q] = np.where(do, app, A[p][p]), np.where(do, aqq, A[q][q])
+    A[p][r] = A[r][p] = np.where(do, apr, A[p][r])
+    A[q][r] = A[r][q] = np.where(do, aqr, A[q][r])
+    A[p][q] = A[q][p] = np.where(do, 0.0, apq)
+    for i in range(3):
+        vp, vq = c * V[i][p] - s * V[i][q], s * V[i][p] + c * V[i][q]
+        V[i][p], V[i][q] = np.where(do, vp, V[i][p]), np.where(do, vq, V[i][q])
+
+
+def estimate_normals(points: np.ndarray, table: np.ndarray, count: np.ndarray, *, viewpoint=(0.0, 0.0, 0.0), min_neighbors: int = 3,
+                     _sweeps: int = NORMALS_SWEEPS, _parts: Optional[dict] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Oriented surface normals of a cloud from its neighbour table -> (normals (N,3) float64, variation (N,) float64): the
+    numpy specification of prg_normals_ragged_f64, bit for bit.  points (N,3) float64; table (N, limit) int32 and count (N,) as
+    `radius_neighbors(points, points, radius, limit)` returns them (pad slots hold N and are never read).  This function is the
+    definition; every step is float64 arithmetic with +, -, *, / and sqrt only, no fused multiply-add, in exactly this order.
+
+    Per row i, with k = min(count[i], limit) and the neighbours p_s = points[table[i, s]], s < k:
+    1. Degenerate rows.  If k < min_neighbors, or a coordinate of points[i] is not finite: normal = (0, 0, 1) — open3d's
+       convention —, variation = 0, and the row is not oriented.  Nothing below applies to it.
+    2. Every "sum over the slots" below is `_normals_sum`: 8 partial sums from +0.0, slot s into partial s mod 8 in ascending s,
+       combined as ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)).
+    3. Mean.  m = (sum x_s, sum y_s, sum z_s) / float(k), three divisions.
+    4. Scatter matrix, a second pass.  d_s = p_s - m; S = the six sums of dx*dx, dx*dy, dx*dz, dy*dy, dy*dz, dz*dz (each product
+       rounded, then summed).  S is not divided by k: neither output needs it.
+    5. Eigen-decomposition of S by cyclic Jacobi, V = I: NORMALS_SWEEPS = 6 sweeps, each the rotations (p, q) = (0, 1), (0, 2),
+       (1, 2) in this order, r the third index.  A rotation is done iff S_pq != 0:
+         theta = (S_qq - S_pp) / (2 * S_pq);   t = sgn(theta) / (|theta| + sqrt(theta * theta + 1)), sgn(0) = +1 — an infinite
+         theta, or a theta whose square overflows, gives t = 0 —;   c = 1 / sqrt(t * t + 1);   s = t * c;   h = t * S_pq;
+         S_pp -= h;  S_qq += h;  (S_pr, S_qr) = (c * S_pr - s * S_qr, s * S_pr + c * S_qr);  S_pq = 0;
+         for every row j of V: (V_jp, V_jq) = (c * V_jp - s * V_jq, s * V_jp + c * V_jq).
+       Six sweeps: Jacobi converges quadratically and a 3x3 matrix with separated eigenvalues is diagonal to the last bit after
+       four or five; tests/test_normals_spec.py checks that a seventh sweep changes no bit of either output on its inputs.
+    6. Normal.  The column of V under the smallest diagonal entry of S, the lowest index on ties; NOT renormalised (its norm is 1
+       to a few ulp).
+    7. Variation.  lambda_min / ((S_00 + S_11) + S_22), 0 where that sum is 0.
+    8. Orientation.  With v = viewpoint and p = points[i]: if (nx * (vx - px) + ny * (vy - py)) + nz * (vz - pz) < 0 the normal
+       is negated; at exactly 0 it stays.
+
+    `min_neighbors` < 3 raises ValueError.  (`_sweeps` and `_parts` are for the tests: another number of sweeps; a dict that
+    receives "scatter", the (N,6) sums of step 4 — zeros on degenerate rows.)"""
+    if int(min_neighbors) != min_neighbors or min_neighbors < 3:
+        raise ValueError("min_neighbors must be an integer >= 3")
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    table = np.asarray(table)
+    count = np.asarray(count).reshape(-1)
+    if table.ndim != 2 or table.shape[0] != len(P) or len(count) != len(P) or table.shape[1] < 1:
+        raise ValueError("table must be (len(points), limit) and count (len(points),)")
+    v = np.asarray(viewpoint, dtype=np.float64).reshape(3)
+    N, limit = table.shape
+    normals = np.zeros((N, 3), dtype=np.float64)
+    normals[:, 2] = 1.0
+    variation = np.zeros((N,), dtype=np.float64)
+    k = np.minimum(np.maximum(count.astype(np.int64), 0), limit)
+    ok = (k >= int(min_neighbors)) & np.isfinite(P).all(axis=1)
+    k = np.where(ok, k, 0)
+    if _parts is not None:
+        _parts["scatter"] = np.zeros((N, 6), dtype=np.float64)
+    if not ok.any():
+        return normals, variation
+    with np.errstate(all="ignore"):
+        valid = np.arange(limit)[None, :] < k[:, None]
+        nb = P[np.where(valid, table, 0).astype(np.int64).clip(0, max(N - 1, 0))]          # (N, limit, 3); pad slots: any row
+        kf = k.astype(np.float64)
+        m = [_normals_sum(nb[:, :, a], k) / kf for a in range(3)]
+        d = [nb[:, :, a] - m[a][:, None] for a in range(3)]
+        S = {(a, b): _normals_sum(d[a] * d[b], k) for a in range(3) for b in range(a, 3)}
+        if _parts is not None:
+            _parts["scatter"][ok] = np.stack([S[0, 0], S[0, 1], S[0, 2], S[1, 1], S[1, 2], S[2, 2]], axis=1)[ok]
+        A = [[S[min(a, b), max(a, b)].copy() for b in range(3)] for a in range(3)]
+        V = [[np.full((N,), 1.0 if a == b else 0.0) for b in range(3)] for a in range(3)]
+        for _ in range(int(_sweeps)):
+            _normals_rotate(A, V, 0, 1)
+            _normals_rotate(A, V, 0, 2)
+            _normals_rotate(A, V, 1, 2)
+        s1 = A[1][1] < A[0][0]
+        l1 = np.where(s1, A[1][1], A[0][0])
+        s2 = A[2][2] < l1
+        lmin = np.where(s2, A[2][2], l1)
+        n = [np.where(s2, V[a][2], np.where(s1, V[a][1], V[a][0])) for a in range(3)]
+        total = (A[0][0] + A[1][1]) + A[2][2]
+        var = np.where(total == 0.0, 0.0, lmin / total)
+        dot = (n[0] * (v[0] - P[:, 0]) + n[1] * (v[1] - P[:, 1])) + n[2] * (v[2] - P[:, 2])
+        flip = dot < 0.0
+        n = np.stack([np.where(flip, -c, c) for c in n], axis=1)
+    normals[ok] = n[ok]
+    variation[ok] = var[ok]
+    return normals, variation
+
+
+def estimate_normals_cloud(points: np.ndarray, radius: float = 0.1, limit: int = 30, viewpoint=(0.0, 0.0, 0.0),
+                           min_neighbors: int = 3) -> Tuple[np.ndarray, np.ndarray]:
+    """`estimate_normals` on the cloud's own neighbour table: `radius_neighbors(points, points, radius, limit)` — per row its
+    `limit` nearest rows within `radius`, itself included, open3d's KDTreeSearchParamHybrid(radius, max_nn=limit) — then the
+    definition above.  -> (normals (N,3), variation (N,))."""
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    table, count = radius_neighbors(P, P, radius, limit)
+    return estimate_normals(P, table, count, viewpoint=viewpoint, min_neighbors=min_neighbors)
+
+
+def estimate_normals_hip(clouds, radius: float = 0.1, limit: int = 30, viewpoints=None, device="cuda"):
+    """[cloud (n,3), ...] -> [(normals (n,3) float64, variation (n,) float64), ...] as `estimate_normals_cloud(cloud, radius,
+    limit, viewpoints[c])` defines them, for clouds that are on the host: all clouds uploaded once as one float64 stack, ONE
+    search and ONE kernel launch (`geometry.estimate_normals`) for the whole list, one copy back.  viewpoints: (len(clouds), 3)
+    or None for the origin."""
+    from . import _lib
+    from . import geometry as G
+    _check_radius_limit(radius, limit)
+    _lib.load()
+    _lib.require_gpu()
+    if not len(clouds):
+        return []
+    clouds = [np.ascontiguousarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds]
+    lens = [len(c) for c in clouds]
+    pts, _ = G.upload_clouds(clouds, device, dtype=np.float64)
+    normals, variation = G.estimate_normals(pts[:int(sum(lens))], lens, radius=radius, limit=limit, viewpoints=viewpoints, want_variation=True)
+    normals, variation = normals.cpu().numpy(), variation.cpu().numpy()
+    o = np.concatenate([[0], np.cumsum(lens)])
+    return [(normals[o[c]:o[c + 1]].copy(), variation[o[c]:o[c + 1]].copy()) for c in range(len(clouds))]
+
+
 def neighbor_pyramid(points: np.ndarray, lengths, num_stages: int, voxel_size: float, radius: float, neighbor_limits) -> dict:
     """The KPConv pyramid of a stack of C clouds, host specification of `geometry.neighbor_pyramid`, built from
     `radius_neighbors` and `voxel_down_sample` only.  points (N,3): the clouds one after the other, lengths (C,) their rows.

@@ -35,6 +35,13 @@ Overlap-targeted poses: `PairStream(..., overlap=(lo, hi), pose_candidates=16, p
 source frame on the device) and adds `predicted_overlap` to every item of the scene: a tuple with the predicted share of seen
 source rows of each of its views, in view order.  With `overlap=None` (the default) nothing is scored and the key is absent.
 
+Normals: `PairStream(..., normals=Normals(radius=0.1, limit=30))` adds `src_normals` and `tgt_normals` to every item: float64,
+one row per row of `src` / `tgt`, `geometry.estimate_normals` of the clouds the item holds — after the augmentation's move,
+cut and noise when `augment` is set — every cloud oriented towards the camera centre of the view that produced it, in the frame
+the cloud is handed out in; the two centres are the item's `src_camera` and `tgt_camera` (3 float64 each).  All clouds of a
+batch go through one search and one kernel launch.  With `normals=None` (the default) every item is exactly the one described
+above.  A fused target of several views has no single camera: `clouds="fused"` with `num_samples > 1` raises.
+
 The stream runs on the calling thread's current HIP stream.  It uses no writer pool and no lanes, writes no file and creates
 nothing under the generator's `samples_folder` (the folder itself is `Generator.__init__`'s doing).
 """
@@ -73,6 +80,21 @@ class Augment:
         if not (np.isfinite(self.translation) and self.translation >= 0):
             raise ValueError("translation must be finite and >= 0")
         PP._check_augment(self.noise, self.point_limit)
+
+
+@dataclass(frozen=True)
+class Normals:
+    """Per-point normals for the items of a `PairStream`: the PCA normal of a row's `limit` nearest rows within `radius` of its
+    own cloud, itself included (open3d's KDTreeSearchParamHybrid(radius, max_nn=limit)), oriented towards the cloud's camera —
+    `postprocess.estimate_normals` states the arithmetic."""
+    radius: float = 0.1
+    limit: int = 30
+
+    def __post_init__(self):
+        if not (np.isfinite(self.radius) and self.radius > 0):
+            raise ValueError("radius must be finite and > 0")
+        if int(self.limit) != self.limit or not 3 <= self.limit <= 1024:
+            raise ValueError("limit must be an integer in 3..1024")
 
 
 def uniform_rotation(rng: np.random.Generator) -> np.ndarray:
@@ -116,7 +138,7 @@ class PairStream:
                  matching_radius: Optional[float] = None, mask_threshold: float = 0.99, has_refine_step: bool = False,
                  save_voxel_size: float = 0.025, to: str = "numpy", augment: Optional[Augment] = None, epoch: int = 0,
                  num_samples: int = 1, clouds: str = "fused", memory_voxel_size: float = 0.002, overlap=None,
-                 pose_candidates: int = 16, pose_spread: float = 3.0):
+                 pose_candidates: int = 16, pose_spread: float = 3.0, normals: Optional[Normals] = None):
         if to not in ("numpy", "torch"):
             raise ValueError("to must be 'numpy' or 'torch'")
         if generator.device.type == "cpu":
@@ -133,6 +155,11 @@ class PairStream:
             raise ValueError("clouds must be 'fused' or 'per_view'")
         if int(num_samples) < 1:
             raise ValueError("num_samples must be >= 1")
+        if normals is not None and not isinstance(normals, Normals):
+            raise ValueError("normals must be a stream.Normals (or None)")
+        if normals is not None and clouds == "fused" and int(num_samples) > 1:
+            raise ValueError("normals= needs one camera per cloud: a fused target of several views has none, use clouds=\"per_view\"")
+        self.normals = normals
         self.num_samples, self.per_view, self.memory_voxel_size = int(num_samples), clouds == "per_view", memory_voxel_size
         self.search = generator._pose_search(overlap, pose_candidates, pose_spread, int(noise_seed), True)
         self.augment, self.epoch = augment, int(epoch)
@@ -168,7 +195,22 @@ class PairStream:
             if sample_idx < self.num_samples - 1:                                              # memory update (sd:2661-2680)
                 memory.update(xyz, valid, self.memory_voxel_size)
                 memory.settle(["scene-{:0>6d}".format(i) for i in idxs])
+        self._poses = poses                                                                    # per view: (B,4,4), for the cameras
         return gen._finish_pairs_launch(memory, views, poses, self.per_view, self.save_voxel_size)
+
+    def _cameras(self, keep, moves):
+        """(2 * len(keep), 3) float64: the camera centre of every cloud of the surviving pairs, in the frame the cloud is handed
+        out in.  Cloud 0 of a scene is its source frame, seen from the origin of the common frame; cloud i >= 1 is view i, whose
+        pose takes the common frame into the camera's, so its centre is the translation of the inverse pose (the float64 inverse
+        `_finish_pairs_launch` moves the cloud back with).  moves[k]: the augmentation's (move_src, move_tgt) of pair k, or None."""
+        cams = np.zeros((2 * len(keep), 3), dtype=np.float64)
+        for k, (j, s, t) in enumerate(keep):
+            for c, i in enumerate((s, t)):
+                if i >= 1:
+                    cams[2 * k + c] = np.linalg.inv(self._poses[i - 1][j].astype(np.float64))[:3, 3]
+                if moves is not None and moves[k][c] is not None:
+                    cams[2 * k + c] = PP.rigid_move(cams[2 * k + c], moves[k][c])[0]
+        return cams
 
     # -- the loaders' augmentation of the surviving pairs of a batch: one launch for all of them -------------------------------
     def _augment(self, pts, sizes, scenes, pairs):
@@ -178,7 +220,7 @@ class PairStream:
         n = len(scenes)
         T = np.tile(np.eye(4), (2 * n, 1, 1))
         has_T = np.zeros(2 * n, dtype=np.uint8)
-        seeds, transforms = [], []
+        seeds, transforms, self._moves = [], [], []
         for k, scene in enumerate(scenes):
             moves = augment_poses(self.noise_seed, scene, self.epoch, aug, pairs[k])
             for c in (0, 1):
@@ -186,6 +228,7 @@ class PairStream:
                     T[2 * k + c], has_T[2 * k + c] = moves[c], 1
                 seeds.append(synthetic.augment_seed_pair(self.noise_seed, scene, c, pairs[k]))
             transforms.append(moves[2])
+            self._moves.append(moves[:2])
         res = G_.augment_clouds(pts, sizes, seeds=seeds, draw=self.epoch, noise=aug.noise, limit=aug.point_limit,
                                 T=T if has_T.any() else None, has_T=has_T if has_T.any() else None)
         if aug.point_limit is not None:
@@ -234,12 +277,18 @@ class PairStream:
                     search, _ = gen.G.rigid_crop_ragged(search, None, d_offs, T=T, has_T=np.tile(np.array([1, 0], np.uint8), len(keep)))
                 corr, c_offs = gen.G.radius_pairs_ragged(search, d_offs, len(keep), int(sizes.max()), self.matching_radius)
                 c_offs = c_offs.cpu().numpy()
+            normals = cams = None
+            if self.normals is not None:             # last: on the clouds the items hold, one search and one launch per batch
+                cams = self._cameras(keep, None if self.augment is None else self._moves)
+                normals = gen.G.estimate_normals(pts, sizes, radius=self.normals.radius, limit=self.normals.limit, viewpoints=cams)
             if self.to == "numpy":
+                normals = None if normals is None else normals.cpu().numpy()
                 pts = pts.cpu().numpy()
                 rows = None if rows is None else rows.cpu().numpy()
                 corr = None if corr is None else corr.cpu().numpy()
                 own = np.copy
             else:
+                cams = None if cams is None else torch.from_numpy(cams).to(pts.device)
                 own = torch.clone
             for k, (j, s, t) in enumerate(keep):
                 item = dict(scene=idxs[j], src=own(pts[k_offs[2 * k]:k_offs[2 * k + 1]]), tgt=own(pts[k_offs[2 * k + 1]:k_offs[2 * k + 2]]),
@@ -254,4 +303,8 @@ class PairStream:
                     item["transform"] = transforms[k] if self.to == "numpy" else torch.from_numpy(transforms[k]).to(pts.device)
                     item["src_rows"] = own(rows[k_offs[2 * k]:k_offs[2 * k + 1]])
                     item["tgt_rows"] = own(rows[k_offs[2 * k + 1]:k_offs[2 * k + 2]])
+                if normals is not None:
+                    item["src_normals"] = own(normals[k_offs[2 * k]:k_offs[2 * k + 1]])
+                    item["tgt_normals"] = own(normals[k_offs[2 * k + 1]:k_offs[2 * k + 2]])
+                    item["src_camera"], item["tgt_camera"] = own(cams[2 * k]), own(cams[2 * k + 1])
                 yield item
